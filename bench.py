@@ -1,16 +1,17 @@
 #!/usr/bin/env python3
 """bench.py -- sampled edges/s + feature-gather GB/s of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is ONE LAUNCH GROUP through the whole hot path on one GPU: `batches_per_step` (= --group,
 default 512 at B = 1024) independent mini-batches, each seed batch -> 2-hop sampling [25,10] -> per-hop
 feature-cache lookup + gather -> end-of-batch clean-up (the op order of the reference's
 GPURunner::RunOnce, SS/engine/server.cu:302-332), served by one hipGraph replay, inputs resident in HBM.
-The timed region is exactly K steps between barrier + synchronize brackets; because K steps of ~1 ms are
-far too short to time (launch latency, clock ramp), the same region is repeated until >= --min-seconds of
-GPU work have been timed and the MEDIAN region (max over ranks per repeat) gives `value`.
+The timed region is exactly K steps between barrier + synchronize brackets (max over ranks), timed once:
+`ms_per_step` = region / K, so K is what sets the length of the measurement.  (--min-seconds S repeats the
+region over the same batches until S seconds have been timed and reports the MEDIAN region.)
+--dump-outputs DIR writes what the last timed step handed its caller (rank 0): tools/bench_legs.py dump_outputs.
 Workload: synthetic RMAT-26 (N = 2^26, E = 2^30), float32[N x 128] counter-hash
 features, B = 1024, seeds = a seeded permutation, GPU p of P takes seeds with id % P == p.
 Mini-batches are served in groups: every kernel launch covers --group (default 524288 / B, at most 512) independent
@@ -353,6 +354,9 @@ def run_leg(c, engine, synth, stripe, replica_memory, headline, bulk=False, shap
     elapsed_max = elapsed = timed.elapsed_max                        # (`elapsed`: the rank-0 sampler / gather split below)
     if headline and not args.no_verify and timed.last_group is not None:
         legs.verify_last_group(c, synth, pipe, counted, timed.last_group)
+    if headline and rank == 0 and args.dump_outputs and timed.last_group is not None:
+        slot, k0, n_lanes = timed.last_group                         # the last timed step is still in its slot
+        legs.dump_outputs(args.dump_outputs, pipe.pools[slot][:n_lanes], k0)
     prof, elapsed_profiled = legs.profiled_pass(c, pipe)
     state_bytes, lds_buckets = pipe.pools[0][0].state_bytes(), pipe.pools[0][0].lds_buckets()
 

@@ -1,7 +1,7 @@
 """The legs of bench.py that are not the hot path's own timed region: argument parsing, the one-JSON-line guard, the two-phase
 bulk pipeline wrapper, the drop-in boundary leg (server binary <-> ipc_service consumer), the in-run PMC traffic measurement, and
-the pieces of a leg that bench.py's run_leg strings together (hotness collective, counting pass, timed regions, profiled pass,
-cold-row regather, report assembly).  bench.py stays the entry point; nothing here touches oracle/ (bench.py's cpu_baseline does)."""
+the pieces of a leg that bench.py's run_leg strings together (hotness collective, counting pass, timed regions, the --dump-outputs writer,
+profiled pass, cold-row regather, report assembly).  bench.py stays the entry point; nothing here touches oracle/ (bench.py's cpu_baseline does)."""
 import argparse
 import ctypes
 import json
@@ -183,8 +183,9 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32, help="timed steps; a step = one launch group of --group mini-batches")
     ap.add_argument("--warmup", type=int, default=8, help="untimed warm-up steps (launch groups)")
-    ap.add_argument("--min-seconds", type=float, default=1.5,
-                    help="repeat the K-step timed region until this much time has been measured (median reported)")
+    ap.add_argument("--min-seconds", type=float, default=0.0,
+                    help="repeat the K-step timed region until this much time has been measured (median reported); the default 0 "
+                         "times exactly --steps steps once")
     ap.add_argument("--max-repeats", type=int, default=400)
     ap.add_argument("--placement", type=str, default="hbm", choices=["hbm", "pinned"],
                     help="pinned: full CSR and full feature table in mapped pinned host memory (the reference's only tier; "
@@ -285,6 +286,9 @@ def parse_args():
                     help="testing: make rank 0 fail this way when the first extra leg starts (the headline line must still go out)")
     ap.add_argument("--force-device", type=int, default=-1,
                     help="put every rank on this GPU (testing the N > 1 code path on a 1-GPU box, with --backend gloo)")
+    ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
+                    help="after the timed steps, write what the headline leg's last timed step handed its caller as DIR/<name>.npy "
+                         "(rank 0; at most 64 MB in all: see dump_outputs)")
     return ap.parse_args()
 
 
@@ -582,8 +586,9 @@ def counting_pass(c, synth, pipe, cache, d, node_map, feature_rows, headline, st
 
 def timed_regions(c, engine, pipe, d, headline):
     """Warm-up, then the timed region: exactly K steps (K hipGraph replays of G batches each) between barrier + synchronize
-    brackets.  The region is repeated (same batches: an epoch over the same seeds, replays are deterministic) until --min-seconds
-    have been timed; every rank runs the same number of repeats, per repeat the MAX over ranks counts, the median repeat is reported."""
+    brackets, timed once by default.  With --min-seconds > 0 the region is repeated (same batches: an epoch over the same seeds, replays
+    are deterministic) until that much has been timed; every rank runs the same number of repeats, per repeat the MAX over ranks counts,
+    the median repeat is reported."""
     args, use_dist, dev = c.args, c.use_dist, c.dev
     first, n_timed, wrap = c.n_warm, c.n_timed, c.wrap
     pipe.run_range(0, c.n_warm, wrap=wrap)
@@ -641,6 +646,53 @@ def verify_last_group(c, synth, pipe, counted, last_group):
     ids = pl.buffer("sampled_ids")[:n]
     assert synth.feature_check_device(pl.buffer("float_features")[:n].contiguous(), ids.contiguous(), D, 7) == 0
     assert int(torch.unique(ids).numel()) == n
+
+
+DUMP_BYTES = 64 * 1000 * 1000
+# the parallel arrays of a batch (engine.read_batch), by what they are indexed with: per seed, per sampled node, per emitted edge
+DUMP_SETS = (("labels", ("labels",)), ("rows", ("sampled_ids", "float_features")),
+             ("edges", ("agg_src_off", "agg_dst_off", "agg_src_ids", "agg_dst_ids")))
+
+
+def dump_outputs(out_dir, pools, first_batch, seed=0):
+    """--dump-outputs: what the timed path handed its caller in its last step -- every lane (mini-batch) of that launch group as
+    engine.read_batch reads it, concatenated in lane order -- as out_dir/<name>.npy: float64 for ids, offsets and counters (exact),
+    float32 for the gathered feature rows.  batch_ids, node_counter and edge_counter go whole.  Each set of DUMP_SETS goes whole while
+    it fits its share of DUMP_BYTES, else as the positions (in the concatenation) drawn from a fixed seed; either way the positions are
+    written beside it as <set>_index.npy.  Returns the bytes written (at most DUMP_BYTES)."""
+    os.makedirs(out_dir, exist_ok=True)
+    nc = np.stack([pl.buffer("node_counter").cpu().numpy() for pl in pools]).astype(np.int64)
+    ec = np.stack([pl.buffer("edge_counter").cpu().numpy() for pl in pools]).astype(np.int64)
+    lanes, hop = np.arange(len(pools)), nc[:, 8]
+    counts = {"labels": nc[:, 9], "rows": nc[lanes, 9 + hop], "edges": ec[lanes, 9 + hop]}
+    D = pools[0].float_feature_len
+    out = {"batch_ids": np.arange(first_batch, first_batch + len(pools)), "node_counter": nc, "edge_counter": ec}
+    left = DUMP_BYTES - sum(a.size * 8 for a in out.values()) - (64 << 10)          # (64 KiB for the .npy headers)
+    share = {"labels": left // 8, "rows": left * 7 // 16, "edges": left * 7 // 16}
+    for i, (name, arrays) in enumerate(DUMP_SETS):
+        n = np.maximum(counts[name], 0)
+        room = min(pools[0].buffer(a).shape[0] for a in arrays)
+        assert int(n.max(initial=0)) <= room, f"a lane's counters claim {int(n.max())} {name}, its buffers hold {room}"   # (checked on the host)
+        total = int(n.sum())
+        cap = share[name] // (8 + sum(4 * D if a == "float_features" else 8 for a in arrays))     # bytes of one position, index included
+        pos = np.arange(total) if total <= cap else np.unique(np.random.default_rng([seed, i]).integers(0, total, size=cap))
+        starts = np.concatenate([[0], np.cumsum(n)])
+        lane_of = np.searchsorted(starts, pos, side="right") - 1
+        parts = {a: [] for a in arrays}
+        for lane in np.unique(lane_of):
+            local = torch.from_numpy(pos[lane_of == lane] - starts[lane]).to(pools[lane].device)
+            for a in arrays:
+                parts[a].append(pools[lane].buffer(a)[local].cpu().numpy())
+        for a in arrays:
+            out[a] = np.concatenate(parts[a]) if parts[a] else np.zeros((0, D) if a == "float_features" else 0)
+        out[name + "_index"] = pos
+    written = 0
+    for name, a in out.items():
+        path = os.path.join(out_dir, name + ".npy")
+        np.save(path, a.astype(np.float32 if name == "float_features" else np.float64))
+        written += os.path.getsize(path)
+    assert written <= DUMP_BYTES, f"--dump-outputs wrote {written} bytes"
+    return written
 
 
 def profiled_pass(c, pipe):
@@ -831,8 +883,8 @@ def leg_report(v):
                                      "`cold.frac` the HBM-only one" % G}
     timed_j = {"steps": args.steps, "repeats": timed.repeats, "median_s": elapsed_max,
                "min_s": float(timed.region_s.min()), "max_s": float(timed.region_s.max()), "total_timed_s": float(timed.region_s.sum()),
-               "note": "exactly K steps per region between barrier+synchronize brackets; region repeated over the "
-                       "same batches until --min-seconds; per repeat the max over ranks; value uses the median"}
+               "note": "exactly K steps per region between barrier+synchronize brackets; one region unless --min-seconds asks for "
+                       "repeats over the same batches; per repeat the max over ranks; value uses the median"}
     if not headline:
         out = {"value": float(tot_edges.item()) / elapsed_max, "unit": "edges/s", "ms_per_step": elapsed_max / args.steps * 1e3,
                "parallelism": layout, "timed_region": timed_j, "roofline": roof,
