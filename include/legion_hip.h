@@ -34,6 +34,13 @@ extern "C" {
 #define LEGION_TESTMODE 2
 #define LEGION_CACHEMISS_FLAG (-2)
 
+/* Feature dtype: the row format of a feature table and of every cache tier built from it.  float32 is the default;
+ * bfloat16 rows hold round_up(D, 8) elements (16-byte aligned rows, zero padded), 2 bytes each, rounded to nearest
+ * even from float32.  Whatever the storage, rows reach the lanes and the trainer as float32 (bf16 -> f32 is exact).
+ * Values other than these are refused (room is left for further formats). */
+#define LEGION_FEATURE_F32 0
+#define LEGION_FEATURE_BF16 1
+
 typedef void* legion_stream_t;            /* hipStream_t in the position of cudaStream_t */
 typedef struct LegionGraphStorage   LegionGraphStorage;    /* SS/storage/graph_storage.cuh:7-24  */
 typedef struct LegionFeatureStorage LegionFeatureStorage;  /* SS/storage/feature_storage.cuh:6-34 */
@@ -100,6 +107,19 @@ LegionFeatureStorage* legion_feature_create(int32_t partition_count, int32_t tot
 void legion_feature_set_ids(LegionFeatureStorage* f, int32_t dev_id, int32_t mode,
                             const int32_t* host_ids, const int32_t* host_labels, int32_t count);
 void legion_feature_destroy(LegionFeatureStorage* f);
+/* legion_feature_create with a feature dtype (LEGION_FEATURE_*).  LEGION_FEATURE_F32 is legion_feature_create (the caller's
+ * table is used in place).  LEGION_FEATURE_BF16: the library converts the caller's float32 table (device-accessible,
+ * N x float_feature_len) into a bf16 table of its own -- in HBM, or in mapped pinned host memory under
+ * LEGION_TABLE_PLACEMENT=pinned -- and frees it in legion_feature_destroy; the caller's table may go once this returns.
+ * NULL for an unknown dtype. */
+LegionFeatureStorage* legion_feature_create_ex(int32_t partition_count, int32_t total_num_nodes, int32_t float_feature_len,
+                                               int32_t feature_dtype, const float* all_float_feature_devptr);
+int32_t legion_feature_dtype(const LegionFeatureStorage* f);
+int64_t legion_feature_row_bytes(const LegionFeatureStorage* f);     /* bytes of one stored row: 4 D (f32), 2 round_up(D, 8) (bf16) */
+const void* legion_feature_table(const LegionFeatureStorage* f);     /* device address of the stored table */
+/* The conversion on its own: src float32[rows x D] -> dst bf16[rows x round_up(D, 8)] (both device-accessible), round to nearest
+ * even, NaN kept a NaN, pad elements zero; enqueued on `stream`. */
+void legion_convert_f32_to_bf16(legion_stream_t stream, const float* src, int64_t rows, int32_t D, uint16_t* dst);
 
 /* MemoryPool + its buffers: SS/engine/server.cu:172-273 (GPURunner::Initialize buffer
  * allocation) and SS/engine/ipc_service.cu:134-211 (the 7 IPC-shared outputs per pipe slot).
@@ -242,6 +262,9 @@ void legion_server_finalize(LegionServer* s);
 /* pybind `sampling_server.Run` equivalent; reads ./meta_config from the cwd */
 int32_t legion_run(const int32_t* fanout, int32_t hop_num, int32_t gpu_number, int32_t in_memory_mode,
                    int32_t cache_mode);
+/* Feature dtype (LEGION_FEATURE_*) of the tables the NEXT legion_server_initialize / legion_run loads: the float32 `features`
+ * file is converted while it is placed.  Returns 0, or -1 for an unknown dtype (nothing changes). */
+int32_t legion_server_set_feature_dtype(int32_t feature_dtype);
 
 LegionIPCEnv* NewIPCEnv(int32_t device_count);
 /* step arithmetic, SS/engine/ipc_service.cu:60-132,213-253 (host only, no GPU needed) */

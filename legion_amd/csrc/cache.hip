@@ -369,7 +369,10 @@ void UnifiedCache::CostModel(int, FeatureStorage* feature, GraphStorage* graph,
                              std::vector<uint64_t>& counters, int32_t train_step)
 {
     const int32_t N = feature->TotalNodeNum();
-    const int32_t D = feature->GetFloatFeatureLen();
+    AdoptFeatureFormat(feature);
+    // D enters the model only through the bytes of a row, as D * sizeof(float): a bf16 row of pitch P costs what a float32 row
+    // of P / 2 elements does (twice the rows for the same budget, half the bytes per missed row)
+    const int32_t D = (int32_t)(lg_feature_row_bytes(feature_dtype_, feature->GetFloatFeatureLen()) / (int64_t)sizeof(float));
     const int64_t* csr_index = graph->GetCSRNodeIndexCPU();
     node_capacity_.clear();
     edge_capacity_.clear();
@@ -477,6 +480,16 @@ void UnifiedCache::FillUp(int cache_agg_mode, FeatureStorage* feature, GraphStor
     FillUpLink(feature, graph);
 }
 
+// rows QF[r * Kg + Ki] of `table` into `cache`, in the cache's row format
+static void fill_rows(int32_t dtype, int32_t capacity, int32_t D, float* cache, const float* table, const int32_t* QF, int32_t Kg,
+                      int32_t Ki, int32_t n)
+{
+    if (dtype == LEGION_FEATURE_BF16)
+        lg::feat_fill_up_bf16(nullptr, capacity, lg_feature_pitch(dtype, D), (uint16_t*)cache, (const uint16_t*)table, QF, Kg, Ki, n);
+    else
+        lg::feat_fill_up(nullptr, capacity, D, cache, table, QF, Kg, Ki, n);
+}
+
 void UnifiedCache::FillUpLocal(FeatureStorage* feature, GraphStorage* graph)
 {
     {   // a new fill: pairs built from the previous node_map (of this or any other cache) are stale from here on
@@ -486,13 +499,14 @@ void UnifiedCache::FillUpLocal(FeatureStorage* feature, GraphStorage* graph)
             if (lg_is_local(d)) graph->DropColumnSlots(d);
     }
     hybrid_ = false;                  // (a clique fill after HybridInit: the gather decodes (owner, row) slots again)
+    AdoptFeatureFormat(feature);
     const int32_t N = feature->TotalNodeNum();
     float* cpu_float_feature = feature->GetAllFloatFeature();
     cpu_float_features_ = cpu_float_feature;
     // (stripes and replica are dense.  Rows padded to whole 128-byte lines were built and measured in round 4 -- a row that is not a
     // whole number of lines costs the same lines at either pitch, 400 bytes at any 16-byte offset cover exactly four -- and removed:
     // DESIGN_HISTORY.md, profiles/r04/gather_pitch.md)
-    const int32_t pitch = float_feature_len_;
+    const int64_t row_bytes = RowBytes();
     for (int32_t i = 0; i < Kc_; i++)
         for (int32_t j = 0; j < Kg_; j++) {
             const int32_t dev_id = i * Kg_ + j;
@@ -504,9 +518,8 @@ void UnifiedCache::FillUpLocal(FeatureStorage* feature, GraphStorage* graph)
             d_float_feature_cache_ptr_[dev_id] = (float**)d_alloc_space(device_count_ * sizeof(float*));
             if (float_feature_len_ > 0) {                      // this member's stripe: rows QF[r*Kg + j]
                 d_free_space(float_feature_cache_[dev_id]);
-                float* new_cache = (float*)d_alloc_space((int64_t)node_capacity_[i] * pitch * sizeof(float));
-                lg::feat_fill_up(nullptr, node_capacity_[i], float_feature_len_, new_cache, cpu_float_feature,
-                                 QF_[i], Kg_, j, N);
+                float* new_cache = (float*)d_alloc_space((int64_t)node_capacity_[i] * row_bytes);
+                fill_rows(feature_dtype_, node_capacity_[i], float_feature_len_, new_cache, cpu_float_feature, QF_[i], Kg_, j, N);
                 HIP_CALL(hipDeviceSynchronize());
                 float_feature_cache_[dev_id] = new_cache;
                 // hot-row replica: ranks 0 .. R-1 of the clique order, identical on every member (Kg = 1 addressing)
@@ -515,11 +528,11 @@ void UnifiedCache::FillUpLocal(FeatureStorage* feature, GraphStorage* graph)
                 replica_[dev_id] = nullptr;
                 replica_rows_[dev_id] = 0;
                 if (replica_bytes_ > 0 && Kg_ > 1) {
-                    int64_t rows = replica_bytes_ / ((int64_t)pitch * sizeof(float));
+                    int64_t rows = replica_bytes_ / row_bytes;
                     rows = std::min<int64_t>(rows, std::min<int64_t>((int64_t)node_capacity_[i] * Kg_, N));
                     if (rows > 0) {
-                        replica_[dev_id] = (float*)d_alloc_space(rows * pitch * sizeof(float));
-                        lg::feat_fill_up(nullptr, (int32_t)rows, float_feature_len_, replica_[dev_id], cpu_float_feature, QF_[i], 1, 0, N);
+                        replica_[dev_id] = (float*)d_alloc_space(rows * row_bytes);
+                        fill_rows(feature_dtype_, (int32_t)rows, float_feature_len_, replica_[dev_id], cpu_float_feature, QF_[i], 1, 0, N);
                         HIP_CALL(hipDeviceSynchronize());
                         replica_rows_[dev_id] = (int32_t)rows;
                     }
@@ -563,6 +576,7 @@ void UnifiedCache::HybridInit(FeatureStorage* feature, GraphStorage* graph, bool
 {
     const int32_t N = feature->TotalNodeNum();
     total_num_nodes_ = N;
+    AdoptFeatureFormat(feature);
     float* table = feature->GetAllFloatFeature();
     const int32_t cpu_cap = cpu_cache_capacity_ < 0 ? 0 : cpu_cache_capacity_;
     const int32_t gpu_cap = gpu_cache_capacity_ < 0 ? 0 : gpu_cache_capacity_;
@@ -602,15 +616,15 @@ void UnifiedCache::HybridInit(FeatureStorage* feature, GraphStorage* graph, bool
         d_float_feature_cache_ptr_[i] = (float**)d_alloc_space(device_count_ * sizeof(float*));     // :647-652
         if (float_feature_len_ > 0) {
             d_free_space(float_feature_cache_[i]);
-            float_feature_cache_[i] = (float*)d_alloc_space((int64_t)gpu_cap * float_feature_len_ * sizeof(float));   // :657
+            float_feature_cache_[i] = (float*)d_alloc_space((int64_t)gpu_cap * RowBytes());   // :657
             if (cpu_cache_host_[i] != nullptr) legion_host_free(cpu_cache_host_[i]);
             void* host = nullptr;
-            cpu_cache_dev_[i] = (float*)legion_host_alloc((int64_t)cpu_cap * float_feature_len_ * sizeof(float), &host);   // :616
+            cpu_cache_dev_[i] = (float*)legion_host_alloc((int64_t)cpu_cap * RowBytes(), &host);   // :616
             cpu_cache_host_[i] = (float*)host;
-            lg::feat_fill_up(nullptr, std::min(gpu_cap, N), float_feature_len_, float_feature_cache_[i], table, order, 1, 0, N);
+            fill_rows(feature_dtype_, std::min(gpu_cap, N), float_feature_len_, float_feature_cache_[i], table, order, 1, 0, N);
             if (N > gpu_cap)
-                lg::feat_fill_up(nullptr, std::min(cpu_cap, N - gpu_cap), float_feature_len_, cpu_cache_dev_[i], table, order + gpu_cap, 1, 0,
-                                 N - gpu_cap);
+                fill_rows(feature_dtype_, std::min(cpu_cap, N - gpu_cap), float_feature_len_, cpu_cache_dev_[i], table, order + gpu_cap, 1, 0,
+                          N - gpu_cap);
             HIP_CALL(hipDeviceSynchronize());
             std::vector<float*> tab(device_count_, nullptr);
             tab[0] = float_feature_cache_[i];
@@ -689,6 +703,10 @@ void UnifiedCache::BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, int32_t 
 void UnifiedCache::BulkPush(int32_t owner_dev, hipStream_t s, const int32_t* fidx, const int64_t* dst, const unsigned long long* cnt,
                             int64_t cap, char* peer_arena)
 {
+    if (feature_dtype_ != LEGION_FEATURE_F32) {      // (refused where the transfer is set up; a bf16 row copied verbatim would be wrong)
+        printf("peer_gather = bulk pushes float32 stripe rows only: this cache holds bf16 rows\n");
+        exit(EXIT_FAILURE);
+    }
     lg::launch_bulk_push(s, float_feature_cache_[owner_dev], float_feature_len_, fidx, dst, cnt, cap, peer_arena);
 }
 
@@ -730,6 +748,8 @@ lg::GatherParams UnifiedCache::GatherParamsOf(int32_t dev_id, int32_t op_id, int
         g.replica = nullptr;
         g.replica_rows = 0;
     }
+    g.dtype = feature_dtype_;
+    g.pitch = RowPitch();
     return g;
 }
 
@@ -789,7 +809,7 @@ extern "C" uint64_t legion_cache_peer_transactions(LegionUnifiedCache* c, int32_
     if (!u) return 0;
     uint64_t h[3] = {0, 0, 0};
     legion_cache_gather_stats3(c, dev_id, h);
-    return h[2] * (uint64_t)u->FloatFeatureLen() * sizeof(float) / 64;
+    return h[2] * (uint64_t)u->RowBytes() / 64;
 }
 
 extern "C" LegionUnifiedCache* legion_cache_create(int64_t cache_memory, int32_t float_feature_len,

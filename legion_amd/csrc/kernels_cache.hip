@@ -237,6 +237,79 @@ void feat_fill_up(hipStream_t s, int32_t capacity, int32_t D, float* cache, cons
     hipCheckError();
 }
 
+// the same for bf16 rows of `pitch` elements (pitch % 8 == 0): 16-byte chunks, the zero padding copied along
+__global__ void feat_fill_up_bf16_kernel(int32_t capacity, int32_t pitch, uint16_t* __restrict__ cache,
+                                         const uint16_t* __restrict__ table, const int32_t* __restrict__ QF,
+                                         int32_t Kg, int32_t Ki, int32_t n)
+{
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int32_t lane = threadIdx.x & 63;
+    const int32_t wave = (blockIdx.x * blockDim.x + threadIdx.x) >> 6;
+    const int32_t nwaves = (gridDim.x * blockDim.x) >> 6;
+    const int32_t C = pitch / 8;
+    for (int32_t r = wave; r < capacity; r += nwaves) {
+        const int64_t t = (int64_t)r * Kg + Ki;
+        if (t >= n) continue;
+        const u4* src = reinterpret_cast<const u4*>(table + (int64_t)QF[t] * pitch);
+        u4* dst = reinterpret_cast<u4*>(cache + (int64_t)r * pitch);
+        for (int32_t c = lane; c < C; c += 64) dst[c] = src[c];
+    }
+}
+
+void feat_fill_up_bf16(hipStream_t s, int32_t capacity, int32_t pitch, uint16_t* cache, const uint16_t* table,
+                       const int32_t* QF, int32_t Kg, int32_t Ki, int32_t n)
+{
+    if (capacity <= 0 || pitch <= 0) return;
+    feat_fill_up_bf16_kernel<<<grid_for((int64_t)capacity * 64, 256, 8192), 256, 0, s>>>(capacity, pitch, cache, table, QF, Kg, Ki, n);
+    hipCheckError();
+}
+
+// float32 -> bfloat16, round to nearest even on the bit pattern (torch's c10::BFloat16 rounding: subnormals are rounded like
+// any other value, finite values past the largest bf16 become +-inf).  NaNs take their own branch: the rounding add would
+// carry some of them into inf; here they keep sign and top payload bits and stay quiet NaNs.  (v_cvt_pk_bf16_f32 keeps NaNs too,
+// but its result for subnormal inputs follows the wave's denormal mode; the integer path does not depend on it.)
+__device__ __forceinline__ uint32_t bf16_rne_bits(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
+
+// one thread per 16-byte chunk of the output (8 elements); elements D .. pitch-1 of a row are written as zero.  Source rows are
+// only dword aligned (4 D bytes), so the loads are scalar; a one-off pass over the table at load time.
+__global__ __launch_bounds__(256) void convert_f32_to_bf16_kernel(const float* __restrict__ src, int64_t rows, int32_t D,
+                                                                   int32_t pitch, uint16_t* __restrict__ dst)
+{
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    const int32_t C = pitch / 8;
+    const int64_t total = rows * C;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < total; i += (int64_t)gridDim.x * 256) {
+        const int64_t r = i / C;
+        const int32_t c0 = (int32_t)(i - r * C) * 8;
+        const float* s = src + r * D;
+        uint32_t w[4];
+#pragma unroll
+        for (int k = 0; k < 4; k++) {
+            const int32_t e = c0 + 2 * k;
+            const uint32_t lo = e < D ? bf16_rne_bits(s[e]) : 0u;
+            const uint32_t hi = e + 1 < D ? bf16_rne_bits(s[e + 1]) : 0u;
+            w[k] = lo | (hi << 16);
+        }
+        reinterpret_cast<u4*>(dst + r * pitch)[c0 / 8] = u4{w[0], w[1], w[2], w[3]};
+    }
+}
+
+void convert_f32_to_bf16(hipStream_t s, const float* src, int64_t rows, int32_t D, int32_t pitch, uint16_t* dst)
+{
+    if (rows <= 0 || D <= 0) return;
+    if (pitch < D || pitch % 8 != 0) {
+        printf("convert_f32_to_bf16: pitch %d must be a multiple of 8 and at least D = %d\n", pitch, D);
+        exit(EXIT_FAILURE);
+    }
+    convert_f32_to_bf16_kernel<<<grid_for(rows * (pitch / 8), 256, 16384), 256, 0, s>>>(src, rows, D, pitch, dst);
+    hipCheckError();
+}
+
 __global__ void topo_neighbor_count_kernel(const int32_t* __restrict__ QT, int32_t Kg, int32_t Ki,
                                            int32_t capacity, int32_t n,
                                            const int64_t* __restrict__ csr_index,

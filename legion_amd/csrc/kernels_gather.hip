@@ -19,11 +19,13 @@
 // loads in flight per lane, so that consecutive lanes read consecutive 16 B of one source row
 // and write consecutive 16 B of the (contiguous) destination.  No divides in the copy loop.
 //
-// Roofline: HBM.  Algorithmic bytes per row = 8*D + 8 (D*4 read + D*4 written + id + index).
+// Roofline: HBM.  Algorithmic bytes per row = 8*D + 8 (D*4 read + D*4 written + id + index); with bf16 sources
+// (GatherParams.dtype, the Bf16x8 instances) 2*P + 4*D + 8, P = D rounded up to 8.
 #include "legion_core.h"
 
 #include <cstdlib>
 #include <cstring>
+#include <type_traits>
 
 namespace lg {
 
@@ -105,13 +107,26 @@ void launch_deliver(hipStream_t s, const LanePtrs* d_lane, const DeliverParams& 
 #ifndef LG_GATHER_TARGET_WG
 #define LG_GATHER_TARGET_WG 8192     // workgroups of a full launch: four rounds of what is resident, so the dispatcher evens out lanes of different length
 #endif
+// bf16 sources (LEGION_FEATURE_BF16): VecT = Bf16x8, 16 bytes = 8 bf16 elements of a source row of pitch P per lane and chunk,
+// widened to 32 bytes of float32 (bits << 16, exact) and stored as two dword-aligned 16-byte stores -- output rows are 4*D bytes,
+// so at any D they are only dword aligned, as on the v4u path.  The last chunk of a row with D % 8 != 0 stores its first D % 8
+// elements one by one (the source's pad elements are never stored), so every D takes the same instance and no TAIL pass.  A
+// missing row loads a 16-byte zero line instead of the destination (a destination row of D < 4 is shorter than a chunk).
+struct Bf16x8 {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    u4 w;
+};
+__device__ __attribute__((aligned(16))) Bf16x8 lg_gather_zero_line;
+
 // LASTOP: the gather of a batch's last op (the dominant launch; traces and counters tell it from the early hops' gathers by
 // name) -- the only one that can carry a hand-over to a trainer-visible pipe slot.
 template <typename VecT, int ROWS = LG_GATHER_ROWS, int UNROLL = LG_GATHER_UNROLL, bool TAIL = false, bool LASTOP = true>
 __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather_kernel(GatherParams gp, const LanePtrs* __restrict__ lanes,
                                                                    bool copy_range)
 {
+    constexpr bool BF16 = std::is_same<VecT, Bf16x8>::value;
     constexpr int VEC = sizeof(VecT) / sizeof(float);
+    static_assert(!BF16 || !TAIL, "bf16 rows end in a partial chunk, not a tail pass");
     static_assert(ROWS <= LG_GATHER_THREADS, "one resolving thread per row of a tile");
     __shared__ const LG_G float* s_ptr[2][ROWS];
 
@@ -146,7 +161,7 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
         deliver_slice(L, *static_cast<const DeliverParams*>(L.deliver), blockIdx.x, step);
     const int32_t tid = threadIdx.x;
     const int32_t D = gp.D;
-    const int32_t C = D / VEC;                         // chunks per row
+    const int32_t C = BF16 ? gp.pitch / 8 : D / VEC;   // chunks per row
     const int32_t dr = LG_GATHER_THREADS / C;          // row / chunk advance per 256-chunk step
     const int32_t dc = LG_GATHER_THREADS - dr * C;
     int32_t tile = blockIdx.x;
@@ -155,30 +170,35 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
     // row-source statistics: armed by the host (UnifiedCache::GatherStats) and switched by a DEVICE word, so that a launch
     // captured in a hipGraph follows the switch too (a pointer baked in at capture time kept counting through every replay)
     const bool counting = gp.stats != nullptr && gp.Kg > 1 && gp.stats[3] != 0ull;
+    // row x of a table: x * D floats, or x * pitch bf16 elements in
+    auto row_at = [&](const float* base, int64_t x) -> const LG_G float* {
+        if constexpr (BF16) return (const LG_G float*)(LG_GPTR(const uint16_t, (const uint16_t*)base) + x * gp.pitch);
+        else return LG_GPTR(const float, base) + x * D;
+    };
     // a row's source: FindFeat (cache.cu:180-215) + the address arithmetic of cache_impl.cuh:259-268
     auto source_of = [&](int32_t id, int32_t g) -> const LG_G float* {
         const LG_G float* p = nullptr;
         if (g < 0) {
             if (id >= 0 && gp.full_table != nullptr)     // :262-266 (the modulo only where it does anything)
-                p = LG_GPTR(const float, gp.full_table) + (int64_t)(id < gp.total_num_nodes ? id : id % gp.total_num_nodes) * D;
+                p = row_at(gp.full_table, (int64_t)(id < gp.total_num_nodes ? id : id % gp.total_num_nodes));
         } else if (gp.hybrid) {      // feat_cache_lookup, cache_impl.cuh:224-231: CPU cache below cpu_cap, this GPU's cache above
             if (g < gp.hybrid_cpu_cap)
-                p = LG_GPTR(const float, gp.hybrid_cpu_cache) + (int64_t)g * D;       // (g % cpu_cap == g)
+                p = row_at(gp.hybrid_cpu_cache, (int64_t)g);       // (g % cpu_cap == g)
             else
-                p = LG_GPTR(const float, gp.local_table) + (int64_t)((g - gp.hybrid_cpu_cap) % gp.hybrid_gpu_cap) * D;
+                p = row_at(gp.local_table, (int64_t)((g - gp.hybrid_cpu_cap) % gp.hybrid_gpu_cap));
         } else {
             int32_t didx = 0, fidx = g;                                                      // :259-260 (one division, and
             if (gp.striped) { didx = g / gp.node_capacity; fidx = g - didx * gp.node_capacity; }  // none without striping)
             const int64_t rank = (int64_t)fidx * gp.Kg + didx;                               // hotness rank of the row (cache_impl.cuh:104-109)
             const bool local_copy = gp.replica != nullptr && rank < gp.replica_rows;
             if (local_copy)      // the clique's hottest rows are also kept locally: same row, no xGMI hop
-                p = LG_GPTR(const float, gp.replica) + rank * gp.D;
+                p = row_at(gp.replica, rank);
             else if (didx == gp.member && gp.local_table != nullptr)     // own stripe: its address came with the launch
-                p = LG_GPTR(const float, gp.local_table) + (int64_t)fidx * gp.D;
+                p = row_at(gp.local_table, (int64_t)fidx);
             else if (gp.skip_remote)     // peer_gather = bulk: the owner pushes this row (bulk_push_kernel); nothing to fetch here
                 p = nullptr;
             else
-                p = LG_GPTR(const float, gp.cache_tables[didx]) + (int64_t)fidx * gp.D;                  // :268
+                p = row_at(gp.cache_tables[didx], (int64_t)fidx);                  // :268
             if (counting) {    // tests / diagnostics / the computed xGMI count: [0] rows read through a stripe pointer, [1] from the
                                // replica, [2] the part of [0] from a peer's stripe -- one atomic per wave and counter
                 const unsigned long long m_rep = __ballot(local_copy), m_str = __ballot(!local_copy);
@@ -252,8 +272,12 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
                 cc[u] = in ? c : C - 1;
                 const LG_G float* p = s_ptr[buf][rr[u]];
                 ok[u] = in && p != nullptr;
-                if (p == nullptr) p = dst_tile + (int64_t)rr[u] * D;     // id < 0: nothing to fetch; read what is there
-                v[u] = ((const LG_G VecT*)p)[cc[u]];   // plain loads: measured 74% of HBM peak vs 63% nontemporal
+                if constexpr (BF16) {
+                    v[u].w = p != nullptr ? ((const LG_G VecT*)p)[cc[u]].w : LG_GPTR(const VecT, &lg_gather_zero_line)->w;
+                } else {
+                    if (p == nullptr) p = dst_tile + (int64_t)rr[u] * D;     // id < 0: nothing to fetch; read what is there
+                    v[u] = ((const LG_G VecT*)p)[cc[u]];   // plain loads: measured 74% of HBM peak vs 63% nontemporal
+                }
                 q += LG_GATHER_THREADS;
                 r += dr;
                 c += dc;
@@ -261,8 +285,26 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; u++) {
-                if (ok[u])     // write-once output: nontemporal stores
-                    __builtin_nontemporal_store(v[u], (LG_G VecT*)(dst_tile + (int64_t)rr[u] * D) + cc[u]);
+                if constexpr (BF16) {
+                    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
+                    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+                    const u4 w = v[u].w;
+                    const u4 lo = w << 16, hi = w & 0xFFFF0000u;      // elements 2k, 2k+1 of the chunk
+                    const int32_t e0 = cc[u] * 8;
+                    LG_G float* d = dst_tile + (int64_t)rr[u] * D + e0;
+                    if (ok[u] && e0 + 8 <= D) {
+                        __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.x, hi.x, lo.y, hi.y}), (LG_G v4u*)d);
+                        __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.z, hi.z, lo.w, hi.w}), (LG_G v4u*)d + 1);
+                    } else if (ok[u]) {                               // the partial last chunk of a row: D - e0 < 8 elements
+                        const uint32_t f[8] = {lo.x, hi.x, lo.y, hi.y, lo.z, hi.z, lo.w, hi.w};
+#pragma unroll
+                        for (int k = 0; k < 8; k++)
+                            if (e0 + k < D) d[k] = __uint_as_float(f[k]);
+                    }
+                } else {
+                    if (ok[u])     // write-once output: nontemporal stores
+                        __builtin_nontemporal_store(v[u], (LG_G VecT*)(dst_tile + (int64_t)rr[u] * D) + cc[u]);
+                }
             }
         }
         if (TAIL) {            // the last D % VEC floats of every row
@@ -350,7 +392,8 @@ void launch_bulk_bucket(hipStream_t s, const GatherParams& g, const LanePtrs* d_
 // peer_gather = bulk, owner side: the rows a requester listed for THIS GPU's stripe, read from local HBM and written straight to
 // their destination rows in the requester's lane arena -- whole rows, 16-byte chunks, consecutive lanes on consecutive chunks:
 // over xGMI these are posted stores of contiguous 512-1024-byte runs instead of the requester's scattered load round trips.
-// The lists (12 bytes per row) are read through the requester's peer mapping.
+// The lists (12 bytes per row) are read through the requester's peer mapping.  float32 stripes only: a bf16 cache is refused together
+// with peer_gather = bulk where the transfer is set up (the arena's rows are float32; this copy does not widen).
 // ------------------------------------------------------------------------------------------
 __global__ __launch_bounds__(256) void bulk_push_kernel(const float* __restrict__ stripe, int32_t D, const int32_t* __restrict__ fidx,
                                                        const int64_t* __restrict__ dst, const unsigned long long* __restrict__ cnt,
@@ -396,6 +439,45 @@ static void launch_gather_v4(hipStream_t s, const GatherParams& g, int32_t grid_
     else gather_kernel<v4, ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
 }
 
+template <int ROWS>
+static void launch_gather_bf16_rows(hipStream_t s, const GatherParams& g, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
+                                    bool copy_range)
+{
+    const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
+    if (g.last_op) gather_kernel<Bf16x8, ROWS, LG_GATHER_UNROLL, false, true><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
+    else gather_kernel<Bf16x8, ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
+}
+
+// bf16 sources, every D (gk: what the kernel gets; grid_rows: what sizes the launch).  Tile size from the tile's SOURCE payload, the
+// rule of the float32 path applied to 2 P bytes per row: D = 128 (256-byte rows) and D = 100 (208) -> 64 rows, D = 256 -> 32,
+// D = 1024 -> 16; few tiles -> 16 rows.  Measured only against the float32 path at the headline shapes, not against other tile
+// sizes (profiles/r07/feature_dtype/: 0.66 of peak at D = 128, 0.47 at D = 100); LEGION_GATHER_ROWS overrides it, and
+// tools/feature_dtype_ab.py --rows R is the sweep still to run.
+static void launch_gather_bf16(hipStream_t s, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
+                               bool copy_range)
+{
+    if (gk.pitch < gk.D || gk.pitch % 8 != 0) {
+        printf("gather: bf16 rows need a pitch that is a multiple of 8 and at least D (pitch %d, D %d)\n", gk.pitch, gk.D);
+        exit(EXIT_FAILURE);
+    }
+    int rows = tuning().gather_rows_per_wg;
+    if (rows <= 0) {
+        rows = 16;
+        const int64_t row_bytes = (int64_t)gk.pitch * 2;
+        const int64_t payload = row_bytes >= 512 ? 16384 : 32768;
+        while (rows < 256 && (int64_t)rows * 2 * row_bytes <= payload + payload / 4) rows *= 2;
+        if ((int64_t)((grid_rows + rows - 1) / rows) * n_lanes < 4096) rows = 16;
+    }
+    switch (rows) {
+        case 16: launch_gather_bf16_rows<16>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 32: launch_gather_bf16_rows<32>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 128: launch_gather_bf16_rows<128>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 256: launch_gather_bf16_rows<256>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        default: launch_gather_bf16_rows<64>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+    }
+    hipCheckError();
+}
+
 static void launch_gather_impl(hipStream_t s, GatherParams g_in, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
 {
     if (g_in.D <= 0 || g_in.max_rows <= 0) return;      // :256 float_feature_len > 0
@@ -403,6 +485,11 @@ static void launch_gather_impl(hipStream_t s, GatherParams g_in, const LanePtrs*
     const GatherParams& gk = g_in;                      // what the kernel gets: max_rows = the clamp
     GatherParams g = g_in;                              // what sizes the launch: the rows a lane typically has (GatherParams.grid_rows)
     if (g.grid_rows > 0 && g.grid_rows < g.max_rows) g.max_rows = g.grid_rows;
+    if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
+    if (g.dtype != LEGION_FEATURE_F32) {
+        printf("gather: unknown feature dtype %d\n", g.dtype);
+        exit(EXIT_FAILURE);
+    }
     const dim3 grid(gather_grid_x(g.max_rows, LG_GATHER_ROWS, n_lanes), n_lanes);     // (the 4-byte vector path, and 64-row tiles at dword alignment)
     const LegionTuning& tune = tuning();
     if (g.D % 4 == 0) {

@@ -90,6 +90,12 @@
 #define LG_LDS_SLOTS_MEDIUM (1 << 22)
 // fewest super tiles (1024 slots) a partition tile of the 64- / 256-bucket classes may have (the launch picks up to
 // LG_PLACE_MAX_K, kernels_sample.hip); sizes run_off
+// feature row format (legion_hip.h LEGION_FEATURE_*): elements per stored row and its bytes
+static inline int32_t lg_feature_pitch(int32_t dtype, int32_t D) { return dtype == LEGION_FEATURE_BF16 ? (D + 7) & ~7 : D; }
+static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
+{
+    return dtype == LEGION_FEATURE_BF16 ? (int64_t)lg_feature_pitch(dtype, D) * 2 : (int64_t)D * 4;
+}
 static inline int32_t lg_lds_k_min(int32_t bucket_bits) { return bucket_bits == LG_LDS_BITS_LARGE ? 4 : 1; }
 #ifndef LG_LDS_TABLE_BITS
 #define LG_LDS_TABLE_BITS 13
@@ -179,6 +185,7 @@ struct BuildInfo {  // SS/include/buildinfo.h (only the fields of the in-memory 
     int32_t total_num_nodes = 0;
     int32_t float_feature_len = 0;
     float* host_float_feature = nullptr;   // device-dereferenceable (HBM or mapped pinned)
+    int32_t feature_dtype = LEGION_FEATURE_F32;   // row format of host_float_feature (LEGION_FEATURE_*)
     int64_t* csr_node_index = nullptr;     // device-dereferenceable
     int32_t* csr_dst_node_ids = nullptr;
     int64_t total_edge_num = 0;
@@ -414,6 +421,9 @@ public:
     virtual int32_t TotalNodeNum() const = 0;
     virtual float* GetAllFloatFeature() const = 0;
     virtual int32_t GetFloatFeatureLen() const = 0;
+    // row format of the table (LEGION_FEATURE_F32 | LEGION_FEATURE_BF16, legion_hip.h): with bf16 GetAllFloatFeature() is the
+    // address of N rows of lg_feature_pitch() bf16 elements, not floats.  Every tier built from the storage keeps its format.
+    virtual int32_t FeatureDtype() const { return LEGION_FEATURE_F32; }
     // SSD tier: unreleased in the reference (feature_storage.cu:146-154 are TODO stubs); kept as no-ops
     virtual void IOSubmit(int32_t*, int32_t*, int32_t*, float*, int32_t, int32_t, hipStream_t) {}
     virtual void IOComplete() {}
@@ -497,6 +507,12 @@ public:
     void SetReplicaMemory(int64_t bytes) { replica_bytes_ = bytes; }
     int32_t ReplicaRows(int32_t dev_id) const { return replica_rows_.empty() ? 0 : replica_rows_[dev_id]; }
     int32_t FloatFeatureLen() const { return float_feature_len_; }
+    // row format of every feature tier (stripes, replica, hybrid caches, the bound table): taken from the FeatureStorage the
+    // tiers are built from (CostModel, FillUpLocal, HybridInit, BindFeatureTable).  Lanes and trainer rows stay float32.
+    void AdoptFeatureFormat(const FeatureStorage* feature) { if (feature) feature_dtype_ = feature->FeatureDtype(); }
+    int32_t FeatureDtype() const { return feature_dtype_; }
+    int32_t RowPitch() const { return lg_feature_pitch(feature_dtype_, float_feature_len_); }       // elements per stored row
+    int64_t RowBytes() const { return lg_feature_row_bytes(feature_dtype_, float_feature_len_); }
     bool gather_stats_on_ = true;        // GatherStats() arms the counters; SetGatherStats pauses them (a device word: graphs follow)
     void SetGatherStats(bool on);
     unsigned long long* GatherStats(int32_t dev_id);   // device {stripe rows, replica rows, peer-stripe rows}, allocated on first use
@@ -518,6 +534,11 @@ public:
     // new / exposed for the C API and the fused kernels
     void SetCapacity(int32_t node_capacity, int32_t edge_capacity);
     void BindFeatureTable(float* table, int32_t total_num_nodes) { cpu_float_features_ = table; total_num_nodes_ = total_num_nodes; }
+    void BindFeatureTable(FeatureStorage* feature)
+    {
+        AdoptFeatureFormat(feature);
+        BindFeatureTable(feature->GetAllFloatFeature(), feature->TotalNodeNum());
+    }
     float* FeatureTable() const { return cpu_float_features_; }
     int32_t NodeCapacity(int32_t dev_id) const;
     int32_t EdgeCapacity(int32_t dev_id) const;
@@ -546,6 +567,7 @@ private:
     std::vector<float*> float_feature_cache_;
     std::vector<float**> d_float_feature_cache_ptr_;
     int32_t float_feature_len_ = 0;
+    int32_t feature_dtype_ = LEGION_FEATURE_F32;
     uint64_t uid_ = 0, fill_generation_ = 0;
     float* cpu_float_features_ = nullptr;
     bool is_presc_ = true;
@@ -766,6 +788,10 @@ struct GatherParams {
     bool hybrid;
     int32_t hybrid_cpu_cap, hybrid_gpu_cap;
     const float* hybrid_cpu_cache;
+    // row format of every source above (LEGION_FEATURE_*): bf16 sources are rows of `pitch` bf16 elements (pitch = D rounded up
+    // to 8, zero padded), read 16 bytes per lane and widened to the float32 output row (bits << 16, exact)
+    int32_t dtype;
+    int32_t pitch;
 };
 
 // Owner-bucketed bulk transfer of a striped gather (LegionTuning.peer_gather = bulk; SURVEY section 7 "hard parts", the
@@ -844,6 +870,12 @@ void build_column_slots(hipStream_t s, const int32_t* col, const int32_t* node_m
 void fill_value_i8(hipStream_t s, char* p, char v, int64_t n);
 void feat_fill_up(hipStream_t s, int32_t capacity, int32_t D, float* cache, const float* table,
                   const int32_t* QF, int32_t Kg, int32_t Ki, int32_t n);
+// the same fill for bf16 rows of `pitch` elements (pitch % 8 == 0: whole 16-byte chunks, padding included)
+void feat_fill_up_bf16(hipStream_t s, int32_t capacity, int32_t pitch, uint16_t* cache, const uint16_t* table,
+                       const int32_t* QF, int32_t Kg, int32_t Ki, int32_t n);
+// f32[rows x D] -> bf16[rows x pitch], round to nearest even, NaN kept a NaN, pad elements zero.  Both sides device-accessible
+// (HBM or mapped pinned host memory).
+void convert_f32_to_bf16(hipStream_t s, const float* src, int64_t rows, int32_t D, int32_t pitch, uint16_t* dst);
 void topo_neighbor_count(hipStream_t s, const int32_t* QT, int32_t Kg, int32_t Ki, int32_t capacity,
                          int32_t n, const int64_t* csr_index, int64_t* counts);
 void inclusive_scan_i64(hipStream_t s, const int64_t* in, int64_t* out, int32_t n);

@@ -338,6 +338,8 @@ extern "C" void legion_gather_rows(legion_stream_t stream, const float* full_tab
     g.hybrid_cpu_cache = nullptr;
     g.total_num_nodes = total_num_nodes;
     g.max_rows = max_rows;
+    g.dtype = LEGION_FEATURE_F32;
+    g.pitch = float_feature_len;
     lg::launch_gather_explicit(static_cast<hipStream_t>(stream), g, sampled_ids, cache_index_out, range_devptr, dst,
                                0x7FFFFFFF);
 }
@@ -361,7 +363,7 @@ static void enqueue_lanes(hipStream_t s, GraphStorage* graph, FeatureStorage* fe
         return;
     }
     if (cache && feature && cache->FeatureTable() == nullptr)
-        cache->BindFeatureTable(feature->GetAllFloatFeature(), feature->TotalNodeNum());
+        cache->BindFeatureTable(feature);
     // inside a whole-batch enqueue every gather reads the {offset, count} snapshot its producer left in
     // hop_scratch[HS_RANGE + 2h] (not overwritten by later hops), so the gathers may also run as a
     // phase of their own after the whole sampler (LG_PHASE_GATHER, on another stream: pipeline.hip)

@@ -542,6 +542,10 @@ extern "C" int32_t legion_pipeline_bulk_enable(LegionPipeline* p)
     if (!p || p->arena.base == nullptr) { printf("legion_hip: bulk transfers need a pipeline created with arena-backed lanes (use_graph bit 5)\n"); return 0; }
     if (p->slots_n > 4) { printf("legion_hip: at most 4 pipeline slots with bulk transfers\n"); return 0; }
     UnifiedCache* cache = reinterpret_cast<UnifiedCache*>(p->cache_handle);
+    if (cache->FeatureDtype() != LEGION_FEATURE_F32 || p->feature->FeatureDtype() != LEGION_FEATURE_F32) {
+        printf("legion_hip: peer_gather = bulk pushes float32 stripe rows only; a bf16 feature storage needs peer_gather = direct\n");
+        return 0;
+    }
     SetGPUDevice(p->dev_id);
     BulkState* b = new BulkState();
     b->Kg = cache->Kg_ > 0 ? cache->Kg_ : 1;

@@ -110,6 +110,66 @@ static Placement place_table(const std::string& path, size_t bytes, bool want_hb
     return pl;
 }
 
+// feature dtype of the tables the next server loads (legion_server_set_feature_dtype; sampling_server --feature-dtype)
+static int32_t g_feature_dtype = LEGION_FEATURE_F32;
+
+// The float32 `features` file (N x D) placed as bf16 rows of pitch P (legion_hip.h LEGION_FEATURE_BF16): N * P * 2 bytes in HBM
+// -- within the same budget as the other full tables -- or in mapped pinned host memory.  The file is read in slices of at most
+// 64 MiB into a mapped pinned staging buffer, from which the conversion kernel rounds each slice into the table: loading never
+// holds a second full copy of the table.  A missing file gives a zero table, as for float32.
+static Placement place_bf16_table(const std::string& path, int64_t N, int32_t D, bool want_hbm)
+{
+    Placement pl;
+    const int32_t P = lg_feature_pitch(LEGION_FEATURE_BF16, D);
+    const size_t bytes = (size_t)N * lg_feature_row_bytes(LEGION_FEATURE_BF16, D);
+    if (want_hbm) {
+        if (g_hbm_budget < 0) {
+            size_t free_b = 0, total_b = 0;
+            HIP_CALL(hipMemGetInfo(&free_b, &total_b));
+            g_hbm_budget = (int64_t)(free_b / 10 * 7);
+        }
+        if ((int64_t)bytes <= g_hbm_budget) {
+            g_hbm_budget -= (int64_t)bytes;
+            pl.dev_ptr = d_alloc_space((int64_t)(bytes ? bytes : 16));
+            pl.in_hbm = true;
+        }
+    }
+    if (!pl.in_hbm) {
+        void* host = nullptr;
+        pl.dev_ptr = legion_host_alloc((int64_t)(bytes ? bytes : 16), &host);
+    }
+    const bool present = file_size(path) >= 0;
+    if (!present || N == 0 || D == 0) {
+        HIP_CALL(hipMemset(pl.dev_ptr, 0, bytes ? bytes : 16));
+        return pl;
+    }
+    if (file_size(path) < (int64_t)N * D * 4) {
+        std::cout << "file too short: " << path << " holds " << file_size(path) << " bytes, meta_config implies " << (int64_t)N * D * 4 << "\n" << std::flush;
+        exit(EXIT_FAILURE);
+    }
+    const int64_t slice_rows = std::max<int64_t>(1, ((int64_t)64 << 20) / ((int64_t)D * 4));
+    void* stage_host = nullptr;
+    float* stage = (float*)legion_host_alloc(std::min<int64_t>(slice_rows, N) * D * 4, &stage_host);
+    int fd = open(path.c_str(), O_RDONLY);
+    if (fd == -1) { std::cout << "cannout open file: " << path << "\n"; exit(EXIT_FAILURE); }
+    for (int64_t r0 = 0; r0 < N; r0 += slice_rows) {
+        const int64_t rows = std::min<int64_t>(slice_rows, N - r0);
+        const size_t want = (size_t)rows * D * 4;
+        size_t done = 0;
+        while (done < want) {
+            const ssize_t r = pread(fd, (char*)stage_host + done, want - done, (off_t)(r0 * D * 4 + (int64_t)done));
+            if (r <= 0) break;
+            done += (size_t)r;
+        }
+        if (done < want) { std::cout << "short read: " << path << "\n" << std::flush; exit(EXIT_FAILURE); }
+        lg::convert_f32_to_bf16(nullptr, stage, rows, D, P, (uint16_t*)pl.dev_ptr + r0 * P);
+        HIP_CALL(hipDeviceSynchronize());      // (the staging buffer is refilled next)
+    }
+    close(fd);
+    legion_host_free(stage_host);
+    return pl;
+}
+
 class StorageManagement {
 public:
     // SS/storage/storage_management.cu:5-23
@@ -226,8 +286,10 @@ public:
         read_file_into(dataset_path_ + "testingset", testing_ids.data(), testing_ids.size() * 4);
         // v2 of the reference leaves features uninitialised and labels zero (:162,:164); this build
         // reads both files when they exist and zero-fills otherwise.
-        Placement fp = place_table(dataset_path_ + "features", (size_t)node_num_ * float_feature_len_ * sizeof(float),
-                                   want_hbm(), false);
+        Placement fp = g_feature_dtype == LEGION_FEATURE_BF16
+                           ? place_bf16_table(dataset_path_ + "features", node_num_, float_feature_len_, want_hbm())
+                           : place_table(dataset_path_ + "features", (size_t)node_num_ * float_feature_len_ * sizeof(float),
+                                         want_hbm(), false);
         if (file_size(dataset_path_ + "labels") >= 0)
             read_file_into(dataset_path_ + "labels", all_labels.data(), all_labels.size() * 4);
         const bool have_partition = file_size(dataset_path_ + "partition") >= (int64_t)node_num_ * 4;
@@ -264,9 +326,13 @@ public:
             info->testing_set_num.push_back((int32_t)info->testing_set_ids[p].size());
         }
         info->host_float_feature = (float*)fp.dev_ptr;
+        info->feature_dtype = g_feature_dtype;
         info->float_feature_len = float_feature_len_;
         info->total_num_nodes = node_num_;
         std::cout << "Feature placement:  " << (fp.in_hbm ? "HBM" : "pinned host") << "\n";
+        if (g_feature_dtype == LEGION_FEATURE_BF16)
+            std::cout << "Feature dtype: bf16 (" << lg_feature_row_bytes(g_feature_dtype, float_feature_len_) << " bytes per row, pitch "
+                      << lg_feature_pitch(g_feature_dtype, float_feature_len_) << "; float32 rows to the trainer)\n";
     }
 
     // SS/storage/storage_management.cu:234-269
@@ -275,6 +341,11 @@ public:
         BuildInfo* info = new BuildInfo();
         EnableP2PAccess();
         info->partition_count = partition_count;
+        if (g_feature_dtype != LEGION_FEATURE_F32 && lg::tuning().peer_gather == 1) {
+            std::cout << "LEGION_PEER_GATHER=bulk pushes float32 stripe rows only: it cannot serve a bf16 feature table "
+                         "(--feature-dtype bf16); use LEGION_PEER_GATHER=direct\n" << std::flush;
+            exit(EXIT_FAILURE);
+        }
         if (!ReadMetaFIle(info, in_memory_mode)) return false;
         SetGPUDevice(0);
         LoadGraph(info);
@@ -1161,6 +1232,13 @@ extern "C" void legion_server_initialize(LegionServer* s, int32_t global_shard_c
 extern "C" void legion_server_presc(LegionServer* s, int32_t cache_agg_mode) { reinterpret_cast<Server*>(s)->PreSc(cache_agg_mode); }
 extern "C" void legion_server_run(LegionServer* s) { reinterpret_cast<Server*>(s)->Run(); }
 extern "C" void legion_server_finalize(LegionServer* s) { reinterpret_cast<Server*>(s)->Finalize(); }
+
+extern "C" int32_t legion_server_set_feature_dtype(int32_t feature_dtype)
+{
+    if (feature_dtype != LEGION_FEATURE_F32 && feature_dtype != LEGION_FEATURE_BF16) return -1;
+    g_feature_dtype = feature_dtype;
+    return 0;
+}
 
 // sampling_server/sampling_server.cpp:7-15
 extern "C" int32_t legion_run(const int32_t* fanout, int32_t hop_num, int32_t gpu_number, int32_t in_memory_mode,

@@ -732,10 +732,17 @@ extern "C" GraphStorage* NewCompleteGraphStorage() { return new CompleteGraphSto
 // =============================================================================================
 class CompleteFeatureStorage : public FeatureStorage {
 public:
+    ~CompleteFeatureStorage() override
+    {
+        if (owned_host_ != nullptr) legion_host_free(owned_host_);
+        else if (owned_dev_ != nullptr) d_free_space(owned_dev_);
+    }
+
     void Build(BuildInfo* info, int /*in_memory_mode*/) override
     {
         Configure(info->partition_count, info->total_num_nodes, info->float_feature_len,
                   info->host_float_feature);
+        dtype_ = info->feature_dtype;
         for (int32_t p = 0; p < partition_count_; p++) {
             if (p < (int32_t)info->training_set_ids.size())
                 SetIds(p, TRAINMODE, info->training_set_ids[p].data(), info->training_labels[p].data(),
@@ -803,10 +810,33 @@ public:
     int32_t TotalNodeNum() const override { return total_num_nodes_; }
     float* GetAllFloatFeature() const override { return float_feature_; }
     int32_t GetFloatFeatureLen() const override { return float_feature_len_; }
+    int32_t FeatureDtype() const override { return dtype_; }
+
+    // a bf16 copy of the float32 table `src` that this storage owns (legion_feature_create_ex): HBM, or mapped pinned host memory
+    // under LEGION_TABLE_PLACEMENT=pinned; converted in place, so there is never a second float32 copy
+    void ConvertTable(const float* src)
+    {
+        dtype_ = LEGION_FEATURE_BF16;
+        const int32_t P = lg_feature_pitch(dtype_, float_feature_len_);
+        const int64_t bytes = (int64_t)total_num_nodes_ * lg_feature_row_bytes(dtype_, float_feature_len_);
+        lg::tuning_refresh();             // (LEGION_TABLE_PLACEMENT as it is now)
+        if (lg::tuning().table_placement == 1) owned_dev_ = legion_host_alloc(bytes, &owned_host_);
+        else owned_dev_ = d_alloc_space(bytes > 0 ? bytes : 16);
+        if (src != nullptr) {
+            lg::convert_f32_to_bf16(nullptr, src, total_num_nodes_, float_feature_len_, P, (uint16_t*)owned_dev_);
+            HIP_CALL(hipDeviceSynchronize());
+        } else {
+            HIP_CALL(hipMemset(owned_dev_, 0, bytes > 0 ? (size_t)bytes : 16));
+        }
+        float_feature_ = (float*)owned_dev_;
+    }
 
 private:
     int32_t partition_count_ = 0, total_num_nodes_ = 0, float_feature_len_ = 0;
     float* float_feature_ = nullptr;
+    int32_t dtype_ = LEGION_FEATURE_F32;
+    void* owned_dev_ = nullptr;       // the bf16 table ConvertTable made (device-side address), and its host side when pinned
+    void* owned_host_ = nullptr;
     std::vector<int32_t*> ids_[3], labels_[3];
     std::vector<int32_t> size_[3];
 };
@@ -1077,6 +1107,44 @@ extern "C" LegionFeatureStorage* legion_feature_create(int32_t partition_count, 
     CompleteFeatureStorage* f = new CompleteFeatureStorage();
     f->Configure(partition_count, total_num_nodes, float_feature_len, const_cast<float*>(all_float_feature));
     return reinterpret_cast<LegionFeatureStorage*>(static_cast<FeatureStorage*>(f));
+}
+
+extern "C" LegionFeatureStorage* legion_feature_create_ex(int32_t partition_count, int32_t total_num_nodes, int32_t float_feature_len,
+                                                          int32_t feature_dtype, const float* all_float_feature)
+{
+    if (feature_dtype == LEGION_FEATURE_F32)
+        return legion_feature_create(partition_count, total_num_nodes, float_feature_len, all_float_feature);
+    if (feature_dtype != LEGION_FEATURE_BF16) {
+        printf("legion_feature_create_ex: unknown feature dtype %d\n", feature_dtype);
+        return nullptr;
+    }
+    CompleteFeatureStorage* f = new CompleteFeatureStorage();
+    f->Configure(partition_count, total_num_nodes, float_feature_len, nullptr);
+    f->ConvertTable(all_float_feature);
+    return reinterpret_cast<LegionFeatureStorage*>(static_cast<FeatureStorage*>(f));
+}
+
+extern "C" int32_t legion_feature_dtype(const LegionFeatureStorage* f_)
+{
+    const FeatureStorage* f = reinterpret_cast<const FeatureStorage*>(f_);
+    return f ? f->FeatureDtype() : LEGION_FEATURE_F32;
+}
+
+extern "C" int64_t legion_feature_row_bytes(const LegionFeatureStorage* f_)
+{
+    const FeatureStorage* f = reinterpret_cast<const FeatureStorage*>(f_);
+    return f ? lg_feature_row_bytes(f->FeatureDtype(), f->GetFloatFeatureLen()) : 0;
+}
+
+extern "C" const void* legion_feature_table(const LegionFeatureStorage* f_)
+{
+    const FeatureStorage* f = reinterpret_cast<const FeatureStorage*>(f_);
+    return f ? f->GetAllFloatFeature() : nullptr;
+}
+
+extern "C" void legion_convert_f32_to_bf16(legion_stream_t stream, const float* src, int64_t rows, int32_t D, uint16_t* dst)
+{
+    lg::convert_f32_to_bf16(static_cast<hipStream_t>(stream), src, rows, D, lg_feature_pitch(LEGION_FEATURE_BF16, D), dst);
 }
 
 extern "C" void legion_feature_set_ids(LegionFeatureStorage* f_, int32_t dev_id, int32_t mode,

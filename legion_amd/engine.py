@@ -192,11 +192,34 @@ class GraphStorage:
             self.handle = None
 
 
-class FeatureStorage:
-    """Full feature table (device tensor float32[N, D], HBM or mapped pinned) + per-GPU seed sets."""
+# feature_dtype of FeatureStorage -> legion_hip.h LEGION_FEATURE_*
+FEATURE_DTYPES = {"float32": 0, "bfloat16": 1}
 
-    def __init__(self, partition_count, features, total_num_nodes=None, float_feature_len=None):
+
+def bf16_pitch(D):
+    """Elements of a stored bf16 row: D rounded up to 8 (16-byte rows, zero padded)."""
+    return (int(D) + 7) // 8 * 8
+
+
+def convert_f32_to_bf16(src):
+    """float32[N, D] device tensor -> int16[N, round_up(D, 8)] device tensor of bf16 bit patterns (the library's conversion)."""
+    assert src.dtype == torch.float32 and src.is_contiguous() and src.dim() == 2 and src.is_cuda
+    N, D = src.shape
+    out = torch.empty((N, bf16_pitch(D)), dtype=torch.int16, device=src.device)
+    _libmod.load().legion_convert_f32_to_bf16(None, _ptr(src), int(N), int(D), _ptr(out))
+    return out
+
+
+class FeatureStorage:
+    """Full feature table + per-GPU seed sets.  feature_dtype="float32" (default): the device tensor float32[N, D] (HBM or mapped
+    pinned) is used in place.  feature_dtype="bfloat16": the library keeps a bf16 copy of it (rows of round_up(D, 8) elements,
+    round to nearest even) and every cache tier built from this storage holds bf16 rows; gathered rows are float32 as before."""
+
+    def __init__(self, partition_count, features, total_num_nodes=None, float_feature_len=None, feature_dtype="float32"):
         self._lib = _libmod.load()
+        if feature_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"feature_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_dtype!r}")
+        self.feature_dtype = feature_dtype
         self.features = features
         if features is not None:
             assert features.dtype == torch.float32 and features.is_contiguous()
@@ -205,9 +228,20 @@ class FeatureStorage:
         self.total_num_nodes = int(total_num_nodes)
         self.float_feature_len = int(float_feature_len)
         self.partition_count = int(partition_count)
-        self.handle = self._lib.legion_feature_create(self.partition_count, self.total_num_nodes,
-                                                      self.float_feature_len, _ptr(features))
+        if feature_dtype == "float32":
+            self.handle = self._lib.legion_feature_create(self.partition_count, self.total_num_nodes,
+                                                          self.float_feature_len, _ptr(features))
+        else:
+            self.handle = self._lib.legion_feature_create_ex(self.partition_count, self.total_num_nodes, self.float_feature_len,
+                                                             FEATURE_DTYPES[feature_dtype], _ptr(features))
+            if not self.handle:
+                raise RuntimeError(f"legion_feature_create_ex failed for {feature_dtype}")
+            self.features = None        # the library owns its converted table; the caller's float32 tensor is not referenced
         self.set_sizes = {}
+
+    @property
+    def row_bytes(self):
+        return int(self._lib.legion_feature_row_bytes(self.handle))
 
     def set_ids(self, dev_id, mode, ids, labels=None):
         ids = np.ascontiguousarray(ids, dtype=np.int32)

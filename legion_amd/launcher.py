@@ -103,9 +103,18 @@ def Run(args):
     # The reference ignores the binary's status (legion_server.py:110).  Here it is returned as a process exit
     # code: subprocess.call gives the exit status itself (os.system's raw wait status, e.g. 256 for exit(1),
     # would wrap to 0 in sys.exit), and a death by signal n becomes 128 + n like a shell reports it.
-    rc = subprocess.call([server_binary(), str(gpu_number), str(int(cache_agg_mode))] +
-                         [str(f) for f in parse_fanout(args.fanout)])
+    rc = subprocess.call(server_argv(gpu_number, cache_agg_mode, args))
     return 128 - rc if rc < 0 else rc
+
+
+# --feature_dtype -> the binary's --feature-dtype value; float32 (the default) adds nothing to its command line
+FEATURE_DTYPES = {"float32": None, "bfloat16": "bf16"}
+
+
+def server_argv(gpu_number, cache_agg_mode, args):
+    argv = [server_binary(), str(gpu_number), str(int(cache_agg_mode))] + [str(f) for f in parse_fanout(args.fanout)]
+    flag = FEATURE_DTYPES[getattr(args, "feature_dtype", "float32")]
+    return argv + (["--feature-dtype", flag] if flag else [])
 
 
 def parse_fanout(value):
@@ -126,6 +135,8 @@ def build_argparser():
     argparser.add_argument('--epoch', type=int, default=2)
     argparser.add_argument('--cache_memory', type=int, default=38000000)
     argparser.add_argument('--usenvlink', type=int, default=1)
+    # storage format of the feature table and caches; the trainer receives float32 rows either way
+    argparser.add_argument('--feature_dtype', type=str, default="float32", choices=sorted(FEATURE_DTYPES))
     return argparser
 
 

@@ -34,6 +34,11 @@ SIGNATURES = {
     "legion_feature_create": (c_p, [c_i32, c_i32, c_i32, c_p]),
     "legion_feature_set_ids": (None, [c_p, c_i32, c_i32, c_p, c_p, c_i32]),
     "legion_feature_destroy": (None, [c_p]),
+    "legion_feature_create_ex": (c_p, [c_i32, c_i32, c_i32, c_i32, c_p]),
+    "legion_feature_dtype": (c_i32, [c_p]),
+    "legion_feature_row_bytes": (c_i64, [c_p]),
+    "legion_feature_table": (c_p, [c_p]),
+    "legion_convert_f32_to_bf16": (None, [c_p, c_p, c_i64, c_i32, c_p]),
     "legion_pool_create": (c_p, [c_i32, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32]),
     "legion_pool_alloc_features": (None, [c_p, c_i64]),
     "legion_pool_set_current_pipe": (None, [c_p, c_i32]),
@@ -83,6 +88,7 @@ SIGNATURES = {
     "legion_server_run": (None, [c_p]),
     "legion_server_finalize": (None, [c_p]),
     "legion_run": (c_i32, [P_I32, c_i32, c_i32, c_i32, c_i32]),
+    "legion_server_set_feature_dtype": (c_i32, [c_i32]),
     "NewIPCEnv": (c_p, [c_i32]),
     "legion_ipc_coordinate": (None, [c_p, c_i32, P_I32, P_I32, P_I32, c_i32, c_i32]),
     "legion_ipc_train_step": (c_i32, [c_p]),
