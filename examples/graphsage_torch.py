@@ -58,6 +58,15 @@ class SAGE(nn.Module):                       # legion_graphsage.py:36-64
         return h
 
 
+def forward(model, blocks, feats):
+    """bfloat16 rows (a server started with --feature-out-dtype bf16) run the forward pass under bf16 autocast; float32 rows
+    run it as they are."""
+    if feats.dtype == torch.bfloat16:
+        with torch.autocast("cuda", dtype=torch.bfloat16):
+            return model(blocks, feats)
+    return model(blocks, feats)
+
+
 def next_batch(ipc_service, feat_len, hops):
     out = ipc_service.get_next(feat_len)               # [ids, feats, labels, (src, dst) for h = H .. 1]
     sizes = ipc_service.get_block_size()               # [n_src, n_dst for h = H .. 1]
@@ -95,7 +104,7 @@ def main():
         with torch.no_grad():
             for _ in range(steps):
                 feats, labels, blocks = next_batch(ipc_service, a.features_num, a.hops_num)
-                pred = model(blocks, feats).argmax(dim=1)
+                pred = forward(model, blocks, feats).argmax(dim=1)
                 hit += int((pred == labels.long()).sum())
                 tot += int(labels.numel())
                 del feats, labels, blocks
@@ -108,7 +117,7 @@ def main():
         loss_sum = 0.0
         for _ in range(train_steps):
             feats, labels, blocks = next_batch(ipc_service, a.features_num, a.hops_num)
-            loss = F.cross_entropy(model(blocks, feats), labels.long())
+            loss = F.cross_entropy(forward(model, blocks, feats).float(), labels.long())
             opt.zero_grad()
             loss.backward()
             opt.step()

@@ -129,6 +129,12 @@ LegionMemoryPool* legion_pool_create(int32_t dev_id, int32_t total_num_nodes, in
                                      int32_t pipeline_depth);
 /* SS/engine/server.cu:275-283: rows = int(1.2 * MaxIdNum) in the reference; caller passes rows. */
 void legion_pool_alloc_features(LegionMemoryPool* p, int64_t rows);
+/* Feature output dtype (LEGION_FEATURE_*): the dtype of the rows the pool's gathers write, independent of the storage dtype.
+ * LEGION_FEATURE_BF16: float_features is a contiguous bf16[rows x D] (stride D, no pad); each row is the bf16 of the float32 row
+ * (round to nearest even, NaN kept a quiet NaN), or a bf16 storage's stored bits verbatim.  Call before
+ * legion_pool_alloc_features: returns 0, or -1 after it (nothing changes), for an unknown dtype or a null pool. */
+int32_t legion_pool_set_feature_out_dtype(LegionMemoryPool* p, int32_t dtype);
+int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p);
 void legion_pool_set_current_pipe(LegionMemoryPool* p, int32_t pipe);
 void legion_pool_set_mode_iter(LegionMemoryPool* p, int32_t mode, int32_t iter);
 int32_t legion_pool_num_ids(const LegionMemoryPool* p);
@@ -265,6 +271,9 @@ int32_t legion_run(const int32_t* fanout, int32_t hop_num, int32_t gpu_number, i
 /* Feature dtype (LEGION_FEATURE_*) of the tables the NEXT legion_server_initialize / legion_run loads: the float32 `features`
  * file is converted while it is placed.  Returns 0, or -1 for an unknown dtype (nothing changes). */
 int32_t legion_server_set_feature_dtype(int32_t feature_dtype);
+/* Feature output dtype (LEGION_FEATURE_*) of the rows the NEXT legion_server_initialize / legion_run hands to its trainers
+ * (published in the shared segment's extension, version 4).  Returns 0, or -1 for an unknown dtype (nothing changes). */
+int32_t legion_server_set_feature_out_dtype(int32_t feature_out_dtype);
 
 LegionIPCEnv* NewIPCEnv(int32_t device_count);
 /* step arithmetic, SS/engine/ipc_service.cu:60-132,213-253 (host only, no GPU needed) */
@@ -307,6 +316,13 @@ LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, LegionFeatureS
                                        LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
                                        const int32_t* fanout, int32_t hop_num, int32_t group_size,
                                        int32_t slots, int64_t feature_rows, int32_t use_graph);
+/* the same with the lanes' feature output dtype (legion_pool_set_feature_out_dtype); legion_pipeline_create is
+ * feature_out_dtype = LEGION_FEATURE_F32.  Returns NULL for an unknown dtype.  bf16 output refuses peer_gather = bulk
+ * (legion_pipeline_bulk_enable returns 0). */
+LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                          LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
+                                          const int32_t* fanout, int32_t hop_num, int32_t group_size,
+                                          int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype);
 /* enqueues batches counter0 .. counter0 + group_size - 1; returns the slot */
 int32_t legion_pipeline_submit(LegionPipeline* p, int32_t counter0, int32_t mode);
 /* only the first n_active lanes work (tail of a run that is not a multiple of group_size) */

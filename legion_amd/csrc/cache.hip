@@ -685,11 +685,12 @@ unsigned long long int* UnifiedCache::GetEdgeAccessedMap(int32_t dev_id)
 // SS/cache/cache.cu:726-748 -- lookup (FindFeat) fused into the gather
 void UnifiedCache::FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id,
                                    hipStream_t strm_hdl, int32_t max_rows, bool use_snapshot, int32_t first_op_id, bool last_op,
-                                   bool skip_remote, int32_t grid_rows)
+                                   bool skip_remote, int32_t grid_rows, int32_t out_dtype)
 {
     lg::GatherParams g = GatherParamsOf(dev_id, op_id, max_rows, use_snapshot, first_op_id, last_op);
     g.skip_remote = skip_remote;
     g.grid_rows = grid_rows;
+    g.out_dtype = out_dtype;
     lg::launch_gather(strm_hdl, g, d_lanes, n_lanes);
 }
 
@@ -750,6 +751,7 @@ lg::GatherParams UnifiedCache::GatherParamsOf(int32_t dev_id, int32_t op_id, int
     }
     g.dtype = feature_dtype_;
     g.pitch = RowPitch();
+    g.out_dtype = LEGION_FEATURE_F32;
     return g;
 }
 

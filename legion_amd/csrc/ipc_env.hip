@@ -71,8 +71,11 @@ typedef struct shmExt_st {
     int64_t arena_chunk_bytes[MAX_DEVICE];
     int32_t arena_sock_pid;
     int32_t ext_reserved2;
+    // version 4: dtype of the feature rows of each server GPU's batches (LEGION_FEATURE_*; 1 = bf16[n x D]), in the pipe slots and
+    // in the views alike.  A trainer end that reads an older version takes float32 rows.
+    int32_t feature_out_dtype[MAX_DEVICE];
 } shmExt;
-#define LEGION_SHM_EXT_VERSION 3
+#define LEGION_SHM_EXT_VERSION 4
 
 typedef struct sharedMemoryInfo_st {
     void* addr;
@@ -247,7 +250,7 @@ public:
         (void)batch_size;
         SetGPUDevice(device_id);
         for (int32_t i = 0; i < pipeline_depth; i++) {
-            void* new_features = lg_alloc_exported((int64_t)num_ids * feature_dim * sizeof(float),
+            void* new_features = lg_alloc_exported((int64_t)num_ids * feature_dim * lg_feature_out_bytes(feature_out_dtype),
                                                    (void*)&shm_->memHandle[device_id][i][1], __FILE__, __LINE__);
             float_features_[device_id].push_back(new_features);
         }
@@ -303,6 +306,7 @@ public:
     void PublishMirror() override
     {
         if (!ext_dev_) return;
+        for (int32_t d = 0; d < MAX_DEVICE; d++) ext_->feature_out_dtype[d] = feature_out_dtype;
         ext_->ext_version = LEGION_SHM_EXT_VERSION;
         __sync_synchronize();
         ext_->ext_magic = LEGION_SHM_EXT_MAGIC;

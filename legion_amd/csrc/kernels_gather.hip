@@ -20,7 +20,8 @@
 // and write consecutive 16 B of the (contiguous) destination.  No divides in the copy loop.
 //
 // Roofline: HBM.  Algorithmic bytes per row = 8*D + 8 (D*4 read + D*4 written + id + index); with bf16 sources
-// (GatherParams.dtype, the Bf16x8 instances) 2*P + 4*D + 8, P = D rounded up to 8.
+// (GatherParams.dtype, the Bf16x8 instances) 2*P + 4*D + 8, P = D rounded up to 8; with bf16 output rows
+// (GatherParams.out_dtype) 2*P + 2*D + 8 from bf16 sources (Bf16Copy), 6*D + 8 from float32 ones (F32Narrow).
 #include "legion_core.h"
 
 #include <cstdlib>
@@ -117,6 +118,32 @@ struct Bf16x8 {
     u4 w;
 };
 __device__ __attribute__((aligned(16))) Bf16x8 lg_gather_zero_line;
+// bf16 OUTPUT rows (GatherParams.out_dtype = LEGION_FEATURE_BF16): D bf16 elements per row, stride D, no pad.  A chunk is 8
+// elements, 16 bytes of output.  Bf16Copy: bf16 source of pitch P, the stored bits copied verbatim (16-byte load, 16-byte
+// store).  F32Narrow: float32 source of D floats, two dword-aligned 16-byte loads narrowed with bf16_rne_bits (the integer
+// path of convert_f32_to_bf16_kernel, not v_cvt_pk_bf16_f32) -- a row's partial last chunk loads only its D % 8 floats, as
+// the row may be the table's last.  Output rows are 2*D bytes: with D even a full chunk is one dword-aligned 16-byte store
+// (16-byte aligned when D % 8 == 0), a partial one stores its dwords one by one; with D odd rows are only 2-byte aligned and
+// every element is stored on its own (correct, not fast).  A missing row loads the zero line and stores nothing.
+struct Bf16Copy {
+    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
+    u4 w;
+};
+struct F32Narrow {
+    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
+    v4u a, b;
+};
+template <typename VecT> struct GatherFormat {
+    static constexpr bool SRC_BF16 = std::is_same<VecT, Bf16x8>::value || std::is_same<VecT, Bf16Copy>::value;
+    static constexpr bool OUT_BF16 = std::is_same<VecT, Bf16Copy>::value || std::is_same<VecT, F32Narrow>::value;
+};
+// torch's float32 -> bfloat16 rounding (kernels_cache.hip bf16_rne_bits: round to nearest even, NaNs kept quiet NaNs)
+__device__ __forceinline__ uint32_t gather_bf16_rne(float f)
+{
+    const uint32_t u = __float_as_uint(f);
+    if ((u & 0x7FFFFFFFu) > 0x7F800000u) return (u >> 16) | 0x40u;
+    return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
+}
 
 // LASTOP: the gather of a batch's last op (the dominant launch; traces and counters tell it from the early hops' gathers by
 // name) -- the only one that can carry a hand-over to a trainer-visible pipe slot.
@@ -124,9 +151,10 @@ template <typename VecT, int ROWS = LG_GATHER_ROWS, int UNROLL = LG_GATHER_UNROL
 __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather_kernel(GatherParams gp, const LanePtrs* __restrict__ lanes,
                                                                    bool copy_range)
 {
-    constexpr bool BF16 = std::is_same<VecT, Bf16x8>::value;
+    constexpr bool BF16 = GatherFormat<VecT>::SRC_BF16;       // bf16 source rows
+    constexpr bool OUT16 = GatherFormat<VecT>::OUT_BF16;      // bf16 output rows
     constexpr int VEC = sizeof(VecT) / sizeof(float);
-    static_assert(!BF16 || !TAIL, "bf16 rows end in a partial chunk, not a tail pass");
+    static_assert(!(BF16 || OUT16) || !TAIL, "bf16 rows end in a partial chunk, not a tail pass");
     static_assert(ROWS <= LG_GATHER_THREADS, "one resolving thread per row of a tile");
     __shared__ const LG_G float* s_ptr[2][ROWS];
 
@@ -161,7 +189,7 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
         deliver_slice(L, *static_cast<const DeliverParams*>(L.deliver), blockIdx.x, step);
     const int32_t tid = threadIdx.x;
     const int32_t D = gp.D;
-    const int32_t C = BF16 ? gp.pitch / 8 : D / VEC;   // chunks per row
+    const int32_t C = BF16 ? gp.pitch / 8 : OUT16 ? (D + 7) / 8 : D / VEC;   // chunks per row
     const int32_t dr = LG_GATHER_THREADS / C;          // row / chunk advance per 256-chunk step
     const int32_t dc = LG_GATHER_THREADS - dr * C;
     int32_t tile = blockIdx.x;
@@ -258,6 +286,7 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
 
         const int32_t nchunks = nr * C;
         LG_G float* dst_tile = LG_GPTR(float, L.float_features) + (int64_t)(off + r0) * D;
+        LG_G uint16_t* dst16 = LG_GPTR(uint16_t, (uint16_t*)L.float_features) + (int64_t)(off + r0) * D;     // (bf16 output)
         int32_t q = tid;
         int32_t r = q / C;
         int32_t c = q - r * C;
@@ -272,8 +301,23 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
                 cc[u] = in ? c : C - 1;
                 const LG_G float* p = s_ptr[buf][rr[u]];
                 ok[u] = in && p != nullptr;
-                if constexpr (BF16) {
-                    v[u].w = p != nullptr ? ((const LG_G VecT*)p)[cc[u]].w : LG_GPTR(const VecT, &lg_gather_zero_line)->w;
+                if constexpr (std::is_same<VecT, F32Narrow>::value) {
+                    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
+                    const int32_t e0 = cc[u] * 8;
+                    if (p == nullptr) {
+                        v[u].a = v[u].b = v4u{0.f, 0.f, 0.f, 0.f};
+                    } else if (e0 + 8 <= D) {
+                        v[u].a = ((const LG_G v4u*)(p + e0))[0];
+                        v[u].b = ((const LG_G v4u*)(p + e0))[1];
+                    } else {                                          // the partial last chunk: no load past the row's end
+                        float f[8];
+#pragma unroll
+                        for (int k = 0; k < 8; k++) f[k] = e0 + k < D ? p[e0 + k] : 0.f;
+                        v[u].a = v4u{f[0], f[1], f[2], f[3]};
+                        v[u].b = v4u{f[4], f[5], f[6], f[7]};
+                    }
+                } else if constexpr (BF16) {
+                    v[u].w = p != nullptr ? ((const LG_G VecT*)p)[cc[u]].w : LG_GPTR(const Bf16x8, &lg_gather_zero_line)->w;
                 } else {
                     if (p == nullptr) p = dst_tile + (int64_t)rr[u] * D;     // id < 0: nothing to fetch; read what is there
                     v[u] = ((const LG_G VecT*)p)[cc[u]];   // plain loads: measured 74% of HBM peak vs 63% nontemporal
@@ -285,7 +329,33 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
             }
 #pragma unroll
             for (int u = 0; u < UNROLL; u++) {
-                if constexpr (BF16) {
+                if constexpr (OUT16) {
+                    typedef uint32_t u4u __attribute__((ext_vector_type(4), aligned(4)));
+                    uint32_t w[4];                                    // elements 2k (low half) and 2k+1 (high half) of the chunk
+                    if constexpr (BF16) {
+                        w[0] = v[u].w.x; w[1] = v[u].w.y; w[2] = v[u].w.z; w[3] = v[u].w.w;
+                    } else {
+                        w[0] = gather_bf16_rne(v[u].a.x) | (gather_bf16_rne(v[u].a.y) << 16);
+                        w[1] = gather_bf16_rne(v[u].a.z) | (gather_bf16_rne(v[u].a.w) << 16);
+                        w[2] = gather_bf16_rne(v[u].b.x) | (gather_bf16_rne(v[u].b.y) << 16);
+                        w[3] = gather_bf16_rne(v[u].b.z) | (gather_bf16_rne(v[u].b.w) << 16);
+                    }
+                    const int32_t e0 = cc[u] * 8;
+                    LG_G uint16_t* d = dst16 + (int64_t)rr[u] * D + e0;
+                    if (ok[u] && (D & 1) == 0) {                      // dword-aligned rows
+                        if (e0 + 8 <= D) {
+                            __builtin_nontemporal_store(u4u{w[0], w[1], w[2], w[3]}, (LG_G u4u*)d);
+                        } else {
+#pragma unroll
+                            for (int k = 0; k < 4; k++)
+                                if (e0 + 2 * k < D) ((LG_G uint32_t*)d)[k] = w[k];
+                        }
+                    } else if (ok[u]) {                               // odd D: 2-byte aligned rows
+#pragma unroll
+                        for (int k = 0; k < 8; k++)
+                            if (e0 + k < D) d[k] = (uint16_t)(w[k >> 1] >> ((k & 1) * 16));
+                    }
+                } else if constexpr (BF16) {
                     typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
                     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
                     const u4 w = v[u].w;
@@ -439,41 +509,45 @@ static void launch_gather_v4(hipStream_t s, const GatherParams& g, int32_t grid_
     else gather_kernel<v4, ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
 }
 
-template <int ROWS>
+template <typename VecT, int ROWS>
 static void launch_gather_bf16_rows(hipStream_t s, const GatherParams& g, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
                                     bool copy_range)
 {
+    // F32Narrow loads 32 bytes per chunk: half the chunks in flight per lane keep the bytes in flight of the others, and its
+    // registers within the 8-wave budget
+    constexpr int UNROLL = std::is_same<VecT, F32Narrow>::value ? LG_GATHER_UNROLL / 2 : LG_GATHER_UNROLL;
     const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
-    if (g.last_op) gather_kernel<Bf16x8, ROWS, LG_GATHER_UNROLL, false, true><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
-    else gather_kernel<Bf16x8, ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
+    if (g.last_op) gather_kernel<VecT, ROWS, UNROLL, false, true><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
+    else gather_kernel<VecT, ROWS, UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
 }
 
-// bf16 sources, every D (gk: what the kernel gets; grid_rows: what sizes the launch).  Tile size from the tile's SOURCE payload, the
-// rule of the float32 path applied to 2 P bytes per row: D = 128 (256-byte rows) and D = 100 (208) -> 64 rows, D = 256 -> 32,
-// D = 1024 -> 16; few tiles -> 16 rows.  Measured only against the float32 path at the headline shapes, not against other tile
-// sizes (profiles/r07/feature_dtype/: 0.66 of peak at D = 128, 0.47 at D = 100); LEGION_GATHER_ROWS overrides it, and
-// tools/feature_dtype_ab.py --rows R is the sweep still to run.
+// bf16 sources or bf16 output rows, every D (gk: what the kernel gets; grid_rows: what sizes the launch).  Tile size from the tile's
+// SOURCE payload, the rule of the float32 path applied to the source row's bytes (2 P for bf16 storage, 4 D for float32): D = 128
+// (256-byte bf16 rows) and D = 100 (208) -> 64 rows, D = 256 -> 32, D = 1024 -> 16; few tiles -> 16 rows.  Measured only against
+// the float32 path at the headline shapes, not against other tile sizes (profiles/r07/feature_dtype/: 0.66 of peak at D = 128,
+// 0.47 at D = 100); LEGION_GATHER_ROWS overrides it, and tools/feature_dtype_ab.py --rows R is the sweep still to run.
+template <typename VecT>
 static void launch_gather_bf16(hipStream_t s, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
                                bool copy_range)
 {
-    if (gk.pitch < gk.D || gk.pitch % 8 != 0) {
+    if (GatherFormat<VecT>::SRC_BF16 && (gk.pitch < gk.D || gk.pitch % 8 != 0)) {
         printf("gather: bf16 rows need a pitch that is a multiple of 8 and at least D (pitch %d, D %d)\n", gk.pitch, gk.D);
         exit(EXIT_FAILURE);
     }
     int rows = tuning().gather_rows_per_wg;
     if (rows <= 0) {
         rows = 16;
-        const int64_t row_bytes = (int64_t)gk.pitch * 2;
+        const int64_t row_bytes = GatherFormat<VecT>::SRC_BF16 ? (int64_t)gk.pitch * 2 : (int64_t)gk.D * 4;
         const int64_t payload = row_bytes >= 512 ? 16384 : 32768;
         while (rows < 256 && (int64_t)rows * 2 * row_bytes <= payload + payload / 4) rows *= 2;
         if ((int64_t)((grid_rows + rows - 1) / rows) * n_lanes < 4096) rows = 16;
     }
     switch (rows) {
-        case 16: launch_gather_bf16_rows<16>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 32: launch_gather_bf16_rows<32>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 128: launch_gather_bf16_rows<128>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 256: launch_gather_bf16_rows<256>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        default: launch_gather_bf16_rows<64>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 16: launch_gather_bf16_rows<VecT, 16>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 32: launch_gather_bf16_rows<VecT, 32>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 128: launch_gather_bf16_rows<VecT, 128>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case 256: launch_gather_bf16_rows<VecT, 256>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        default: launch_gather_bf16_rows<VecT, 64>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
     }
     hipCheckError();
 }
@@ -485,11 +559,15 @@ static void launch_gather_impl(hipStream_t s, GatherParams g_in, const LanePtrs*
     const GatherParams& gk = g_in;                      // what the kernel gets: max_rows = the clamp
     GatherParams g = g_in;                              // what sizes the launch: the rows a lane typically has (GatherParams.grid_rows)
     if (g.grid_rows > 0 && g.grid_rows < g.max_rows) g.max_rows = g.grid_rows;
-    if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
-    if (g.dtype != LEGION_FEATURE_F32) {
-        printf("gather: unknown feature dtype %d\n", g.dtype);
+    if ((g.dtype != LEGION_FEATURE_F32 && g.dtype != LEGION_FEATURE_BF16) || (g.out_dtype != LEGION_FEATURE_F32 && g.out_dtype != LEGION_FEATURE_BF16)) {
+        printf("gather: unknown feature dtype %d or output dtype %d\n", g.dtype, g.out_dtype);
         exit(EXIT_FAILURE);
     }
+    if (g.out_dtype == LEGION_FEATURE_BF16) {
+        if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16<Bf16Copy>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
+        return launch_gather_bf16<F32Narrow>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
+    }
+    if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16<Bf16x8>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
     const dim3 grid(gather_grid_x(g.max_rows, LG_GATHER_ROWS, n_lanes), n_lanes);     // (the 4-byte vector path, and 64-row tiles at dword alignment)
     const LegionTuning& tune = tuning();
     if (g.D % 4 == 0) {

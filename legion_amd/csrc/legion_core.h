@@ -96,6 +96,8 @@ static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
 {
     return dtype == LEGION_FEATURE_BF16 ? (int64_t)lg_feature_pitch(dtype, D) * 2 : (int64_t)D * 4;
 }
+// bytes of one element of a row handed to the caller (a pool's feature output dtype, LEGION_FEATURE_*)
+static inline int64_t lg_feature_out_bytes(int32_t out_dtype) { return out_dtype == LEGION_FEATURE_BF16 ? 2 : 4; }
 static inline int32_t lg_lds_k_min(int32_t bucket_bits) { return bucket_bits == LG_LDS_BITS_LARGE ? 4 : 1; }
 #ifndef LG_LDS_TABLE_BITS
 #define LG_LDS_TABLE_BITS 13
@@ -322,6 +324,10 @@ public:
     int32_t batch_size = 0;
     int32_t float_feature_len = 0;
     int64_t feature_rows = 0;
+    // dtype of the rows gathered into the feature buffer (LEGION_FEATURE_*): bf16 = rows of D bf16 elements.  Fixed by the first
+    // legion_pool_alloc_features (features_allocated); the buffer's element size follows it, its capacity in rows does not
+    int32_t feature_out_dtype = LEGION_FEATURE_F32;
+    bool features_allocated = false;
     int64_t grid_rows_hint = 0;        // > 0: rows a batch typically has (the Runner's pipe-slot pool holds the worst case: launches are sized for the usual one)
     int32_t dev_id = 0;
     bool owns_buffers = false;
@@ -523,7 +529,7 @@ public:
     // first_op_id < op_id: one launch also covers the new-node ranges of the earlier ops first_op_id, +3, ...
     void FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id,
                          hipStream_t strm_hdl, int32_t max_rows, bool use_snapshot, int32_t first_op_id = -1, bool last_op = true,
-                         bool skip_remote = false, int32_t grid_rows = 0);
+                         bool skip_remote = false, int32_t grid_rows = 0, int32_t out_dtype = LEGION_FEATURE_F32);
     // peer_gather = bulk (lg::BulkLists): the requester's bucket pass over every row of its group's batches, and the owner's push
     void BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id, hipStream_t s, int32_t max_rows,
                     const lg::BulkLists& lists, const char* arena_base);
@@ -587,6 +593,9 @@ private:
 class IPCEnv {  // SS/engine/ipc_service.h:6-33
 public:
     virtual ~IPCEnv() = default;
+    // dtype of the rows handed to the trainers (LEGION_FEATURE_*): sizes the pipe-slot feature buffers and is published to the
+    // trainer end (set before InitializeFeaturesBuffer)
+    int32_t feature_out_dtype = LEGION_FEATURE_F32;
     virtual void Coordinate(BuildInfo* info) = 0;
     virtual int32_t GetMaxStep() = 0;
     virtual void InitializeSamplesBuffer(int32_t batch_size, int32_t num_ids, int32_t feature_dim,
@@ -707,7 +716,8 @@ struct PoolArena {
 };
 void lg_set_pool_arena(PoolArena* arena);
 PoolArena* lg_get_pool_arena();
-int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len);
+int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len,
+                            int32_t feature_out_dtype = LEGION_FEATURE_F32);
 
 // alloc helpers, SS/engine/server_imp.cuh:2-51
 extern "C" void* d_alloc_space(int64_t num_bytes);
@@ -792,6 +802,9 @@ struct GatherParams {
     // to 8, zero padded), read 16 bytes per lane and widened to the float32 output row (bits << 16, exact)
     int32_t dtype;
     int32_t pitch;
+    // row format of the destination (LEGION_FEATURE_*, the pool's feature output dtype): bf16 output rows are D bf16 elements,
+    // stride D, no pad -- bf16 sources copied verbatim, float32 ones rounded to nearest even
+    int32_t out_dtype;
 };
 
 // Owner-bucketed bulk transfer of a striped gather (LegionTuning.peer_gather = bulk; SURVEY section 7 "hard parts", the

@@ -5,6 +5,8 @@
 // --disk = Run()'s in_memory_mode 0: meta_config carries fifteen fields and the caches are the hybrid CPU-cache / GPU-cache tier
 // --feature-dtype bf16: the feature table and every cache tier hold bfloat16 rows (legion_hip.h LEGION_FEATURE_BF16); the
 // trainer still receives float32 rows.  --feature-dtype f32 is the default.
+// --feature-out-dtype bf16: the trainer receives bfloat16 rows (legion_server_set_feature_out_dtype), whatever the storage dtype;
+// --feature-out-dtype f32 is the default.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -15,7 +17,7 @@
 int main(int argc, char** argv)
 {
     if (argc < 3) {
-        std::printf("usage: %s <gpu_number> <cache_agg_mode> [fanout ...] [--disk] [--feature-dtype f32|bf16]\n", argv[0]);
+        std::printf("usage: %s <gpu_number> <cache_agg_mode> [fanout ...] [--disk] [--feature-dtype f32|bf16] [--feature-out-dtype f32|bf16]\n", argv[0]);
         return 2;
     }
     std::vector<int32_t> fanout;
@@ -27,6 +29,13 @@ int main(int argc, char** argv)
             const int32_t dtype = std::strcmp(v, "bf16") == 0 ? LEGION_FEATURE_BF16 : std::strcmp(v, "f32") == 0 ? LEGION_FEATURE_F32 : -1;
             if (legion_server_set_feature_dtype(dtype) != 0) {
                 std::printf("--feature-dtype: expected f32 or bf16, got '%s'\n", v);
+                return 2;
+            }
+        } else if (std::strcmp(argv[i], "--feature-out-dtype") == 0) {
+            const char* v = i + 1 < argc ? argv[++i] : "";
+            const int32_t dtype = std::strcmp(v, "bf16") == 0 ? LEGION_FEATURE_BF16 : std::strcmp(v, "f32") == 0 ? LEGION_FEATURE_F32 : -1;
+            if (legion_server_set_feature_out_dtype(dtype) != 0) {
+                std::printf("--feature-out-dtype: expected f32 or bf16, got '%s'\n", v);
                 return 2;
             }
         } else fanout.push_back(std::atoi(argv[i]));

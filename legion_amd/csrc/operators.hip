@@ -156,7 +156,8 @@ static void do_feature_lookup(hipStream_t s, UnifiedCache* cache, const LanePtrs
     const bool prof = pp->prof_on && (size_t)(2 * pp->prof_used + 1) < pp->prof_events.size();
     if (prof) HIP_CALL(hipEventRecord(pp->prof_events[2 * pp->prof_used], s));
     cache->FeatCacheLookup(d_lanes, n_lanes, op_id, dev_id, s, (int32_t)max_rows, use_snapshot, first_op_id,
-                           hop + 1 >= pool0->max_new.size(), false, (int32_t)std::min<int64_t>(pool0->grid_rows_hint, max_rows));
+                           hop + 1 >= pool0->max_new.size(), false, (int32_t)std::min<int64_t>(pool0->grid_rows_hint, max_rows),
+                           pool0->feature_out_dtype);
     if (prof) {
         HIP_CALL(hipEventRecord(pp->prof_events[2 * pp->prof_used + 1], s));
         pp->prof_op[pp->prof_used] = op_id;
@@ -340,6 +341,7 @@ extern "C" void legion_gather_rows(legion_stream_t stream, const float* full_tab
     g.max_rows = max_rows;
     g.dtype = LEGION_FEATURE_F32;
     g.pitch = float_feature_len;
+    g.out_dtype = LEGION_FEATURE_F32;
     lg::launch_gather_explicit(static_cast<hipStream_t>(stream), g, sampled_ids, cache_index_out, range_devptr, dst,
                                0x7FFFFFFF);
 }

@@ -111,15 +111,21 @@ struct LegionPipeline {
     void* priv_arena = nullptr;               // the block of shuffled chunks the lanes' private arrays were carved from (arena pipelines)
     bool arena_borrowed = false;              // the arena belongs to the caller (legion_pipeline_bulk_enable_shared)
     int64_t feature_rows = 0;
+    int32_t feature_out_dtype = LEGION_FEATURE_F32;      // of every lane (legion_pool_set_feature_out_dtype)
 };
 
-extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                                  LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
-                                                  const int32_t* fanout, int32_t hop_num, int32_t group_size,
-                                                  int32_t slots, int64_t feature_rows, int32_t use_graph)
+extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                                     LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
+                                                     const int32_t* fanout, int32_t hop_num, int32_t group_size,
+                                                     int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype)
 {
     if (!graph || !feature || !cache) { printf("invalid storage ptr\n"); return nullptr; }
+    if (feature_out_dtype != LEGION_FEATURE_F32 && feature_out_dtype != LEGION_FEATURE_BF16) {
+        printf("legion_hip: unknown feature output dtype %d\n", feature_out_dtype);
+        return nullptr;
+    }
     LegionPipeline* p = new LegionPipeline();
+    p->feature_out_dtype = feature_out_dtype;
     p->graph = reinterpret_cast<GraphStorage*>(graph);
     p->feature = reinterpret_cast<FeatureStorage*>(feature);
     p->cache_handle = cache;
@@ -152,7 +158,7 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
         const int32_t D = p->feature->GetFloatFeatureLen();
         int64_t num_ids = batch_size, per = batch_size;
         for (int32_t h = 0; h < hop_num; h++) { per *= fanout[h]; num_ids += per; }
-        p->arena.bytes = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, D) * p->group_size * p->slots_n;
+        p->arena.bytes = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, D, feature_out_dtype) * p->group_size * p->slots_n;
         // The arena is built from shuffled physical chunks (storage.hip d_alloc_scattered; LegionTuning.arena_scatter_mb = 0: one plain
         // allocation).  use_graph bit 6: it must be reachable from another process or GPU (peer_gather = bulk: owners push rows into
         // it) -- then its chunks are created exportable, other GPUs of this process are granted access when they are linked
@@ -177,13 +183,14 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
         lg_set_pool_arena(nullptr);
         lg_alloc_count_begin();
         LegionMemoryPool* probe = legion_pool_create(dev_id, p->feature->TotalNodeNum(), batch_size, fanout, hop_num, p->feature->GetFloatFeatureLen(), 1);
+        legion_pool_set_feature_out_dtype(probe, feature_out_dtype);
         if (feature_rows > 0) legion_pool_alloc_features(probe, feature_rows);
         const int64_t asked = lg_alloc_count_end();
         legion_pool_destroy(probe);
         lg_set_pool_arena(trainer_arena);
         int64_t num_ids = batch_size, per = batch_size;
         for (int32_t h = 0; h < hop_num; h++) { per *= fanout[h]; num_ids += per; }
-        const int64_t visible = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, p->feature->GetFloatFeatureLen());
+        const int64_t visible = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, p->feature->GetFloatFeatureLen(), feature_out_dtype);
         const int64_t lane = std::max<int64_t>(asked - visible, 0) + (64 << 10);
         p->priv_arena = lg_private_arena_begin(lane * p->group_size * p->slots_n + ((int64_t)8 << 20), lg::tuning().arena_scatter_mb);
     }
@@ -192,6 +199,7 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
         for (int32_t g = 0; g < p->group_size; g++) {
             LegionMemoryPool* h = legion_pool_create(dev_id, p->feature->TotalNodeNum(), batch_size, fanout, hop_num,
                                                      p->feature->GetFloatFeatureLen(), 1);
+            legion_pool_set_feature_out_dtype(h, feature_out_dtype);
             if (feature_rows > 0) legion_pool_alloc_features(h, feature_rows);
             handles.push_back(h);
             sl.pools.push_back(reinterpret_cast<MemoryPool*>(h));
@@ -213,6 +221,15 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
     lg_set_pool_arena(nullptr);
     if (p->priv_arena) lg_private_arena_end();
     return p;
+}
+
+extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                                  LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
+                                                  const int32_t* fanout, int32_t hop_num, int32_t group_size,
+                                                  int32_t slots, int64_t feature_rows, int32_t use_graph)
+{
+    return legion_pipeline_create_ex(graph, feature, cache, dev_id, batch_size, fanout, hop_num, group_size, slots, feature_rows,
+                                     use_graph, LEGION_FEATURE_F32);
 }
 
 static void slot_wait(LegionPipeline* p, Slot& sl)
@@ -546,6 +563,10 @@ extern "C" int32_t legion_pipeline_bulk_enable(LegionPipeline* p)
         printf("legion_hip: peer_gather = bulk pushes float32 stripe rows only; a bf16 feature storage needs peer_gather = direct\n");
         return 0;
     }
+    if (p->feature_out_dtype != LEGION_FEATURE_F32) {
+        printf("legion_hip: peer_gather = bulk pushes float32 rows only; bf16 feature output needs peer_gather = direct\n");
+        return 0;
+    }
     SetGPUDevice(p->dev_id);
     BulkState* b = new BulkState();
     b->Kg = cache->Kg_ > 0 ? cache->Kg_ : 1;
@@ -721,10 +742,10 @@ extern "C" int32_t legion_pipeline_bulk_phase_a(LegionPipeline* p, int32_t count
     // the gathers in the op order of a whole-batch enqueue (operators.hip enqueue_lanes: the seeds ride along with hop 1 when a
     // later gather follows), each skipping the rows of other members' stripes
     const bool seeds_ride = p->hop_num >= 2;
-    if (!seeds_ride) cache->FeatCacheLookup(d_lanes, n_active, 1, p->dev_id, X, max_rows, true, -1, p->hop_num == 0, true);
+    if (!seeds_ride) cache->FeatCacheLookup(d_lanes, n_active, 1, p->dev_id, X, max_rows, true, -1, p->hop_num == 0, true, 0, p->feature_out_dtype);
     for (int32_t h = 0; h < p->hop_num; h++)
         cache->FeatCacheLookup(d_lanes, n_active, INTRABATCH_CON * (h + 1) + 1, p->dev_id, X, max_rows, true, (h == 0 && seeds_ride) ? 1 : -1,
-                               h + 1 == p->hop_num, /*skip_remote=*/true);
+                               h + 1 == p->hop_num, /*skip_remote=*/true, 0, p->feature_out_dtype);
     HIP_CALL(hipStreamSynchronize(X));
     sl.next_iter = -1;
     p->last_slot = si;

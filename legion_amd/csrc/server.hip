@@ -112,6 +112,8 @@ static Placement place_table(const std::string& path, size_t bytes, bool want_hb
 
 // feature dtype of the tables the next server loads (legion_server_set_feature_dtype; sampling_server --feature-dtype)
 static int32_t g_feature_dtype = LEGION_FEATURE_F32;
+// dtype of the rows the next server hands to its trainers (legion_server_set_feature_out_dtype; sampling_server --feature-out-dtype)
+static int32_t g_feature_out_dtype = LEGION_FEATURE_F32;
 
 // The float32 `features` file (N x D) placed as bf16 rows of pitch P (legion_hip.h LEGION_FEATURE_BF16): N * P * 2 bytes in HBM
 // -- within the same budget as the other full tables -- or in mapped pinned host memory.  The file is read in slices of at most
@@ -332,7 +334,11 @@ public:
         std::cout << "Feature placement:  " << (fp.in_hbm ? "HBM" : "pinned host") << "\n";
         if (g_feature_dtype == LEGION_FEATURE_BF16)
             std::cout << "Feature dtype: bf16 (" << lg_feature_row_bytes(g_feature_dtype, float_feature_len_) << " bytes per row, pitch "
-                      << lg_feature_pitch(g_feature_dtype, float_feature_len_) << "; float32 rows to the trainer)\n";
+                      << lg_feature_pitch(g_feature_dtype, float_feature_len_) << "; "
+                      << (g_feature_out_dtype == LEGION_FEATURE_BF16 ? "bf16" : "float32") << " rows to the trainer)\n";
+        if (g_feature_out_dtype == LEGION_FEATURE_BF16)
+            std::cout << "Feature output dtype: bf16 (trainers receive bfloat16 rows; a trainer end built from the reference's sources "
+                         "cannot read them)\n";
     }
 
     // SS/storage/storage_management.cu:234-269
@@ -341,6 +347,11 @@ public:
         BuildInfo* info = new BuildInfo();
         EnableP2PAccess();
         info->partition_count = partition_count;
+        if (g_feature_out_dtype != LEGION_FEATURE_F32 && lg::tuning().peer_gather == 1) {
+            std::cout << "LEGION_PEER_GATHER=bulk pushes float32 rows only: it cannot hand bf16 rows to the trainer "
+                         "(--feature-out-dtype bf16); use LEGION_PEER_GATHER=direct\n" << std::flush;
+            exit(EXIT_FAILURE);
+        }
         if (g_feature_dtype != LEGION_FEATURE_F32 && lg::tuning().peer_gather == 1) {
             std::cout << "LEGION_PEER_GATHER=bulk pushes float32 stripe rows only: it cannot serve a bf16 feature table "
                          "(--feature-dtype bf16); use LEGION_PEER_GATHER=direct\n" << std::flush;
@@ -387,10 +398,10 @@ private:
 
 // =============================================================================================
 struct LegionPipeline;
-extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                                  LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
-                                                  const int32_t* fanout, int32_t hop_num, int32_t group_size,
-                                                  int32_t slots, int64_t feature_rows, int32_t use_graph);
+extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                                     LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
+                                                     const int32_t* fanout, int32_t hop_num, int32_t group_size,
+                                                     int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype);
 extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
 extern "C" void legion_pipeline_prepare(LegionPipeline* p, int32_t mode, int32_t n_active, int32_t batch_size);
 extern "C" legion_stream_t legion_pipeline_stream(LegionPipeline* p);
@@ -444,6 +455,7 @@ public:
         cache->InitializeCacheController(local_dev_id_, total_num_nodes);
 
         memorypool_ = new MemoryPool(interbatch_concurrency_);
+        memorypool_->feature_out_dtype = g_feature_out_dtype;
         float_feature_len_ = feature->GetFloatFeatureLen();
         lg_pool_alloc_private(memorypool_, local_dev_id_, total_num_nodes, batch_size, fanout.data(), hop_num,
                               float_feature_len_);
@@ -506,9 +518,16 @@ public:
         {
             size_t free_b = 0, total_b = 0;
             HIP_CALL(hipMemGetInfo(&free_b, &total_b));
-            const int64_t worst_bytes = (int64_t)memorypool_->num_ids * float_feature_len_ * (int64_t)sizeof(float);
+            const int64_t worst_bytes = (int64_t)memorypool_->num_ids * float_feature_len_ * lg_feature_out_bytes(g_feature_out_dtype);
             if (lg::tuning().runner_overflow != 0 && (int64_t)interbatch_concurrency_ * worst_bytes <= (int64_t)(free_b / 10)) slot_rows = memorypool_->num_ids;
         }
+        if (g_feature_out_dtype != LEGION_FEATURE_F32 && (!use_groups_ || env->GetCounterMirror(local_dev_id_, 0) == nullptr)) {
+            // the dtype reaches the trainer end through the shared extension (shmExt version 4), published by the lane-group path only
+            std::cout << "bf16 feature output needs the lane-group runner (LEGION_RUNNER_GRAPH) and the shared counter mirror "
+                         "(LEGION_SHM_MIRROR)\n" << std::flush;
+            exit(EXIT_FAILURE);
+        }
+        env->feature_out_dtype = g_feature_out_dtype;
         env->InitializeFeaturesBuffer(0, (int32_t)slot_rows, float_feature_len_, local_dev_id_, interbatch_concurrency_);
         for (int i = 0; i < interbatch_concurrency_; i++)
             memorypool_->SetFloatFeatures(env->GetFloatFeatures(local_dev_id_, i), i);
@@ -624,7 +643,8 @@ public:
             if (float_feature_len_ > 0 && batch_rows > lane_feature_rows_ && overflow_[p] != nullptr) {
                 UnifiedCache* cache = (UnifiedCache*)(params->cache);
                 const LanePtrs* desc = d_overflow_desc_ + ((size_t)p * slots_ + g.slot) * lanes_ + lane;
-                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, overflow_stream_, memorypool_->num_ids, true, 1);
+                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, overflow_stream_, memorypool_->num_ids, true, 1,
+                                       true, false, 0, memorypool_->feature_out_dtype);
                 HIP_CALL(hipStreamSynchronize(overflow_stream_));
                 off[1] = (char*)overflow_[p] - arena_.base;
                 if (lp->err_host != nullptr) *(volatile int32_t*)lp->err_host &= ~LG_ERR_FEATURE_ROWS;      // this batch is whole again; the lane's next batch starts clean
@@ -644,7 +664,8 @@ public:
             const LanePtrs* desc = d_desc_ + ((size_t)p * slots_ + g.slot) * lanes_ + lane;     // lane -> pipe slot p
             UnifiedCache* cache = (UnifiedCache*)(params->cache);
             if (float_feature_len_ > 0 && max_rows > 0)   // one launch: gather of every row of the batch + the hand-over copies
-                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, s, (int32_t)max_rows, true, 1, true, false, lane_rule_rows_);
+                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, s, (int32_t)max_rows, true, 1, true, false, lane_rule_rows_,
+                                       memorypool_->feature_out_dtype);
             else
                 lg::launch_deliver(s, desc, deliver_[p]);
             HIP_CALL(hipEventRecord(batch_done_[p], s));
@@ -818,7 +839,8 @@ private:
         lanes_ = std::min(lanes_, LargestGroup(env, lanes_));
         const bool lane_features = handover_ != 1 && float_feature_len_ > 0;        // forced `gather`: rows never land in a lane
         lane_features_ = lane_features;
-        const int64_t arena_lane = lg_pool_arena_bytes(memorypool_->batch_size, memorypool_->num_ids, lane_features ? feature_rows : 0, float_feature_len_);
+        const int64_t arena_lane = lg_pool_arena_bytes(memorypool_->batch_size, memorypool_->num_ids, lane_features ? feature_rows : 0, float_feature_len_,
+                                                       g_feature_out_dtype);
         const int64_t lane_bytes = arena_lane + (int64_t)memorypool_->num_ids * 40 + (int64_t)memorypool_->max_slots * 28;
         size_t free_b = 0, total_b = 0;
         HIP_CALL(hipMemGetInfo(&free_b, &total_b));
@@ -830,7 +852,7 @@ private:
         // stops the server as before)
         int64_t overflow_bytes = 0;
         if (lane_features && handover_ == 0 && feature_rows < memorypool_->num_ids && tune.runner_overflow != 0) {
-            overflow_bytes = (((int64_t)memorypool_->num_ids * float_feature_len_ * (int64_t)sizeof(float)) + 4095) & ~(int64_t)4095;
+            overflow_bytes = (((int64_t)memorypool_->num_ids * float_feature_len_ * lg_feature_out_bytes(g_feature_out_dtype)) + 4095) & ~(int64_t)4095;
             if (interbatch_concurrency_ * overflow_bytes > (int64_t)(free_b / 10) || (int64_t)lanes_ * slots_ * lane_bytes + interbatch_concurrency_ * overflow_bytes > (int64_t)(free_b / 10 * 7))
                 overflow_bytes = 0;
         }
@@ -851,9 +873,10 @@ private:
         HIP_CALL(hipHostGetDevicePointer((void**)&arena_.mirror_dev, arena_.mirror_host, 0));
         lg_set_pool_arena(&arena_);
         // use_graph bits: 1 graph replay, 16 weave (the next group's head on a second stream under this group's heavy kernels)
-        pipe_ = legion_pipeline_create((LegionGraphStorage*)params->graph, (LegionFeatureStorage*)params->feature,
-                                       (LegionUnifiedCache*)params->cache, local_dev_id_, memorypool_->batch_size,
-                                       fanout.data(), hop_num_, lanes_, slots_, lane_features ? feature_rows : 0, 1 | 16);
+        pipe_ = legion_pipeline_create_ex((LegionGraphStorage*)params->graph, (LegionFeatureStorage*)params->feature,
+                                          (LegionUnifiedCache*)params->cache, local_dev_id_, memorypool_->batch_size,
+                                          fanout.data(), hop_num_, lanes_, slots_, lane_features ? feature_rows : 0, 1 | 16,
+                                          g_feature_out_dtype);
         lg_set_pool_arena(nullptr);
         for (int pp = 0; pp < interbatch_concurrency_ && pp < INTERBATCH_CON; pp++)
             overflow_[pp] = overflow_bytes > 0 ? (float*)(arena_.base + arena_.bytes - (int64_t)(interbatch_concurrency_ - pp) * overflow_bytes) : nullptr;
@@ -1237,6 +1260,13 @@ extern "C" int32_t legion_server_set_feature_dtype(int32_t feature_dtype)
 {
     if (feature_dtype != LEGION_FEATURE_F32 && feature_dtype != LEGION_FEATURE_BF16) return -1;
     g_feature_dtype = feature_dtype;
+    return 0;
+}
+
+extern "C" int32_t legion_server_set_feature_out_dtype(int32_t feature_out_dtype)
+{
+    if (feature_out_dtype != LEGION_FEATURE_F32 && feature_out_dtype != LEGION_FEATURE_BF16) return -1;
+    g_feature_out_dtype = feature_out_dtype;
     return 0;
 }
 

@@ -1169,10 +1169,10 @@ static thread_local PoolArena* g_pool_arena = nullptr;
 void lg_set_pool_arena(PoolArena* arena) { g_pool_arena = arena; }
 PoolArena* lg_get_pool_arena() { return g_pool_arena; }
 static inline int64_t arena_round(int64_t b) { return (b + 255) & ~(int64_t)255; }
-int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len)
+int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len, int32_t feature_out_dtype)
 {
     return 3 * arena_round(num_ids * 4) + arena_round(batch_size * 4) + 2 * arena_round(64) +
-           arena_round(feature_rows * float_feature_len * 4);
+           arena_round(feature_rows * float_feature_len * lg_feature_out_bytes(feature_out_dtype));
 }
 static void* arena_take(int64_t bytes)
 {
@@ -1225,18 +1225,35 @@ extern "C" void legion_pool_alloc_features(LegionMemoryPool* p_, int64_t rows)
     if (!mp) { printf("invalid memorypool ptr\n"); return; }
     SetGPUDevice(mp->dev_id);
     const int32_t cur = mp->GetCurrentPipe();
+    const int64_t row_bytes = (int64_t)mp->float_feature_len * lg_feature_out_bytes(mp->feature_out_dtype);
+    mp->features_allocated = true;
     for (int i = 0; i < mp->PipelineDepth(); i++) {
         mp->SetCurrentPipe(i);
         if (mp->arena_backed) {           // (once per pool: the arena is sized for exactly one feature buffer per lane)
             if (g_pool_arena == nullptr) { printf("legion_hip: arena-backed pool without its arena\n"); exit(EXIT_FAILURE); }
-            mp->SetFloatFeatures((float*)arena_take(rows * (int64_t)mp->float_feature_len * sizeof(float)), i);
+            mp->SetFloatFeatures((float*)arena_take(rows * row_bytes), i);
             continue;
         }
         d_free_space(mp->GetFloatFeatures());
-        mp->SetFloatFeatures((float*)d_alloc_space(rows * (int64_t)mp->float_feature_len * sizeof(float)), i);
+        mp->SetFloatFeatures((float*)d_alloc_space(rows * row_bytes), i);
     }
     mp->SetCurrentPipe(cur);
     mp->feature_rows = rows;
+}
+
+// dtype of the rows the pool's gathers write (LEGION_FEATURE_*); only before the pool's first legion_pool_alloc_features
+extern "C" int32_t legion_pool_set_feature_out_dtype(LegionMemoryPool* p_, int32_t dtype)
+{
+    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
+    if (!mp || (dtype != LEGION_FEATURE_F32 && dtype != LEGION_FEATURE_BF16) || mp->features_allocated) return -1;
+    mp->feature_out_dtype = dtype;
+    return 0;
+}
+
+extern "C" int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p_)
+{
+    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
+    return mp ? mp->feature_out_dtype : -1;
 }
 
 extern "C" void legion_pool_set_current_pipe(LegionMemoryPool* p_, int32_t pipe)

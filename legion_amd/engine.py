@@ -23,7 +23,7 @@ TRAINMODE, VALIDMODE, TESTMODE = 0, 1, 2
 CACHEMISS_FLAG = -2
 
 _TYPESTR = {torch.int32: "<i4", torch.int64: "<i8", torch.float32: "<f4", torch.int8: "|i1",
-            torch.uint8: "|u1"}
+            torch.uint8: "|u1", torch.int16: "<i2"}
 
 
 class _RawDevice:
@@ -40,6 +40,8 @@ def device_view(ptr, shape, dtype, device):
         n *= int(s)
     if not ptr or n == 0:
         return torch.empty(tuple(shape), dtype=dtype, device=device)
+    if dtype == torch.bfloat16:      # (no typestr for bfloat16 in the array interface: its bits as int16)
+        return torch.as_tensor(_RawDevice(ptr, shape, torch.int16), device=device).view(torch.bfloat16)
     return torch.as_tensor(_RawDevice(ptr, shape, dtype), device=device)
 
 
@@ -266,7 +268,11 @@ class MemoryPool:
             "cache_search_buffer": (9, torch.int32), "tmp_part_ind": (10, torch.int8),
             "tmp_part_off": (11, torch.int32), "position_map": (12, torch.int32), "node_slot": (13, torch.int32)}
 
-    def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1):
+    def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1, feature_out_dtype="float32"):
+        """feature_out_dtype: dtype of the rows the pool's gathers write ("float32" or "bfloat16": bf16[rows, D], the float32 row
+        rounded to nearest even, or a bf16 storage's rows verbatim), independent of the FeatureStorage's dtype."""
+        if feature_out_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         self._lib = _libmod.load()
         self.dev_id = int(dev_id)
         self.device = _torch_device(self.dev_id)
@@ -279,6 +285,7 @@ class MemoryPool:
                                                    _i32_array(self.fanout), len(self.fanout),
                                                    self.float_feature_len, int(pipeline_depth))
         self.num_ids = int(self._lib.legion_pool_num_ids(self.handle))
+        self.set_feature_out_dtype(feature_out_dtype)
 
     @classmethod
     def _borrowed(cls, handle, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, feature_rows):
@@ -295,6 +302,17 @@ class MemoryPool:
         self._borrowed_handle = True
         return self
 
+    @property
+    def feature_out_dtype(self):
+        return {v: k for k, v in FEATURE_DTYPES.items()}[int(self._lib.legion_pool_feature_out_dtype(self.handle))]
+
+    def set_feature_out_dtype(self, dtype):
+        """Only before alloc_features (the C ABI refuses it after: RuntimeError)."""
+        if dtype not in FEATURE_DTYPES:
+            raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {dtype!r}")
+        if self._lib.legion_pool_set_feature_out_dtype(self.handle, FEATURE_DTYPES[dtype]) != 0:
+            raise RuntimeError("legion_pool_set_feature_out_dtype: the feature buffer is already allocated")
+
     def alloc_features(self, rows):
         self.feature_rows = int(rows)
         self._lib.legion_pool_alloc_features(self.handle, self.feature_rows)
@@ -304,6 +322,8 @@ class MemoryPool:
 
     def buffer(self, name):
         which, dtype = self._BUF[name]
+        if name == "float_features" and self.feature_out_dtype == "bfloat16":
+            dtype = torch.bfloat16
         ptr = self._lib.legion_pool_buffer(self.handle, which)
         if name in ("node_counter", "edge_counter"):
             shape = (16,)
@@ -390,15 +410,19 @@ class Pipeline:
     process are granted access at bulk_link, other processes map them from file descriptors at bulk_import ("plain": the old name)."""
 
     def __init__(self, graph, feature, cache, dev_id, batch_size, fanout, group_size, feature_rows, use_graph=True,
-                 slots=2, overlap=False, split=False, weave=False, arena=False):      # (split: accepted and ignored -- removed in round 5)
+                 slots=2, overlap=False, split=False, weave=False, arena=False,      # (split: accepted and ignored -- removed in round 5)
+                 feature_out_dtype="float32"):
+        if feature_out_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         self._lib = _libmod.load()
         self.group_size, self.slots = int(group_size), int(slots)
         self.fanout = [int(f) for f in fanout]
-        self.handle = self._lib.legion_pipeline_create(graph.handle, feature.handle, cache.handle, int(dev_id),
-                                                       int(batch_size), _i32_array(self.fanout), len(self.fanout),
-                                                       self.group_size, self.slots, int(feature_rows),
-                                                       (1 if use_graph else 0) | (2 if overlap else 0) | (4 if split else 0) |
-                                                       (16 if weave else 0) | (32 if arena else 0) | (64 if arena in ("shared", "plain") else 0))
+        self.handle = self._lib.legion_pipeline_create_ex(graph.handle, feature.handle, cache.handle, int(dev_id),
+                                                          int(batch_size), _i32_array(self.fanout), len(self.fanout),
+                                                          self.group_size, self.slots, int(feature_rows),
+                                                          (1 if use_graph else 0) | (2 if overlap else 0) | (4 if split else 0) |
+                                                          (16 if weave else 0) | (32 if arena else 0) | (64 if arena in ("shared", "plain") else 0),
+                                                          FEATURE_DTYPES[feature_out_dtype])
         self.pools = [[MemoryPool._borrowed(self._lib.legion_pipeline_pool(self.handle, s, g), dev_id,
                                             feature.total_num_nodes, batch_size, fanout, feature.float_feature_len,
                                             feature_rows) for g in range(self.group_size)]
@@ -672,5 +696,10 @@ def read_batch(memorypool):
            "agg_src_ids": memorypool.buffer("agg_src_ids")[:n_edges].cpu().numpy().copy(),
            "agg_dst_ids": memorypool.buffer("agg_dst_ids")[:n_edges].cpu().numpy().copy()}
     if memorypool.feature_rows > 0:
-        out["float_features"] = memorypool.buffer("float_features")[:n_nodes].cpu().numpy().copy()
+        rows = memorypool.buffer("float_features")[:n_nodes]
+        if rows.dtype == torch.bfloat16:     # (numpy has no bfloat16: the rows' bits, as uint16)
+            rows = rows.view(torch.int16)
+        out["float_features"] = rows.cpu().numpy().copy()
+        if out["float_features"].dtype == np.int16:
+            out["float_features"] = out["float_features"].view(np.uint16)
     return out

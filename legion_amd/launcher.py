@@ -114,7 +114,8 @@ FEATURE_DTYPES = {"float32": None, "bfloat16": "bf16"}
 def server_argv(gpu_number, cache_agg_mode, args):
     argv = [server_binary(), str(gpu_number), str(int(cache_agg_mode))] + [str(f) for f in parse_fanout(args.fanout)]
     flag = FEATURE_DTYPES[getattr(args, "feature_dtype", "float32")]
-    return argv + (["--feature-dtype", flag] if flag else [])
+    out = FEATURE_DTYPES[getattr(args, "trainer_feature_dtype", "float32")]
+    return argv + (["--feature-dtype", flag] if flag else []) + (["--feature-out-dtype", out] if out else [])
 
 
 def parse_fanout(value):
@@ -137,6 +138,8 @@ def build_argparser():
     argparser.add_argument('--usenvlink', type=int, default=1)
     # storage format of the feature table and caches; the trainer receives float32 rows either way
     argparser.add_argument('--feature_dtype', type=str, default="float32", choices=sorted(FEATURE_DTYPES))
+    # dtype of the rows the trainer receives (independent of the storage dtype): bfloat16 hands over bf16[n x D] rows
+    argparser.add_argument('--trainer_feature_dtype', type=str, default="float32", choices=sorted(FEATURE_DTYPES))
     return argparser
 
 

@@ -49,6 +49,8 @@ SIGNATURES = {
     "legion_pool_lds_buckets": (c_i32, [c_p]),
     "legion_pool_state_bytes": (c_i64, [c_p]),
     "legion_pool_error": (c_i32, [c_p]),
+    "legion_pool_set_feature_out_dtype": (c_i32, [c_p, c_i32]),
+    "legion_pool_feature_out_dtype": (c_i32, [c_p]),
     "legion_cache_create": (c_p, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "legion_cache_init_controller": (None, [c_p, c_i32]),
     "legion_cache_set_replica_memory": (None, [c_p, c_i64]),
@@ -89,6 +91,7 @@ SIGNATURES = {
     "legion_server_finalize": (None, [c_p]),
     "legion_run": (c_i32, [P_I32, c_i32, c_i32, c_i32, c_i32]),
     "legion_server_set_feature_dtype": (c_i32, [c_i32]),
+    "legion_server_set_feature_out_dtype": (c_i32, [c_i32]),
     "NewIPCEnv": (c_p, [c_i32]),
     "legion_ipc_coordinate": (None, [c_p, c_i32, P_I32, P_I32, P_I32, c_i32, c_i32]),
     "legion_ipc_train_step": (c_i32, [c_p]),
@@ -102,6 +105,7 @@ SIGNATURES = {
     "legion_group_destroy": (None, [c_p]),
     "legion_enqueue_group": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),
     "legion_pipeline_create": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32]),
+    "legion_pipeline_create_ex": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32]),
     "legion_pipeline_submit": (c_i32, [c_p, c_i32, c_i32]),
     "legion_pipeline_submit_n": (c_i32, [c_p, c_i32, c_i32, c_i32]),
     "legion_enqueue_group_n": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),

@@ -75,6 +75,8 @@ typedef struct shmExt_st {
     int64_t arena_chunk_bytes[MAX_DEVICE];
     int32_t arena_sock_pid;
     int32_t ext_reserved2;
+    // version 4: dtype of the feature rows (0 float32, 1 bfloat16), pipe slots and views alike
+    int32_t feature_out_dtype[MAX_DEVICE];
 } shmExt;
 static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size is part of the wire format");
 
@@ -319,6 +321,8 @@ public:
         return &mirror_->view[slab_device_][current_pipe_][0];
     }
     void* Arena() const { return arena_; }
+    // feature rows of the server's batches are bfloat16 (shmExt version 4), else float32
+    bool Bf16Rows() const { return mirror_ != nullptr && mirror_->ext_version >= 4 && mirror_->feature_out_dtype[slab_device_] == 1; }
     long long ArenaBytes() const { return arena_bytes_; }
     void Post()
     {
@@ -395,7 +399,8 @@ static int32_t h_edge_counter[16];
 struct SlotTensors { torch::Tensor ids, feats, labels, src, dst; };
 static SlotTensors slot_base[INTERBATCH_CON];
 static bool slot_base_ready[INTERBATCH_CON] = {false, false};
-static torch::Tensor arena_i32, arena_f32;     // the whole lane arena as int32 / float32 (direct views)
+static torch::Tensor arena_i32, arena_f32;     // the whole lane arena as int32 / float32 / bfloat16 (direct views)
+static torch::Tensor arena_bf16;
 static bool arena_ready = false;
 // extent (in elements) of the device allocation behind an IPC-opened pointer
 static long long whole_buffer(void* p, size_t elem)
@@ -428,6 +433,7 @@ void FinalizeIPC()
     }
     arena_i32 = torch::Tensor();
     arena_f32 = torch::Tensor();
+    arena_bf16 = torch::Tensor();
     arena_ready = false;
     if (env == nullptr) return;
     env->Finalize();
@@ -463,14 +469,16 @@ std::vector<torch::Tensor> get_next(int feature_dim)
             const auto dev = torch::Device(torch::kCUDA, env->Device());
             arena_i32 = torch::from_blob(env->Arena(), {env->ArenaBytes() / 4}, torch::TensorOptions().dtype(torch::kI32).device(dev));
             arena_f32 = torch::from_blob(env->Arena(), {env->ArenaBytes() / 4}, torch::TensorOptions().dtype(torch::kF32).device(dev));
+            arena_bf16 = torch::from_blob(env->Arena(), {env->ArenaBytes() / 2}, torch::TensorOptions().dtype(torch::kBFloat16).device(dev));
             arena_ready = true;
         }
-        const long long o_ids = vw[0] / 4, o_feat = vw[1] / 4, o_lab = vw[2] / 4, o_src = vw[3] / 4, o_dst = vw[4] / 4;
+        const bool bf16 = env->Bf16Rows();
+        const long long o_ids = vw[0] / 4, o_feat = vw[1] / (bf16 ? 2 : 4), o_lab = vw[2] / 4, o_src = vw[3] / 4, o_dst = vw[4] / 4;
         std::vector<torch::Tensor> ret;
         ret.reserve(3 + 2 * hop_num);
         const long long n_total = std::max(h_node_counter[INTRABATCH_CON * 3 + hop_num], 0);
         ret.push_back(arena_i32.as_strided({n_total}, {1}, o_ids));
-        ret.push_back(arena_f32.as_strided({n_total, (long long)feature_dim}, {(long long)feature_dim, 1}, o_feat));
+        ret.push_back((bf16 ? arena_bf16 : arena_f32).as_strided({n_total, (long long)feature_dim}, {(long long)feature_dim, 1}, o_feat));
         ret.push_back(arena_i32.as_strided({(long long)std::max(h_node_counter[INTRABATCH_CON * 3], 0)}, {1}, o_lab));
         for (int i = hop_num; i > 0; i--) {
             const long long n_edges = std::max(h_edge_counter[INTRABATCH_CON * 3 + i], 0);
@@ -483,9 +491,10 @@ std::vector<torch::Tensor> get_next(int feature_dim)
     if (!slot_base_ready[pipe]) {
         const auto dev = torch::Device(torch::kCUDA, env->Device());
         const auto i32 = torch::TensorOptions().dtype(torch::kI32).device(dev);
-        const auto f32 = torch::TensorOptions().dtype(torch::kF32).device(dev);
+        const bool bf16 = env->Bf16Rows();
+        const auto feat = torch::TensorOptions().dtype(bf16 ? torch::kBFloat16 : torch::kF32).device(dev);
         b.ids = torch::from_blob(env->GetIds(), {whole_buffer(env->GetIds(), 4)}, i32);
-        b.feats = torch::from_blob(env->GetFloatFeatures(), {whole_buffer(env->GetFloatFeatures(), 4)}, f32);
+        b.feats = torch::from_blob(env->GetFloatFeatures(), {whole_buffer(env->GetFloatFeatures(), bf16 ? 2 : 4)}, feat);
         b.labels = torch::from_blob(env->GetLabels(), {whole_buffer(env->GetLabels(), 4)}, i32);
         b.src = torch::from_blob(env->GetAggSrc(), {whole_buffer(env->GetAggSrc(), 4)}, i32);
         b.dst = torch::from_blob(env->GetAggDst(), {whole_buffer(env->GetAggDst(), 4)}, i32);

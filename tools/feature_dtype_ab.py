@@ -1,15 +1,17 @@
 #!/usr/bin/env python3
-"""float32 vs bfloat16 feature storage on the bench.py workload, alternated in fresh child processes.
+"""Feature storage dtype x feature output dtype on the bench.py workload, alternated in fresh child processes.
 
-    python tools/feature_dtype_ab.py [--repeats 3] [--timeout 900] [--rows 0] [--out FILE] -- <bench.py arguments>
+    python tools/feature_dtype_ab.py [--arms f32:f32,bf16:f32] [--repeats 3] [--timeout 900] [--rows 0] [--out FILE] -- <bench.py arguments>
 
-Each child runs bench.py unchanged, with engine.FeatureStorage defaulting to the dtype under test (float32 = bench.py as it
-is).  Children alternate float32, bfloat16, float32, ... --repeats times each; every child runs under its own time limit
-and the first failing child ends the run.  bench.py's own verification compares rows with the float32 table, so both dtypes
-run with --no-verify (the bf16 rows are covered by tests/test_gpu_feature_bf16.py).  Per dtype the report gives ms/step
-(median, min, max), the last-hop gather's average launch time, and its algorithmic GB/s and fraction of the 8 TB/s peak at
-8 D + 8 bytes per float32 row and 2 P + 4 D + 8 per bf16 row (P = D rounded up to 8).  --rows R: bf16 children run with
-LEGION_GATHER_ROWS=R (the gather's tile size; 0 = the library's choice)."""
+An arm is storage:out, each f32 or bf16: the dtype the feature table and caches hold (engine.FeatureStorage feature_dtype) and
+the dtype of the rows handed over (engine.MemoryPool / Pipeline feature_out_dtype).  Each child runs bench.py unchanged, with
+those constructors defaulting to the arm's dtypes (f32:f32 = bench.py as it is).  Children alternate the arms in the order
+given, --repeats times each; every child runs under its own time limit and the first failing child ends the run.  bench.py's
+own verification compares float32 rows with the float32 table, so every arm runs with --no-verify (the bf16 rows are covered
+by tests/test_gpu_feature_bf16.py and tests/test_gpu_feature_out_bf16.py).  Per arm the report gives ms/step (median, min,
+max), the last-hop gather's average launch time, and its algorithmic GB/s and fraction of the 8 TB/s peak at the arm's bytes
+per row (P = D rounded up to 8): f32:f32 8 D + 8, bf16:f32 2 P + 4 D + 8, bf16:bf16 2 P + 2 D + 8, f32:bf16 6 D + 8.
+--rows R: children of arms with a bf16 side run with LEGION_GATHER_ROWS=R (the gather's tile size; 0 = the library's choice)."""
 import argparse
 import json
 import os
@@ -21,22 +23,33 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 PEAK_GBPS = 8000.0
 
 
-def child(dtype, bench_args):
+DTYPES = {"f32": "float32", "bf16": "bfloat16"}
+
+
+def child(arm, bench_args):
     sys.path.insert(0, ROOT)
     from legion_amd import engine
-    init = engine.FeatureStorage.__init__
+    storage, out = (DTYPES[x] for x in arm.split(":"))
 
-    def patched(self, *a, feature_dtype=dtype, **kw):
-        init(self, *a, feature_dtype=feature_dtype, **kw)
+    def default(cls, key, value):
+        init = cls.__init__
 
-    engine.FeatureStorage.__init__ = patched
+        def patched(self, *a, **kw):
+            kw.setdefault(key, value)
+            init(self, *a, **kw)
+        cls.__init__ = patched
+
+    default(engine.FeatureStorage, "feature_dtype", storage)
+    default(engine.MemoryPool, "feature_out_dtype", out)
+    default(engine.Pipeline, "feature_out_dtype", out)
     sys.argv = [os.path.join(ROOT, "bench.py")] + bench_args
     import runpy
     runpy.run_path(sys.argv[0], run_name="__main__")
 
 
-def bytes_per_row(dtype, D):
-    return 8 * D + 8 if dtype == "float32" else 2 * ((D + 7) // 8 * 8) + 4 * D + 8
+def bytes_per_row(arm, D):
+    storage, out = arm.split(":")
+    return (4 * D if storage == "f32" else 2 * ((D + 7) // 8 * 8)) + (4 * D if out == "f32" else 2 * D) + 8
 
 
 def main():
@@ -45,21 +58,26 @@ def main():
     argv = sys.argv[1:]
     split = argv.index("--") if "--" in argv else len(argv)
     ap = argparse.ArgumentParser()
+    ap.add_argument("--arms", type=str, default="f32:f32,bf16:f32", help="storage:out,... (f32 or bf16 each)")
     ap.add_argument("--repeats", type=int, default=3)
     ap.add_argument("--timeout", type=int, default=900, help="seconds per child")
     ap.add_argument("--rows", type=int, default=0)
     ap.add_argument("--out", type=str, default="")
     args = ap.parse_args(argv[:split])
+    arms = args.arms.split(",")
+    for arm in arms:
+        if len(arm.split(":")) != 2 or any(x not in DTYPES for x in arm.split(":")):
+            ap.error(f"--arms: {arm!r} is not storage:out with f32 or bf16 on each side")
     bench_args = argv[split + 1:] + ["--no-verify"]
     D = 128
     for i, a in enumerate(bench_args):
         if a == "--dim":
             D = int(bench_args[i + 1])
-    runs = {"float32": [], "bfloat16": []}
+    runs = {arm: [] for arm in arms}
     for rep in range(args.repeats):
-        for dtype in ("float32", "bfloat16"):
+        for dtype in arms:
             env = dict(os.environ)
-            if dtype == "bfloat16" and args.rows:
+            if dtype != "f32:f32" and args.rows:
                 env["LEGION_GATHER_ROWS"] = str(args.rows)
             cmd = ["timeout", "-k", "10", str(args.timeout), sys.executable, os.path.abspath(__file__), "--child", dtype, "--"] + bench_args
             p = subprocess.run(cmd, cwd=ROOT, env=env, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True)
@@ -85,9 +103,10 @@ def main():
                          "last_gather_us_median": statistics.median(us), "last_gather_us_min": min(us), "last_gather_us_max": max(us),
                          "gather_gbps_median": statistics.median(g), "gather_frac_of_peak_median": statistics.median(g) / PEAK_GBPS,
                          "runs": rs}
-    f, b = report["float32"], report["bfloat16"]
-    report["bf16_over_f32"] = {"ms_per_step": b["ms_per_step_median"] / f["ms_per_step_median"],
-                               "last_gather_us": b["last_gather_us_median"] / f["last_gather_us_median"]}
+    f = report[arms[0]]
+    report["over_" + arms[0]] = {arm: {"ms_per_step": report[arm]["ms_per_step_median"] / f["ms_per_step_median"],
+                                       "last_gather_us": report[arm]["last_gather_us_median"] / f["last_gather_us_median"]}
+                                 for arm in arms[1:]}
     text = json.dumps(report, indent=1)
     print(text)
     if args.out:
