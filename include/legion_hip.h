@@ -135,6 +135,15 @@ void legion_pool_alloc_features(LegionMemoryPool* p, int64_t rows);
  * legion_pool_alloc_features: returns 0, or -1 after it (nothing changes), for an unknown dtype or a null pool. */
 int32_t legion_pool_set_feature_out_dtype(LegionMemoryPool* p, int32_t dtype);
 int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p);
+/* Sampling mode of the pool's hops.  1 (default): every frontier entry of degree D at fan-out f gets min(f, D) independent draws
+ * with replacement (SS/engine/operator_impl.cu:228-242).  0: without replacement (DGL's replace=False): min(f, D) distinct
+ * adjacency positions -- D <= f: all of them in CSR order; D > f: Floyd's algorithm over the same per-slot draw
+ * (legion_draw_distinct_batch).  Sizes, buffers and every later step are the same in both modes.  Returns 0, or -1 (nothing
+ * changes) once the pool has sampled a hop (eagerly or into a captured graph), for a value other than 0 / 1, for 0 when a fan-out
+ * of the pool exceeds LEGION_DISTINCT_MAX_FANOUT, or for a null pool. */
+#define LEGION_DISTINCT_MAX_FANOUT 256
+int32_t legion_pool_set_sample_replace(LegionMemoryPool* p, int32_t replace);
+int32_t legion_pool_sample_replace(const LegionMemoryPool* p);
 void legion_pool_set_current_pipe(LegionMemoryPool* p, int32_t pipe);
 void legion_pool_set_mode_iter(LegionMemoryPool* p, int32_t mode, int32_t iter);
 int32_t legion_pool_num_ids(const LegionMemoryPool* p);
@@ -151,7 +160,8 @@ void* legion_pool_buffer(LegionMemoryPool* p, int32_t which);
 int32_t legion_pool_lds_buckets(const LegionMemoryPool* p);
 int64_t legion_pool_state_bytes(const LegionMemoryPool* p);
 /* Sticky error bits raised on the device for this pool (0 = none): 1 a de-duplication bucket that fits no LDS table, 2 batch larger than the
- * feature buffer (gather stopped at its end; the reference overruns, SS/engine/server.cu:277), 4 internal.  The
+ * feature buffer (gather stopped at its end; the reference overruns, SS/engine/server.cu:277), 4 internal, 8 a hop not sampled
+ * (a fan-out above LEGION_DISTINCT_MAX_FANOUT without replacement, or lanes of one group with different sampling modes).  The
  * word lives in host-visible memory: reading it after the batch completed needs no copy. */
 int32_t legion_pool_error(const LegionMemoryPool* p);
 void legion_pool_destroy(LegionMemoryPool* p);
@@ -274,6 +284,9 @@ int32_t legion_server_set_feature_dtype(int32_t feature_dtype);
 /* Feature output dtype (LEGION_FEATURE_*) of the rows the NEXT legion_server_initialize / legion_run hands to its trainers
  * (published in the shared segment's extension, version 4).  Returns 0, or -1 for an unknown dtype (nothing changes). */
 int32_t legion_server_set_feature_out_dtype(int32_t feature_out_dtype);
+/* Sampling mode (legion_pool_set_sample_replace) of every pool the NEXT legion_server_initialize / legion_run creates, PreSC's
+ * included.  Returns 0, or -1 for a value other than 0 / 1 (nothing changes).  The trainer side needs no change. */
+int32_t legion_server_set_sample_replace(int32_t replace);
 
 LegionIPCEnv* NewIPCEnv(int32_t device_count);
 /* step arithmetic, SS/engine/ipc_service.cu:60-132,213-253 (host only, no GPU needed) */
@@ -323,6 +336,9 @@ LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatu
                                           LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
                                           const int32_t* fanout, int32_t hop_num, int32_t group_size,
                                           int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype);
+/* sampling mode of every lane (legion_pool_set_sample_replace).  Returns 0, or -1 (nothing changes) once the pipeline has
+ * submitted a group, for a value other than 0 / 1 or for 0 with a fan-out above LEGION_DISTINCT_MAX_FANOUT. */
+int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace);
 /* enqueues batches counter0 .. counter0 + group_size - 1; returns the slot */
 int32_t legion_pipeline_submit(LegionPipeline* p, int32_t counter0, int32_t mode);
 /* only the first n_active lanes work (tail of a run that is not a multiple of group_size) */
@@ -376,6 +392,11 @@ void legion_gather_rows(legion_stream_t stream, const float* full_table, const f
 /* the draw of SS/engine/operator_impl.cu:235-238 evaluated on the GPU for n (idx, deg) pairs */
 void legion_draw_batch(legion_stream_t stream, const int32_t* idx, const int32_t* deg, int32_t* out,
                        int32_t n);
+/* the picks of sampling without replacement for n frontier entries: entry i has its first slot at base[i] (q * f) and degree
+ * deg[i]; out[i * f + k] = its pick k (an adjacency position) or -1 for k >= min(f, deg[i]).  Returns 0, or -1 for f outside
+ * [1, LEGION_DISTINCT_MAX_FANOUT] (nothing is launched). */
+int32_t legion_draw_distinct_batch(legion_stream_t stream, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out,
+                                   int32_t n);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -101,6 +101,51 @@ void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, in
     hipCheckError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Sampling without replacement (HopParams.replace == 0, DGL's replace=False).  Frontier entry q of a hop with fan-out f owns
+// slots q*f + k, k < f, as with replacement; its row of degree D yields min(f, D) picks:
+//   D <= f: position k (every neighbour in CSR order, no draw);
+//   D >  f: Floyd's algorithm in slot order -- t_k = draw(q*f + k, j_k + 1) with j_k = D - f + k, and pick_k = t_k unless one
+//           of pick_0 .. pick_{k-1} took it, then j_k.  A uniform f-subset of [0, D): distinct adjacency positions.
+// The draws are independent (one per slot, in parallel); only the resolution is serial per entry, ~f^2/2 comparisons.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int32_t floyd_draw(uint32_t x, int32_t deg, int32_t f, int32_t k)      // t_k from slot's x = minstd_pow(idx + 1)
+{
+    return draw_from_x(x, deg - f + k + 1);
+}
+
+// the picks of one entry with D > f: p[0 .. n) hold t_0 .. t_{n-1} and are replaced, in place, by pick_0 .. pick_{n-1}
+// (n <= f: a super tile resolves the slots it owns and those before them; later picks never change earlier ones)
+template <typename T>
+__device__ __forceinline__ void floyd_resolve(T* p, int32_t n, int32_t jbase)                      // jbase = D - f
+{
+    for (int32_t k = 1; k < n; k++) {
+        const int32_t t = p[k];
+        bool taken = false;
+        for (int32_t i = 0; i < k; i++) taken |= (p[i] == t);
+        if (taken) p[k] = jbase + k;
+    }
+}
+
+// the rule stand-alone (tests): entry i has its first slot at base[i] and degree deg[i]; out[i*f + k] = pick_k or -1
+__global__ void draw_distinct_batch_kernel(const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n)
+{
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t D = deg[i] > 0 ? deg[i] : 0;
+    int32_t* p = out + (int64_t)i * f;
+    for (int32_t k = 0; k < f; k++)
+        p[k] = k >= D ? -1 : (D <= f ? k : floyd_draw(minstd_pow((uint32_t)(base[i] + k) + 1u), D, f, k));
+    if (D > f) floyd_resolve(p, f, D - f);
+}
+
+void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n)
+{
+    if (n <= 0) return;
+    draw_distinct_batch_kernel<<<(n + 255) / 256, 256, 0, s>>>(base, deg, f, out, n);
+    hipCheckError();
+}
+
 // the per-batch buffers the two bracket kernels touch, as global-address-space pointers
 struct BracketLane {
     LG_G int32_t* sampled_ids; LG_G int32_t* labels; LG_G int32_t* node_counter; LG_G int32_t* edge_counter;
@@ -293,7 +338,10 @@ __device__ __forceinline__ HopGeom hop_geometry(const SampleArgs& a)
 // !SINGLE (256-bucket class): the kernel samples K super tiles (a partition tile), counts their claims per bucket and
 // reserves, with one atomic per bucket, that many places of each bucket's claim list (run_off: {first place, count} per
 // partition tile and bucket); place_kernel writes the pairs (see there).  SINGLE + STAGED (64-bucket class): below.
-template <int BB, bool SINGLE, bool STAGED = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
+// DISTINCT: sampling without replacement (see floyd_resolve): the slots' draws go to s_pick, indexed by slot - j0 * f (the super
+// tile's slots and, for an entry that began in the previous super tile, its earlier ones); one thread per entry with D > f then
+// resolves them in place, and the slots read their picks from there.  Fan-outs up to LG_DISTINCT_MAX_FANOUT (the span of s_pick).
+template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
 __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_SGPRS))) void sample_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NB = 1 << BB;
@@ -301,6 +349,7 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
     static_assert(NB <= LG_TILE, "one thread per bucket in the prefix");
     const SampleArgs a = lane_args(hp, lanes);
     __shared__ RowHdr s_hdr[LG_SUPER];
+    __shared__ int32_t s_pick[DISTINCT ? LG_SUPER + LG_DISTINCT_MAX_FANOUT - 1 : 1];
     __shared__ int32_t s_bcnt[NB], s_boff[SINGLE ? NB : 1], s_list[STAGED ? NB : 1];
     static_assert(!STAGED || (SINGLE && NB <= 64), "the staged form scans its buckets with one wave");
 
@@ -359,6 +408,31 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
             }
             __syncthreads();
 
+            if constexpr (DISTINCT) {
+                // the draws of the slots whose entry has D > f; then one thread per such entry resolves its picks (the first
+                // entry's thread also draws the slots it had in the previous super tile: they come first in Floyd's order)
+                const int32_t sbase = j0 * count;
+#pragma unroll
+                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
+                    const int32_t idx = idx0 + u * LG_TILE + tid;
+                    if (idx < g.total) {
+                        const int32_t q = idx / count;
+                        const int32_t k = idx - q * count;
+                        const int32_t deg = s_hdr[q - j0].deg;
+                        if (deg > count) s_pick[idx - sbase] = floyd_draw(x[u], deg, count, k);
+                    }
+                }
+                __syncthreads();
+                for (int32_t t = tid; t < nsrc; t += LG_TILE) {
+                    const int32_t deg = s_hdr[t].deg;
+                    if (deg <= count) continue;
+                    if (t == 0)
+                        for (int32_t k = 0; k < idx0 - sbase; k++) s_pick[k] = floyd_draw(minstd_pow((uint32_t)(sbase + k) + 1u), deg, count, k);
+                    floyd_resolve(s_pick + t * count, min(count, last + 1 - (j0 + t) * count), deg - count);
+                }
+                __syncthreads();
+            }
+
             if (SINGLE && tid < NB) s_bcnt[tid] = 0;     // (made visible by the barrier above the loads' use below)
             int32_t dst[LG_SLOTS_PER_LANE], fs[LG_SLOTS_PER_LANE];
 #pragma unroll
@@ -371,7 +445,8 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                     const int32_t k = idx - q * count;
                     const RowHdr h = s_hdr[q - j0];
                     if (k < h.deg) {                                           // :232-233 (src < 0 has deg 0)
-                        const int32_t pick = draw_from_x(x[u], h.deg);         // :235-238
+                        const int32_t pick = !DISTINCT ? draw_from_x(x[u], h.deg)                          // :235-238
+                                                       : (h.deg <= count ? k : s_pick[idx - j0 * count]);
                         // column slots: the same sector read as 8 bytes brings the neighbour's feature-cache slot along.  Picks
                         // from the full CSR (slot P: all but the cached-topology rows) address it through pointers that came
                         // with the launch; only a cached row's pick loads its column array's address from the table first
@@ -1172,17 +1247,20 @@ void launch_random_sample(hipStream_t s, const HopParams& p, const LanePtrs* d_l
         const size_t stage = (size_t)k * LG_SUPER * sizeof(unsigned long long);
         switch (p.lds_bucket_bits) {
         case LG_LDS_BITS_SMALL:
-            sample_kernel<LG_LDS_BITS_SMALL, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            if (p.replace) sample_kernel<LG_LDS_BITS_SMALL, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            else sample_kernel<LG_LDS_BITS_SMALL, true, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
             hipCheckError();
             dedup_lists_kernel<LG_LDS_BITS_SMALL, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_SMALL, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
             break;
         case LG_LDS_BITS_SMALL16:
-            sample_kernel<LG_LDS_BITS_SMALL16, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            if (p.replace) sample_kernel<LG_LDS_BITS_SMALL16, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            else sample_kernel<LG_LDS_BITS_SMALL16, true, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
             hipCheckError();
             dedup_lists_kernel<LG_LDS_BITS_SMALL16, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_SMALL16, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
             break;
         case LG_LDS_BITS_MEDIUM:
-            sample_kernel<LG_LDS_BITS_MEDIUM, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            if (p.replace) sample_kernel<LG_LDS_BITS_MEDIUM, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+            else sample_kernel<LG_LDS_BITS_MEDIUM, true, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
             hipCheckError();
             // (a bucket of up to CL x 1024 claims is worked on from registers, whatever the number of passes over its sub-buckets)
             if (p.dedup_claims == LG_DEDUP_CLAIMS_BIG) dedup_lists_kernel<LG_LDS_BITS_MEDIUM, LG_DEDUP_CLAIMS_BIG, LG_DEDUP_BIG_TABLE_BITS><<<dim3(1 << LG_LDS_BITS_MEDIUM, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
@@ -1190,7 +1268,8 @@ void launch_random_sample(hipStream_t s, const HopParams& p, const LanePtrs* d_l
             else dedup_lists_kernel<LG_LDS_BITS_MEDIUM, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_MEDIUM, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
             break;
         default:
-            sample_kernel<LG_LDS_BITS_LARGE, false><<<pgrid, LG_TILE, 0, s>>>(q, d_lanes);
+            if (p.replace) sample_kernel<LG_LDS_BITS_LARGE, false><<<pgrid, LG_TILE, 0, s>>>(q, d_lanes);
+            else sample_kernel<LG_LDS_BITS_LARGE, false, false, true><<<pgrid, LG_TILE, 0, s>>>(q, d_lanes);
             hipCheckError();
             place_kernel<LG_LDS_BITS_LARGE><<<pgrid, LG_PLACE_THREADS, stage, s>>>(q, d_lanes);
             hipCheckError();

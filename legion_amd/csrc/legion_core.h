@@ -134,6 +134,8 @@ enum HopScratch {
 #define LG_ERR_TABLE_FULL 1       // a de-duplication bucket did not fit its LDS table even in 2^14 sub-bucket passes (not a hash problem: cannot happen)
 #define LG_ERR_FEATURE_ROWS 2     // the batch has more rows than the feature buffer: the gather stopped at its end
 #define LG_ERR_CHAIN 4            // compact_kernel gave up waiting for an earlier tile's status word / a winner's position (cannot happen)
+#define LG_ERR_SAMPLE_MODE 8      // a hop was not sampled: a fan-out above LG_DISTINCT_MAX_FANOUT without replacement, or lanes of one
+                                  // group with different sampling modes (set on the host; the setters refuse both)
 
 // Device code: a pointer that was loaded from memory (LanePtrs, pointer tables, LDS) is "generic" to
 // the compiler, which then emits flat_* instructions; those count on lgkmcnt as well as vmcnt, so every
@@ -167,6 +169,7 @@ enum HopScratch {
 #define LG_TILE 256            // compaction tile == threads per workgroup in the sampler kernels
 #define LG_SLOTS_PER_LANE 4    // independent slots each lane keeps in flight
 #define LG_SUPER (LG_TILE * LG_SLOTS_PER_LANE)   // slots one workgroup owns per iteration
+#define LG_DISTINCT_MAX_FANOUT LEGION_DISTINCT_MAX_FANOUT   // largest fan-out of sampling without replacement (the sampler's LDS span of an entry's picks)
 
 // Per-vertex row header: where the adjacency of v lives (slot of the CSR pointer tables: P = the
 // full CSR, d < P = GPU d's cached CSR), its first edge and its degree.  One 16-byte read resolves
@@ -312,6 +315,7 @@ public:
     int32_t* err_host = nullptr;       // host-visible error word (mapped pinned), err_dev = its device address
     int32_t* err_dev = nullptr;
     int32_t ErrorBits() const { return err_host ? *(volatile int32_t*)err_host : 0; }
+    void RaiseError(int32_t bits) { if (err_host) __atomic_fetch_or(err_host, bits, __ATOMIC_SEQ_CST); }
     // lanes of a GPURunner group (lg_set_pool_arena): the trainer-visible arrays live in the runner's arena (not freed
     // here) and the counters are mirrored to host-visible memory by the end-of-batch kernel
     bool arena_backed = false;
@@ -328,6 +332,11 @@ public:
     // legion_pool_alloc_features (features_allocated); the buffer's element size follows it, its capacity in rows does not
     int32_t feature_out_dtype = LEGION_FEATURE_F32;
     bool features_allocated = false;
+    // 1: the sampler draws with replacement (the reference's draw); 0: without (distinct adjacency positions per frontier entry, DGL's
+    // replace=False).  Fixed once the pool has sampled a hop, eagerly or into a captured graph (sample_used)
+    int32_t sample_replace = 1;
+    bool sample_used = false;
+    int32_t max_fanout = 0;            // largest fan-out the pool was sized for
     int64_t grid_rows_hint = 0;        // > 0: rows a batch typically has (the Runner's pipe-slot pool holds the worst case: launches are sized for the usual one)
     int32_t dev_id = 0;
     bool owns_buffers = false;
@@ -757,6 +766,7 @@ struct HopParams {                  // what every lane of a launch shares
     int32_t lds_bucket_bits;        // LG_LDS_BITS_SMALL / SMALL16 / MEDIUM / LARGE (the pool's)
     int32_t lds_k;                  // super tiles per partition tile in this hop (set by launch_random_sample)
     int32_t dedup_claims;           // 64-bucket class: claims per thread the (last) hop's de-duplication keeps in registers: LG_DEDUP_CLAIMS, _MID or _BIG by what PreSC saw
+    int32_t replace;                // 1: draws with replacement (the reference's); 0: distinct positions per entry (MemoryPool::sample_replace)
 };
 void launch_random_sample(hipStream_t s, const HopParams& p, const LanePtrs* d_lanes, int32_t n_lanes);
 
@@ -850,6 +860,7 @@ void cache_row_headers(hipStream_t s, RowHdr* hdr, const int32_t* QT, int32_t Kg
 void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* map32,
                  const char* map8, int32_t* out32, char* out8);
 void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* out, int32_t n);
+void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n);
 
 // a roctx range for the enclosing scope (markers.hip): visible to rocprofv3 --marker-trace, near-free otherwise
 struct Range {

@@ -7,6 +7,8 @@
 // trainer still receives float32 rows.  --feature-dtype f32 is the default.
 // --feature-out-dtype bf16: the trainer receives bfloat16 rows (legion_server_set_feature_out_dtype), whatever the storage dtype;
 // --feature-out-dtype f32 is the default.
+// --sample-replace 0: every pool samples without replacement (legion_server_set_sample_replace); 1, the reference's draw with
+// replacement, is the default.
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
@@ -17,7 +19,7 @@
 int main(int argc, char** argv)
 {
     if (argc < 3) {
-        std::printf("usage: %s <gpu_number> <cache_agg_mode> [fanout ...] [--disk] [--feature-dtype f32|bf16] [--feature-out-dtype f32|bf16]\n", argv[0]);
+        std::printf("usage: %s <gpu_number> <cache_agg_mode> [fanout ...] [--disk] [--feature-dtype f32|bf16] [--feature-out-dtype f32|bf16] [--sample-replace 0|1]\n", argv[0]);
         return 2;
     }
     std::vector<int32_t> fanout;
@@ -36,6 +38,13 @@ int main(int argc, char** argv)
             const int32_t dtype = std::strcmp(v, "bf16") == 0 ? LEGION_FEATURE_BF16 : std::strcmp(v, "f32") == 0 ? LEGION_FEATURE_F32 : -1;
             if (legion_server_set_feature_out_dtype(dtype) != 0) {
                 std::printf("--feature-out-dtype: expected f32 or bf16, got '%s'\n", v);
+                return 2;
+            }
+        } else if (std::strcmp(argv[i], "--sample-replace") == 0) {
+            const char* v = i + 1 < argc ? argv[++i] : "";
+            const int32_t replace = std::strcmp(v, "1") == 0 ? 1 : std::strcmp(v, "0") == 0 ? 0 : -1;
+            if (legion_server_set_sample_replace(replace) != 0) {
+                std::printf("--sample-replace: expected 0 or 1, got '%s'\n", v);
                 return 2;
             }
         } else fanout.push_back(std::atoi(argv[i]));

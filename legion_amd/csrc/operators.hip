@@ -100,7 +100,13 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
         printf("Sampling Parameters Error\n");   // counter_update's complaint, operator_impl.cu:86-88
         return;
     }
+    if (!pool0->sample_replace && count > LG_DISTINCT_MAX_FANOUT) {
+        printf("Sampling Parameters Error: fan-out %d without replacement (at most %d)\n", count, LG_DISTINCT_MAX_FANOUT);
+        pool0->RaiseError(LG_ERR_SAMPLE_MODE);
+        return;
+    }
     lg::Range mark("op%d sample%s fanout=%d lanes=%d", op_id, is_presc ? " (presc)" : "", count, n_lanes);
+    pool0->sample_used = true;              // the mode is fixed from here on (legion_pool_set_sample_replace)
     lg::HopParams p;
     p.op_id = op_id;
     p.count = count;
@@ -129,6 +135,7 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
         if (per_bucket > (int64_t)LG_DEDUP_CLAIMS_MID * 1024 && pool0->lds_bucket_bits == LG_LDS_BITS_MEDIUM) p.dedup_claims = LG_DEDUP_CLAIMS_BIG;
         else if (per_bucket > (int64_t)LG_DEDUP_CLAIMS * 1024) p.dedup_claims = LG_DEDUP_CLAIMS_MID;
     }
+    p.replace = pool0->sample_replace;
     lg::launch_random_sample(s, p, d_lanes, n_lanes);
 }
 
@@ -352,6 +359,14 @@ extern "C" void legion_draw_batch(legion_stream_t stream, const int32_t* idx, co
     lg::launch_draw_batch(static_cast<hipStream_t>(stream), idx, deg, out, n);
 }
 
+extern "C" int32_t legion_draw_distinct_batch(legion_stream_t stream, const int32_t* base, const int32_t* deg, int32_t f,
+                                              int32_t* out, int32_t n)
+{
+    if (f < 1 || f > LG_DISTINCT_MAX_FANOUT || n < 0) return -1;
+    lg::launch_draw_distinct_batch(static_cast<hipStream_t>(stream), base, deg, f, out, n);
+    return 0;
+}
+
 // One whole mini-batch in the op order of GPURunner::RunOnce / RunPreSc (SS/engine/server.cu:285-332)
 // without the IPC hand-off: what a Runner enqueues per batch, exposed for callers that own the
 // buffers themselves (tests, bench.py, an in-process trainer).
@@ -459,6 +474,15 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
 {
     if (!graph || !feature || !group || group->pools.empty()) { std::cout << "invalid storage ptr\n"; return; }
     if (n_active < 1 || n_active > (int32_t)group->pools.size()) n_active = (int32_t)group->pools.size();
+    // every lane samples with lane 0's mode (HopParams is shared by the launch): lanes that disagree are refused, and every lane's
+    // mode is fixed from here on (legion_pool_set_sample_replace)
+    for (int32_t i = 0; i < n_active; i++)
+        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace) {
+            printf("legion_hip: lanes of one group with different sampling modes; nothing enqueued\n");
+            for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
+            return;
+        }
+    for (int32_t i = 0; i < n_active; i++) group->pools[i]->sample_used = true;
     enqueue_lanes(static_cast<hipStream_t>(strm_hdl), reinterpret_cast<GraphStorage*>(graph),
                   reinterpret_cast<FeatureStorage*>(feature), cache_of(cache), group->d_lanes, n_active, group->pools[0],
                   group->iter_state, batch_size, counter0, dev_id, mode, false, fanout, hop_num, phase);

@@ -232,6 +232,19 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
                                      use_graph, LEGION_FEATURE_F32);
 }
 
+// every lane of every slot takes the mode; refused once any lane has sampled (a captured graph never mixes modes)
+extern "C" int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace)
+{
+    if (!p || (replace != 0 && replace != 1)) return -1;
+    for (Slot& sl : p->slots)
+        for (MemoryPool* mp : sl.pools)
+            if (mp->sample_used || (replace == 0 && mp->max_fanout > LG_DISTINCT_MAX_FANOUT)) return -1;
+    for (Slot& sl : p->slots)
+        for (MemoryPool* mp : sl.pools)
+            if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(mp), replace) != 0) return -1;
+    return 0;
+}
+
 static void slot_wait(LegionPipeline* p, Slot& sl)
 {
     if (!sl.busy) return;

@@ -114,6 +114,8 @@ static Placement place_table(const std::string& path, size_t bytes, bool want_hb
 static int32_t g_feature_dtype = LEGION_FEATURE_F32;
 // dtype of the rows the next server hands to its trainers (legion_server_set_feature_out_dtype; sampling_server --feature-out-dtype)
 static int32_t g_feature_out_dtype = LEGION_FEATURE_F32;
+// sampling mode of every pool the next server creates (legion_server_set_sample_replace; sampling_server --sample-replace)
+static int32_t g_sample_replace = 1;
 
 // The float32 `features` file (N x D) placed as bf16 rows of pitch P (legion_hip.h LEGION_FEATURE_BF16): N * P * 2 bytes in HBM
 // -- within the same budget as the other full tables -- or in mapped pinned host memory.  The file is read in slices of at most
@@ -460,6 +462,11 @@ public:
         lg_pool_alloc_private(memorypool_, local_dev_id_, total_num_nodes, batch_size, fanout.data(), hop_num,
                               float_feature_len_);
         num_ids_ = memorypool_->num_ids;
+        if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(memorypool_), g_sample_replace) != 0) {
+            printf("legion_hip: sampling without replacement takes fan-outs up to %d\n", LG_DISTINCT_MAX_FANOUT);
+            exit(EXIT_FAILURE);
+        }
+        if (g_sample_replace == 0) std::cout << "Sampling: without replacement\n";
         env->InitializeSamplesBuffer(batch_size, num_ids_, float_feature_len_, local_dev_id_, interbatch_concurrency_);
         current_pipe_ = 0;
         for (int i = 0; i < INTERBATCH_CON; i++) {
@@ -773,6 +780,7 @@ private:
                       << (as_view || memorypool_->feature_rows < memorypool_->num_ids ? " = 1.2 x the PreSC maximum" : "") << "); its tail rows were not gathered\n";
         if (bits & LG_ERR_TABLE_FULL) std::cout << "ERROR (gpu " << local_dev_id_ << "): a de-duplication bucket fits no LDS table\n";
         if (bits & LG_ERR_CHAIN) std::cout << "ERROR (gpu " << local_dev_id_ << "): unresolved first-touch chain\n";
+        if (bits & LG_ERR_SAMPLE_MODE) std::cout << "ERROR (gpu " << local_dev_id_ << "): a hop was not sampled (sampling mode)\n";
         std::cout << std::flush;
         // An unresolved bucket or chain means positions in this batch are garbage: it must not reach a trainer.
         // Same convention as every other device-side failure at this boundary (include/legion_hip.h, the reference's
@@ -780,7 +788,7 @@ private:
         // buffer stays a warning where the rows were gathered into the pipe slot's own buffer (ids, edges and the rows that fit
         // are correct; the reference overruns here, SS/engine/server.cu:277) -- but a VIEW of a lane's feature buffer with more
         // rows than the buffer has would show the trainer the neighbouring lane's arrays as rows: never posted.
-        if ((bits & (LG_ERR_TABLE_FULL | LG_ERR_CHAIN)) || (as_view && (bits & LG_ERR_FEATURE_ROWS))) {
+        if ((bits & (LG_ERR_TABLE_FULL | LG_ERR_CHAIN | LG_ERR_SAMPLE_MODE)) || (as_view && (bits & LG_ERR_FEATURE_ROWS))) {
             std::cout << "legion_hip: corrupt batch on gpu " << local_dev_id_ << ", not posted; stopping the server\n" << std::flush;
             // trainers blocked in sem_wait must not wait for ever: mark the mirror object (this build's trainer end checks it
             // after every wake-up and fails), wake every waiter, unlink the names -- then go (no destructors: other runner
@@ -878,6 +886,10 @@ private:
                                           fanout.data(), hop_num_, lanes_, slots_, lane_features ? feature_rows : 0, 1 | 16,
                                           g_feature_out_dtype);
         lg_set_pool_arena(nullptr);
+        if (pipe_ != nullptr && legion_pipeline_set_sample_replace(pipe_, g_sample_replace) != 0) {
+            printf("legion_hip: sampling without replacement takes fan-outs up to %d\n", LG_DISTINCT_MAX_FANOUT);
+            exit(EXIT_FAILURE);
+        }
         for (int pp = 0; pp < interbatch_concurrency_ && pp < INTERBATCH_CON; pp++)
             overflow_[pp] = overflow_bytes > 0 ? (float*)(arena_.base + arena_.bytes - (int64_t)(interbatch_concurrency_ - pp) * overflow_bytes) : nullptr;
         if (overflow_bytes > 0) {
@@ -1267,6 +1279,13 @@ extern "C" int32_t legion_server_set_feature_out_dtype(int32_t feature_out_dtype
 {
     if (feature_out_dtype != LEGION_FEATURE_F32 && feature_out_dtype != LEGION_FEATURE_BF16) return -1;
     g_feature_out_dtype = feature_out_dtype;
+    return 0;
+}
+
+extern "C" int32_t legion_server_set_sample_replace(int32_t replace)
+{
+    if (replace != 0 && replace != 1) return -1;
+    g_sample_replace = replace;
     return 0;
 }
 

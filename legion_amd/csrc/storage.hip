@@ -966,6 +966,8 @@ void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nod
     int64_t num_ids = batch_size, per = batch_size;         // server.cu:187-199
     mp->max_new.assign(1, batch_size);
     for (int i = 0; i < hop_num; i++) { per *= fanout[i]; num_ids += per; mp->max_new.push_back(per); }
+    mp->max_fanout = 0;
+    for (int i = 0; i < hop_num; i++) mp->max_fanout = std::max(mp->max_fanout, fanout[i]);
     if (num_ids >= ((int64_t)1 << 31) - 16384) {          // positions and slot indices are int32, as in the reference (operator_impl.cu:208)
         printf("legion_hip: batch %d with this fan-out needs %lld slots / %lld ids; the limit is 2^31\n", batch_size, (long long)per,
                (long long)num_ids);
@@ -1254,6 +1256,22 @@ extern "C" int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p_)
 {
     const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
     return mp ? mp->feature_out_dtype : -1;
+}
+
+// 1: sampling with replacement (default), 0: without (fan-outs up to LG_DISTINCT_MAX_FANOUT); only before the pool samples a hop
+extern "C" int32_t legion_pool_set_sample_replace(LegionMemoryPool* p_, int32_t replace)
+{
+    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
+    if (!mp || (replace != 0 && replace != 1) || mp->sample_used) return -1;
+    if (replace == 0 && mp->max_fanout > LG_DISTINCT_MAX_FANOUT) return -1;
+    mp->sample_replace = replace;
+    return 0;
+}
+
+extern "C" int32_t legion_pool_sample_replace(const LegionMemoryPool* p_)
+{
+    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
+    return mp ? mp->sample_replace : -1;
 }
 
 extern "C" void legion_pool_set_current_pipe(LegionMemoryPool* p_, int32_t pipe)

@@ -268,9 +268,12 @@ class MemoryPool:
             "cache_search_buffer": (9, torch.int32), "tmp_part_ind": (10, torch.int8),
             "tmp_part_off": (11, torch.int32), "position_map": (12, torch.int32), "node_slot": (13, torch.int32)}
 
-    def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1, feature_out_dtype="float32"):
+    def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1, feature_out_dtype="float32",
+                 replace=True):
         """feature_out_dtype: dtype of the rows the pool's gathers write ("float32" or "bfloat16": bf16[rows, D], the float32 row
-        rounded to nearest even, or a bf16 storage's rows verbatim), independent of the FeatureStorage's dtype."""
+        rounded to nearest even, or a bf16 storage's rows verbatim), independent of the FeatureStorage's dtype.
+        replace: as DGL's NeighborSampler keyword -- True samples with replacement (the reference's draw), False takes min(f, D)
+        distinct neighbours of each frontier entry (fan-outs up to 256)."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         self._lib = _libmod.load()
@@ -286,6 +289,7 @@ class MemoryPool:
                                                    self.float_feature_len, int(pipeline_depth))
         self.num_ids = int(self._lib.legion_pool_num_ids(self.handle))
         self.set_feature_out_dtype(feature_out_dtype)
+        self.set_replace(replace)
 
     @classmethod
     def _borrowed(cls, handle, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, feature_rows):
@@ -312,6 +316,17 @@ class MemoryPool:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {dtype!r}")
         if self._lib.legion_pool_set_feature_out_dtype(self.handle, FEATURE_DTYPES[dtype]) != 0:
             raise RuntimeError("legion_pool_set_feature_out_dtype: the feature buffer is already allocated")
+
+    @property
+    def replace(self):
+        return int(self._lib.legion_pool_sample_replace(self.handle)) == 1
+
+    def set_replace(self, replace):
+        """Only before the pool samples its first hop (the C ABI refuses it after: RuntimeError)."""
+        if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
+            raise ValueError(f"replace must be True or False, not {replace!r}")
+        if self._lib.legion_pool_set_sample_replace(self.handle, int(bool(replace))) != 0:
+            raise RuntimeError("legion_pool_set_sample_replace: the pool has sampled already, or a fan-out is above 256 without replacement")
 
     def alloc_features(self, rows):
         self.feature_rows = int(rows)
@@ -411,7 +426,8 @@ class Pipeline:
 
     def __init__(self, graph, feature, cache, dev_id, batch_size, fanout, group_size, feature_rows, use_graph=True,
                  slots=2, overlap=False, split=False, weave=False, arena=False,      # (split: accepted and ignored -- removed in round 5)
-                 feature_out_dtype="float32"):
+                 feature_out_dtype="float32", replace=True):
+        """replace: MemoryPool's (every lane samples with / without replacement)."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         self._lib = _libmod.load()
@@ -427,6 +443,15 @@ class Pipeline:
                                             feature.total_num_nodes, batch_size, fanout, feature.float_feature_len,
                                             feature_rows) for g in range(self.group_size)]
                       for s in range(self.slots)]
+        if not replace:
+            self.set_replace(False)
+
+    def set_replace(self, replace):
+        """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
+        if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
+            raise ValueError(f"replace must be True or False, not {replace!r}")
+        if self._lib.legion_pipeline_set_sample_replace(self.handle, int(bool(replace))) != 0:
+            raise RuntimeError("legion_pipeline_set_sample_replace: the pipeline has sampled already, or a fan-out is above 256 without replacement")
 
     def submit(self, counter0, mode=TRAINMODE, n_active=None):
         if n_active is None or n_active >= self.group_size:

@@ -115,7 +115,9 @@ def server_argv(gpu_number, cache_agg_mode, args):
     argv = [server_binary(), str(gpu_number), str(int(cache_agg_mode))] + [str(f) for f in parse_fanout(args.fanout)]
     flag = FEATURE_DTYPES[getattr(args, "feature_dtype", "float32")]
     out = FEATURE_DTYPES[getattr(args, "trainer_feature_dtype", "float32")]
-    return argv + (["--feature-dtype", flag] if flag else []) + (["--feature-out-dtype", out] if out else [])
+    argv += (["--feature-dtype", flag] if flag else []) + (["--feature-out-dtype", out] if out else [])
+    # --sample_replace 0 -> the binary's --sample-replace 0 (without replacement); 1 (the default) adds nothing
+    return argv + (["--sample-replace", "0"] if int(getattr(args, "sample_replace", 1)) == 0 else [])
 
 
 def parse_fanout(value):
@@ -140,6 +142,8 @@ def build_argparser():
     argparser.add_argument('--feature_dtype', type=str, default="float32", choices=sorted(FEATURE_DTYPES))
     # dtype of the rows the trainer receives (independent of the storage dtype): bfloat16 hands over bf16[n x D] rows
     argparser.add_argument('--trainer_feature_dtype', type=str, default="float32", choices=sorted(FEATURE_DTYPES))
+    # 1: neighbours drawn with replacement (the reference's draw); 0: without (DGL's replace=False), fan-outs up to 256
+    argparser.add_argument('--sample_replace', type=int, default=1, choices=[0, 1])
     return argparser
 
 

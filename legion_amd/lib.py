@@ -51,6 +51,8 @@ SIGNATURES = {
     "legion_pool_error": (c_i32, [c_p]),
     "legion_pool_set_feature_out_dtype": (c_i32, [c_p, c_i32]),
     "legion_pool_feature_out_dtype": (c_i32, [c_p]),
+    "legion_pool_set_sample_replace": (c_i32, [c_p, c_i32]),
+    "legion_pool_sample_replace": (c_i32, [c_p]),
     "legion_cache_create": (c_p, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "legion_cache_init_controller": (None, [c_p, c_i32]),
     "legion_cache_set_replica_memory": (None, [c_p, c_i64]),
@@ -92,6 +94,7 @@ SIGNATURES = {
     "legion_run": (c_i32, [P_I32, c_i32, c_i32, c_i32, c_i32]),
     "legion_server_set_feature_dtype": (c_i32, [c_i32]),
     "legion_server_set_feature_out_dtype": (c_i32, [c_i32]),
+    "legion_server_set_sample_replace": (c_i32, [c_i32]),
     "NewIPCEnv": (c_p, [c_i32]),
     "legion_ipc_coordinate": (None, [c_p, c_i32, P_I32, P_I32, P_I32, c_i32, c_i32]),
     "legion_ipc_train_step": (c_i32, [c_p]),
@@ -106,6 +109,7 @@ SIGNATURES = {
     "legion_enqueue_group": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),
     "legion_pipeline_create": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32]),
     "legion_pipeline_create_ex": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32]),
+    "legion_pipeline_set_sample_replace": (c_i32, [c_p, c_i32]),
     "legion_pipeline_submit": (c_i32, [c_p, c_i32, c_i32]),
     "legion_pipeline_submit_n": (c_i32, [c_p, c_i32, c_i32, c_i32]),
     "legion_enqueue_group_n": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),
@@ -127,6 +131,7 @@ SIGNATURES = {
     # 4. kernel-level
     "legion_gather_rows": (None, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_i32]),
     "legion_draw_batch": (None, [c_p, c_p, c_p, c_p, c_i32]),
+    "legion_draw_distinct_batch": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
