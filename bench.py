@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py -- sampled edges/s + feature-gather GB/s of the hot path on MI355X.
 
-    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR]
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
     (N > 1: python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...)
 
 A "step" is ONE LAUNCH GROUP through the whole hot path on one GPU: `batches_per_step` (= --group,
@@ -21,12 +21,15 @@ One process per GPU.  The path shards by seeds with no per-batch exchange; the o
 the one-time all-reduce (RCCL) of the PreSC hotness counters that sizes the caches.  Weak scaling:
 every rank runs K batches of B seeds; value = total sampled edges of all ranks / max-over-ranks time.
 
-Prints ONE JSON line (rank 0).  `roofline` is for the dominant kernel, the hop-2 gather:
+Prints ONE JSON line (rank 0).  A plain run does only what that line's headline needs: set-up, counting pass (the timed batches'
+edges), warm-up, the K timed steps, --dump-outputs, the line (`metric`, `value`, `unit`, `ms_per_step`, `dtype`, `config` ...).
+--full adds everything else below -- verification, the profiled pass, the legs behind the headline -- which takes minutes.
+`roofline` (--full) is for the dominant kernel, the hop-2 gather:
 achieved = rows * (8*D + 8) bytes / HIP-event time around that launch, summed over the timed steps.
 `roofline.unique_row_frac` says how many of that launch's rows are distinct (a repeat may be served by the
 256 MiB Infinity Cache); `roofline.cold` is the same launch over rows that never repeat (the HBM-only figure),
 `roofline.traffic` the FETCH_SIZE + WRITE_SIZE bytes per launch collected by child processes of this run.
-`other_shapes[0]` (N = 1, default command) is Legion's default batch size, B = 8000, on the same tables.
+`other_shapes[0]` (N = 1, --full at the default shape) is Legion's default batch size, B = 8000, on the same tables.
 `cpu_baseline` is the oracle's C restatement (oracle/, test infrastructure) timed on the host cores
 on a bounded sample of the same batches -- a reported baseline, not a target.
 The legs around the timed region (argument parsing, the boundary leg, the PMC children, the pieces run_leg strings
@@ -157,7 +160,7 @@ def main():
     stripe = args.stripe and world > 1
     head = run_leg(c, engine, synth, stripe, args.replica_memory if stripe else 0, headline=True)
     out = head["json"] if rank == 0 else None
-    if world > 1 and not stripe and not args.no_striped_leg:
+    if args.full and world > 1 and not stripe and not args.no_striped_leg:
         if rank == 0:
             one_line.arm(out, args.extra_legs_deadline)
         try:
@@ -187,8 +190,8 @@ def main():
             os._exit(1)
 
     # ---- N = 1, the default shape: Legion's default batch size on the same tables, driver-timed in the same run ----------------
-    # (like the boundary and traffic legs, part of the FULL default run only: --no-boundary, which every measurement script passes, skips it)
-    if world == 1 and not args.no_other_shapes and not args.no_boundary and args.placement == "hbm" and B == 1024 and args.nodes == 0 and not args.no_cache:
+    # (like the boundary and traffic legs, part of --full at the default shape only: --no-boundary skips it)
+    if args.full and world == 1 and not args.no_other_shapes and not args.no_boundary and args.placement == "hbm" and B == 1024 and args.nodes == 0 and not args.no_cache:
         out["other_shapes"] = []
         for sb, sf in ((8000, [25, 10]), (8000, [15, 10, 5])):      # Legion's default batch size at BASELINE's two fan-outs
             try:
@@ -203,14 +206,14 @@ def main():
 
     if rank == 0:
         try:
-            if world == 1 and not args.no_boundary and args.placement == "hbm":
+            if args.full and world == 1 and not args.no_boundary and args.placement == "hbm":
                 out.update(legs.boundary_leg(args, c.fanout))
                 one_line.refresh()
-            if args.cpu_seconds > 0 and world == 1:      # reported at N = 1 only
+            if args.full and args.cpu_seconds > 0 and world == 1:      # reported at N = 1 only
                 out["cpu_baseline"] = cpu_baseline(indptr, col, c.mine, N, B, c.fanout, c.n_warm, args.cpu_seconds,
                                                    features if args.placement == "hbm" else None)
                 one_line.refresh()
-            if world == 1 and not args.no_boundary and not args.no_traffic_leg and args.placement == "hbm":
+            if args.full and world == 1 and not args.no_boundary and not args.no_traffic_leg and args.placement == "hbm":
                 legs.measured_traffic(args, out["roofline"], c.G)
         except Exception as e:      # (an armed exit hook must not outlive the interpreter: see above)
             import traceback
@@ -243,7 +246,8 @@ def fail_as_requested(how):
 def run_leg(c, engine, synth, stripe, replica_memory, headline, bulk=False, shape_leg=False):
     """One cache layout over the resident workload: objects -> PreSC -> hotness all-reduce -> cost model -> fills -> pipeline ->
     counting pass -> warm-up -> timed regions -> eager pass with HIP events around the gathers (-> headline: the cold-row regather).
-    Returns {"json": rank 0's report of the leg}.  The headline leg also verifies; the extra legs are shorter.  shape_leg: another
+    Returns {"json": rank 0's report of the leg}.  Without --full only the headline leg runs, up to its timed regions and --dump-outputs;
+    with it the headline leg also verifies and profiles, and the extra legs are shorter.  shape_leg: another
     batch shape of the same workload on one GPU (`other_shapes`), reported in the extra legs' short form."""
     args, world, rank, dev, use_dist = c.args, c.world, c.rank, c.dev, c.use_dist
     if not headline and not shape_leg and args.fail_extra_leg and rank == 0:        # (tests of OneLine)
@@ -348,16 +352,20 @@ def run_leg(c, engine, synth, stripe, replica_memory, headline, bulk=False, shap
     # ---- counting pass, timed regions, the verification of what the last replay left, the profiled pass ---------------------------
     have_map = cache.node_capacity(d) > 0 and not args.no_cache
     node_map = cache.array("node_map", d) if have_map else torch.empty(0, dtype=torch.int32, device=dev)
-    counted = legs.counting_pass(c, synth, pipe, cache, d, node_map, feature_rows, headline or shape_leg, stripe, bulk)
+    counted = legs.counting_pass(c, synth, pipe, cache, d, node_map, feature_rows, (headline or shape_leg) and args.full, stripe, bulk)
     edges, rows, hop_edges, hop_slots = counted.edges, counted.rows, counted.hop_edges, counted.hop_slots
     timed = legs.timed_regions(c, engine, pipe, d, headline)
     elapsed_max = elapsed = timed.elapsed_max                        # (`elapsed`: the rank-0 sampler / gather split below)
-    if headline and not args.no_verify and timed.last_group is not None:
+    if headline and args.full and not args.no_verify and timed.last_group is not None:
         legs.verify_last_group(c, synth, pipe, counted, timed.last_group)
     if headline and rank == 0 and args.dump_outputs and timed.last_group is not None:
         slot, k0, n_lanes = timed.last_group                         # the last timed step is still in its slot
         legs.dump_outputs(args.dump_outputs, pipe.pools[slot][:n_lanes], k0)
-    prof, elapsed_profiled = legs.profiled_pass(c, pipe)
+    if args.full:
+        prof, elapsed_profiled = legs.profiled_pass(c, pipe)
+    else:                                                            # (a plain run: no per-kernel figures, no second pass)
+        legs.check_kernel_errors(pipe)
+        prof, elapsed_profiled = {}, 0.0
     state_bytes, lds_buckets = pipe.pools[0][0].state_bytes(), pipe.pools[0][0].lds_buckets()
 
     # ---- roofline of the dominant kernel: the last hop's gather (op 3H+1) -------------------------
@@ -379,7 +387,8 @@ def run_leg(c, engine, synth, stripe, replica_memory, headline, bulk=False, shap
                      float(rows[:, h + 1].sum()) * 8.0 for h in range(H))
     t_sampling = max(elapsed - t_all_gathers, 1e-9)
     per_rank = legs.per_rank_info(c, timed, counted, achieved, t_last, n_last, pipe, bulk) if use_dist else None
-    traffic_committed, traffic_committed_src, rocprof_us, rocprof_src = legs.committed_profiles(c, rows_last, n_last)
+    traffic_committed, traffic_committed_src, rocprof_us, rocprof_src = (legs.committed_profiles(c, rows_last, n_last) if args.full else
+                                                                         (None, None, None, None))
 
     out = None
     if rank == 0:
@@ -388,9 +397,9 @@ def run_leg(c, engine, synth, stripe, replica_memory, headline, bulk=False, shap
     # ---- the same launch alone and over rows that never repeat (a one-GPU run: the figure is about the kernel, not the job).  The
     #      headline's line exists by now: from here on it goes out even if an optional leg ends the process (a native exit() of the
     #      library, SIGTERM, a hang) -- this leg, the other shapes, the boundary, the CPU baseline and the traffic children follow. ----
-    if headline and world == 1 and rank == 0 and getattr(c, "one_line", None) is not None:
+    if headline and args.full and world == 1 and rank == 0 and getattr(c, "one_line", None) is not None:
         c.one_line.arm(out, args.post_legs_deadline)
-    if (headline or shape_leg) and world == 1 and not bulk and not args.no_cold_leg and (not args.no_boundary or args.cold_leg):
+    if (headline or shape_leg) and args.full and world == 1 and not bulk and not args.no_cold_leg and (not args.no_boundary or args.cold_leg):
         try:
             if headline and args.fail_extra_leg:             # (tests of the guard at N = 1: the first leg behind the headline fails this way)
                 fail_as_requested(args.fail_extra_leg)

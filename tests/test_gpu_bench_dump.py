@@ -32,6 +32,7 @@ def run_dump(out_dir):
 def test_exact_steps_and_the_last_steps_outputs(hip, tmp_path):
     d, out = run_dump(tmp_path / "a")
     assert d["steps"] == 3 and d["timed_region"]["repeats"] == 1 and d["ms_per_step"] > 0
+    assert "roofline" not in d and "sampling_only" not in d            # a run without --full: the headline and nothing beside it
     assert abs(d["ms_per_step"] / 1e3 * 3 - d["timed_region"]["median_s"]) < 1e-9
     assert sum(os.path.getsize(f) for f in glob.glob(str(tmp_path / "a" / "*.npy"))) <= legs.DUMP_BYTES
     assert all(a.dtype == (np.float32 if k == "float_features" else np.float64) for k, a in out.items())

@@ -43,7 +43,7 @@ def _last_json(text):
 def test_scale_command_line_two_ranks_on_one_gpu(hip, stripe):
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--backend", "gloo",
-           "--force-device", "0"] + SMALL + (["--stripe"] if stripe else [])
+           "--force-device", "0", "--full"] + SMALL + (["--stripe"] if stripe else [])
     res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     d = _last_json(res.stdout)
@@ -107,7 +107,8 @@ def test_scale_command_line_four_ranks_on_one_gpu(hip):
     (cache_agg_mode 2), stripes exchanged as IPC handles between four processes, the bulk leg's arenas mapped from file descriptors
     across four processes -- every leg completes and agrees with the others on what was gathered."""
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "4", "--master-addr", "127.0.0.1",
-           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--force-device", "0"] + SMALL
+           "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "4", "--backend", "gloo", "--force-device", "0",
+           "--full"] + SMALL
     res = subprocess.run(cmd, cwd=ROOT, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=900)
     assert res.returncode == 0, res.stderr[-4000:]
     d = _last_json(res.stdout)

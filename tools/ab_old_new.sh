@@ -16,7 +16,8 @@ PY
 for r in $(seq 1 $ROUNDS); do
   for side in old new; do
     D=$R; [ $side = old ] && D=$R/.old_r04
-    ( cd $D && timeout -k 5 600 python3 bench.py --cpu-seconds 0 --no-boundary --no-overlap-leg --no-verify "$@" > /tmp/ab_$side.json 2> /tmp/ab_$side.err < /dev/null )
+    FULL=--full; [ $side = old ] && FULL=          # (the round-4 tree's bench.py ran everything by default and has no --full)
+    ( cd $D && timeout -k 5 600 python3 bench.py $FULL --cpu-seconds 0 --no-boundary --no-overlap-leg --no-verify "$@" > /tmp/ab_$side.json 2> /tmp/ab_$side.err < /dev/null )
     line /tmp/ab_$side.json "$TAG $side r$r" | tee -a $OUT
   done
 done

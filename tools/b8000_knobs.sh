@@ -2,7 +2,7 @@
 # B = 8000 whole-job lines under a few arrangements, same box:  bash tools/b8000_knobs.sh  -> gpurun_out/b8000_knobs.txt
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.."; pwd)}; OUT=$R/gpurun_out/b8000_knobs.txt; : > $OUT
 run() { tag=$1; shift
-  timeout -k 5 600 python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify "$@" > /tmp/k.json 2> /tmp/k.err < /dev/null
+  timeout -k 5 600 python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify "$@" > /tmp/k.json 2> /tmp/k.err < /dev/null
   python3 - /tmp/k.json "$tag" <<'PY' | tee -a $OUT
 import json, sys
 try:

@@ -183,6 +183,11 @@ def parse_args():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=32, help="timed steps; a step = one launch group of --group mini-batches")
     ap.add_argument("--warmup", type=int, default=8, help="untimed warm-up steps (launch groups)")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beside the headline figure: verification, the profiled pass (roofline, sampling_only, "
+                         "feature_gather_GBps), cache hit rates, the cold regather, other shapes, boundary, CPU baseline, traffic children, "
+                         "the striped legs at N > 1 (the --no-* options below pick among them).  Without it a run sets up, warms up, times "
+                         "--steps steps, writes --dump-outputs and prints the headline line")
     ap.add_argument("--min-seconds", type=float, default=0.0,
                     help="repeat the K-step timed region until this much time has been measured (median reported); the default 0 "
                          "times exactly --steps steps once")
@@ -242,7 +247,7 @@ def parse_args():
                     help="skip the `other_shapes` legs (N = 1, the default shape only: B = 8000 at [25,10] and at [15,10,5] on the same tables, "
                          "--other-shapes-steps timed steps each, ~25 s each)")
     ap.add_argument("--other-shapes-steps", type=int, default=5)
-    ap.add_argument("--cold-leg", action="store_true", help="run roofline.cold / roofline.alone even with --no-boundary (they belong to the full default run)")
+    ap.add_argument("--cold-leg", action="store_true", help="run roofline.cold / roofline.alone even with --no-boundary (implies --full)")
     ap.add_argument("--no-cold-leg", action="store_true",
                     help="skip roofline.cold / roofline.alone (the last hop's gather launched again alone, and over rows that never repeat)")
     ap.add_argument("--boundary-modes", type=str, default="views,slab",
@@ -283,13 +288,17 @@ def parse_args():
                     help="N = 1: seconds the legs behind the headline leg (cold regather, other shapes, boundary, CPU baseline, traffic children; "
                          "~170 s when nothing hangs) may take together before the headline line goes out alone")
     ap.add_argument("--fail-extra-leg", type=str, default="", choices=["", "raise", "exit", "sigterm", "hang"],
-                    help="testing: make rank 0 fail this way when the first extra leg starts (the headline line must still go out)")
+                    help="testing: make rank 0 fail this way when the first extra leg starts (the headline line must still go out; "
+                         "implies --full)")
     ap.add_argument("--force-device", type=int, default=-1,
                     help="put every rank on this GPU (testing the N > 1 code path on a 1-GPU box, with --backend gloo)")
     ap.add_argument("--dump-outputs", type=str, default="", metavar="DIR",
                     help="after the timed steps, write what the headline leg's last timed step handed its caller as DIR/<name>.npy "
                          "(rank 0; at most 64 MB in all: see dump_outputs)")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.cold_leg or args.fail_extra_leg:        # asking for a leg behind the headline, or for one to fail, asks for those legs
+        args.full = True
+    return args
 
 
 def boundary_leg(args, fanout):
@@ -395,7 +404,7 @@ def measured_traffic(args, roof, G):
         shape += ["--nodes", str(args.nodes), "--edges", str(args.edges)]
     if args.scramble:
         shape += ["--scramble"]
-    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--presc-steps", "64", "--cpu-seconds", "0",
+    child = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--presc-steps", "64", "--cpu-seconds", "0",
              "--no-verify", "--no-boundary", "--no-other-shapes", "--no-cold-leg", "--min-seconds", "0.01"] + shape
     got, rows_child, note = {}, None, None
     tmp = tempfile.mkdtemp(prefix="legion_pmc_", dir="/tmp")
@@ -509,10 +518,10 @@ def hotness_collective(c, engine, cache, d, red_dev):
 
 
 def counting_pass(c, synth, pipe, cache, d, node_map, feature_rows, headline, stripe, bulk):
-    """Untimed, deterministic pass over exactly the timed batches: per batch its edges, rows per hop, slots per hop; over the first
-    launch group the hit rate and how many of the last hop's rows are DISTINCT (roofline.unique_row_frac: a row gathered by several
-    mini-batches of one launch may be served by the 256 MiB Infinity Cache the second time); the headline leg also verifies the
-    size-independent parity properties on the first batch."""
+    """Untimed, deterministic pass over exactly the timed batches: per batch its edges, rows per hop, slots per hop.  With --full also,
+    over the first launch group, the hit rate and how many of the last hop's rows are DISTINCT (roofline.unique_row_frac: a row gathered
+    by several mini-batches of one launch may be served by the 256 MiB Infinity Cache the second time); `headline` (passed only with
+    --full) also verifies the size-independent parity properties on the first batch."""
     args, H, D, G, n_timed, wrap, dev = c.args, c.H, c.D, c.G, c.n_timed, c.wrap, c.dev
     first = c.n_warm
     r = type("Counted", (), {})()
@@ -528,16 +537,22 @@ def counting_pass(c, synth, pipe, cache, d, node_map, feature_rows, headline, st
         cache.gather_stats3(d)                   # arms the row-source counters for this (untimed) pass only
     if bulk:
         pipe.count_rows = True
+    views = {}                                   # (slot, lane) -> the lane's two counters (the library's memory: fixed addresses)
     for k in range(n_timed):
         if k % G == 0:
             slot = pipe.submit((first + k) % wrap if wrap else first + k)
             pipe.wait(slot)
+            for lane, p in enumerate(pipe.pools[slot]):
+                if (slot, lane) not in views:
+                    views[slot, lane] = (p.buffer("node_counter"), p.buffer("edge_counter"))
+            # one copy per counter and group instead of two copies per batch
+            ncs = torch.stack([views[slot, lane][0] for lane in range(G)]).cpu().numpy()
+            ecs = torch.stack([views[slot, lane][1] for lane in range(G)]).cpu().numpy()
         pl = pipe.pools[slot][k % G]
-        nc = pl.buffer("node_counter").cpu().numpy()
-        ec = pl.buffer("edge_counter").cpu().numpy()
+        nc, ec = ncs[k % G], ecs[k % G]
         r.edges[k] = ec[9 + H]
         r.rows[k, 0] = nc[9]
-        if node_map.numel() > 0 and (args.placement == "pinned" or k < G):
+        if args.full and node_map.numel() > 0 and (args.placement == "pinned" or k < G):
             slots = node_map[pl.buffer("sampled_ids")[:int(nc[9 + H])].long()]
             hm = slots >= 0
             r.feat_hit_rows += int(hm.sum())
@@ -709,13 +724,18 @@ def profiled_pass(c, pipe):
     prof = pipe.profile_read()
     pipe.profile_end()
     prof = {op: (ms - warm.get(op, (0.0, 0))[0], cnt - warm.get(op, (0.0, 0))[1]) for op, (ms, cnt) in prof.items()}
-    err_bits = 0                              # LG_ERR_* bits a kernel raised for any lane (table full, feature rows, chain)
+    check_kernel_errors(pipe)
+    return prof, elapsed_profiled
+
+
+def check_kernel_errors(pipe):
+    """Raises if a kernel raised LG_ERR_* bits for any lane so far (table full, feature rows, chain): the figure of such a run is void."""
+    err_bits = 0
     for row in pipe.pools:
         for pl in row:
             err_bits |= pl.error()
     if err_bits:
         raise RuntimeError(f"a kernel raised error bits {err_bits:#x} during the run (legion_core.h LG_ERR_*)")
-    return prof, elapsed_profiled
 
 
 def cold_regather(c, pipe, node_map, bytes_per_row, repeats=7):
@@ -805,8 +825,9 @@ def per_rank_info(c, timed, counted, achieved, t_last, n_last, pipe, bulk):
     lk0, lk1 = timed.lk0, timed.lk1
     window_s = timed.t_lk1 - timed.t_lk0
     mine_info = {"rank": rank, "pci_bus_id": lk1["pci_bus_id"], "gpu_metrics_revision": lk1["gpu_metrics_revision"],
-                 "edges_per_sec": float(counted.edges.sum()) / max(timed.own_region, 1e-9),
-                 "gather_roofline_frac": achieved / HBM_PEAK_GBPS, "gather_avg_launch_us": t_last / max(n_last, 1) * 1e6}
+                 "edges_per_sec": float(counted.edges.sum()) / max(timed.own_region, 1e-9)}
+    if args.full:                                              # (from the profiled pass)
+        mine_info.update({"gather_roofline_frac": achieved / HBM_PEAK_GBPS, "gather_avg_launch_us": t_last / max(n_last, 1) * 1e6})
     if lk0["supported"] and lk1["supported"]:
         xr = lk1["xgmi_read_bytes"] - lk0["xgmi_read_bytes"]
         mine_info.update({"xgmi_read_bytes": xr, "xgmi_write_bytes": lk1["xgmi_write_bytes"] - lk0["xgmi_write_bytes"],
@@ -940,6 +961,18 @@ def leg_report(v):
                        "link_counters": args.link_counters,
                        "cost_model_counters": list(counters),
                        "hot_row_replica_rows": cache.replica_rows(d)},
+            "edges_per_step": float(edges.sum()) / args.steps, "rows_per_step": float(rows.sum()) / args.steps,
+            "edges_per_batch": float(edges.mean()), "rows_per_batch": float(rows.sum(axis=1).mean()),
+            "setup_seconds": setup_s,
+            "first_touch_state": {"form": "none per vertex: a hop's claims are de-duplicated bucket by bucket in LDS", "bytes_per_lane": state_bytes,
+                                  "lanes": G * args.slots, "lds_buckets_per_lane": lds_buckets},
+        }
+        if not args.full:      # a plain run: the headline figure and what it was measured on, nothing that takes work of its own
+            if collective is not None:
+                out["collective"] = collective
+                out["per_rank"] = per_rank
+            return out
+        out.update({
             "feature_gather_GBps": payload_gbps * 1.0,
             "feature_gather_GBps_note": "payload bytes read (rows*D*4) / HIP-event time of all gather launches, rank 0",
             "sampling_only": {"edges_per_sec": float(edges.sum()) / t_sampling, "algorithmic_GBps": samp_bytes / t_sampling / 1e9,
@@ -948,16 +981,11 @@ def leg_report(v):
                                       "arrangement the head of the next group runs hidden under this group's heavy kernels, so this is the "
                                       "sampler time that is NOT hidden); the sampling kernel is bound by the part's rate of random 128-byte requests, "
                                       "the de-duplication and compaction by their dependent chains: DESIGN.md section 4.2"},
-            "edges_per_step": float(edges.sum()) / args.steps, "rows_per_step": float(rows.sum()) / args.steps,
-            "edges_per_batch": float(edges.mean()), "rows_per_batch": float(rows.sum(axis=1).mean()),
             "seed_feature_cache_hits_step0": counted.hits,
             "roofline": roof,
-            "setup_seconds": setup_s,
-            "first_touch_state": {"form": "none per vertex: a hop's claims are de-duplicated bucket by bucket in LDS", "bytes_per_lane": state_bytes,
-                                  "lanes": G * args.slots, "lds_buckets_per_lane": lds_buckets},
             "feature_cache_hit_rate": counted.feat_hit_rows / max(counted.feat_hit_rows + counted.feat_miss_rows, 1),
             "feature_cache_hit_rate_over": "every timed batch" if args.placement == "pinned" else "the first timed step",
-        }
+        })
         if args.hybrid and counted.tiers is not None:
             t_cpu, t_gpu, t_miss = counted.tiers
             pcie_gbps = t_cpu / max(t_cpu + t_gpu + t_miss, 1) * float(rows.sum() * D * 4) / t_all_gathers / 1e9 if t_all_gathers > 0 else 0.0

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.."; pwd)}
 OUT=$R/gpurun_out/env_ab_$VAR.txt; mkdir -p $R/gpurun_out; : > $OUT
 for i in $(seq $N); do
   for v in $A $B; do
-    env $VAR=$v timeout -k 5 400 python3 $R/bench.py --no-boundary --no-overlap-leg --cpu-seconds 0 "$@" 2> /tmp/env_ab.err < /dev/null | tail -1 > /tmp/env_ab.json
+    env $VAR=$v timeout -k 5 400 python3 $R/bench.py --full --no-boundary --no-overlap-leg --cpu-seconds 0 "$@" 2> /tmp/env_ab.err < /dev/null | tail -1 > /tmp/env_ab.json
     python3 - $VAR $v >> $OUT <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ An arm is storage:out, each f32 or bf16: the dtype the feature table and caches 
 the dtype of the rows handed over (engine.MemoryPool / Pipeline feature_out_dtype).  Each child runs bench.py unchanged, with
 those constructors defaulting to the arm's dtypes (f32:f32 = bench.py as it is).  Children alternate the arms in the order
 given, --repeats times each; every child runs under its own time limit and the first failing child ends the run.  bench.py's
-own verification compares float32 rows with the float32 table, so every arm runs with --no-verify (the bf16 rows are covered
+own verification compares float32 rows with the float32 table, so every arm runs with --full --no-verify (the bf16 rows are covered
 by tests/test_gpu_feature_bf16.py and tests/test_gpu_feature_out_bf16.py).  Per arm the report gives ms/step (median, min,
 max), the last-hop gather's average launch time, and its algorithmic GB/s and fraction of the 8 TB/s peak at the arm's bytes
 per row (P = D rounded up to 8): f32:f32 8 D + 8, bf16:f32 2 P + 4 D + 8, bf16:bf16 2 P + 2 D + 8, f32:bf16 6 D + 8.
@@ -68,7 +68,7 @@ def main():
     for arm in arms:
         if len(arm.split(":")) != 2 or any(x not in DTYPES for x in arm.split(":")):
             ap.error(f"--arms: {arm!r} is not storage:out with f32 or bf16 on each side")
-    bench_args = argv[split + 1:] + ["--no-verify"]
+    bench_args = argv[split + 1:] + ["--full", "--no-verify"]
     D = 128
     for i, a in enumerate(bench_args):
         if a == "--dim":

@@ -36,7 +36,7 @@ for shape in $LIST; do
     tmp=/tmp/gpmc_${shape}_g$k
     rm -rf $tmp; mkdir -p $tmp
     t0=$(date +%s)
-    timeout -k 5 600 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $tmp -- python3 $R/bench.py $args $EXTRA_BENCH_ARGS --steps 2 --warmup 1 --presc-steps 64 --cpu-seconds 0 --no-verify --no-boundary --no-overlap-leg --min-seconds 0.01 > $tmp/bench.json 2> $tmp/err.txt < /dev/null
+    timeout -k 5 600 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $tmp -- python3 $R/bench.py --full $args $EXTRA_BENCH_ARGS --steps 2 --warmup 1 --presc-steps 64 --cpu-seconds 0 --no-verify --no-boundary --no-overlap-leg --min-seconds 0.01 > $tmp/bench.json 2> $tmp/err.txt < /dev/null
     rc=$?
     dst=$OUT/$shape/g$k
     mkdir -p $dst

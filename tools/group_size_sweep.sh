@@ -10,7 +10,7 @@ for s in $SHAPES; do
     rmat28) ARGS="--scale 28 --edge-factor 4 --dim 128 --batch 8000 --fanout 15,10,5" ;;
   esac
   for g in $GROUPS_; do
-    timeout -k 5 900 python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-overlap-leg --presc-steps 64 --steps 8 --warmup 2 --group $g $ARGS > $OUT/${s}_g$g.json 2> $OUT/${s}_g$g.err < /dev/null
+    timeout -k 5 900 python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-overlap-leg --presc-steps 64 --steps 8 --warmup 2 --group $g $ARGS > $OUT/${s}_g$g.json 2> $OUT/${s}_g$g.err < /dev/null
     python3 - $OUT/${s}_g$g.json ${s}_g$g <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ cd /tmp
 for rep in 1 2; do
 for v in base hot65536 hot262144 hot1048576 hot16777216; do
   if [ $v = base ]; then L=$R/legion_amd/liblegion_hip.so; else L=$R/tools/lds_tuning/variants/$v/liblegion_hip.so; fi
-  LEGION_HIP_LIB=$L timeout -k 5 300 python3 $R/bench.py --no-boundary --cold-leg --cpu-seconds 0 --no-verify --steps 20 --warmup 5 2> /tmp/ha.err < /dev/null | tail -1 > /tmp/ha.json
+  LEGION_HIP_LIB=$L timeout -k 5 300 python3 $R/bench.py --full --no-boundary --cold-leg --cpu-seconds 0 --no-verify --steps 20 --warmup 5 2> /tmp/ha.err < /dev/null | tail -1 > /tmp/ha.json
   python3 - $v >> $OUT <<'PY'
 import json, sys
 try:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for r in $(seq 1 $ROUNDS); do
   for v in $VARS; do
     LIBV=""; [ $v != v0 ] && LIBV=$R/tools/lds_tuning/variants/$v/liblegion_hip.so
-    LEGION_HIP_LIB=$LIBV timeout -k 5 400 python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 "$@" > /tmp/ab.json 2> /tmp/ab.err < /dev/null
+    LEGION_HIP_LIB=$LIBV timeout -k 5 400 python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 "$@" > /tmp/ab.json 2> /tmp/ab.err < /dev/null
     python3 - "$TAG $v" <<'PY' | tee -a $OUT
 import json, sys
 try:

@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 for v in $VARS; do
   LIBV=""; [ $v != v0 ] && LIBV=$R/tools/lds_tuning/variants/$v/liblegion_hip.so
   rm -rf /tmp/tlv
-  LEGION_HIP_LIB=$LIBV timeout -k 5 600 rocprofv3 --kernel-trace --marker-trace --output-format csv -d /tmp/tlv -- python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --steps 8 --warmup 2 --min-seconds 0.3 "$@" > /tmp/lv.json 2> /tmp/lv.err < /dev/null
+  LEGION_HIP_LIB=$LIBV timeout -k 5 600 rocprofv3 --kernel-trace --marker-trace --output-format csv -d /tmp/tlv -- python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --steps 8 --warmup 2 --min-seconds 0.3 "$@" > /tmp/lv.json 2> /tmp/lv.err < /dev/null
   python3 $R/tools/trace_group.py /tmp/tlv /tmp/lv.md > /dev/null 2>&1
   python3 - /tmp/lv.json "$TAG $v" /tmp/lv.md <<'PY' | tee -a $OUT
 import json, sys

@@ -10,7 +10,7 @@ for rep in 1 2; do
 for v in base ntcold262144 ntcold1048576 ntcold4194304 ntcold1073741824; do
   if [ $v = base ]; then L=$R/legion_amd/liblegion_hip.so; else L=$R/tools/lds_tuning/variants/$v/liblegion_hip.so; fi
   for shape in "" "--batch 8000"; do
-  LEGION_HIP_LIB=$L timeout -k 5 300 python3 $R/bench.py --no-boundary --cold-leg --cpu-seconds 0 --steps 20 --warmup 5 $shape 2> /tmp/nc.err < /dev/null | tail -1 > /tmp/nc.json
+  LEGION_HIP_LIB=$L timeout -k 5 300 python3 $R/bench.py --full --no-boundary --cold-leg --cpu-seconds 0 --steps 20 --warmup 5 $shape 2> /tmp/nc.err < /dev/null | tail -1 > /tmp/nc.json
   python3 - $v "$shape" >> $OUT <<'PY'
 import json, sys
 try:

@@ -8,7 +8,7 @@ mkdir -p $R/gpurun_out/r06; : > $OUT
 cd /tmp && export TMPDIR=/tmp
 for grp in "FETCH_SIZE" "WRITE_SIZE" "TCC_HIT_sum TCC_MISS_sum"; do
   d=/tmp/pmc_cw_$(echo $grp | cut -d' ' -f1); rm -rf $d; mkdir -p $d
-  timeout -k 5 500 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $d -- python3 $R/bench.py --steps 2 --warmup 1 --presc-steps 64 \
+  timeout -k 5 500 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $d -- python3 $R/bench.py --full --steps 2 --warmup 1 --presc-steps 64 \
       --cpu-seconds 0 --no-verify --no-boundary --cold-leg --min-seconds 0.01 > $d/bench.json 2> $d/err.txt < /dev/null
   python3 - $d "$grp" >> $OUT <<'PY'
 import csv, glob, sys, collections

@@ -11,7 +11,7 @@ for grp in "SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_LDS" "FETCH_SIZE" "
            "SQ_INSTS_VALU SQ_INSTS_VMEM SQ_INSTS_LDS SQ_INSTS_SALU" "SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_LDS_ADDR_CONFLICT SQ_LDS_ATOMIC_RETURN"; do
   i=$((i+1))
   mkdir -p $OUT/g$i
-  timeout -k 5 500 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/g$i -- python3 $R/bench.py --steps 2 --warmup 1 --presc-steps 64 \
+  timeout -k 5 500 rocprofv3 --kernel-trace --pmc $grp --output-format csv -d $OUT/g$i -- python3 $R/bench.py --full --steps 2 --warmup 1 --presc-steps 64 \
       --cpu-seconds 0 --no-verify --no-boundary --no-overlap-leg --min-seconds 0.01 "$@" > $OUT/g$i/bench.json 2> $OUT/g$i/err.txt < /dev/null
   echo "group $i ($grp) rc=$?"
   find $OUT/g$i -name "*agent_info.csv" -delete

@@ -2,9 +2,9 @@
 # The light stream's priority (LegionTuning.weave_priority: -1 low, 0 equal) over several shapes, alternating, one box -> gpurun_out/priority_ab.txt
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.."; pwd)}; OUT=$R/gpurun_out/priority_ab.txt; : > $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --steps 20 --warmup 5 > /dev/null 2>&1
+python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --steps 20 --warmup 5 > /dev/null 2>&1
 one() { tag=$1; v=$2; shift; shift
-  LEGION_WEAVE_PRIORITY=$v timeout -k 5 400 python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 "$@" 2> /dev/null < /dev/null > /tmp/pa.json
+  LEGION_WEAVE_PRIORITY=$v timeout -k 5 400 python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 "$@" 2> /dev/null < /dev/null > /tmp/pa.json
   python3 - "$tag priority=$v" <<'PY' | tee -a $OUT
 import json, sys
 d = json.loads(open("/tmp/pa.json").read().strip().splitlines()[-1])

@@ -3,9 +3,9 @@
 #   bash tools/sample_grid_sweep.sh   -> gpurun_out/sample_grid_sweep.txt
 R=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.."; pwd)}; OUT=$R/gpurun_out/sample_grid_sweep.txt; : > $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --steps 20 --warmup 5 > /dev/null 2>&1
+python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --steps 20 --warmup 5 > /dev/null 2>&1
 one() { tag=$1; v=$2; shift; shift
-  LEGION_SAMPLE_MAX_WG=$v timeout -k 5 300 python3 $R/bench.py --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 --steps 20 --warmup 5 "$@" 2> /dev/null < /dev/null > /tmp/sg.json
+  LEGION_SAMPLE_MAX_WG=$v timeout -k 5 300 python3 $R/bench.py --full --cpu-seconds 0 --no-boundary --no-verify --min-seconds 0.5 --steps 20 --warmup 5 "$@" 2> /dev/null < /dev/null > /tmp/sg.json
   python3 - "$tag max_wg=$v" <<'PY' | tee -a $OUT
 import json, sys
 d = json.loads(open("/tmp/sg.json").read().strip().splitlines()[-1])

@@ -6,7 +6,7 @@
 An arm is `replace` (engine.MemoryPool / Pipeline replace=True: bench.py as it is) or `distinct` (those constructors defaulting to
 replace=False).  Each child runs bench.py unchanged; children alternate the arms in the order given, --repeats times each; every child
 runs under its own time limit and the first failing child ends the run.  bench.py's verification replays the oracle's draw with
-replacement, so every arm runs with --no-verify (the distinct batches are covered by tests/test_gpu_sample_distinct.py).  Per arm the
+replacement, so every arm runs with --full --no-verify (the distinct batches are covered by tests/test_gpu_sample_distinct.py).  Per arm the
 report gives ms/step and the sampler chain's time per step (median, min, max): edges_per_step over bench.py's
 sampling_only.edges_per_sec, i.e. the timed region minus the HIP-event time of every gather, over the step's sampled edges."""
 import argparse
@@ -55,7 +55,7 @@ def main():
     for arm in arms:
         if arm not in ARMS:
             ap.error(f"--arms: {arm!r} is not one of {sorted(ARMS)}")
-    bench_args = argv[split + 1:] + ["--no-verify"]
+    bench_args = argv[split + 1:] + ["--full", "--no-verify"]
     runs = {arm: [] for arm in arms}
     for rep in range(args.repeats):
         for arm in arms:

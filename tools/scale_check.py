@@ -1,7 +1,7 @@
 """Reads the bench line(s) of an N > 1 run (the driver's SCALE_rNN.json, a file of JSON lines, or stdin) and checks that what ran is
 what DESIGN.md section 6 says runs -- so that the first 8-GPU record can be judged the day it exists:
 
-    python tools/scale_check.py SCALE_r05.json            # or:  python bench.py --gpus 2 ... | python tools/scale_check.py -
+    python tools/scale_check.py SCALE_r05.json            # or:  python bench.py --gpus 2 --full ... | python tools/scale_check.py -
 
 For every line with n_gpus > 1:
   * `collective.world_size_seen_by_all_reduce == n_gpus` and `collective.issued_by` names the library (RCCL issued by liblegion_hip,
@@ -111,7 +111,9 @@ def main():
     for n in sorted(by_n):
         ln = by_n[n]
         D = int(str(ln["config"]["workload"]).split("[N x ")[1].split("]")[0]) if "[N x " in str(ln["config"].get("workload", "")) else 128
-        print(f"---- n_gpus = {n}: {ln['value'] / 1e9:.2f} G edges/s, gather {ln['roofline']['frac']:.3f} of the HBM peak")
+        frac = (ln.get("roofline") or {}).get("frac")
+        print(f"---- n_gpus = {n}: {ln['value'] / 1e9:.2f} G edges/s, " +
+              (f"gather {frac:.3f} of the HBM peak" if frac is not None else "no roofline (a bench run without --full)"))
         if n == 1:
             continue
         rep.check(ln.get("scaling") == "weak", f"N={n}: scaling declared {ln.get('scaling')!r}")
