@@ -97,7 +97,8 @@ def test_conversion_keeps_nans(hip):
 
 
 # ---- 2. parity through the C ABI -------------------------------------------------------------------------------------------
-CASES = [(D, cache, fanout) for i, D in enumerate([1, 4, 7, 100, 128, 256, 602, 1024])
+CASES = [(D, cache, fanout) for i, D in enumerate([1, 4, 7, 100, 128, 256, 602, 1024,
+                                                   2049, 2056, 4096])      # more than 256 chunks a row: pitch / 8, (D + 7) / 8 > 256
          for j, cache in enumerate(["none", "partial", "whole"])
          for fanout in [[[6], [5, 4], [4, 3, 2]][(i + j) % 3]]]
 

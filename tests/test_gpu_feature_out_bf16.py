@@ -97,6 +97,10 @@ CASES = [(storage, D, cache, fanout) for storage in ("float32", "bfloat16")
          for i, D in enumerate([1, 4, 7, 100, 128, 256, 602, 1024])
          for j, cache in enumerate(["none", "partial", "whole"])
          for fanout in [[[6], [5, 4], [4, 3, 2]][(i + j) % 3]]]
+CASES += [(storage, D, cache, fanout) for storage in ("float32", "bfloat16")      # more than 256 chunks a row: pitch / 8,
+          for i, D in enumerate([2049, 2056, 4096], start=8)                      # (D + 7) / 8 > 256 (after the cases above,
+          for j, cache in enumerate(["none", "partial", "whole"])                 # whose ids stay as they were)
+          for fanout in [[[6], [5, 4], [4, 3, 2]][(i + j) % 3]]]
 
 
 @pytest.mark.parametrize("storage,D,cache,fanout", CASES)

@@ -57,9 +57,10 @@ def test_draw_dense_slots_all_small_degrees(hip, oracle):
     assert np.array_equal(out.cpu().numpy(), want)
 
 
-@pytest.mark.parametrize("D", [100, 128, 256, 602, 7, 4, 1, 1024])
+@pytest.mark.parametrize("D", [100, 128, 256, 602, 7, 4, 1, 1024,
+                               1026, 1028, 1030, 2048, 4099])      # more than 256 chunks a row (C > LG_GATHER_THREADS), tails of 2 and 3
 def test_gather_rows(hip, D):
-    N, cap, Kg = 5000, 700, 2
+    N, cap, Kg = (5000 if D <= 1024 else 3000), 700, 2
     rng = np.random.RandomState(D)
     table = synth.features_numpy(0, N, D, 7)
     node_map = np.full(N, -2, dtype=np.int32)
