@@ -10,19 +10,19 @@
 //     0 <= g < cpu_cap : dst[off + r] = cpu_cache[g]                (hit in the mapped pinned CPU cache)
 //     g >= cpu_cap     : dst[off + r] = gpu_cache[(g - cpu_cap) % gpu_cap]
 //     g <  0           : left to the storage tier (the full table when one is bound, else the row is not written)
-// Rows are copied verbatim (byte-identical, no arithmetic).
+// Rows are copied verbatim (byte-identical, no arithmetic), or converted by the row format (GatherRow below).
 //
 // The reference runs one thread per float on a fixed 32x1024 grid with a 64-bit div/mod per
-// element.  Here a workgroup owns a tile of 64 consecutive output rows: 64 lanes resolve the
+// element.  Here a workgroup owns a tile of ROWS consecutive output rows (gather_plan.h): ROWS lanes resolve the
 // tile's ids to source row pointers once (the id->slot table is direct mapped, one 4-byte read)
 // and park them in LDS; then all 256 lanes stream the tile as 16-byte chunks, four independent
 // loads in flight per lane, so that consecutive lanes read consecutive 16 B of one source row
 // and write consecutive 16 B of the (contiguous) destination.  No divides in the copy loop.
 //
-// Roofline: HBM.  Algorithmic bytes per row = 8*D + 8 (D*4 read + D*4 written + id + index); with bf16 sources
-// (GatherParams.dtype, the Bf16x8 instances) 2*P + 4*D + 8, P = D rounded up to 8; with bf16 output rows
-// (GatherParams.out_dtype) 2*P + 2*D + 8 from bf16 sources (Bf16Copy), 6*D + 8 from float32 ones (F32Narrow).
+// Roofline: HBM.  Algorithmic bytes per row = 8*D + 8 for float32 rows (D*4 read + D*4 written + id + index); the bf16 formats'
+// are on their GatherRow.
 #include "legion_core.h"
+#include "gather_plan.h"
 
 #include <cstdlib>
 #include <cstring>
@@ -30,9 +30,7 @@
 
 namespace lg {
 
-#define LG_GATHER_ROWS 64
 #define LG_GATHER_THREADS 256
-#define LG_GATHER_UNROLL 4
 
 // ------------------------------------------------------------------------------------------
 // Hand-over of a finished mini-batch from a lane of a launch group to one of the two trainer-visible pipe
@@ -91,51 +89,108 @@ void launch_deliver(hipStream_t s, const LanePtrs* d_lane, const DeliverParams& 
     hipCheckError();
 }
 
-// VecT: float4 for rows that are multiples of 16 bytes; `v4u` -- the same 16 bytes per lane at 4-byte alignment -- for every other
-// width of at least 4 floats (gfx950 global loads / stores of 16 bytes need dword alignment only; the compiler emits
-// global_load_dwordx4 for both), with the D % 4 trailing floats of each row moved by a scalar pass (TAIL); float below that.
-//
-// A workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its lane and keeps the walk software-pipelined: while
-// tile t is being copied, the first ROWS threads already hold the ids of tile t+1 (loaded one step earlier), have its
-// slot lookups (node_map[id], the one scattered read of the resolve) in flight together with the copy's loads, and fetch the
-// ids of tile t+2.  The copy of a tile therefore never waits for its own resolve chain (id -> slot -> pointer): with one tile
-// per workgroup that chain was 40 % of a workgroup's life during which it streamed nothing.  Loads of the copy loop are
-// unconditional (a missing row reads the destination instead, chunks past the tile's end re-read its last chunk), so no
-// branch sits between the prefetch and the copy and all of them are in flight together; only the stores are predicated.
-#ifndef LG_GATHER_MIN_WAVES
-#define LG_GATHER_MIN_WAVES 8        // waves per SIMD the register allocation must leave room for
-#endif
-#ifndef LG_GATHER_TARGET_WG
-#define LG_GATHER_TARGET_WG 8192     // workgroups of a full launch: four rounds of what is resident, so the dispatcher evens out lanes of different length
-#endif
-// bf16 sources (LEGION_FEATURE_BF16): VecT = Bf16x8, 16 bytes = 8 bf16 elements of a source row of pitch P per lane and chunk,
-// widened to 32 bytes of float32 (bits << 16, exact) and stored as two dword-aligned 16-byte stores -- output rows are 4*D bytes,
-// so at any D they are only dword aligned, as on the v4u path.  The last chunk of a row with D % 8 != 0 stores its first D % 8
-// elements one by one (the source's pad elements are never stored), so every D takes the same instance and no TAIL pass.  A
-// missing row loads a 16-byte zero line instead of the destination (a destination row of D < 4 is shorter than a chunk).
+// Row formats (gather_plan.h): gather_kernel<VecT, ROWS, UNROLL, TAIL, LASTOP> takes the loads and stores of its rows from
+// GatherRow<VecT, TAIL>, keyed on its own template arguments so that the instances keep their names.
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+// float32 -> float32 (F32, F32Tail: VecT = f32x4; F32Scalar: float), rows copied verbatim.  F32Tail (D = 602: 2408-byte rows) moves
+// the same 16 bytes per lane at 4-byte alignment -- gfx950 global loads / stores of 16 bytes need dword alignment only; the compiler
+// emits global_load_dwordx4 for both -- and the D % 4 trailing floats of each row in the kernel's TAIL pass (0.65 of peak at D = 602,
+// instead of the 8- / 4-byte vector paths of rounds 1-2).  Its VecT is F32's: an aligned(4) typedef does not survive as a template
+// argument (both mangle as Dv4_f), so TAIL alone tells the two apart.
+template <typename VecT, bool TAIL> struct GatherRow {
+    static_assert(std::is_same<VecT, f32x4>::value || std::is_same<VecT, float>::value, "float32 rows; bf16 rows have no TAIL pass");
+    typedef float Out;
+    static __device__ int32_t chunks(const GatherParams& gp) { return gp.D / (int32_t)(sizeof(VecT) / sizeof(float)); }
+    static __device__ const LG_G float* row_at(const GatherParams& gp, const float* base, int64_t x) { return LG_GPTR(const float, base) + x * gp.D; }
+    static __device__ VecT load(const LG_G float* p, bool, LG_G float* dst_tile, int32_t r, int32_t c, int32_t D)
+    {
+        if (p == nullptr) p = dst_tile + (int64_t)r * D;     // id < 0: nothing to fetch; read what is there
+        return ((const LG_G VecT*)p)[c];      // plain loads: measured 74% of HBM peak vs 63% nontemporal
+    }
+    static __device__ void store(const VecT& v, bool ok, LG_G float* dst_tile, int32_t r, int32_t c, int32_t D)
+    {
+        if (ok) __builtin_nontemporal_store(v, (LG_G VecT*)(dst_tile + (int64_t)r * D) + c);     // write-once output: nontemporal stores
+    }
+};
+
+// bf16 source rows (LEGION_FEATURE_BF16 storage) of pitch P: 16 bytes = 8 elements per chunk.  A missing row loads a 16-byte zero line
+// instead of the destination (a destination row of D < 4 is shorter than a chunk).
 struct Bf16x8 {
     typedef uint32_t u4 __attribute__((ext_vector_type(4)));
     u4 w;
 };
+struct Bf16Copy : Bf16x8 {};
 __device__ __attribute__((aligned(16))) Bf16x8 lg_gather_zero_line;
-// bf16 OUTPUT rows (GatherParams.out_dtype = LEGION_FEATURE_BF16): D bf16 elements per row, stride D, no pad.  A chunk is 8
-// elements, 16 bytes of output.  Bf16Copy: bf16 source of pitch P, the stored bits copied verbatim (16-byte load, 16-byte
-// store).  F32Narrow: float32 source of D floats, two dword-aligned 16-byte loads narrowed with bf16_rne_bits (the integer
-// path of convert_f32_to_bf16_kernel, not v_cvt_pk_bf16_f32) -- a row's partial last chunk loads only its D % 8 floats, as
-// the row may be the table's last.  Output rows are 2*D bytes: with D even a full chunk is one dword-aligned 16-byte store
-// (16-byte aligned when D % 8 == 0), a partial one stores its dwords one by one; with D odd rows are only 2-byte aligned and
-// every element is stored on its own (correct, not fast).  A missing row loads the zero line and stores nothing.
-struct Bf16Copy {
-    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-    u4 w;
+template <typename VecT, typename OutT> struct GatherRowBf16Src {
+    typedef OutT Out;
+    static __device__ int32_t chunks(const GatherParams& gp) { return gp.pitch / 8; }
+    static __device__ const LG_G float* row_at(const GatherParams& gp, const float* base, int64_t x)
+    {
+        return (const LG_G float*)(LG_GPTR(const uint16_t, (const uint16_t*)base) + x * gp.pitch);
+    }
+    static __device__ VecT load(const LG_G float* p, bool has, LG_G Out*, int32_t, int32_t c, int32_t)
+    {
+        VecT v;
+        v.w = has ? ((const LG_G VecT*)p)[c].w : LG_GPTR(const Bf16x8, &lg_gather_zero_line)->w;
+        return v;
+    }
 };
-struct F32Narrow {
-    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
-    v4u a, b;
+
+// bf16 -> float32: a chunk's 8 elements widened to 32 bytes of float32 (bits << 16, exact) and stored as two dword-aligned 16-byte
+// stores -- output rows are 4*D bytes, so at any D they are only dword aligned, as in F32Tail.  The last chunk of a row with D % 8 != 0
+// stores its first D % 8 elements one by one (the source's pad elements are never stored), so every D takes the same instance and no
+// TAIL pass.  Algorithmic bytes per row 2*P + 4*D + 8, P = D rounded up to 8.
+template <> struct GatherRow<Bf16x8, false> : GatherRowBf16Src<Bf16x8, float> {
+    static __device__ void store(const Bf16x8& v, bool ok, LG_G float* dst_tile, int32_t r, int32_t c, int32_t D)
+    {
+        typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
+        typedef Bf16x8::u4 u4;
+        const u4 lo = v.w << 16, hi = v.w & 0xFFFF0000u;      // elements 2k, 2k+1 of the chunk
+        const int32_t e0 = c * 8;
+        LG_G float* d = dst_tile + (int64_t)r * D + e0;
+        if (ok && e0 + 8 <= D) {
+            __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.x, hi.x, lo.y, hi.y}), (LG_G v4u*)d);
+            __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.z, hi.z, lo.w, hi.w}), (LG_G v4u*)d + 1);
+        } else if (ok) {                               // the partial last chunk of a row: D - e0 < 8 elements
+            const uint32_t f[8] = {lo.x, hi.x, lo.y, hi.y, lo.z, hi.z, lo.w, hi.w};
+#pragma unroll
+            for (int k = 0; k < 8; k++)
+                if (e0 + k < D) d[k] = __uint_as_float(f[k]);
+        }
+    }
 };
-template <typename VecT> struct GatherFormat {
-    static constexpr bool SRC_BF16 = std::is_same<VecT, Bf16x8>::value || std::is_same<VecT, Bf16Copy>::value;
-    static constexpr bool OUT_BF16 = std::is_same<VecT, Bf16Copy>::value || std::is_same<VecT, F32Narrow>::value;
+
+// bf16 OUTPUT rows (GatherParams.out_dtype = LEGION_FEATURE_BF16): D elements per row, stride D, no pad; a chunk is 8 elements, 16
+// bytes of output, w[k] its elements 2k (low half) and 2k+1 (high half).  Output rows are 2*D bytes: with D even a full chunk is one
+// dword-aligned 16-byte store (16-byte aligned when D % 8 == 0), a partial one stores its dwords one by one; with D odd rows are only
+// 2-byte aligned and every element is stored on its own (correct, not fast).
+__device__ __forceinline__ void gather_store_bf16(const uint32_t (&w)[4], bool ok, LG_G uint16_t* dst_tile, int32_t r, int32_t c, int32_t D)
+{
+    typedef uint32_t u4u __attribute__((ext_vector_type(4), aligned(4)));
+    const int32_t e0 = c * 8;
+    LG_G uint16_t* d = dst_tile + (int64_t)r * D + e0;
+    if (ok && (D & 1) == 0) {                      // dword-aligned rows
+        if (e0 + 8 <= D) {
+            __builtin_nontemporal_store(u4u{w[0], w[1], w[2], w[3]}, (LG_G u4u*)d);
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; k++)
+                if (e0 + 2 * k < D) ((LG_G uint32_t*)d)[k] = w[k];
+        }
+    } else if (ok) {                               // odd D: 2-byte aligned rows
+#pragma unroll
+        for (int k = 0; k < 8; k++)
+            if (e0 + k < D) d[k] = (uint16_t)(w[k >> 1] >> ((k & 1) * 16));
+    }
+}
+
+// bf16 -> bf16: the stored bits copied verbatim (16-byte load, 16-byte store).  A missing row stores nothing.  Algorithmic bytes per
+// row 2*P + 2*D + 8.
+template <> struct GatherRow<Bf16Copy, false> : GatherRowBf16Src<Bf16Copy, uint16_t> {
+    static __device__ void store(const Bf16Copy& v, bool ok, LG_G uint16_t* dst_tile, int32_t r, int32_t c, int32_t D)
+    {
+        gather_store_bf16({v.w.x, v.w.y, v.w.z, v.w.w}, ok, dst_tile, r, c, D);
+    }
 };
 // torch's float32 -> bfloat16 rounding (kernels_cache.hip bf16_rne_bits: round to nearest even, NaNs kept quiet NaNs)
 __device__ __forceinline__ uint32_t gather_bf16_rne(float f)
@@ -145,16 +200,67 @@ __device__ __forceinline__ uint32_t gather_bf16_rne(float f)
     return (u + 0x7FFFu + ((u >> 16) & 1u)) >> 16;
 }
 
+// float32 -> bf16: a source row of D floats, two dword-aligned 16-byte loads per chunk narrowed with gather_bf16_rne (the integer
+// path of convert_f32_to_bf16_kernel, not v_cvt_pk_bf16_f32).  A row's partial last chunk loads only its D % 8 floats, as the row may
+// be the table's last.  A missing row loads zeros and stores nothing.  Algorithmic bytes per row 6*D + 8.
+struct F32Narrow {
+    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
+    v4u a, b;
+};
+template <> struct GatherRow<F32Narrow, false> {
+    typedef uint16_t Out;
+    typedef F32Narrow::v4u v4u;
+    static __device__ int32_t chunks(const GatherParams& gp) { return (gp.D + 7) / 8; }
+    static __device__ const LG_G float* row_at(const GatherParams& gp, const float* base, int64_t x) { return LG_GPTR(const float, base) + x * gp.D; }
+    static __device__ F32Narrow load(const LG_G float* p, bool, LG_G uint16_t*, int32_t, int32_t c, int32_t D)
+    {
+        F32Narrow v;
+        const int32_t e0 = c * 8;
+        if (p == nullptr) {
+            v.a = v.b = v4u{0.f, 0.f, 0.f, 0.f};
+        } else if (e0 + 8 <= D) {
+            v.a = ((const LG_G v4u*)(p + e0))[0];
+            v.b = ((const LG_G v4u*)(p + e0))[1];
+        } else {                                          // the partial last chunk: no load past the row's end
+            float f[8];
+#pragma unroll
+            for (int k = 0; k < 8; k++) f[k] = e0 + k < D ? p[e0 + k] : 0.f;
+            v.a = v4u{f[0], f[1], f[2], f[3]};
+            v.b = v4u{f[4], f[5], f[6], f[7]};
+        }
+        return v;
+    }
+    static __device__ void store(const F32Narrow& v, bool ok, LG_G uint16_t* dst_tile, int32_t r, int32_t c, int32_t D)
+    {
+        gather_store_bf16({gather_bf16_rne(v.a.x) | (gather_bf16_rne(v.a.y) << 16), gather_bf16_rne(v.a.z) | (gather_bf16_rne(v.a.w) << 16),
+                           gather_bf16_rne(v.b.x) | (gather_bf16_rne(v.b.y) << 16), gather_bf16_rne(v.b.z) | (gather_bf16_rne(v.b.w) << 16)},
+                          ok, dst_tile, r, c, D);
+    }
+};
+
+// A workgroup walks the tiles blockIdx.x, blockIdx.x + gridDim.x, ... of its lane and keeps the walk software-pipelined: while
+// tile t is being copied, the first ROWS threads already hold the ids of tile t+1 (loaded one step earlier), have its
+// slot lookups (node_map[id], the one scattered read of the resolve) in flight together with the copy's loads, and fetch the
+// ids of tile t+2.  The copy of a tile therefore never waits for its own resolve chain (id -> slot -> pointer): with one tile
+// per workgroup that chain was 40 % of a workgroup's life during which it streamed nothing.  Loads of the copy loop are
+// unconditional (a missing row loads what its format says, chunks past the tile's end re-read its last chunk), so no
+// branch sits between the prefetch and the copy and all of them are in flight together; only the stores are predicated.
+#ifndef LG_GATHER_MIN_WAVES
+#define LG_GATHER_MIN_WAVES 8        // waves per SIMD the register allocation must leave room for
+#endif
+#ifndef LG_GATHER_TARGET_WG
+#define LG_GATHER_TARGET_WG 8192     // workgroups of a full launch: four rounds of what is resident, so the dispatcher evens out lanes of different length
+#endif
+
 // LASTOP: the gather of a batch's last op (the dominant launch; traces and counters tell it from the early hops' gathers by
 // name) -- the only one that can carry a hand-over to a trainer-visible pipe slot.
-template <typename VecT, int ROWS = LG_GATHER_ROWS, int UNROLL = LG_GATHER_UNROLL, bool TAIL = false, bool LASTOP = true>
+template <typename VecT, int ROWS, int UNROLL, bool TAIL, bool LASTOP>
 __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather_kernel(GatherParams gp, const LanePtrs* __restrict__ lanes,
                                                                    bool copy_range)
 {
-    constexpr bool BF16 = GatherFormat<VecT>::SRC_BF16;       // bf16 source rows
-    constexpr bool OUT16 = GatherFormat<VecT>::OUT_BF16;      // bf16 output rows
+    typedef GatherRow<VecT, TAIL> Row;
+    typedef typename Row::Out Out;
     constexpr int VEC = sizeof(VecT) / sizeof(float);
-    static_assert(!(BF16 || OUT16) || !TAIL, "bf16 rows end in a partial chunk, not a tail pass");
     static_assert(ROWS <= LG_GATHER_THREADS, "one resolving thread per row of a tile");
     __shared__ const LG_G float* s_ptr[2][ROWS];
 
@@ -189,7 +295,7 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
         deliver_slice(L, *static_cast<const DeliverParams*>(L.deliver), blockIdx.x, step);
     const int32_t tid = threadIdx.x;
     const int32_t D = gp.D;
-    const int32_t C = BF16 ? gp.pitch / 8 : OUT16 ? (D + 7) / 8 : D / VEC;   // chunks per row
+    const int32_t C = Row::chunks(gp);
     const int32_t dr = LG_GATHER_THREADS / C;          // row / chunk advance per 256-chunk step
     const int32_t dc = LG_GATHER_THREADS - dr * C;
     int32_t tile = blockIdx.x;
@@ -198,35 +304,30 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
     // row-source statistics: armed by the host (UnifiedCache::GatherStats) and switched by a DEVICE word, so that a launch
     // captured in a hipGraph follows the switch too (a pointer baked in at capture time kept counting through every replay)
     const bool counting = gp.stats != nullptr && gp.Kg > 1 && gp.stats[3] != 0ull;
-    // row x of a table: x * D floats, or x * pitch bf16 elements in
-    auto row_at = [&](const float* base, int64_t x) -> const LG_G float* {
-        if constexpr (BF16) return (const LG_G float*)(LG_GPTR(const uint16_t, (const uint16_t*)base) + x * gp.pitch);
-        else return LG_GPTR(const float, base) + x * D;
-    };
     // a row's source: FindFeat (cache.cu:180-215) + the address arithmetic of cache_impl.cuh:259-268
     auto source_of = [&](int32_t id, int32_t g) -> const LG_G float* {
         const LG_G float* p = nullptr;
         if (g < 0) {
             if (id >= 0 && gp.full_table != nullptr)     // :262-266 (the modulo only where it does anything)
-                p = row_at(gp.full_table, (int64_t)(id < gp.total_num_nodes ? id : id % gp.total_num_nodes));
+                p = Row::row_at(gp, gp.full_table, (int64_t)(id < gp.total_num_nodes ? id : id % gp.total_num_nodes));
         } else if (gp.hybrid) {      // feat_cache_lookup, cache_impl.cuh:224-231: CPU cache below cpu_cap, this GPU's cache above
             if (g < gp.hybrid_cpu_cap)
-                p = row_at(gp.hybrid_cpu_cache, (int64_t)g);       // (g % cpu_cap == g)
+                p = Row::row_at(gp, gp.hybrid_cpu_cache, (int64_t)g);       // (g % cpu_cap == g)
             else
-                p = row_at(gp.local_table, (int64_t)((g - gp.hybrid_cpu_cap) % gp.hybrid_gpu_cap));
+                p = Row::row_at(gp, gp.local_table, (int64_t)((g - gp.hybrid_cpu_cap) % gp.hybrid_gpu_cap));
         } else {
             int32_t didx = 0, fidx = g;                                                      // :259-260 (one division, and
             if (gp.striped) { didx = g / gp.node_capacity; fidx = g - didx * gp.node_capacity; }  // none without striping)
             const int64_t rank = (int64_t)fidx * gp.Kg + didx;                               // hotness rank of the row (cache_impl.cuh:104-109)
             const bool local_copy = gp.replica != nullptr && rank < gp.replica_rows;
             if (local_copy)      // the clique's hottest rows are also kept locally: same row, no xGMI hop
-                p = row_at(gp.replica, rank);
+                p = Row::row_at(gp, gp.replica, rank);
             else if (didx == gp.member && gp.local_table != nullptr)     // own stripe: its address came with the launch
-                p = row_at(gp.local_table, (int64_t)fidx);
+                p = Row::row_at(gp, gp.local_table, (int64_t)fidx);
             else if (gp.skip_remote)     // peer_gather = bulk: the owner pushes this row (bulk_push_kernel); nothing to fetch here
                 p = nullptr;
             else
-                p = row_at(gp.cache_tables[didx], (int64_t)fidx);                  // :268
+                p = Row::row_at(gp, gp.cache_tables[didx], (int64_t)fidx);                  // :268
             if (counting) {    // tests / diagnostics / the computed xGMI count: [0] rows read through a stripe pointer, [1] from the
                                // replica, [2] the part of [0] from a peer's stripe -- one atomic per wave and counter
                 const unsigned long long m_rep = __ballot(local_copy), m_str = __ballot(!local_copy);
@@ -285,8 +386,7 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
         }
 
         const int32_t nchunks = nr * C;
-        LG_G float* dst_tile = LG_GPTR(float, L.float_features) + (int64_t)(off + r0) * D;
-        LG_G uint16_t* dst16 = LG_GPTR(uint16_t, (uint16_t*)L.float_features) + (int64_t)(off + r0) * D;     // (bf16 output)
+        LG_G Out* dst_tile = LG_GPTR(Out, (Out*)L.float_features) + (int64_t)(off + r0) * D;
         int32_t q = tid;
         int32_t r = q / C;
         int32_t c = q - r * C;
@@ -301,83 +401,16 @@ __global__ __launch_bounds__(LG_GATHER_THREADS, LG_GATHER_MIN_WAVES) void gather
                 cc[u] = in ? c : C - 1;
                 const LG_G float* p = s_ptr[buf][rr[u]];
                 ok[u] = in && p != nullptr;
-                if constexpr (std::is_same<VecT, F32Narrow>::value) {
-                    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
-                    const int32_t e0 = cc[u] * 8;
-                    if (p == nullptr) {
-                        v[u].a = v[u].b = v4u{0.f, 0.f, 0.f, 0.f};
-                    } else if (e0 + 8 <= D) {
-                        v[u].a = ((const LG_G v4u*)(p + e0))[0];
-                        v[u].b = ((const LG_G v4u*)(p + e0))[1];
-                    } else {                                          // the partial last chunk: no load past the row's end
-                        float f[8];
-#pragma unroll
-                        for (int k = 0; k < 8; k++) f[k] = e0 + k < D ? p[e0 + k] : 0.f;
-                        v[u].a = v4u{f[0], f[1], f[2], f[3]};
-                        v[u].b = v4u{f[4], f[5], f[6], f[7]};
-                    }
-                } else if constexpr (BF16) {
-                    v[u].w = p != nullptr ? ((const LG_G VecT*)p)[cc[u]].w : LG_GPTR(const Bf16x8, &lg_gather_zero_line)->w;
-                } else {
-                    if (p == nullptr) p = dst_tile + (int64_t)rr[u] * D;     // id < 0: nothing to fetch; read what is there
-                    v[u] = ((const LG_G VecT*)p)[cc[u]];   // plain loads: measured 74% of HBM peak vs 63% nontemporal
-                }
+                v[u] = Row::load(p, p != nullptr, dst_tile, rr[u], cc[u], D);
                 q += LG_GATHER_THREADS;
                 r += dr;
                 c += dc;
                 if (c >= C) { c -= C; r += 1; }
             }
 #pragma unroll
-            for (int u = 0; u < UNROLL; u++) {
-                if constexpr (OUT16) {
-                    typedef uint32_t u4u __attribute__((ext_vector_type(4), aligned(4)));
-                    uint32_t w[4];                                    // elements 2k (low half) and 2k+1 (high half) of the chunk
-                    if constexpr (BF16) {
-                        w[0] = v[u].w.x; w[1] = v[u].w.y; w[2] = v[u].w.z; w[3] = v[u].w.w;
-                    } else {
-                        w[0] = gather_bf16_rne(v[u].a.x) | (gather_bf16_rne(v[u].a.y) << 16);
-                        w[1] = gather_bf16_rne(v[u].a.z) | (gather_bf16_rne(v[u].a.w) << 16);
-                        w[2] = gather_bf16_rne(v[u].b.x) | (gather_bf16_rne(v[u].b.y) << 16);
-                        w[3] = gather_bf16_rne(v[u].b.z) | (gather_bf16_rne(v[u].b.w) << 16);
-                    }
-                    const int32_t e0 = cc[u] * 8;
-                    LG_G uint16_t* d = dst16 + (int64_t)rr[u] * D + e0;
-                    if (ok[u] && (D & 1) == 0) {                      // dword-aligned rows
-                        if (e0 + 8 <= D) {
-                            __builtin_nontemporal_store(u4u{w[0], w[1], w[2], w[3]}, (LG_G u4u*)d);
-                        } else {
-#pragma unroll
-                            for (int k = 0; k < 4; k++)
-                                if (e0 + 2 * k < D) ((LG_G uint32_t*)d)[k] = w[k];
-                        }
-                    } else if (ok[u]) {                               // odd D: 2-byte aligned rows
-#pragma unroll
-                        for (int k = 0; k < 8; k++)
-                            if (e0 + k < D) d[k] = (uint16_t)(w[k >> 1] >> ((k & 1) * 16));
-                    }
-                } else if constexpr (BF16) {
-                    typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
-                    typedef uint32_t u4 __attribute__((ext_vector_type(4)));
-                    const u4 w = v[u].w;
-                    const u4 lo = w << 16, hi = w & 0xFFFF0000u;      // elements 2k, 2k+1 of the chunk
-                    const int32_t e0 = cc[u] * 8;
-                    LG_G float* d = dst_tile + (int64_t)rr[u] * D + e0;
-                    if (ok[u] && e0 + 8 <= D) {
-                        __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.x, hi.x, lo.y, hi.y}), (LG_G v4u*)d);
-                        __builtin_nontemporal_store(__builtin_bit_cast(v4u, u4{lo.z, hi.z, lo.w, hi.w}), (LG_G v4u*)d + 1);
-                    } else if (ok[u]) {                               // the partial last chunk of a row: D - e0 < 8 elements
-                        const uint32_t f[8] = {lo.x, hi.x, lo.y, hi.y, lo.z, hi.z, lo.w, hi.w};
-#pragma unroll
-                        for (int k = 0; k < 8; k++)
-                            if (e0 + k < D) d[k] = __uint_as_float(f[k]);
-                    }
-                } else {
-                    if (ok[u])     // write-once output: nontemporal stores
-                        __builtin_nontemporal_store(v[u], (LG_G VecT*)(dst_tile + (int64_t)rr[u] * D) + cc[u]);
-                }
-            }
+            for (int u = 0; u < UNROLL; u++) Row::store(v[u], ok[u], dst_tile, rr[u], cc[u], D);
         }
-        if (TAIL) {            // the last D % VEC floats of every row
+        if constexpr (TAIL) {            // the last D % VEC floats of every row
             const int32_t tail = D - C * VEC;
             for (int32_t i = tid; i < nr * tail; i += LG_GATHER_THREADS) {
                 const int32_t tr = i / tail, k = C * VEC + (i - tr * tail);
@@ -500,115 +533,39 @@ static inline int32_t gather_grid_x(int32_t max_rows, int32_t rows_per_tile, int
     return gx < 1 ? 1 : gx;
 }
 
-template <int ROWS>
-static void launch_gather_v4(hipStream_t s, const GatherParams& g, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
+// the instance of format F with the plan's tile size (walking ROWS = 16, 32, ... 256 over the sizes gather_info(F).tiles has); the
+// LASTOP instance for the gather of a batch's last op
+template <typename VecT, GatherFormat F, int ROWS = 16>
+static void launch_format(hipStream_t s, int32_t rows, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
 {
-    typedef float v4 __attribute__((ext_vector_type(4)));
-    const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
-    if (g.last_op) gather_kernel<v4, ROWS, LG_GATHER_UNROLL, false, true><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
-    else gather_kernel<v4, ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
+    constexpr GatherFormatInfo fi = gather_info(F);
+    if constexpr ((fi.tiles & ROWS) != 0) {
+        const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
+        if (rows == ROWS && gk.last_op) gather_kernel<VecT, ROWS, fi.unroll, fi.tail, true><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
+        else if (rows == ROWS) gather_kernel<VecT, ROWS, fi.unroll, fi.tail, false><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
+    }
+    if constexpr (ROWS < 256) launch_format<VecT, F, ROWS * 2>(s, rows, gk, grid_rows, d_lanes, n_lanes, copy_range);
 }
 
-template <typename VecT, int ROWS>
-static void launch_gather_bf16_rows(hipStream_t s, const GatherParams& g, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
-                                    bool copy_range)
+// gk: what the kernel gets (max_rows = the clamp); grid_rows: what sizes the launch, the rows a lane typically has (GatherParams.grid_rows)
+static void launch_gather_impl(hipStream_t s, GatherParams gk, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
 {
-    // F32Narrow loads 32 bytes per chunk: half the chunks in flight per lane keep the bytes in flight of the others, and its
-    // registers within the 8-wave budget
-    constexpr int UNROLL = std::is_same<VecT, F32Narrow>::value ? LG_GATHER_UNROLL / 2 : LG_GATHER_UNROLL;
-    const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
-    if (g.last_op) gather_kernel<VecT, ROWS, UNROLL, false, true><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
-    else gather_kernel<VecT, ROWS, UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(g, d_lanes, copy_range);
-}
-
-// bf16 sources or bf16 output rows, every D (gk: what the kernel gets; grid_rows: what sizes the launch).  Tile size from the tile's
-// SOURCE payload, the rule of the float32 path applied to the source row's bytes (2 P for bf16 storage, 4 D for float32): D = 128
-// (256-byte bf16 rows) and D = 100 (208) -> 64 rows, D = 256 -> 32, D = 1024 -> 16; few tiles -> 16 rows.  Measured only against
-// the float32 path at the headline shapes, not against other tile sizes (profiles/r07/feature_dtype/: 0.66 of peak at D = 128,
-// 0.47 at D = 100); LEGION_GATHER_ROWS overrides it, and tools/feature_dtype_ab.py --rows R is the sweep still to run.
-template <typename VecT>
-static void launch_gather_bf16(hipStream_t s, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes,
-                               bool copy_range)
-{
-    if (GatherFormat<VecT>::SRC_BF16 && (gk.pitch < gk.D || gk.pitch % 8 != 0)) {
-        printf("gather: bf16 rows need a pitch that is a multiple of 8 and at least D (pitch %d, D %d)\n", gk.pitch, gk.D);
-        exit(EXIT_FAILURE);
+    if (gk.D <= 0 || gk.max_rows <= 0) return;      // :256 float_feature_len > 0
+    if (gk.node_capacity < 1) gk.node_capacity = 1;
+    const int32_t grid_rows = gk.grid_rows > 0 && gk.grid_rows < gk.max_rows ? gk.grid_rows : gk.max_rows;
+    const GatherPlan p = gather_plan(gk.dtype, gk.out_dtype, gk.D, gk.pitch, grid_rows, n_lanes, tuning().gather_rows_per_wg);
+    if (p.error == GatherPlan::BAD_DTYPE) printf("gather: unknown feature dtype %d or output dtype %d\n", gk.dtype, gk.out_dtype);
+    if (p.error == GatherPlan::BAD_PITCH) printf("gather: bf16 rows need a pitch that is a multiple of 8 and at least D (pitch %d, D %d)\n", gk.pitch, gk.D);
+    if (p.error != GatherPlan::OK) exit(EXIT_FAILURE);
+    typedef GatherFormat GF;
+    switch (p.format) {     // the row type of each format
+        case GF::F32:       launch_format<f32x4, GF::F32>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Tail:   launch_format<f32x4, GF::F32Tail>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Scalar: launch_format<float, GF::F32Scalar>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::Bf16x8:    launch_format<Bf16x8, GF::Bf16x8>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::Bf16Copy:  launch_format<Bf16Copy, GF::Bf16Copy>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Narrow: launch_format<F32Narrow, GF::F32Narrow>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
     }
-    int rows = tuning().gather_rows_per_wg;
-    if (rows <= 0) {
-        rows = 16;
-        const int64_t row_bytes = GatherFormat<VecT>::SRC_BF16 ? (int64_t)gk.pitch * 2 : (int64_t)gk.D * 4;
-        const int64_t payload = row_bytes >= 512 ? 16384 : 32768;
-        while (rows < 256 && (int64_t)rows * 2 * row_bytes <= payload + payload / 4) rows *= 2;
-        if ((int64_t)((grid_rows + rows - 1) / rows) * n_lanes < 4096) rows = 16;
-    }
-    switch (rows) {
-        case 16: launch_gather_bf16_rows<VecT, 16>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 32: launch_gather_bf16_rows<VecT, 32>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 128: launch_gather_bf16_rows<VecT, 128>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case 256: launch_gather_bf16_rows<VecT, 256>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        default: launch_gather_bf16_rows<VecT, 64>(s, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-    }
-    hipCheckError();
-}
-
-static void launch_gather_impl(hipStream_t s, GatherParams g_in, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
-{
-    if (g_in.D <= 0 || g_in.max_rows <= 0) return;      // :256 float_feature_len > 0
-    if (g_in.node_capacity < 1) g_in.node_capacity = 1;
-    const GatherParams& gk = g_in;                      // what the kernel gets: max_rows = the clamp
-    GatherParams g = g_in;                              // what sizes the launch: the rows a lane typically has (GatherParams.grid_rows)
-    if (g.grid_rows > 0 && g.grid_rows < g.max_rows) g.max_rows = g.grid_rows;
-    if ((g.dtype != LEGION_FEATURE_F32 && g.dtype != LEGION_FEATURE_BF16) || (g.out_dtype != LEGION_FEATURE_F32 && g.out_dtype != LEGION_FEATURE_BF16)) {
-        printf("gather: unknown feature dtype %d or output dtype %d\n", g.dtype, g.out_dtype);
-        exit(EXIT_FAILURE);
-    }
-    if (g.out_dtype == LEGION_FEATURE_BF16) {
-        if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16<Bf16Copy>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
-        return launch_gather_bf16<F32Narrow>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
-    }
-    if (g.dtype == LEGION_FEATURE_BF16) return launch_gather_bf16<Bf16x8>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range);
-    const dim3 grid(gather_grid_x(g.max_rows, LG_GATHER_ROWS, n_lanes), n_lanes);     // (the 4-byte vector path, and 64-row tiles at dword alignment)
-    const LegionTuning& tune = tuning();
-    if (g.D % 4 == 0) {
-        // rows per workgroup (LegionTuning.gather_rows_per_wg; 0 = the default below).  A launch of one or a few lanes (the
-        // Runner's per-batch hand-over) has too few 64-row tiles to keep 256 CUs busy: 16-row tiles give it 4 x the
-        // workgroups; a full lane group is indifferent to the tile size at D = 128
-        // Default for a full group, early in round 3 (one tile per workgroup, 256-lane groups, profiles/r03/gather_experiments.txt): the
-        // tile whose payload is 32 KB -- D = 256 with 32 rows 0.758 of peak against 0.727 with 64; D = 64 with 128 rows 0.710 against
-        // 0.685 with 64; D = 128 with 64 or 128 rows 0.776 / 0.777, with 32 rows 0.751.  Re-measured at the end of the round: below
-        int rows = tune.gather_rows_per_wg;
-        if (rows <= 0) {
-            rows = 16;
-            // (round 3, with the pipelined walk and 512-lane groups: 16 KB of payload for rows of 512 bytes and more -- 32 rows at
-            // D = 128: the same at the headline, +1.4 % at B = 8000, +2...3 % on the cold three-hop shapes; D = 256 with 16 rows
-            // +1 % -- and 32 KB below that: D = 64 with 128 rows 8.31 G edges/s, with 64 rows 8.17 G)
-            const int64_t payload = g.D * 4 >= 512 ? 16384 : 32768;
-            while (rows < 256 && (int64_t)rows * 2 * g.D * 4 <= payload + payload / 4) rows *= 2;       // D = 100 -> 64, D = 128 -> 32, D = 256 -> 16
-            if ((int64_t)((g.max_rows + rows - 1) / rows) * n_lanes < 4096) rows = 16;      // (a launch of few tiles: 4 x the workgroups)
-        }
-        switch (rows) {
-            case 16: launch_gather_v4<16>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range); break;
-            case 32: launch_gather_v4<32>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range); break;
-            case 128: launch_gather_v4<128>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range); break;
-            case 256: launch_gather_v4<256>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range); break;
-            default: launch_gather_v4<64>(s, gk, g.max_rows, d_lanes, n_lanes, copy_range); break;
-        }
-    } else if (g.D > 4) {
-        // rows that are not multiples of 16 bytes (D = 602: 2408-byte rows): 16-byte chunks at dword alignment + a scalar
-        // tail, instead of the 8- / 4-byte vector paths of rounds 1-2 (0.65 of peak at D = 602)
-        typedef float v4u __attribute__((ext_vector_type(4), aligned(4)));
-        const bool small = (int64_t)((g.max_rows + LG_GATHER_ROWS - 1) / LG_GATHER_ROWS) * n_lanes < 4096;
-        const bool r16 = small || (int64_t)g.D * 4 * 64 > 65536;
-        const dim3 gr = r16 ? dim3(gather_grid_x(g.max_rows, 16, n_lanes), n_lanes) : grid;
-        if (r16 && g.last_op) gather_kernel<v4u, 16, LG_GATHER_UNROLL, true, true><<<gr, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-        else if (r16) gather_kernel<v4u, 16, LG_GATHER_UNROLL, true, false><<<gr, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-        else if (g.last_op) gather_kernel<v4u, LG_GATHER_ROWS, LG_GATHER_UNROLL, true, true><<<gr, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-        else gather_kernel<v4u, LG_GATHER_ROWS, LG_GATHER_UNROLL, true, false><<<gr, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-    } else if (g.last_op)
-        gather_kernel<float><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-    else
-        gather_kernel<float, LG_GATHER_ROWS, LG_GATHER_UNROLL, false, false><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
     hipCheckError();
 }
 
