@@ -6,6 +6,7 @@
 hipcc cross-compiles without a GPU.  Outputs stay inside the package directory (git-ignored,
 shipped to the GPU box by gpurun).
 """
+import glob
 import os
 import subprocess
 import sys
@@ -33,7 +34,8 @@ def _newer(target, deps):
 def build_lib(force=False, verbose=True):
     objdir = os.path.join(HERE, "_obj")
     os.makedirs(objdir, exist_ok=True)
-    headers = [os.path.join(CSRC, "legion_core.h"), os.path.join(CSRC, "runner_schedule.h"), os.path.join(HERE, "..", "include", "legion_hip.h")]
+    # every header a source may include: a changed plan header (gather_plan.h, sample_plan.h) rebuilds its kernels too
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "legion_hip.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
@@ -74,7 +76,6 @@ def build_lib(force=False, verbose=True):
 
 def build_trainer(verbose=True, force=False):
     tdir = os.path.join(HERE, "trainer")
-    import glob
     built = glob.glob(os.path.join(tdir, "ipc_service*.so"))
     srcs = [os.path.join(tdir, "ipc_service.cpp"), os.path.join(tdir, "vmm_probe.h"), os.path.join(tdir, "setup.py")]
     if built and not force and not _newer(built[0], srcs):
@@ -89,7 +90,7 @@ def build_trainer(verbose=True, force=False):
 
 def build_variant(name, extra_flags, verbose=True):
     """liblegion_hip.so with other compile-time constants, for tuning sweeps:
-        python -m legion_amd.build --variant v16 -DLG_LDS_BUCKET_BITS=4 ...
+        python -m legion_amd.build --variant claims8 -DLG_DEDUP_CLAIMS=8 ...
     -> tools/lds_tuning/variants/<name>/liblegion_hip.so (git-ignored; travels to the GPU box).  Select it at run time with
     LEGION_HIP_LIB=<path> (legion_amd/lib.py); the library in place is never overwritten."""
     out = os.path.join(HERE, "..", "tools", "lds_tuning", "variants", name)

@@ -601,7 +601,6 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
 // Workgroups of 1024 threads (one slot per thread and super tile): with the 64 KB stage of K = 8 two of them share a CU, i.e. 32
 // waves per CU keep this stream's loads in flight (round 4's 256-thread workgroups left 8 waves per CU: 107 us per 64-lane
 // group of B = 8000 for 250 MB).
-#define LG_PLACE_MAX_K 8
 #define LG_PLACE_THREADS 1024
 template <int BB>
 __global__ __launch_bounds__(LG_PLACE_THREADS) void place_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
@@ -890,9 +889,6 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 #ifndef LG_SCATTER_MIN_WAVES_LAST
 #define LG_SCATTER_MIN_WAVES_LAST 8
 #endif
-#ifndef LG_COMPACT_THREADS
-#define LG_COMPACT_THREADS 256
-#endif
 #define LG_SPIN_LIMIT (1 << 24)       // polls of one word before a waiter gives up with LG_ERR_CHAIN (seconds; a wait is microseconds)
 #define LG_ST_AGG (1ull << 62)
 #define LG_ST_PREF (2ull << 62)
@@ -1175,7 +1171,6 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 // counted per bucket in LDS, ONE global atomicAdd per non-empty bucket reserves its entries, a second sweep places them.
 // A list that outgrows its capacity is not used (its count says so; that bucket's workgroup scans sampled_ids instead).
 // ------------------------------------------------------------------------------------------
-#define LG_LIST_CHUNK 8192
 template <int BB>
 __global__ __launch_bounds__(LG_TILE) void list_known_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
@@ -1210,91 +1205,61 @@ __global__ __launch_bounds__(LG_TILE) void list_known_kernel(HopParams hp, const
     }
 }
 
-void launch_random_sample(hipStream_t s, const HopParams& p, const LanePtrs* d_lanes, int32_t n_lanes)
+// the de-duplication instance <BB, CL>, when the class is built for CL claims per thread (sample_plan.h SAMPLE_CLASSES) and the plan
+// asks for them
+template <int BB, int CL>
+static bool launch_dedup(hipStream_t s, const SampleHopPlan& plan, const HopParams& q, const LanePtrs* d_lanes, int32_t n_lanes)
 {
-    // Fixed grids that stride over super tiles; grid.y = lanes (independent mini-batches of a group).
-    int32_t max_super = (p.max_slots + LG_SUPER - 1) / LG_SUPER;
-    if (max_super < 1) max_super = 1;
-    int32_t gx = max_super < 1024 ? max_super : 1024;
-    const int max_wg = tuning().sample_max_wg;
-    while (gx > 64 && (int64_t)gx * n_lanes > max_wg) gx /= 2;  // keep the whole launch near 2 x resident capacity
-    while (gx > 1 && (int64_t)gx * n_lanes > max_wg && max_wg < 4096) gx /= 2;   // (experiments with fewer workgroups)
-    {
-        // Equal workgroups that fill the machine about twice leave its second round half empty: between one and six rounds' worth
-        // (8 workgroups of this kernel per CU x 256 CUs), take ONE round of longer-lived workgroups instead.  Measured (one_round_ab.txt):
-        // 64 lanes at B = 8000 (3 904 -> 2 048 workgroups) +1 %, 128 lanes at B = 4096 +1.4 %, 256 lanes and D = 256 the same within
-        // the noise; 512 lanes at B = 1024 (15 rounds) are not touched.
-        const int64_t resident = 8 * 256, total = (int64_t)gx * n_lanes;
-        if (total > resident && total < 6 * resident) gx = (int32_t)std::max<int64_t>(1, resident / n_lanes);
-    }
-    const dim3 grid(gx, n_lanes);
-    {
-        // buckets per lane follow the pool's largest hop (legion_core.h).  8 / 16 / 64 buckets: the sampling kernel writes the claim
-        // lists itself (64: staged per super tile in LDS).  256 buckets: it samples partition tiles of K super tiles and place_kernel
-        // writes the lists; K follows THIS hop: as large as the staging allows (LG_PLACE_MAX_K) unless that leaves the launch with
-        // fewer than ~8 k workgroups by the hop's capacity (a hop typically fills a quarter of it: ~2 k active ones; measured at
-        // B = 8000: 2 k -> 8 k +1...2 %, beyond: the same), and never below the class's minimum (run_off is sized by it, storage.hip)
-        HopParams q = p;
-        const bool small = p.lds_bucket_bits == LG_LDS_BITS_SMALL || p.lds_bucket_bits == LG_LDS_BITS_SMALL16;
-        const int32_t k_lo = lg_lds_k_min(p.lds_bucket_bits);
-        int32_t k = (small || p.lds_bucket_bits == LG_LDS_BITS_MEDIUM) ? 1 : LG_PLACE_MAX_K;
-        const int want_wg = tuning().lds_part_wg;
-        while (k > k_lo && (int64_t)(max_super / k) * n_lanes < want_wg) k /= 2;
-        q.lds_k = k;
-        int32_t gp = (max_super + k - 1) / k;                  // one workgroup per partition tile ...
-        while (gp > 16 && (int64_t)gp * n_lanes > 16384) gp = (gp + 1) / 2;  // ... within reason
-        const dim3 pgrid(gp, n_lanes);
-        const size_t stage = (size_t)k * LG_SUPER * sizeof(unsigned long long);
-        switch (p.lds_bucket_bits) {
-        case LG_LDS_BITS_SMALL:
-            if (p.replace) sample_kernel<LG_LDS_BITS_SMALL, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            else sample_kernel<LG_LDS_BITS_SMALL, true, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            hipCheckError();
-            dedup_lists_kernel<LG_LDS_BITS_SMALL, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_SMALL, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            break;
-        case LG_LDS_BITS_SMALL16:
-            if (p.replace) sample_kernel<LG_LDS_BITS_SMALL16, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            else sample_kernel<LG_LDS_BITS_SMALL16, true, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            hipCheckError();
-            dedup_lists_kernel<LG_LDS_BITS_SMALL16, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_SMALL16, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            break;
-        case LG_LDS_BITS_MEDIUM:
-            if (p.replace) sample_kernel<LG_LDS_BITS_MEDIUM, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            else sample_kernel<LG_LDS_BITS_MEDIUM, true, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-            hipCheckError();
-            // (a bucket of up to CL x 1024 claims is worked on from registers, whatever the number of passes over its sub-buckets)
-            if (p.dedup_claims == LG_DEDUP_CLAIMS_BIG) dedup_lists_kernel<LG_LDS_BITS_MEDIUM, LG_DEDUP_CLAIMS_BIG, LG_DEDUP_BIG_TABLE_BITS><<<dim3(1 << LG_LDS_BITS_MEDIUM, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            else if (p.dedup_claims == LG_DEDUP_CLAIMS_MID) dedup_lists_kernel<LG_LDS_BITS_MEDIUM, LG_DEDUP_CLAIMS_MID><<<dim3(1 << LG_LDS_BITS_MEDIUM, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            else dedup_lists_kernel<LG_LDS_BITS_MEDIUM, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_MEDIUM, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            break;
-        default:
-            if (p.replace) sample_kernel<LG_LDS_BITS_LARGE, false><<<pgrid, LG_TILE, 0, s>>>(q, d_lanes);
-            else sample_kernel<LG_LDS_BITS_LARGE, false, false, true><<<pgrid, LG_TILE, 0, s>>>(q, d_lanes);
-            hipCheckError();
-            place_kernel<LG_LDS_BITS_LARGE><<<pgrid, LG_PLACE_THREADS, stage, s>>>(q, d_lanes);
-            hipCheckError();
-            if (p.dedup_claims == LG_DEDUP_CLAIMS_MID) dedup_lists_kernel<LG_LDS_BITS_LARGE, LG_DEDUP_CLAIMS_MID><<<dim3(1 << LG_LDS_BITS_LARGE, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            else dedup_lists_kernel<LG_LDS_BITS_LARGE, LG_DEDUP_CLAIMS><<<dim3(1 << LG_LDS_BITS_LARGE, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
-            break;
+    if constexpr (CL <= sample_class(BB).max_claims) {
+        if (plan.dedup_claims == CL) {
+            dedup_lists_kernel<BB, CL, lg_dedup_table_bits(CL)><<<dim3(1 << BB, n_lanes), LG_DEDUP_THREADS, 0, s>>>(q, d_lanes);
+            return true;
         }
     }
+    return false;
+}
+
+// one hop of class BB (sample_plan.h SAMPLE_CLASSES), as sample_hop_plan sized it: sample (+ place) -> de-duplicate -> compact (-> list)
+template <int BB>
+static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams& p, const LanePtrs* d_lanes, int32_t n_lanes)
+{
+    constexpr SampleClassInfo ci = sample_class(BB);
+    HopParams q = p;
+    q.lds_k = plan.k;
+    const dim3 grid(plan.sample_gx, n_lanes);
+    if (p.replace) sample_kernel<BB, ci.single, ci.staged><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    else sample_kernel<BB, ci.single, ci.staged, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
     hipCheckError();
-    // compaction: LG_COMPACT_THREADS per workgroup (a workgroup iteration takes 4 x that many consecutive slots), as many workgroups per
-    // lane as the sampling launch has per 1024 slots' worth
-    {
-        const dim3 cgrid(std::max(1, (int)grid.x * LG_TILE / LG_COMPACT_THREADS), n_lanes);
-        if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-        else compact_kernel<false, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    if constexpr (!ci.single) {
+        place_kernel<BB><<<dim3(plan.place_gx, n_lanes), LG_PLACE_THREADS, (size_t)plan.stage_bytes, s>>>(q, d_lanes);
+        hipCheckError();
+    }
+    if (!launch_dedup<BB, LG_DEDUP_CLAIMS_BIG>(s, plan, q, d_lanes, n_lanes) && !launch_dedup<BB, LG_DEDUP_CLAIMS_MID>(s, plan, q, d_lanes, n_lanes) &&
+        !launch_dedup<BB, LG_DEDUP_CLAIMS>(s, plan, q, d_lanes, n_lanes)) {
+        printf("legion_hip: no dedup_lists_kernel for %d buckets and %d claims per thread\n", 1 << BB, plan.dedup_claims);
+        exit(EXIT_FAILURE);
     }
     hipCheckError();
+    const dim3 cgrid(plan.compact_gx, n_lanes);
+    if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    else compact_kernel<false, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    hipCheckError();
     if (!p.last_hop) {       // later hops must recognise the nodes this one added: their buckets' lists
-        int32_t chunks = (p.max_slots + LG_LIST_CHUNK - 1) / LG_LIST_CHUNK;
-        if (chunks > 256) chunks = 256;
-        if (p.lds_bucket_bits == LG_LDS_BITS_SMALL) list_known_kernel<LG_LDS_BITS_SMALL><<<dim3(chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);
-        else if (p.lds_bucket_bits == LG_LDS_BITS_SMALL16) list_known_kernel<LG_LDS_BITS_SMALL16><<<dim3(chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);
-        else if (p.lds_bucket_bits == LG_LDS_BITS_MEDIUM) list_known_kernel<LG_LDS_BITS_MEDIUM><<<dim3(chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);
-        else list_known_kernel<LG_LDS_BITS_LARGE><<<dim3(chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);
+        list_known_kernel<BB><<<dim3(plan.known_chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);
         hipCheckError();
+    }
+}
+
+void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits, int64_t last_hop_claims_hint, const LanePtrs* d_lanes,
+                          int32_t n_lanes)
+{
+    const LegionTuning tune = tuning();
+    const SampleHopPlan plan = sample_hop_plan(bucket_bits, p.max_slots, n_lanes, p.last_hop, last_hop_claims_hint, tune.sample_max_wg, tune.lds_part_wg);
+    switch (sample_class(bucket_bits).bits) {
+    case LG_LDS_BITS_SMALL: return launch_hop<LG_LDS_BITS_SMALL>(s, plan, p, d_lanes, n_lanes);
+    case LG_LDS_BITS_SMALL16: return launch_hop<LG_LDS_BITS_SMALL16>(s, plan, p, d_lanes, n_lanes);
+    case LG_LDS_BITS_MEDIUM: return launch_hop<LG_LDS_BITS_MEDIUM>(s, plan, p, d_lanes, n_lanes);
+    default: return launch_hop<LG_LDS_BITS_LARGE>(s, plan, p, d_lanes, n_lanes);
     }
 }
 

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/legion_hip.h"
+#include "sample_plan.h"
 
 #define INTERBATCH_CON LEGION_INTERBATCH_CON
 #define INTRABATCH_CON LEGION_INTRABATCH_CON
@@ -61,35 +62,10 @@
 // then the claims with atomicMin on (vertex, pending | slot) -- and marks every claim that is not the lowest slot of a new
 // vertex.  Nothing survives the hop, nothing to clear, nothing that scales with N.  A bucket whose vertices do not fit the
 // table is handled in several passes over sub-buckets, so the result never depends on the hash.
-// Buckets per lane follow the pool's largest hop, so that a bucket sees a few thousand claims: 8 (or 16, dense graphs) up to 2^19
-// slots per lane (B = 1024-class batches), 64 up to 2^22 (B = 8000 with [25,10]), 256 beyond (B = 8000 with [15,10,5] has 6 M,
-// with [25,10,10] 20 M; larger hops run more passes per bucket).  The kernels are instantiated for the four classes.
+// Buckets per lane (8, 16, 64 or 256) follow the pool's largest hop; the classes, their constants and every launch decision that
+// rests on them are in sample_plan.h.
 // (Rounds 1-4 also had a uint32[N] array per lane and a per-lane open-addressing table in memory, claimed with one atomicMin per
 // pick: slower by 5-14 % wherever the LDS form applied, removed in round 5 when it applied everywhere -- DESIGN_HISTORY.md.)
-#define LG_LDS_BITS_SMALL 3
-#define LG_LDS_BITS_SMALL16 4                    // the same class with 16 buckets: dense graphs, see lg_set_pool_claims_hint
-#ifndef LG_LDS_BITS_MEDIUM
-#define LG_LDS_BITS_MEDIUM 6
-#endif
-#ifndef LG_LDS_BITS_LARGE
-#define LG_LDS_BITS_LARGE 8
-#endif
-#ifndef LG_DEDUP_CLAIMS
-#define LG_DEDUP_CLAIMS 5                       // claims a thread of a de-duplication workgroup keeps in registers (a bucket of at most LG_DEDUP_CLAIMS x 1024 is "resident")
-#endif
-#ifndef LG_DEDUP_CLAIMS_MID
-#define LG_DEDUP_CLAIMS_MID 10                  // ... 10 where PreSC saw buckets of 5-10 k claims (B = 8000 on the less repetitive graphs: uk-union size, RMAT-28): 64 KB
-#endif                                          // table, two workgroups per CU as with 5
-#ifndef LG_DEDUP_CLAIMS_BIG
-#define LG_DEDUP_CLAIMS_BIG 20                  // ... 20 beyond (B = 8000 [15,10,5] on RMAT-26: 15 k per bucket)
-#endif
-#ifndef LG_DEDUP_BIG_TABLE_BITS
-#define LG_DEDUP_BIG_TABLE_BITS 14               // ... and the log2 words of its LDS table (14: 128 KB)
-#endif
-#define LG_LDS_SLOTS_SMALL (1 << 19)
-#define LG_LDS_SLOTS_MEDIUM (1 << 22)
-// fewest super tiles (1024 slots) a partition tile of the 64- / 256-bucket classes may have (the launch picks up to
-// LG_PLACE_MAX_K, kernels_sample.hip); sizes run_off
 // feature row format (legion_hip.h LEGION_FEATURE_*): elements per stored row and its bytes
 static inline int32_t lg_feature_pitch(int32_t dtype, int32_t D) { return dtype == LEGION_FEATURE_BF16 ? (D + 7) & ~7 : D; }
 static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
@@ -98,14 +74,6 @@ static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
 }
 // bytes of one element of a row handed to the caller (a pool's feature output dtype, LEGION_FEATURE_*)
 static inline int64_t lg_feature_out_bytes(int32_t out_dtype) { return out_dtype == LEGION_FEATURE_BF16 ? 2 : 4; }
-static inline int32_t lg_lds_k_min(int32_t bucket_bits) { return bucket_bits == LG_LDS_BITS_LARGE ? 4 : 1; }
-#ifndef LG_LDS_TABLE_BITS
-#define LG_LDS_TABLE_BITS 13
-#endif
-#define LG_LDS_TABLE (1 << LG_LDS_TABLE_BITS)   // 64-bit words of LDS per (lane, bucket) workgroup
-#ifndef LG_LDS_FILL_16THS
-#define LG_LDS_FILL_16THS 14                    // a pass may fill its table up to this many sixteenths (bound: known + claims of the pass)
-#endif
 __host__ __device__ inline uint32_t lg_tab_hash(int32_t id)
 {
     uint32_t x = (uint32_t)id;
@@ -163,12 +131,6 @@ enum HopScratch {
 #ifndef LG_CLAIM_CNT_STRIDE
 #define LG_CLAIM_CNT_STRIDE 32        // ints between the claim-list counts of two buckets: a line each (the 8 / 16 reservations of a super tile go to different lines)
 #endif
-#define LG_CLAIM_CHUNK_BITS 9
-#define LG_CLAIM_CHUNK (1 << LG_CLAIM_CHUNK_BITS)
-
-#define LG_TILE 256            // compaction tile == threads per workgroup in the sampler kernels
-#define LG_SLOTS_PER_LANE 4    // independent slots each lane keeps in flight
-#define LG_SUPER (LG_TILE * LG_SLOTS_PER_LANE)   // slots one workgroup owns per iteration
 #define LG_DISTINCT_MAX_FANOUT LEGION_DISTINCT_MAX_FANOUT   // largest fan-out of sampling without replacement (the sampler's LDS span of an entry's picks)
 
 // Per-vertex row header: where the adjacency of v lives (slot of the CSR pointer tables: P = the
@@ -763,12 +725,12 @@ struct HopParams {                  // what every lane of a launch shares
     int32_t max_slots;              // capacity of slot_dst for this hop
     unsigned long long* edge_access_time;  // presample only (single lane), else null
     unsigned long long* topo_transactions; // presample only: 64-byte transactions the hop's topology reads amount to
-    int32_t lds_bucket_bits;        // LG_LDS_BITS_SMALL / SMALL16 / MEDIUM / LARGE (the pool's)
     int32_t lds_k;                  // super tiles per partition tile in this hop (set by launch_random_sample)
-    int32_t dedup_claims;           // 64-bucket class: claims per thread the (last) hop's de-duplication keeps in registers: LG_DEDUP_CLAIMS, _MID or _BIG by what PreSC saw
     int32_t replace;                // 1: draws with replacement (the reference's); 0: distinct positions per entry (MemoryPool::sample_replace)
 };
-void launch_random_sample(hipStream_t s, const HopParams& p, const LanePtrs* d_lanes, int32_t n_lanes);
+// bucket_bits, last_hop_claims_hint: the pool's (MemoryPool); the launch follows sample_hop_plan (sample_plan.h)
+void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits, int64_t last_hop_claims_hint, const LanePtrs* d_lanes,
+                          int32_t n_lanes);
 
 // hand-over of a lane's finished batch to a trainer-visible pipe slot (kernels_gather.hip)
 struct DeliverParams {

@@ -12,8 +12,8 @@
 //   * FindTopo runs inside the sampling kernel and FindFeat inside the gather kernel; their
 //     outputs (tmp_part_ind/tmp_part_off, cache_search_buffer) are still written;
 //   * counter_update is folded into the kernels that produce the counts;
-//   * the accessed bitmap is fused into the position map (see legion_core.h), so BatchGenerate
-//     does not memset N/8 bytes per batch and IOComplete restores the map in every mode.
+//   * there is no accessed bitmap and no position map: first touches keep no per-vertex state (see
+//     legion_core.h), so BatchGenerate has nothing to memset and IOComplete nothing to restore.
 #include "legion_core.h"
 
 #include <iostream>
@@ -125,18 +125,9 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
     p.max_slots = (int32_t)(hop < pool0->max_new.size() ? pool0->max_new[hop] : pool0->max_slots);
     p.edge_access_time = (is_presc && cache) ? cache->GetEdgeAccessedMap(dev_id) : nullptr;   // :473
     p.topo_transactions = (is_presc && cache) ? cache->Controller(dev_id)->GetTopoTransactions() : nullptr;
-    p.lds_bucket_bits = pool0->lds_bucket_bits;
-    p.lds_k = 1;                             // (launch_random_sample picks the hop's partition tile)
-    // 64- and 256-bucket classes, last hop: how many claims a de-duplication thread keeps in registers follows what PreSC saw in that hop
-    // (+10 %: buckets are not even; a bucket that still outgrows its workgroup's registers re-reads its list, sweep by sweep)
-    p.dedup_claims = LG_DEDUP_CLAIMS;
-    if (p.last_hop && (pool0->lds_bucket_bits == LG_LDS_BITS_MEDIUM || pool0->lds_bucket_bits == LG_LDS_BITS_LARGE)) {
-        const int64_t per_bucket = (pool0->last_hop_claims_hint * 11 / 10) >> pool0->lds_bucket_bits;
-        if (per_bucket > (int64_t)LG_DEDUP_CLAIMS_MID * 1024 && pool0->lds_bucket_bits == LG_LDS_BITS_MEDIUM) p.dedup_claims = LG_DEDUP_CLAIMS_BIG;
-        else if (per_bucket > (int64_t)LG_DEDUP_CLAIMS * 1024) p.dedup_claims = LG_DEDUP_CLAIMS_MID;
-    }
+    p.lds_k = 1;                             // (launch_random_sample sets the hop's partition tile)
     p.replace = pool0->sample_replace;
-    lg::launch_random_sample(s, p, d_lanes, n_lanes);
+    lg::launch_random_sample(s, p, pool0->lds_bucket_bits, pool0->last_hop_claims_hint, d_lanes, n_lanes);
 }
 
 static void do_feature_lookup(hipStream_t s, UnifiedCache* cache, const LanePtrs* d_lanes, int32_t n_lanes,

@@ -981,51 +981,23 @@ void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nod
     mp->float_feature_len = float_feature_len;
     mp->SetCacheSearchBuffer((int32_t*)d_alloc_space(num_ids * sizeof(int32_t)));
     {
-        // first touches (legion_core.h): no per-vertex state; one claim list and one known list per hash bucket
-        const int64_t slots = hop_num > 0 ? per : batch_size;
-        const int64_t n_super = (slots + LG_SUPER - 1) / LG_SUPER + 1;
-        // Buckets per lane.  Slots say how large a hop CAN get; PreSC (when this thread's creator passed its maxima on,
-        // lg_set_pool_claims_hint) says how many claims the largest hop really has.  64 buckets serve a hop as long as a bucket's
-        // claims fit the registers of its workgroup (LG_DEDUP_CLAIMS_BIG x 1024; it then runs its passes over sub-buckets from the
-        // registers) -- e.g. B = 8000 with [15,10,5]: 6 M slots but ~0.9 M claims in hop 3 -- and the sampling kernel writes 64
-        // lists itself; beyond that 256 buckets, whose lists a second kernel writes (place_kernel).  Without PreSC's numbers: by slots.
-        const int64_t hint_claims = g_pool_claims_hint[0] * 11 / 10;      // (+10 %: buckets are not even; one that still outgrows the registers re-reads its list)
-        const bool medium = hint_claims > 0 ? hint_claims <= (int64_t)64 * LG_DEDUP_CLAIMS_BIG * 1024 && slots <= ((int64_t)1 << 24)
-                                            : slots <= LG_LDS_SLOTS_MEDIUM;
-        mp->lds_bucket_bits = slots <= LG_LDS_SLOTS_SMALL ? LG_LDS_BITS_SMALL : (medium ? LG_LDS_BITS_MEDIUM : LG_LDS_BITS_LARGE);
-        mp->last_hop_claims_hint = g_pool_claims_hint[0];
-        if (mp->lds_bucket_bits == LG_LDS_BITS_SMALL) {
-            // The small class has 8 or 16 buckets per lane.  Slots say how large a hop CAN get, not how many of them hold an
-            // edge: on a dense graph (ogbn-products: 60 k edges per batch of 1024 where RMAT-26 has 35 k) a bucket of 8 holds
-            // more vertices than one LDS table takes and every workgroup runs two passes (217 us instead of ~110 per
-            // 256-lane group).  PreSC has seen the real numbers: 16 buckets where 8 would overflow one pass, else 8 (which
-            // is 8 us faster per group where both fit).
-            const int64_t one_pass = LG_LDS_TABLE / 16 * LG_LDS_FILL_16THS;
-            const int64_t need = (g_pool_claims_hint[0] + g_pool_claims_hint[1]) * 11 / 10;      // (+10 %: buckets are not even)
-            if (tune.lds_small_buckets == 16 || (tune.lds_small_buckets != 8 && need / 8 > one_pass)) mp->lds_bucket_bits = LG_LDS_BITS_SMALL16;
-        }
-        const int64_t n_buckets = (int64_t)1 << mp->lds_bucket_bits;
-        {
-            // one claim list per bucket, twice an even share each (a bucket that outgrows its list is served from the hop's
-            // slots instead, kernels_sample.hip)
-            mp->claim_cap = (int32_t)(2 * ((slots + n_buckets - 1) / n_buckets) + 256);
-            if (tune.lds_claim_cap > 0) mp->claim_cap = tune.lds_claim_cap;      // tests: force the fallback
-            const int64_t chunks = ((int64_t)mp->claim_cap + LG_CLAIM_CHUNK - 1) / LG_CLAIM_CHUNK;      // (interleaved by chunk: LanePtrs)
-            mp->claim_pairs = (unsigned long long*)d_alloc_space(n_buckets * chunks * LG_CLAIM_CHUNK * sizeof(unsigned long long));
-            mp->claim_cnt = (int32_t*)d_alloc_space(n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t));
-            HIP_CALL(hipMemset(mp->claim_cnt, 0, n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t)));
-        }
-        if (n_buckets > 64) {        // 256 buckets: {first place, count} per partition tile and bucket (sample_kernel -> place_kernel)
-            const int64_t n_parts = (n_super + lg_lds_k_min(mp->lds_bucket_bits) - 1) / lg_lds_k_min(mp->lds_bucket_bits) + 1;
-            mp->run_off = (int32_t*)d_alloc_space(n_parts * n_buckets * 2 * sizeof(int32_t));
-        }
-        // per-bucket lists of the nodes hops 1 .. H-1 add (later hops must recognise them): twice an even share each;
-        // a bucket that outgrows its list is served by scanning sampled_ids instead (kernels_sample.hip)
+        // first touches (legion_core.h): no per-vertex state; one claim list and one known list per hash bucket, sized by the plan
+        // (sample_plan.h; PreSC's maxima when this thread's creator passed them on, lg_set_pool_claims_hint)
         int64_t listed = 0;
         for (int i = 1; i < hop_num; i++) listed += mp->max_new[i];
-        if (listed > 0) {
-            mp->known_cap = (int32_t)(2 * ((listed + n_buckets - 1) / n_buckets) + 256);
-            if (tune.lds_known_cap > 0) mp->known_cap = tune.lds_known_cap;   // tests: force the scan
+        const SamplePoolPlan plan = sample_pool_plan(hop_num > 0 ? per : batch_size, listed, g_pool_claims_hint[0], g_pool_claims_hint[1],
+                                                     tune.lds_small_buckets, tune.lds_claim_cap, tune.lds_known_cap);
+        mp->lds_bucket_bits = plan.bucket_bits;
+        mp->last_hop_claims_hint = g_pool_claims_hint[0];
+        const int64_t n_buckets = (int64_t)1 << plan.bucket_bits;
+        mp->claim_cap = plan.claim_cap;
+        mp->claim_pairs = (unsigned long long*)d_alloc_space(n_buckets * plan.claim_chunks * LG_CLAIM_CHUNK * sizeof(unsigned long long));      // (interleaved by chunk: LanePtrs)
+        mp->claim_cnt = (int32_t*)d_alloc_space(n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t));
+        HIP_CALL(hipMemset(mp->claim_cnt, 0, n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t)));
+        if (plan.run_off_parts > 0)      // 256 buckets: {first place, count} per partition tile and bucket (sample_kernel -> place_kernel)
+            mp->run_off = (int32_t*)d_alloc_space(plan.run_off_parts * n_buckets * 2 * sizeof(int32_t));
+        if (plan.known_cap > 0) {        // per-bucket lists of the nodes hops 1 .. H-1 add
+            mp->known_cap = plan.known_cap;
             mp->known_pairs = (unsigned long long*)d_alloc_space(n_buckets * mp->known_cap * sizeof(unsigned long long));
             mp->known_cnt = (int32_t*)d_alloc_space(n_buckets * sizeof(int32_t));
             HIP_CALL(hipMemset(mp->known_cnt, 0, n_buckets * sizeof(int32_t)));

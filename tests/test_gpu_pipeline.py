@@ -448,7 +448,7 @@ def test_lds_small_class_picks_16_buckets_on_a_dense_graph(hip, monkeypatch):
             g, c = gpu.run(0, it, 0, is_presc=True), cpu.run(0, it, 0, is_presc=True)
             compare_batches(g, c, f"presc {it}: ")
         last_edges, before = int(g["edge_counter"][11] - g["edge_counter"][10]), int(g["node_counter"][10])
-        assert ((last_edges + before) * 11 // 10 // 8 > 7168) == (want == 16), (last_edges, before)    # (storage.hip's rule)
+        assert ((last_edges + before) * 11 // 10 // 8 > 7168) == (want == 16), (last_edges, before)    # (sample_plan.h's rule, restated)
         gpu.cache.candidate_selection(0, gpu.graph)
         gpu.cache.set_capacity(64, 8)
         gpu.cache.fill_up(gpu.feature, gpu.graph)
@@ -617,7 +617,7 @@ def test_lds_dedup_big_buckets_after_presc(hip, batch, scale, per_thread, bucket
         compare_batches(g, c, f"presc {it}: ")
         last_edges = max(last_edges, int(g["edge_counter"][12] - g["edge_counter"][11]))
     lo, hi = {(10, 64): (5, 10), (20, 64): (10, 20), (10, 256): (20, 160)}[(per_thread, buckets)]
-    assert 64 * lo * 1024 * 10 // 11 < last_edges <= 64 * hi * 1024 * 10 // 11, last_edges        # (operators.hip / storage.hip's rules)
+    assert 64 * lo * 1024 * 10 // 11 < last_edges <= 64 * hi * 1024 * 10 // 11, last_edges        # (sample_plan.h's rules, restated)
     gpu.cache.candidate_selection(0, gpu.graph)
     gpu.cache.set_capacity(2000, 200)
     gpu.cache.fill_up(gpu.feature, gpu.graph)
