@@ -144,6 +144,19 @@ int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p);
 #define LEGION_DISTINCT_MAX_FANOUT 256
 int32_t legion_pool_set_sample_replace(LegionMemoryPool* p, int32_t replace);
 int32_t legion_pool_sample_replace(const LegionMemoryPool* p);
+/* Edge-id mode of the pool (DGL's block.edata[dgl.EID]); 0 is the default.  1: every sampled edge e of a batch also gets
+ * agg_edge_ids[e] (int64, legion_pool_buffer 14), indexed like agg_src_ids[e] / agg_dst_ids[e] -- the same cumulative per-hop
+ * ranges (edge_counter), capacity num_ids:  agg_edge_ids[e] = indptr[agg_dst_ids[e]] + the adjacency position the slot drew, with
+ * the FULL CSR's indptr -- also for a row that was read from a cached topology (the fill copies a row in CSR order).  So
+ * indptr[s] <= id < indptr[s + 1] and col[id] == agg_src_ids[e]; parallel edges get their own ids.  A slot without an edge
+ * (k >= min(f, D), a negative column entry, a frontier entry < 0) has no id.  Everything else a batch holds is bit for bit what it
+ * is with the mode off, in both sampling modes.  Two arrays (int32 per slot, int64 per edge) are allocated when the mode is turned
+ * on, outside any lane arena; with the mode off nothing is allocated and no kernel differs.  In-process only for now: the server,
+ * the shared segment and the trainer end do not carry edge ids.  Returns 0, or -1 (nothing changes) once
+ * the pool has sampled a hop (eagerly or into a captured graph), for a value other than 0 / 1, or for a null pool.  Lanes of a
+ * pipeline take the mode through legion_pipeline_set_edge_ids. */
+int32_t legion_pool_set_edge_ids(LegionMemoryPool* p, int32_t on);
+int32_t legion_pool_edge_ids(const LegionMemoryPool* p);
 void legion_pool_set_current_pipe(LegionMemoryPool* p, int32_t pipe);
 void legion_pool_set_mode_iter(LegionMemoryPool* p, int32_t mode, int32_t iter);
 int32_t legion_pool_num_ids(const LegionMemoryPool* p);
@@ -151,7 +164,8 @@ int32_t legion_pool_num_ids(const LegionMemoryPool* p);
  *        6 edge_counter (the IPC slot order, SS/engine/ipc_service.cu:163-169,203);
  *        7 agg_src_ids 8 agg_dst_ids 9 cache_search_buffer 10 tmp_part_ind 11 tmp_part_off
  *        12 position_map (always null here); 13 node_slot (new: int32[num_ids], the feature-cache slot the sampler carried for
- *        each node of the batch, -3 = not carried: the gather looks node_map up).  Returns the device pointer of the CURRENT pipe slot. */
+ *        each node of the batch, -3 = not carried: the gather looks node_map up); 14 agg_edge_ids (int64[num_ids], null unless the
+ *        pool's edge-id mode is on: legion_pool_set_edge_ids).  Returns the device pointer of the CURRENT pipe slot. */
 void* legion_pool_buffer(LegionMemoryPool* p, int32_t which);
 /* New in this build.  The reference keeps first touches in accessed_map (N bits, memset per batch) + position_map (N entries,
  * SS/engine/memorypool.cuh:120-135); a pool here keeps NOTHING per vertex: a hop's claims are de-duplicated bucket by bucket in
@@ -161,7 +175,8 @@ int32_t legion_pool_lds_buckets(const LegionMemoryPool* p);
 int64_t legion_pool_state_bytes(const LegionMemoryPool* p);
 /* Sticky error bits raised on the device for this pool (0 = none): 1 a de-duplication bucket that fits no LDS table, 2 batch larger than the
  * feature buffer (gather stopped at its end; the reference overruns, SS/engine/server.cu:277), 4 internal, 8 a hop not sampled
- * (a fan-out above LEGION_DISTINCT_MAX_FANOUT without replacement, or lanes of one group with different sampling modes).  The
+ * (a fan-out above LEGION_DISTINCT_MAX_FANOUT without replacement, or lanes of one group with different sampling or edge-id
+ * modes).  The
  * word lives in host-visible memory: reading it after the batch completed needs no copy. */
 int32_t legion_pool_error(const LegionMemoryPool* p);
 void legion_pool_destroy(LegionMemoryPool* p);
@@ -339,6 +354,9 @@ LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatu
 /* sampling mode of every lane (legion_pool_set_sample_replace).  Returns 0, or -1 (nothing changes) once the pipeline has
  * submitted a group, for a value other than 0 / 1 or for 0 with a fan-out above LEGION_DISTINCT_MAX_FANOUT. */
 int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace);
+/* edge-id mode of every lane (legion_pool_set_edge_ids; a lane's ids: legion_pool_buffer(legion_pipeline_pool(..), 14)).  Returns
+ * 0, or -1 (nothing changes) once the pipeline has submitted a group or for a value other than 0 / 1. */
+int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on);
 /* enqueues batches counter0 .. counter0 + group_size - 1; returns the slot */
 int32_t legion_pipeline_submit(LegionPipeline* p, int32_t counter0, int32_t mode);
 /* only the first n_active lanes work (tail of a run that is not a multiple of group_size) */

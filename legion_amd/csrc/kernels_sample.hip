@@ -245,6 +245,8 @@ struct SampleArgs {
     LG_G int32_t* err_flag;
     LG_G unsigned long long* claim_pairs; LG_G int32_t* run_off; LG_G int32_t* claim_cnt; int32_t claim_cap, ids_cap;
     LG_G unsigned long long* known_pairs; LG_G int32_t* known_cnt; int32_t known_cap;
+    // edge-id mode (the EIDS instances of sample_kernel / compact_kernel; nobody else reads these)
+    const LG_G int64_t* indptr_full; LG_G int32_t* slot_pick; LG_G int64_t* agg_edge_ids;
 };
 
 // 16-byte header load / store through a global-address-space pointer (no implicit struct copy across
@@ -291,6 +293,8 @@ __device__ __forceinline__ SampleArgs lane_args(const HopParams& p, const LanePt
     a.run_off = LG_GPTR(int32_t, L.run_off);
     a.claim_cnt = LG_GPTR(int32_t, L.claim_cnt); a.claim_cap = L.claim_cap; a.ids_cap = L.ids_cap;
     a.known_pairs = LG_GPTR(unsigned long long, L.known_pairs); a.known_cnt = LG_GPTR(int32_t, L.known_cnt); a.known_cap = L.known_cap;
+    a.indptr_full = LG_GPTR(const int64_t, p.indptr_full); a.slot_pick = LG_GPTR(int32_t, L.slot_pick);
+    a.agg_edge_ids = LG_GPTR(int64_t, L.agg_edge_ids);
     return a;
 }
 
@@ -341,7 +345,10 @@ __device__ __forceinline__ HopGeom hop_geometry(const SampleArgs& a)
 // DISTINCT: sampling without replacement (see floyd_resolve): the slots' draws go to s_pick, indexed by slot - j0 * f (the super
 // tile's slots and, for an entry that began in the previous super tile, its earlier ones); one thread per entry with D > f then
 // resolves them in place, and the slots read their picks from there.  Fan-outs up to LG_DISTINCT_MAX_FANOUT (the span of s_pick).
-template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
+// EIDS: edge-id mode (HopParams.edge_ids): the adjacency position a slot drew goes to slot_pick, next to slot_dst -- the same for a
+// row of the full CSR and for its copy in a cached topology (the fill copies a row in CSR order); compact_kernel<.., EIDS> adds the
+// full CSR's row start.  4 bytes per slot with an edge, no branch on where the row lives, no LDS.
+template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false, bool EIDS = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
 __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_SGPRS))) void sample_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NB = 1 << BB;
@@ -435,11 +442,13 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
 
             if (SINGLE && tid < NB) s_bcnt[tid] = 0;     // (made visible by the barrier above the loads' use below)
             int32_t dst[LG_SLOTS_PER_LANE], fs[LG_SLOTS_PER_LANE];
+            int32_t pk[EIDS ? LG_SLOTS_PER_LANE : 1];
 #pragma unroll
             for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
                 const int32_t idx = idx0 + u * LG_TILE + tid;
                 dst[u] = -1;
                 fs[u] = LG_FS_UNKNOWN;
+                if constexpr (EIDS) pk[u] = 0;
                 if (idx < g.total) {
                     const int32_t q = idx / count;
                     const int32_t k = idx - q * count;
@@ -451,6 +460,7 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                         // from the full CSR (slot P: all but the cached-topology rows) address it through pointers that came
                         // with the launch; only a cached row's pick loads its column array's address from the table first
                         const int64_t at = h.start + (int64_t)pick;
+                        if constexpr (EIDS) pk[u] = pick;
                         if (h.slot == a.partition_count) {
                             // (non-temporal: a pick brings a whole 128-byte line in for 4-8 bytes, and most lines are not picked from
                             // again before they are evicted -- tools/micro/random_load_policy.hip: 48.9 -> 53.5 G random loads/s, every
@@ -489,6 +499,8 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                     __builtin_nontemporal_store(dst[u], &a.slot_dst[idx]);
                     a.slot_pos[idx] = -1;      // "no position yet": compact_kernel publishes a first touch's position here (plain store: no difference)
                     if (a.slot_fs != nullptr && dst[u] >= 0) __builtin_nontemporal_store(fs[u], &a.slot_fs[idx]);     // (read for first-touch slots only)
+                    if constexpr (EIDS)
+                        if (dst[u] >= 0) __builtin_nontemporal_store(pk[u], &a.slot_pick[idx]);                       // (read for slots with an edge only)
                 }
             }
             if (SINGLE && STAGED) {
@@ -889,6 +901,10 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 #ifndef LG_SCATTER_MIN_WAVES_LAST
 #define LG_SCATTER_MIN_WAVES_LAST 8
 #endif
+#ifndef LG_SCATTER_MIN_WAVES_LAST_EIDS
+#define LG_SCATTER_MIN_WAVES_LAST_EIDS 6      // the last hop's edge-id instance needs 74 VGPRs: held to 8 waves per SIMD (64) it spills 44 bytes
+                                              // per lane, to 7 (72) still 12; at 6 it uses no scratch
+#endif
 #define LG_SPIN_LIMIT (1 << 24)       // polls of one word before a waiter gives up with LG_ERR_CHAIN (seconds; a wait is microseconds)
 #define LG_ST_AGG (1ull << 62)
 #define LG_ST_PREF (2ull << 62)
@@ -899,9 +915,14 @@ __device__ __forceinline__ unsigned long long st_word(unsigned long long status,
 __device__ __forceinline__ int32_t st_edges(unsigned long long w) { return (int32_t)((w >> 31) & 0x7FFFFFFFull); }
 __device__ __forceinline__ int32_t st_nodes(unsigned long long w) { return (int32_t)(w & 0x7FFFFFFFull); }
 
-template <bool LAST, int CT>       // LAST: the last hop writes no frontier headers and no position state (fewer registers, more waves per SIMD); CT: threads
+// EIDS (edge-id mode, HopParams.edge_ids): every edge e also gets agg_edge_ids[e] = indptr_full[vertex the slot sampled for] + the
+// position the slot drew (slot_pick, sample_kernel<.., EIDS>): the edge's place in the FULL CSR's column array, also for a row that
+// was read from a cached topology.  Both loads depend on the slot index only and go out with the others of that kind (the row
+// pointer is one 8-byte load the f consecutive slots of a frontier entry share); int64 from the load to the store.  A template
+// flag, not a null check: the default instances keep their registers and their waves per SIMD.
+template <bool LAST, int CT, bool EIDS = false>       // LAST: the last hop writes no frontier headers and no position state (fewer registers, more waves per SIMD); CT: threads
                                    // per workgroup = slots per 'tile row' (a workgroup iteration takes LG_SLOTS_PER_LANE * CT consecutive slots)
-__global__ __launch_bounds__(CT, LAST ? LG_SCATTER_MIN_WAVES_LAST : LG_SCATTER_MIN_WAVES) __attribute__((amdgpu_num_sgpr(80)))
+__global__ __launch_bounds__(CT, LAST ? (EIDS ? LG_SCATTER_MIN_WAVES_LAST_EIDS : LG_SCATTER_MIN_WAVES_LAST) : LG_SCATTER_MIN_WAVES) __attribute__((amdgpu_num_sgpr(80)))
 void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NW = LG_SLOTS_PER_LANE * (CT / 64);     // waves' worth of slots in a workgroup iteration (16 or 32)
@@ -946,16 +967,25 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
         // what depends on the slot INDEX only -- the vertex the slot sampled for, its position, the carried cache slot -- is loaded
         // together with slot_dst, for every slot of the tile: more bytes (invalid slots too), one dependent round trip less (-4 %, round 4)
         int32_t src_of[LG_SLOTS_PER_LANE], src_pos[LG_SLOTS_PER_LANE], fsv[LG_SLOTS_PER_LANE];
+        int32_t pk[EIDS ? LG_SLOTS_PER_LANE : 1];
+        int64_t row0[EIDS ? LG_SLOTS_PER_LANE : 1];
 #pragma unroll
         for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
             const int32_t idx = idx0 + u * CT + tid;
             src_of[u] = 0; src_pos[u] = 0; fsv[u] = LG_FS_UNKNOWN;
+            if constexpr (EIDS) { pk[u] = 0; row0[u] = 0; }
             if (idx < total) {
                 const int32_t q = idx / a.count;
                 src_of[u] = frontier[q];
                 src_pos[u] = seeds ? q : a.agg_src_off[f_off + q];
                 if (a.slot_fs != nullptr) fsv[u] = a.slot_fs[idx];
+                if constexpr (EIDS) pk[u] = a.slot_pick[idx];      // (stale where the slot has no edge: not used there)
             }
+        }
+        if constexpr (EIDS) {
+#pragma unroll
+            for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
+                if (idx0 + u * CT + tid < total && src_of[u] >= 0) row0[u] = a.indptr_full[src_of[u]];
         }
 #pragma unroll
         for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
@@ -996,6 +1026,7 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 #pragma unroll
         for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
             const int32_t idx = idx0 + u * CT + tid;
+            if constexpr (EIDS) row0[u] += (int64_t)pk[u];        // the edge id, where the slot has an edge (int64 from here to the store)
             if (v[u] >= 0) {
                 const bool first = (mf[u] >> lane) & 1ull;
                 if (!first) fsv[u] = LG_FS_UNKNOWN;
@@ -1099,6 +1130,10 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
                 a.agg_src_ids[e] = dst;                            // :256, :276
                 a.agg_dst_ids[e] = src_of[u];                      // :257, :277
                 a.agg_dst_off[e] = src_pos[u];
+            }
+            if constexpr (EIDS) {
+                if (NT) __builtin_nontemporal_store(row0[u], &a.agg_edge_ids[e]);
+                else a.agg_edge_ids[e] = row0[u];
             }
             if (!LAST) store_hdr(a.fh_edge + e, nh[u]);
             const int32_t n = n_at[u];
@@ -1227,8 +1262,13 @@ static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams
     HopParams q = p;
     q.lds_k = plan.k;
     const dim3 grid(plan.sample_gx, n_lanes);
-    if (p.replace) sample_kernel<BB, ci.single, ci.staged><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-    else sample_kernel<BB, ci.single, ci.staged, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    if (!p.edge_ids) {
+        if (p.replace) sample_kernel<BB, ci.single, ci.staged><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+        else sample_kernel<BB, ci.single, ci.staged, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    } else {       // edge-id mode: the instances that also leave each slot's pick (slot_pick)
+        if (p.replace) sample_kernel<BB, ci.single, ci.staged, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+        else sample_kernel<BB, ci.single, ci.staged, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    }
     hipCheckError();
     if constexpr (!ci.single) {
         place_kernel<BB><<<dim3(plan.place_gx, n_lanes), LG_PLACE_THREADS, (size_t)plan.stage_bytes, s>>>(q, d_lanes);
@@ -1241,8 +1281,13 @@ static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams
     }
     hipCheckError();
     const dim3 cgrid(plan.compact_gx, n_lanes);
-    if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-    else compact_kernel<false, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    if (!p.edge_ids) {
+        if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+        else compact_kernel<false, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    } else {       // edge-id mode: ... and the instances that turn it into agg_edge_ids
+        if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS, true><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+        else compact_kernel<false, LG_COMPACT_THREADS, true><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    }
     hipCheckError();
     if (!p.last_hop) {       // later hops must recognise the nodes this one added: their buckets' lists
         list_known_kernel<BB><<<dim3(plan.known_chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);

@@ -103,7 +103,7 @@ enum HopScratch {
 #define LG_ERR_FEATURE_ROWS 2     // the batch has more rows than the feature buffer: the gather stopped at its end
 #define LG_ERR_CHAIN 4            // compact_kernel gave up waiting for an earlier tile's status word / a winner's position (cannot happen)
 #define LG_ERR_SAMPLE_MODE 8      // a hop was not sampled: a fan-out above LG_DISTINCT_MAX_FANOUT without replacement, or lanes of one
-                                  // group with different sampling modes (set on the host; the setters refuse both)
+                                  // group with different sampling or edge-id modes (set on the host; the setters refuse both)
 
 // Device code: a pointer that was loaded from memory (LanePtrs, pointer tables, LDS) is "generic" to
 // the compiler, which then emits flat_* instructions; those count on lgkmcnt as well as vmcnt, so every
@@ -209,6 +209,10 @@ struct LanePtrs {
     float* float_features;
     int32_t feature_rows;
     int32_t max_slots;
+    // edge-id mode (MemoryPool::edge_ids), else both null: the adjacency position each slot drew (sample_kernel -> compact_kernel)
+    // and, per edge of the batch, its position in the FULL CSR's column array -- indexed like agg_src_ids
+    int32_t* slot_pick;                // [max_slots]
+    int64_t* agg_edge_ids;             // [num_ids]
 };
 
 // ---------------------------------------------------------------------------------------------
@@ -299,6 +303,13 @@ public:
     int32_t sample_replace = 1;
     bool sample_used = false;
     int32_t max_fanout = 0;            // largest fan-out the pool was sized for
+    // 1: every sampled edge e also gets agg_edge_ids[e] = its position in the full CSR's column array (DGL's dgl.EID), next to
+    // agg_src_ids[e].  The two arrays below exist only then (lg_pool_alloc_edge_ids: plain allocations of the pool, never part of a
+    // lane arena -- the trainer-visible arrays and the wire do not change).  Fixed once the pool has sampled a hop (sample_used)
+    int32_t edge_ids = 0;
+    int32_t* slot_pick = nullptr;      // [max_slots] see LanePtrs
+    int64_t* agg_edge_ids = nullptr;   // [num_ids]
+    int32_t lanes_epoch = 0;           // bumped when the pool's lane descriptor changes after creation (a lane group re-uploads its copy)
     int64_t grid_rows_hint = 0;        // > 0: rows a batch typically has (the Runner's pipe-slot pool holds the worst case: launches are sized for the usual one)
     int32_t dev_id = 0;
     bool owns_buffers = false;
@@ -667,6 +678,8 @@ bool lg_is_local(int32_t dev);
 
 void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
                            const int32_t* fanout, int32_t hop_num, int32_t float_feature_len);
+// the two arrays of the edge-id mode (MemoryPool::edge_ids), part of the pool's private allocation: made when the mode is turned on
+void lg_pool_alloc_edge_ids(MemoryPool* mp);
 // how many pools of this shape the caller is about to keep in flight on the device (Pipeline: lanes x slots);
 // feeds the direct-vs-table choice of the position state (LEGION_DEDUP=auto).  Thread-local; 0 = one pool.
 // what PreSC saw of the LAST hop, the largest one: its edges (= the claims its de-duplication takes) and the batch's nodes
@@ -727,6 +740,8 @@ struct HopParams {                  // what every lane of a launch shares
     unsigned long long* topo_transactions; // presample only: 64-byte transactions the hop's topology reads amount to
     int32_t lds_k;                  // super tiles per partition tile in this hop (set by launch_random_sample)
     int32_t replace;                // 1: draws with replacement (the reference's); 0: distinct positions per entry (MemoryPool::sample_replace)
+    int32_t edge_ids;               // 1: the hop also writes agg_edge_ids (MemoryPool::edge_ids): the flagged sample / compact instances
+    const int64_t* indptr_full;     // the full CSR's row pointers (slot P of the pointer tables): read by those instances only
 };
 // bucket_bits, last_hop_claims_hint: the pool's (MemoryPool); the launch follows sample_hop_plan (sample_plan.h)
 void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits, int64_t last_hop_claims_hint, const LanePtrs* d_lanes,

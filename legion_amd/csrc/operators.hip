@@ -33,6 +33,7 @@ static inline UnifiedCache* cache_of(LegionUnifiedCache* c) { return reinterpret
 // ---- lane-group bodies: every operator works on n lanes (n = 1 for the reference-shaped calls) ----
 struct LegionLaneGroup {
     std::vector<MemoryPool*> pools;
+    std::vector<int32_t> epochs;      // each pool's lanes_epoch when d_lanes was written
     LanePtrs* d_lanes = nullptr;      // contiguous device copy of every pool's current lane
     int32_t* iter_state = nullptr;    // device {next iteration of lane 0, stride} for graph replay, or null
 };
@@ -127,6 +128,8 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
     p.topo_transactions = (is_presc && cache) ? cache->Controller(dev_id)->GetTopoTransactions() : nullptr;
     p.lds_k = 1;                             // (launch_random_sample sets the hop's partition tile)
     p.replace = pool0->sample_replace;
+    p.edge_ids = pool0->edge_ids;
+    p.indptr_full = graph->GetCSRNodeIndexCPU();
     lg::launch_random_sample(s, p, pool0->lds_bucket_bits, pool0->last_hop_claims_hint, d_lanes, n_lanes);
 }
 
@@ -434,12 +437,28 @@ extern "C" LegionLaneGroup* legion_group_create(LegionMemoryPool** pools, int32_
     for (int32_t i = 0; i < n; i++) {
         MemoryPool* mp = reinterpret_cast<MemoryPool*>(pools[i]);
         g->pools.push_back(mp);
+        g->epochs.push_back(mp->lanes_epoch);
         h.push_back(mp->HostLane(mp->GetCurrentPipe()));
     }
     SetGPUDevice(g->pools[0]->dev_id);
     g->d_lanes = (LanePtrs*)d_alloc_space((int64_t)n * sizeof(LanePtrs));
     HIP_CALL(hipMemcpy(g->d_lanes, h.data(), h.size() * sizeof(LanePtrs), hipMemcpyHostToDevice));
     return g;
+}
+
+// a pool whose lane descriptor changed after the group was made (legion_pool_set_edge_ids: possible only before the pool has
+// sampled, so never between the replays of a captured graph): its entry of d_lanes is written again
+extern "C" void legion_group_refresh(LegionLaneGroup* g)
+{
+    if (!g) return;
+    for (size_t i = 0; i < g->pools.size(); i++) {
+        MemoryPool* mp = g->pools[i];
+        if (g->epochs[i] == mp->lanes_epoch) continue;
+        SetGPUDevice(mp->dev_id);
+        const LanePtrs h = mp->HostLane(mp->GetCurrentPipe());
+        HIP_CALL(hipMemcpy(g->d_lanes + i, &h, sizeof(LanePtrs), hipMemcpyHostToDevice));
+        g->epochs[i] = mp->lanes_epoch;
+    }
 }
 
 extern "C" void legion_group_set_iter_state(LegionLaneGroup* g, int32_t* iter_state_devptr) { if (g) g->iter_state = iter_state_devptr; }
@@ -465,10 +484,22 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
 {
     if (!graph || !feature || !group || group->pools.empty()) { std::cout << "invalid storage ptr\n"; return; }
     if (n_active < 1 || n_active > (int32_t)group->pools.size()) n_active = (int32_t)group->pools.size();
-    // every lane samples with lane 0's mode (HopParams is shared by the launch): lanes that disagree are refused, and every lane's
-    // mode is fixed from here on (legion_pool_set_sample_replace)
+    // every lane samples with lane 0's modes (HopParams is shared by the launch): lanes that disagree are refused, and every lane's
+    // modes are fixed from here on (legion_pool_set_sample_replace, legion_pool_set_edge_ids)
+    {
+        bool stale = false;
+        for (size_t i = 0; i < group->pools.size(); i++) stale |= group->epochs[i] != group->pools[i]->lanes_epoch;
+        hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+        if (stale) HIP_CALL(hipStreamIsCapturing(static_cast<hipStream_t>(strm_hdl), &cap));
+        if (stale && cap != hipStreamCaptureStatusNone) {      // (a copy cannot run inside a capture: legion_pipeline_set_edge_ids refreshes its groups itself)
+            printf("legion_hip: a lane's mode changed after its group was made; nothing captured\n");
+            for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
+            return;
+        }
+        if (stale) legion_group_refresh(group);
+    }
     for (int32_t i = 0; i < n_active; i++)
-        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace) {
+        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace || group->pools[i]->edge_ids != group->pools[0]->edge_ids) {
             printf("legion_hip: lanes of one group with different sampling modes; nothing enqueued\n");
             for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
             return;

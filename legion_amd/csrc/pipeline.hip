@@ -55,6 +55,7 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
                                            const int32_t* fanout, int32_t hop_num, int32_t phase);
 extern "C" void legion_pool_profile_begin(LegionMemoryPool* p_, int32_t max_ops);
 extern "C" const void* legion_group_lane_desc(LegionLaneGroup* g, int32_t lane);
+extern "C" void legion_group_refresh(LegionLaneGroup* g);
 
 struct Slot {
     std::vector<MemoryPool*> pools;           // G lanes
@@ -242,6 +243,22 @@ extern "C" int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t
     for (Slot& sl : p->slots)
         for (MemoryPool* mp : sl.pools)
             if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(mp), replace) != 0) return -1;
+    return 0;
+}
+
+// edge-id mode of every lane of every slot (legion_pool_set_edge_ids); refused once any lane has sampled
+extern "C" int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on)
+{
+    if (!p || (on != 0 && on != 1)) return -1;
+    for (Slot& sl : p->slots)
+        for (MemoryPool* mp : sl.pools)
+            if (mp->sample_used) return -1;
+    SetGPUDevice(p->dev_id);
+    for (Slot& sl : p->slots) {
+        for (MemoryPool* mp : sl.pools)
+            if (legion_pool_set_edge_ids(reinterpret_cast<LegionMemoryPool*>(mp), on) != 0) return -1;
+        legion_group_refresh(sl.group);          // the slot's copy of its lanes' descriptors, before anything is captured
+    }
     return 0;
 }
 

@@ -880,6 +880,8 @@ LanePtrs MemoryPool::HostLane(int32_t pipe) const
     h.float_features = float_features_[pipe];
     int64_t rows = feature_rows < num_ids ? feature_rows : num_ids;
     h.feature_rows = (int32_t)rows;
+    h.slot_pick = slot_pick;
+    h.agg_edge_ids = agg_edge_ids;
     return h;
 }
 
@@ -929,6 +931,10 @@ void MemoryPool::Finalize()
     d_free_space(hop_scratch);
     d_free_space(fh_edge);
     fh_edge = nullptr;
+    d_free_space(slot_pick);
+    d_free_space(agg_edge_ids);
+    slot_pick = nullptr;
+    agg_edge_ids = nullptr;
     cache_search_buffer_ = agg_src_ids_ = agg_dst_ids_ = tmp_part_off_ = nullptr;
     tmp_part_ind_ = nullptr;
     slot_dst = hop_scratch = nullptr;
@@ -1031,6 +1037,17 @@ void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nod
     mp->fh_edge = (RowHdr*)d_alloc_space(num_ids * sizeof(RowHdr));
     mp->hop_scratch = (int32_t*)d_alloc_space(HS_WORDS * sizeof(int32_t));
     HIP_CALL(hipMemset(mp->hop_scratch, 0, HS_WORDS * sizeof(int32_t)));
+}
+
+// edge-id mode: the per-slot picks and the per-edge ids, sized like slot_dst and agg_src_ids.  Plain allocations of the pool even
+// where its trainer-visible arrays live in a lane arena (the arena's layout and the wire do not change)
+void lg_pool_alloc_edge_ids(MemoryPool* mp)
+{
+    if (mp->slot_pick != nullptr && mp->agg_edge_ids != nullptr) return;
+    SetGPUDevice(mp->dev_id);
+    mp->slot_pick = (int32_t*)d_alloc_space((int64_t)mp->max_slots * sizeof(int32_t));
+    mp->agg_edge_ids = (int64_t*)d_alloc_space((int64_t)mp->num_ids * sizeof(int64_t));
+    HIP_CALL(hipMemset(mp->agg_edge_ids, 0xff, (size_t)mp->num_ids * sizeof(int64_t)));      // -1: no edge yet
 }
 
 // ---- C API ----------------------------------------------------------------------------------
@@ -1246,6 +1263,26 @@ extern "C" int32_t legion_pool_sample_replace(const LegionMemoryPool* p_)
     return mp ? mp->sample_replace : -1;
 }
 
+// 1: every sampled edge also gets its position in the full CSR's column array (agg_edge_ids, DGL's dgl.EID); 0 (default): nothing
+// of that exists.  Only before the pool samples a hop; turning it on allocates the two arrays, which stay until the pool goes
+extern "C" int32_t legion_pool_set_edge_ids(LegionMemoryPool* p_, int32_t on)
+{
+    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
+    if (!mp || (on != 0 && on != 1) || mp->sample_used) return -1;
+    if (on == mp->edge_ids) return 0;
+    if (on) lg_pool_alloc_edge_ids(mp);
+    mp->edge_ids = on;
+    mp->lanes_epoch++;                     // (lane groups made before this re-upload their copy of the lane: operators.hip)
+    mp->InvalidateDeviceLanes();
+    return 0;
+}
+
+extern "C" int32_t legion_pool_edge_ids(const LegionMemoryPool* p_)
+{
+    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
+    return mp ? mp->edge_ids : -1;
+}
+
 extern "C" void legion_pool_set_current_pipe(LegionMemoryPool* p_, int32_t pipe)
 {
     MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
@@ -1283,6 +1320,7 @@ extern "C" void* legion_pool_buffer(LegionMemoryPool* p_, int32_t which)
         case 11: return mp->GetTmpPartOff();
         case 12: return mp->GetPositionMap();      // always null: no per-vertex state in this build
         case 13: return mp->node_slot;             // [num_ids] feature-cache slot carried per node (LG_FS_UNKNOWN = -3: look it up), or null
+        case 14: return mp->edge_ids ? mp->agg_edge_ids : nullptr;      // int64[num_ids], edge-id mode only (legion_pool_set_edge_ids)
         default: return nullptr;
     }
 }

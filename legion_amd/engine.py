@@ -266,16 +266,21 @@ class MemoryPool:
             "node_counter": (5, torch.int32), "edge_counter": (6, torch.int32),
             "agg_src_ids": (7, torch.int32), "agg_dst_ids": (8, torch.int32),
             "cache_search_buffer": (9, torch.int32), "tmp_part_ind": (10, torch.int8),
-            "tmp_part_off": (11, torch.int32), "position_map": (12, torch.int32), "node_slot": (13, torch.int32)}
+            "tmp_part_off": (11, torch.int32), "position_map": (12, torch.int32), "node_slot": (13, torch.int32),
+            "agg_edge_ids": (14, torch.int64)}
 
     def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1, feature_out_dtype="float32",
-                 replace=True):
+                 replace=True, edge_ids=False):
         """feature_out_dtype: dtype of the rows the pool's gathers write ("float32" or "bfloat16": bf16[rows, D], the float32 row
         rounded to nearest even, or a bf16 storage's rows verbatim), independent of the FeatureStorage's dtype.
         replace: as DGL's NeighborSampler keyword -- True samples with replacement (the reference's draw), False takes min(f, D)
-        distinct neighbours of each frontier entry (fan-outs up to 256)."""
+        distinct neighbours of each frontier entry (fan-outs up to 256).
+        edge_ids: True also records, per sampled edge, its position in the graph's column array (DGL's dgl.EID): buffer("agg_edge_ids"),
+        int64, indexed like agg_src_ids; read_batch returns it as "agg_edge_ids"."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
+        if not isinstance(edge_ids, bool):
+            raise ValueError(f"edge_ids must be True or False, not {edge_ids!r}")
         self._lib = _libmod.load()
         self.dev_id = int(dev_id)
         self.device = _torch_device(self.dev_id)
@@ -290,6 +295,8 @@ class MemoryPool:
         self.num_ids = int(self._lib.legion_pool_num_ids(self.handle))
         self.set_feature_out_dtype(feature_out_dtype)
         self.set_replace(replace)
+        if edge_ids:
+            self.set_edge_ids(True)
 
     @classmethod
     def _borrowed(cls, handle, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, feature_rows):
@@ -328,6 +335,18 @@ class MemoryPool:
         if self._lib.legion_pool_set_sample_replace(self.handle, int(bool(replace))) != 0:
             raise RuntimeError("legion_pool_set_sample_replace: the pool has sampled already, or a fan-out is above 256 without replacement")
 
+    @property
+    def edge_ids(self):
+        return int(self._lib.legion_pool_edge_ids(self.handle)) == 1
+
+    def set_edge_ids(self, on):
+        """Only before the pool samples its first hop (the C ABI refuses it after: RuntimeError).  A Pipeline's lanes take the mode
+        through Pipeline.set_edge_ids."""
+        if not isinstance(on, bool):
+            raise ValueError(f"edge_ids must be True or False, not {on!r}")
+        if self._lib.legion_pool_set_edge_ids(self.handle, int(on)) != 0:
+            raise RuntimeError("legion_pool_set_edge_ids: the pool has sampled already")
+
     def alloc_features(self, rows):
         self.feature_rows = int(rows)
         self._lib.legion_pool_alloc_features(self.handle, self.feature_rows)
@@ -340,6 +359,8 @@ class MemoryPool:
         if name == "float_features" and self.feature_out_dtype == "bfloat16":
             dtype = torch.bfloat16
         ptr = self._lib.legion_pool_buffer(self.handle, which)
+        if name == "agg_edge_ids" and not ptr:
+            raise RuntimeError("agg_edge_ids: the pool's edge-id mode is off (MemoryPool(..., edge_ids=True) / set_edge_ids)")
         if name in ("node_counter", "edge_counter"):
             shape = (16,)
         elif name == "labels":
@@ -426,10 +447,13 @@ class Pipeline:
 
     def __init__(self, graph, feature, cache, dev_id, batch_size, fanout, group_size, feature_rows, use_graph=True,
                  slots=2, overlap=False, split=False, weave=False, arena=False,      # (split: accepted and ignored -- removed in round 5)
-                 feature_out_dtype="float32", replace=True):
-        """replace: MemoryPool's (every lane samples with / without replacement)."""
+                 feature_out_dtype="float32", replace=True, edge_ids=False):
+        """replace: MemoryPool's (every lane samples with / without replacement).  edge_ids: MemoryPool's (every lane records its
+        edges' ids)."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
+        if not isinstance(edge_ids, bool):
+            raise ValueError(f"edge_ids must be True or False, not {edge_ids!r}")
         self._lib = _libmod.load()
         self.group_size, self.slots = int(group_size), int(slots)
         self.fanout = [int(f) for f in fanout]
@@ -445,6 +469,8 @@ class Pipeline:
                       for s in range(self.slots)]
         if not replace:
             self.set_replace(False)
+        if edge_ids:
+            self.set_edge_ids(True)
 
     def set_replace(self, replace):
         """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
@@ -452,6 +478,17 @@ class Pipeline:
             raise ValueError(f"replace must be True or False, not {replace!r}")
         if self._lib.legion_pipeline_set_sample_replace(self.handle, int(bool(replace))) != 0:
             raise RuntimeError("legion_pipeline_set_sample_replace: the pipeline has sampled already, or a fan-out is above 256 without replacement")
+
+    @property
+    def edge_ids(self):
+        return all(pool.edge_ids for lanes in self.pools for pool in lanes)
+
+    def set_edge_ids(self, on):
+        """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
+        if not isinstance(on, bool):
+            raise ValueError(f"edge_ids must be True or False, not {on!r}")
+        if self._lib.legion_pipeline_set_edge_ids(self.handle, int(on)) != 0:
+            raise RuntimeError("legion_pipeline_set_edge_ids: the pipeline has sampled already")
 
     def submit(self, counter0, mode=TRAINMODE, n_active=None):
         if n_active is None or n_active >= self.group_size:
@@ -720,6 +757,8 @@ def read_batch(memorypool):
            "agg_dst_off": memorypool.buffer("agg_dst_off")[:n_edges].cpu().numpy().copy(),
            "agg_src_ids": memorypool.buffer("agg_src_ids")[:n_edges].cpu().numpy().copy(),
            "agg_dst_ids": memorypool.buffer("agg_dst_ids")[:n_edges].cpu().numpy().copy()}
+    if memorypool.edge_ids:
+        out["agg_edge_ids"] = memorypool.buffer("agg_edge_ids")[:n_edges].cpu().numpy().copy()
     if memorypool.feature_rows > 0:
         rows = memorypool.buffer("float_features")[:n_nodes]
         if rows.dtype == torch.bfloat16:     # (numpy has no bfloat16: the rows' bits, as uint16)

@@ -53,6 +53,8 @@ SIGNATURES = {
     "legion_pool_feature_out_dtype": (c_i32, [c_p]),
     "legion_pool_set_sample_replace": (c_i32, [c_p, c_i32]),
     "legion_pool_sample_replace": (c_i32, [c_p]),
+    "legion_pool_set_edge_ids": (c_i32, [c_p, c_i32]),
+    "legion_pool_edge_ids": (c_i32, [c_p]),
     "legion_cache_create": (c_p, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "legion_cache_init_controller": (None, [c_p, c_i32]),
     "legion_cache_set_replica_memory": (None, [c_p, c_i64]),
@@ -110,6 +112,7 @@ SIGNATURES = {
     "legion_pipeline_create": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32]),
     "legion_pipeline_create_ex": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32]),
     "legion_pipeline_set_sample_replace": (c_i32, [c_p, c_i32]),
+    "legion_pipeline_set_edge_ids": (c_i32, [c_p, c_i32]),
     "legion_pipeline_submit": (c_i32, [c_p, c_i32, c_i32]),
     "legion_pipeline_submit_n": (c_i32, [c_p, c_i32, c_i32, c_i32]),
     "legion_enqueue_group_n": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),
