@@ -760,7 +760,7 @@ def read_batch(memorypool):
     if memorypool.edge_ids:
         out["agg_edge_ids"] = memorypool.buffer("agg_edge_ids")[:n_edges].cpu().numpy().copy()
     if memorypool.feature_rows > 0:
-        rows = memorypool.buffer("float_features")[:n_nodes]
+        rows = memorypool.buffer("float_features")[:max(n_nodes, 0)]     # (the batch past the end counts a negative size)
         if rows.dtype == torch.bfloat16:     # (numpy has no bfloat16: the rows' bits, as uint16)
             rows = rows.view(torch.int16)
         out["float_features"] = rows.cpu().numpy().copy()

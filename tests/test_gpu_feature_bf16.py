@@ -18,16 +18,12 @@ from legion_amd import engine, synth
 from oracle import ffi
 from tests.gpu_harness import CpuSide, GpuSide
 from tests.helpers import Workload, compare_batches
+from tests.mode_ref import rounded
 from tests.server_proc import start_server
 from tests.test_gpu_boundary import check_trainer_batches, write_dataset
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-
-
-def rounded(f):
-    """The float32 table as a bf16 storage serves it: torch's rounding, widened back (exact)."""
-    return torch.from_numpy(np.ascontiguousarray(f)).to(torch.bfloat16).float().numpy()
 
 
 def torch_bf16_bits(x):

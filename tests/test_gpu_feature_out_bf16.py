@@ -18,21 +18,13 @@ from legion_amd import engine, synth
 from oracle import ffi
 from tests.gpu_harness import CpuSide, GpuSide
 from tests.helpers import Workload, compare_batches
+from tests.mode_ref import bf16_bits, rounded
 from tests.server_proc import start_server
 from tests.test_gpu_boundary import check_trainer_batches, write_dataset
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 SENTINEL = 0x7A5C      # a bf16 no gather writes in these tests (their tables hold no such value)
-
-
-def rounded(f):
-    return torch.from_numpy(np.ascontiguousarray(f)).to(torch.bfloat16).float().numpy()
-
-
-def bf16_bits(rows):
-    """torch's bf16 of float32 rows, as uint16 bits."""
-    return torch.from_numpy(np.ascontiguousarray(rows)).to(torch.bfloat16).view(torch.int16).numpy().view(np.uint16)
 
 
 def out_sides(wl, batch, fanout, storage, cache_memory=0, feature_rows=None):
