@@ -98,6 +98,30 @@ int32_t legion_graph_column_slots(const LegionGraphStorage* g, int32_t dev);
  * SS/storage/graph_storage_impl.cuh:33-53): device pointers to int64 index[capacity + 1] and int32 dst[index[capacity]]; nulls before a
  * fill.  Introspection: tests/test_gpu_ref_graph_cache.py compares them with what the reference's own kernels produce (oracle/_ref). */
 void legion_graph_cached_csr(const LegionGraphStorage* g, int32_t dev, const int64_t** index_out, const int32_t** dst_out);
+/* Weighted neighbour sampling (DGL's NeighborSampler prob=), new in this build; with replacement only.
+ * Weights: the caller's float32 w[E] on the device, aligned with the full CSR's column array.  The sanitised weight is
+ *   w'[i] = w[i] if w[i] is finite and > 0, else 0        (negative values, NaN, +-inf and -0 count as 0).
+ * Prefix table: edge_cdf, float32[E], indexed like the column array, a plain allocation of the library.  For row v with
+ * s = indptr[v] and degree D:  edge_cdf[s + i] = (float)(sum_{j <= i} (double)w'[s + j]) -- accumulated in double, rounded once.  How
+ * the sum is associated is not fixed; what holds is: non-decreasing inside a row; w'[s + i] == 0  =>  edge_cdf[s + i] ==
+ * edge_cdf[s + i - 1] (== 0 at i = 0); |edge_cdf - exact| <= 2^-23 * exact (D < 2^29).  Where every partial sum is exactly
+ * representable in float32 the table is unique.  Row totals must stay below FLT_MAX.
+ * Pick of slot idx = q * f + k, k < min(f, D), on a pool in weighted mode (legion_pool_set_sample_weighted):
+ *   T = edge_cdf[s + D - 1];  D == 0 or T == 0: the slot has no edge, exactly like k >= deg (slot_dst = -1: no claim, no hotness, no id);
+ *   else r = (double)(x - 1) / 2147483646.0 with x = minstd(idx + 1) (the r of the uniform draw), t = r * (double)T and
+ *   pick = #{ i in [0, D) : (double)edge_cdf[s + i] <= t }   -- an upper-bound binary search, ceil(log2(D + 1)) dependent 4-byte loads.
+ * t < T, so pick <= D - 1, and edge_cdf[s + pick] > t >= edge_cdf[s + pick - 1]: an entry of weight zero is never drawn.  s is always the
+ * FULL CSR's indptr[v], also for a row whose columns are read from a cached topology (the fill copies rows in CSR order): only the
+ * table lives with the full CSR.  With all weights 1.0f and D < 2^24 the pick is floor(r * D), the uniform draw: the batch is bit for
+ * bit the unweighted one.  Every frontier entry still owns slots q*f .. q*f + f - 1 and yields min(f, D) edges, or 0 when T == 0: no
+ * buffer size changes.  Not offered: weighted sampling without replacement; the server, the launcher and the wire (in-process and
+ * pipeline only, like edge ids); a table per rank of a multi-process clique is untested.
+ * legion_graph_set_edge_weights builds the table on the device current at the call, enqueued on `stream`; the caller's array may go
+ * once the stream has completed, and a weighted hop on ANOTHER stream (a pipeline's) must not start before.  Calling it again
+ * replaces the table.  Returns 0, or -1 for a null graph or null weights, or once a
+ * weighted hop has been enqueued against this graph.  legion_graph_edge_cdf: the table, or null before that call (introspection). */
+int32_t legion_graph_set_edge_weights(LegionGraphStorage* g, legion_stream_t stream, const float* w_devptr);
+const float* legion_graph_edge_cdf(const LegionGraphStorage* g);
 
 /* FeatureStorage: SS/storage/feature_storage.cu:18-90.  ids/labels are HOST arrays copied to
  * device `dev_id`; mode selects the training / validation / testing set. */
@@ -157,6 +181,14 @@ int32_t legion_pool_sample_replace(const LegionMemoryPool* p);
  * pipeline take the mode through legion_pipeline_set_edge_ids. */
 int32_t legion_pool_set_edge_ids(LegionMemoryPool* p, int32_t on);
 int32_t legion_pool_edge_ids(const LegionMemoryPool* p);
+/* Weighted mode of the pool (see legion_graph_set_edge_weights for the pick rule); 0 is the default.  1: every slot picks its
+ * adjacency position by the graph's prefix table instead of the uniform draw; everything after the pick (de-duplication, compaction,
+ * counters, gathers, hotness, edge ids) is unchanged.  Nothing is allocated in the pool.  Returns 0, or -1 (nothing changes) once the
+ * pool has sampled a hop, for a value other than 0 / 1, for a null pool, or for 1 while the pool samples without replacement;
+ * legion_pool_set_sample_replace(p, 0) returns -1 on a weighted pool.  A weighted hop against a graph without a table is not
+ * sampled (error bit 8).  Lanes of a pipeline take the mode through legion_pipeline_set_sample_weighted. */
+int32_t legion_pool_set_sample_weighted(LegionMemoryPool* p, int32_t on);
+int32_t legion_pool_sample_weighted(const LegionMemoryPool* p);
 void legion_pool_set_current_pipe(LegionMemoryPool* p, int32_t pipe);
 void legion_pool_set_mode_iter(LegionMemoryPool* p, int32_t mode, int32_t iter);
 int32_t legion_pool_num_ids(const LegionMemoryPool* p);
@@ -175,8 +207,8 @@ int32_t legion_pool_lds_buckets(const LegionMemoryPool* p);
 int64_t legion_pool_state_bytes(const LegionMemoryPool* p);
 /* Sticky error bits raised on the device for this pool (0 = none): 1 a de-duplication bucket that fits no LDS table, 2 batch larger than the
  * feature buffer (gather stopped at its end; the reference overruns, SS/engine/server.cu:277), 4 internal, 8 a hop not sampled
- * (a fan-out above LEGION_DISTINCT_MAX_FANOUT without replacement, or lanes of one group with different sampling or edge-id
- * modes).  The
+ * (a fan-out above LEGION_DISTINCT_MAX_FANOUT without replacement, lanes of one group with different sampling, edge-id or
+ * weighted modes, or a weighted hop against a graph without a prefix table: legion_graph_set_edge_weights).  The
  * word lives in host-visible memory: reading it after the batch completed needs no copy. */
 int32_t legion_pool_error(const LegionMemoryPool* p);
 void legion_pool_destroy(LegionMemoryPool* p);
@@ -357,6 +389,9 @@ int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace);
 /* edge-id mode of every lane (legion_pool_set_edge_ids; a lane's ids: legion_pool_buffer(legion_pipeline_pool(..), 14)).  Returns
  * 0, or -1 (nothing changes) once the pipeline has submitted a group or for a value other than 0 / 1. */
 int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on);
+/* weighted mode of every lane (legion_pool_set_sample_weighted).  Returns 0, or -1 (nothing changes) once the pipeline has submitted
+ * a group, for a value other than 0 / 1, or for 1 on a pipeline that samples without replacement. */
+int32_t legion_pipeline_set_sample_weighted(LegionPipeline* p, int32_t on);
 /* enqueues batches counter0 .. counter0 + group_size - 1; returns the slot */
 int32_t legion_pipeline_submit(LegionPipeline* p, int32_t counter0, int32_t mode);
 /* only the first n_active lanes work (tail of a run that is not a multiple of group_size) */
@@ -415,6 +450,10 @@ void legion_draw_batch(legion_stream_t stream, const int32_t* idx, const int32_t
  * [1, LEGION_DISTINCT_MAX_FANOUT] (nothing is launched). */
 int32_t legion_draw_distinct_batch(legion_stream_t stream, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out,
                                    int32_t n);
+/* the weighted pick rule on its own (legion_graph_set_edge_weights), for n slots: slot idx[i] in the row that starts at row_start[i]
+ * of cdf and has deg[i] entries; out[i] = pick, or -1 for deg[i] <= 0 or a row total of 0 */
+void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, const int64_t* row_start, const int32_t* deg,
+                                const float* cdf, int32_t* out, int32_t n);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -146,6 +146,55 @@ void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_
     hipCheckError();
 }
 
+// ------------------------------------------------------------------------------------------
+// Weighted sampling (HopParams.weighted == 1, DGL's prob=; with replacement).  cdf is the graph's prefix-sum table (kernels_weights.hip):
+// per row the inclusive sums of the sanitised weights, float32, indexed like the full CSR's column array.  Slot idx of a row
+// {s, D} with total T = cdf[s + D - 1]:  t = r * (double)T with the r of draw_from_x, and
+//   pick = #{ i in [0, D) : (double)cdf[s + i] <= t }
+// an upper-bound binary search, ceil(log2(D + 1)) dependent 4-byte loads.  t < T, so pick <= D - 1, and cdf[pick] > t >= cdf[pick - 1]:
+// an entry of weight zero is never drawn.  T == 0: the row yields no edge.  With unit weights (D < 2^24) cdf[s + i] = i + 1 and the
+// pick is floor(r * D): draw_from_x.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ double weighted_target(uint32_t x, float total)      // x = minstd_pow(idx + 1)
+{
+    double r = (double)(uint32_t)(x - 1u);
+    r /= 2147483646.0;
+    return r * (double)total;
+}
+// one probe of the search over [lo, lo + n): the entry at lo + n / 2 is v
+__device__ __forceinline__ void weighted_step(float v, double t, int32_t& lo, int32_t& n)
+{
+    const int32_t half = n >> 1;
+    if ((double)v <= t) { lo += half + 1; n -= half + 1; }
+    else n = half;
+}
+
+__global__ void draw_weighted_batch_kernel(const int32_t* idx, const int64_t* row_start, const int32_t* deg, const float* cdf, int32_t* out, int32_t n)
+{
+    const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int32_t D = deg[i];
+    int32_t pick = -1;
+    if (D > 0) {
+        const float* c = cdf + row_start[i];
+        const float T = c[D - 1];
+        if (T > 0.0f) {
+            const double t = weighted_target(minstd_pow((uint32_t)idx[i] + 1u), T);
+            int32_t lo = 0, m = D;
+            while (m > 0) weighted_step(c[lo + (m >> 1)], t, lo, m);
+            pick = min(lo, D - 1);
+        }
+    }
+    out[i] = pick;
+}
+
+void launch_draw_weighted_batch(hipStream_t s, const int32_t* idx, const int64_t* row_start, const int32_t* deg, const float* cdf, int32_t* out, int32_t n)
+{
+    if (n <= 0) return;
+    draw_weighted_batch_kernel<<<(n + 255) / 256, 256, 0, s>>>(idx, row_start, deg, cdf, out, n);
+    hipCheckError();
+}
+
 // the per-batch buffers the two bracket kernels touch, as global-address-space pointers
 struct BracketLane {
     LG_G int32_t* sampled_ids; LG_G int32_t* labels; LG_G int32_t* node_counter; LG_G int32_t* edge_counter;
@@ -247,6 +296,8 @@ struct SampleArgs {
     LG_G unsigned long long* known_pairs; LG_G int32_t* known_cnt; int32_t known_cap;
     // edge-id mode (the EIDS instances of sample_kernel / compact_kernel; nobody else reads these)
     const LG_G int64_t* indptr_full; LG_G int32_t* slot_pick; LG_G int64_t* agg_edge_ids;
+    // weighted mode (the WEIGHTED instances of sample_kernel; they read indptr_full too)
+    const LG_G float* edge_cdf;
 };
 
 // 16-byte header load / store through a global-address-space pointer (no implicit struct copy across
@@ -295,6 +346,7 @@ __device__ __forceinline__ SampleArgs lane_args(const HopParams& p, const LanePt
     a.known_pairs = LG_GPTR(unsigned long long, L.known_pairs); a.known_cnt = LG_GPTR(int32_t, L.known_cnt); a.known_cap = L.known_cap;
     a.indptr_full = LG_GPTR(const int64_t, p.indptr_full); a.slot_pick = LG_GPTR(int32_t, L.slot_pick);
     a.agg_edge_ids = LG_GPTR(int64_t, L.agg_edge_ids);
+    a.edge_cdf = LG_GPTR(const float, p.edge_cdf);
     return a;
 }
 
@@ -348,7 +400,13 @@ __device__ __forceinline__ HopGeom hop_geometry(const SampleArgs& a)
 // EIDS: edge-id mode (HopParams.edge_ids): the adjacency position a slot drew goes to slot_pick, next to slot_dst -- the same for a
 // row of the full CSR and for its copy in a cached topology (the fill copies a row in CSR order); compact_kernel<.., EIDS> adds the
 // full CSR's row start.  4 bytes per slot with an edge, no branch on where the row lives, no LDS.
-template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false, bool EIDS = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
+// WEIGHTED: weighted mode (HopParams.weighted, with replacement only): the pick is the upper-bound search of the row's prefix sums
+// (weighted_step) in place of draw_from_x; nothing else differs.  The table is indexed like the FULL column array, so the row's base
+// is h.start for a row of the full CSR and indptr_full[frontier vertex] for a row read from a cached topology -- loaded per slot,
+// by those slots only: staging it with the headers would take 8 KB more LDS per workgroup (24 KB: 6 workgroups per CU instead
+// of 8) for a load that the f slots of an entry, on adjacent lanes, share anyway.  A lane's four searches advance together, so four
+// probes are in flight per lane as four column loads are; the first probes of an entry's f slots fall into the same lines.
+template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false, bool EIDS = false, bool WEIGHTED = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
 __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_SGPRS))) void sample_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NB = 1 << BB;
@@ -359,6 +417,8 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
     __shared__ int32_t s_pick[DISTINCT ? LG_SUPER + LG_DISTINCT_MAX_FANOUT - 1 : 1];
     __shared__ int32_t s_bcnt[NB], s_boff[SINGLE ? NB : 1], s_list[STAGED ? NB : 1];
     static_assert(!STAGED || (SINGLE && NB <= 64), "the staged form scans its buckets with one wave");
+    static_assert(!(WEIGHTED && DISTINCT), "weighted sampling is with replacement only");
+    static_assert(!WEIGHTED || LG_SLOTS_PER_LANE == 4, "the lock-step search below names its four slots");
 
     const HopGeom g = hop_geometry(a);
     const int32_t tid = threadIdx.x;
@@ -443,6 +503,45 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
             if (SINGLE && tid < NB) s_bcnt[tid] = 0;     // (made visible by the barrier above the loads' use below)
             int32_t dst[LG_SLOTS_PER_LANE], fs[LG_SLOTS_PER_LANE];
             int32_t pk[EIDS ? LG_SLOTS_PER_LANE : 1];
+            int32_t wpick[WEIGHTED ? LG_SLOTS_PER_LANE : 1];      // WEIGHTED: the slot's pick, -1: no edge (k >= min(f, D) or a row total of 0)
+            if constexpr (WEIGHTED) {
+                const LG_G float* wc[LG_SLOTS_PER_LANE];
+                int32_t wn[LG_SLOTS_PER_LANE], wlo[LG_SLOTS_PER_LANE], wdeg[LG_SLOTS_PER_LANE];
+                double wt[LG_SLOTS_PER_LANE];
+#pragma unroll
+                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
+                    const int32_t idx = idx0 + u * LG_TILE + tid;
+                    wn[u] = 0; wlo[u] = 0; wdeg[u] = 0; wc[u] = a.edge_cdf;
+                    if (idx < g.total) {
+                        const int32_t q = idx / count;
+                        const RowHdr h = s_hdr[q - j0];
+                        if (idx - q * count < h.deg) {
+                            // (a cached row's vertex is real: frontier entries < 0 have degree 0)
+                            const int64_t base = h.slot == a.partition_count ? h.start : a.indptr_full[g.frontier[q]];
+                            wc[u] = a.edge_cdf + base;
+                            wdeg[u] = h.deg;
+                        }
+                    }
+                }
+                float wtot[LG_SLOTS_PER_LANE];
+#pragma unroll
+                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) wtot[u] = wdeg[u] > 0 ? wc[u][wdeg[u] - 1] : 0.0f;
+#pragma unroll
+                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
+                    wt[u] = weighted_target(x[u], wtot[u]);
+                    if (wtot[u] > 0.0f) wn[u] = wdeg[u];
+                }
+                while ((wn[0] | wn[1] | wn[2] | wn[3]) != 0) {          // (all >= 0)
+                    float v[LG_SLOTS_PER_LANE];
+#pragma unroll
+                    for (int u = 0; u < LG_SLOTS_PER_LANE; u++) v[u] = wn[u] > 0 ? wc[u][wlo[u] + (wn[u] >> 1)] : 0.0f;
+#pragma unroll
+                    for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
+                        if (wn[u] > 0) weighted_step(v[u], wt[u], wlo[u], wn[u]);
+                }
+#pragma unroll
+                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) wpick[u] = wtot[u] > 0.0f ? min(wlo[u], wdeg[u] - 1) : -1;
+            }
 #pragma unroll
             for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
                 const int32_t idx = idx0 + u * LG_TILE + tid;
@@ -453,8 +552,9 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                     const int32_t q = idx / count;
                     const int32_t k = idx - q * count;
                     const RowHdr h = s_hdr[q - j0];
-                    if (k < h.deg) {                                           // :232-233 (src < 0 has deg 0)
-                        const int32_t pick = !DISTINCT ? draw_from_x(x[u], h.deg)                          // :235-238
+                    if (WEIGHTED ? wpick[u] >= 0 : k < h.deg) {                // :232-233 (src < 0 has deg 0)
+                        const int32_t pick = WEIGHTED ? wpick[u]
+                                           : !DISTINCT ? draw_from_x(x[u], h.deg)                          // :235-238
                                                        : (h.deg <= count ? k : s_pick[idx - j0 * count]);
                         // column slots: the same sector read as 8 bytes brings the neighbour's feature-cache slot along.  Picks
                         // from the full CSR (slot P: all but the cached-topology rows) address it through pointers that came
@@ -1262,9 +1362,12 @@ static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams
     HopParams q = p;
     q.lds_k = plan.k;
     const dim3 grid(plan.sample_gx, n_lanes);
-    if (!p.edge_ids) {
+    if (!p.edge_ids && !p.weighted) {
         if (p.replace) sample_kernel<BB, ci.single, ci.staged><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
         else sample_kernel<BB, ci.single, ci.staged, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    } else if (p.weighted) {      // weighted mode (with replacement: do_random_sample refuses anything else), with or without edge ids
+        if (!p.edge_ids) sample_kernel<BB, ci.single, ci.staged, false, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+        else sample_kernel<BB, ci.single, ci.staged, false, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
     } else {       // edge-id mode: the instances that also leave each slot's pick (slot_pick)
         if (p.replace) sample_kernel<BB, ci.single, ci.staged, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
         else sample_kernel<BB, ci.single, ci.staged, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);

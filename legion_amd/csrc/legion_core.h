@@ -103,7 +103,8 @@ enum HopScratch {
 #define LG_ERR_FEATURE_ROWS 2     // the batch has more rows than the feature buffer: the gather stopped at its end
 #define LG_ERR_CHAIN 4            // compact_kernel gave up waiting for an earlier tile's status word / a winner's position (cannot happen)
 #define LG_ERR_SAMPLE_MODE 8      // a hop was not sampled: a fan-out above LG_DISTINCT_MAX_FANOUT without replacement, or lanes of one
-                                  // group with different sampling or edge-id modes (set on the host; the setters refuse both)
+                                  // group with different sampling, edge-id or weighted modes (set on the host; the setters refuse
+                                  // these), or a weighted hop against a graph without a prefix table (legion_graph_set_edge_weights)
 
 // Device code: a pointer that was loaded from memory (LanePtrs, pointer tables, LDS) is "generic" to
 // the compiler, which then emits flat_* instructions; those count on lgkmcnt as well as vmcnt, so every
@@ -309,6 +310,11 @@ public:
     int32_t edge_ids = 0;
     int32_t* slot_pick = nullptr;      // [max_slots] see LanePtrs
     int64_t* agg_edge_ids = nullptr;   // [num_ids]
+    // 1: weighted sampling (DGL's prob=): a slot picks adjacency position i of its row with probability w'[i] / row total, by an
+    // upper-bound search of the graph's per-row prefix-sum table (GraphStorage::EdgeCdf, legion_graph_set_edge_weights) in place of
+    // the uniform draw.  With replacement only (the setters refuse sample_replace == 0 beside it).  Nothing is allocated in the pool:
+    // the table lives with the graph.  Fixed once the pool has sampled a hop (sample_used)
+    int32_t sample_weighted = 0;
     int32_t lanes_epoch = 0;           // bumped when the pool's lane descriptor changes after creation (a lane group re-uploads its copy)
     int64_t grid_rows_hint = 0;        // > 0: rows a batch typically has (the Runner's pipe-slot pool holds the worst case: launches are sized for the usual one)
     int32_t dev_id = 0;
@@ -363,6 +369,14 @@ public:
     virtual int32_t NodeNum() const = 0;
     virtual int64_t EdgeNum() const = 0;
     virtual const RowHdr* GetRowHeaders(int32_t part_id) const = 0;   // new: [N] per GPU
+    // Weighted sampling (new): edge_cdf, float32[E] indexed like the full column array -- per row the inclusive prefix sums of the
+    // sanitised weights (finite and > 0, else 0), accumulated in double and rounded once (kernels_weights.hip).  One plain
+    // allocation on the device current at the call, built on `s`; a second call replaces the contents.  -1 (nothing changes) for null
+    // weights or once a weighted hop has been enqueued against this graph (MarkWeightedUsed: captured graphs hold the pointer and
+    // batches in flight read it).
+    virtual int32_t SetEdgeWeights(hipStream_t s, const float* w) = 0;
+    virtual const float* EdgeCdf() const = 0;                         // null before SetEdgeWeights
+    virtual void MarkWeightedUsed() = 0;
     // "Column slots" (new): a copy of the full column array in which every entry is the pair {neighbour id, feature-cache
     // slot of that neighbour = node_map[id]} (8 bytes).  The sampler's scattered 4-byte pick costs a whole 64-byte sector
     // either way; read as 8 bytes it brings the neighbour's cache slot along for free, and the gather no longer fetches a
@@ -742,6 +756,8 @@ struct HopParams {                  // what every lane of a launch shares
     int32_t replace;                // 1: draws with replacement (the reference's); 0: distinct positions per entry (MemoryPool::sample_replace)
     int32_t edge_ids;               // 1: the hop also writes agg_edge_ids (MemoryPool::edge_ids): the flagged sample / compact instances
     const int64_t* indptr_full;     // the full CSR's row pointers (slot P of the pointer tables): read by those instances only
+    int32_t weighted;               // 1: picks by the prefix-sum table instead of the uniform draw (MemoryPool::sample_weighted): the WEIGHTED instances
+    const float* edge_cdf;          // GraphStorage::EdgeCdf(), indexed like col_full; those instances also read indptr_full (cached rows)
 };
 // bucket_bits, last_hop_claims_hint: the pool's (MemoryPool); the launch follows sample_hop_plan (sample_plan.h)
 void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits, int64_t last_hop_claims_hint, const LanePtrs* d_lanes,
@@ -838,6 +854,14 @@ void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* m
                  const char* map8, int32_t* out32, char* out8);
 void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* out, int32_t n);
 void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n);
+// the weighted pick rule on its own (tests): out[i] = pick of slot idx[i] in the row {row_start[i], deg[i]} of cdf, or -1
+void launch_draw_weighted_batch(hipStream_t s, const int32_t* idx, const int64_t* row_start, const int32_t* deg, const float* cdf,
+                                int32_t* out, int32_t n);
+// the per-row prefix-sum table of weighted sampling (kernels_weights.hip): cdf[E] from w[E] and the full CSR's indptr[n_rows + 1];
+// long_rows: scratch of the build, int32[1 + long_cap] with long_cap = lg_weights_long_rows_cap(E) (a count, then the rows a whole
+// workgroup scans)
+int64_t lg_weights_long_rows_cap(int64_t num_edges);
+void build_edge_cdf(hipStream_t s, const int64_t* indptr, int32_t n_rows, const float* w, float* cdf, int32_t* long_rows, int32_t long_cap);
 
 // a roctx range for the enclosing scope (markers.hip): visible to rocprofv3 --marker-trace, near-free otherwise
 struct Range {

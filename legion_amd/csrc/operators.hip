@@ -106,8 +106,14 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
         pool0->RaiseError(LG_ERR_SAMPLE_MODE);
         return;
     }
+    if (pool0->sample_weighted && (graph->EdgeCdf() == nullptr || !pool0->sample_replace)) {      // (enqueue_lanes has refused the batch already)
+        printf("Sampling Parameters Error: a weighted hop needs the graph's edge weights (legion_graph_set_edge_weights) and replacement\n");
+        pool0->RaiseError(LG_ERR_SAMPLE_MODE);
+        return;
+    }
     lg::Range mark("op%d sample%s fanout=%d lanes=%d", op_id, is_presc ? " (presc)" : "", count, n_lanes);
     pool0->sample_used = true;              // the mode is fixed from here on (legion_pool_set_sample_replace)
+    if (pool0->sample_weighted) graph->MarkWeightedUsed();      // ... and so is the graph's table (legion_graph_set_edge_weights)
     lg::HopParams p;
     p.op_id = op_id;
     p.count = count;
@@ -130,6 +136,8 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
     p.replace = pool0->sample_replace;
     p.edge_ids = pool0->edge_ids;
     p.indptr_full = graph->GetCSRNodeIndexCPU();
+    p.weighted = pool0->sample_weighted;
+    p.edge_cdf = graph->EdgeCdf();
     lg::launch_random_sample(s, p, pool0->lds_bucket_bits, pool0->last_hop_claims_hint, d_lanes, n_lanes);
 }
 
@@ -353,6 +361,12 @@ extern "C" void legion_draw_batch(legion_stream_t stream, const int32_t* idx, co
     lg::launch_draw_batch(static_cast<hipStream_t>(stream), idx, deg, out, n);
 }
 
+extern "C" void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, const int64_t* row_start, const int32_t* deg,
+                                           const float* cdf, int32_t* out, int32_t n)
+{
+    lg::launch_draw_weighted_batch(static_cast<hipStream_t>(stream), idx, row_start, deg, cdf, out, n);
+}
+
 extern "C" int32_t legion_draw_distinct_batch(legion_stream_t stream, const int32_t* base, const int32_t* deg, int32_t f,
                                               int32_t* out, int32_t n)
 {
@@ -424,6 +438,11 @@ extern "C" void legion_enqueue_batch(legion_stream_t strm_hdl, LegionGraphStorag
 {
     MemoryPool* mp = reinterpret_cast<MemoryPool*>(memorypool);
     if (!graph || !feature || !mp) { std::cout << "invalid storage ptr\n"; return; }
+    if (mp->sample_weighted && reinterpret_cast<GraphStorage*>(graph)->EdgeCdf() == nullptr) {      // nothing of the batch is enqueued
+        printf("legion_hip: a weighted pool against a graph without edge weights (legion_graph_set_edge_weights); nothing enqueued\n");
+        mp->RaiseError(LG_ERR_SAMPLE_MODE);
+        return;
+    }
     enqueue_lanes(static_cast<hipStream_t>(strm_hdl), reinterpret_cast<GraphStorage*>(graph),
                   reinterpret_cast<FeatureStorage*>(feature), cache_of(cache), mp->DeviceLane(), 1, mp, mp->iter_state,
                   batch_size, counter, dev_id, mode, is_presc, fanout, hop_num);
@@ -499,12 +518,19 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
         if (stale) legion_group_refresh(group);
     }
     for (int32_t i = 0; i < n_active; i++)
-        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace || group->pools[i]->edge_ids != group->pools[0]->edge_ids) {
+        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace || group->pools[i]->edge_ids != group->pools[0]->edge_ids ||
+            group->pools[i]->sample_weighted != group->pools[0]->sample_weighted) {
             printf("legion_hip: lanes of one group with different sampling modes; nothing enqueued\n");
             for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
             return;
         }
+    if (group->pools[0]->sample_weighted && reinterpret_cast<GraphStorage*>(graph)->EdgeCdf() == nullptr) {
+        printf("legion_hip: weighted lanes against a graph without edge weights (legion_graph_set_edge_weights); nothing enqueued\n");
+        for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
+        return;
+    }
     for (int32_t i = 0; i < n_active; i++) group->pools[i]->sample_used = true;
+    if (group->pools[0]->sample_weighted) reinterpret_cast<GraphStorage*>(graph)->MarkWeightedUsed();
     enqueue_lanes(static_cast<hipStream_t>(strm_hdl), reinterpret_cast<GraphStorage*>(graph),
                   reinterpret_cast<FeatureStorage*>(feature), cache_of(cache), group->d_lanes, n_active, group->pools[0],
                   group->iter_state, batch_size, counter0, dev_id, mode, false, fanout, hop_num, phase);

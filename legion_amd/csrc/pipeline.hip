@@ -239,7 +239,7 @@ extern "C" int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t
     if (!p || (replace != 0 && replace != 1)) return -1;
     for (Slot& sl : p->slots)
         for (MemoryPool* mp : sl.pools)
-            if (mp->sample_used || (replace == 0 && mp->max_fanout > LG_DISTINCT_MAX_FANOUT)) return -1;
+            if (mp->sample_used || (replace == 0 && (mp->max_fanout > LG_DISTINCT_MAX_FANOUT || mp->sample_weighted))) return -1;
     for (Slot& sl : p->slots)
         for (MemoryPool* mp : sl.pools)
             if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(mp), replace) != 0) return -1;
@@ -258,6 +258,24 @@ extern "C" int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on)
         for (MemoryPool* mp : sl.pools)
             if (legion_pool_set_edge_ids(reinterpret_cast<LegionMemoryPool*>(mp), on) != 0) return -1;
         legion_group_refresh(sl.group);          // the slot's copy of its lanes' descriptors, before anything is captured
+    }
+    return 0;
+}
+
+// weighted mode of every lane of every slot (legion_pool_set_sample_weighted); refused once any lane has sampled, or for 1 beside
+// sampling without replacement.  The lane descriptors are written again as legion_pipeline_set_edge_ids writes them (the mode itself
+// travels with each launch, not in the descriptor: the refresh is a no-op unless another mode changed them too)
+extern "C" int32_t legion_pipeline_set_sample_weighted(LegionPipeline* p, int32_t on)
+{
+    if (!p || (on != 0 && on != 1)) return -1;
+    for (Slot& sl : p->slots)
+        for (MemoryPool* mp : sl.pools)
+            if (mp->sample_used || (on == 1 && mp->sample_replace == 0)) return -1;
+    SetGPUDevice(p->dev_id);
+    for (Slot& sl : p->slots) {
+        for (MemoryPool* mp : sl.pools)
+            if (legion_pool_set_sample_weighted(reinterpret_cast<LegionMemoryPool*>(mp), on) != 0) return -1;
+        legion_group_refresh(sl.group);
     }
     return 0;
 }

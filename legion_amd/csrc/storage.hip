@@ -674,8 +674,32 @@ public:
     int32_t** GetCSRXMatrix(int32_t part_id) const override { return csr_dst_x_.empty() ? nullptr : csr_dst_x_[part_id]; }
     const int32_t* GetColumnSlotsFull(int32_t part_id) const override { return colx_full_.empty() ? nullptr : colx_full_[part_id]; }
 
+    // weighted sampling (legion_core.h): the prefix-sum table over the full column array, built on the device current at the call
+    int32_t SetEdgeWeights(hipStream_t s, const float* w) override
+    {
+        if (w == nullptr || weighted_used_) return -1;
+        if (edge_cdf_ == nullptr) {
+            HIP_CALL(hipGetDevice(&edge_cdf_dev_));
+            edge_cdf_ = (float*)d_alloc_space((edge_num_ > 0 ? edge_num_ : 1) * (int64_t)sizeof(float));
+            cdf_long_cap_ = (int32_t)lg::lg_weights_long_rows_cap(edge_num_);
+            cdf_long_rows_ = (int32_t*)d_alloc_space(((int64_t)cdf_long_cap_ + 1) * sizeof(int32_t));
+        }
+        if (edge_num_ > 0) lg::build_edge_cdf(s, csr_node_index_cpu_, node_num_, w, edge_cdf_, cdf_long_rows_, cdf_long_cap_);
+        return 0;
+    }
+    const float* EdgeCdf() const override { return edge_cdf_; }
+    void MarkWeightedUsed() override { weighted_used_ = true; }
+
     void Finalize() override
     {
+        if (edge_cdf_ != nullptr) {
+            SetGPUDevice(edge_cdf_dev_);
+            HIP_CALL(hipDeviceSynchronize());
+            d_free_space(edge_cdf_);
+            d_free_space(cdf_long_rows_);
+            edge_cdf_ = nullptr;
+            cdf_long_rows_ = nullptr;
+        }
         for (int32_t i = 0; i < (int32_t)csr_dst_x_.size(); i++) DropColumnSlots(i);
         for (void* p : owned_) d_free_space(p);
         owned_.clear();
@@ -725,6 +749,11 @@ private:
     std::vector<int32_t**> csr_dst_x_;   // [P] device tables of pair arrays (column slots), null until built
     std::vector<int32_t*> colx_full_;    // [P] this GPU's {id, feature-cache slot} copy of the full column array
     std::vector<uint64_t> colx_stamp_;   // [P] (cache uid, fill generation) the pairs were built from
+    float* edge_cdf_ = nullptr;          // [E] per-row prefix sums of the sanitised edge weights, or null (SetEdgeWeights)
+    int32_t* cdf_long_rows_ = nullptr;   // scratch of its build: {count, rows longer than a wave scans}
+    int32_t cdf_long_cap_ = 0;
+    int edge_cdf_dev_ = 0;
+    bool weighted_used_ = false;         // a weighted hop has been enqueued against this graph: the table stays as it is
 };
 
 extern "C" GraphStorage* NewCompleteGraphStorage() { return new CompleteGraphStorage(); }
@@ -1083,6 +1112,21 @@ extern "C" void legion_graph_cached_csr(const LegionGraphStorage* g_, int32_t de
     if (dst_out) *dst_out = ok ? g->CachedCSRDst(dev) : nullptr;
 }
 
+// weighted sampling: the per-row prefix-sum table from the caller's float32 w[E] (aligned with the full column array), built on
+// `stream` on the current device; replaced by a later call, refused once a weighted hop has been enqueued against the graph
+extern "C" int32_t legion_graph_set_edge_weights(LegionGraphStorage* g_, legion_stream_t stream, const float* w_devptr)
+{
+    GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
+    if (!g || !w_devptr) return -1;
+    return g->SetEdgeWeights(static_cast<hipStream_t>(stream), w_devptr);
+}
+
+extern "C" const float* legion_graph_edge_cdf(const LegionGraphStorage* g_)
+{
+    const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
+    return g ? g->EdgeCdf() : nullptr;
+}
+
 extern "C" void legion_graph_destroy(LegionGraphStorage* g_)
 {
     GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
@@ -1252,6 +1296,7 @@ extern "C" int32_t legion_pool_set_sample_replace(LegionMemoryPool* p_, int32_t 
 {
     MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
     if (!mp || (replace != 0 && replace != 1) || mp->sample_used) return -1;
+    if (replace == 0 && mp->sample_weighted) return -1;      // weighted sampling is with replacement only
     if (replace == 0 && mp->max_fanout > LG_DISTINCT_MAX_FANOUT) return -1;
     mp->sample_replace = replace;
     return 0;
@@ -1281,6 +1326,24 @@ extern "C" int32_t legion_pool_edge_ids(const LegionMemoryPool* p_)
 {
     const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
     return mp ? mp->edge_ids : -1;
+}
+
+// 1: weighted sampling -- a slot picks adjacency position i with probability w'[i] / row total, by the graph's prefix-sum table
+// (legion_graph_set_edge_weights); 0 (default): the uniform draw.  With replacement only; only before the pool samples a hop.
+// Nothing is allocated and the lane descriptor does not change: the table travels with the launch (HopParams)
+extern "C" int32_t legion_pool_set_sample_weighted(LegionMemoryPool* p_, int32_t on)
+{
+    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
+    if (!mp || (on != 0 && on != 1) || mp->sample_used) return -1;
+    if (on == 1 && mp->sample_replace == 0) return -1;
+    mp->sample_weighted = on;
+    return 0;
+}
+
+extern "C" int32_t legion_pool_sample_weighted(const LegionMemoryPool* p_)
+{
+    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
+    return mp ? mp->sample_weighted : -1;
 }
 
 extern "C" void legion_pool_set_current_pipe(LegionMemoryPool* p_, int32_t pipe)

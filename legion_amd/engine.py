@@ -175,6 +175,33 @@ class GraphStorage:
         self.handle = self._lib.legion_graph_create(self.partition_count, self.node_num, self.edge_num,
                                                     _ptr(indptr), _ptr(col))
 
+    def set_edge_weights(self, weights, stream=None):
+        """Per-edge weights for weighted sampling (MemoryPool / Pipeline weighted=True; DGL's prob=): float32[E], aligned with col,
+        a torch tensor (any device) or a numpy array.  Builds the graph's per-row prefix-sum table on the current device; a weight
+        that is not finite and > 0 counts as 0.  May be called again until a weighted hop has been enqueued (then RuntimeError).
+        The build runs on `stream` (default: the current one): synchronise before a Pipeline, which has streams of its own, samples."""
+        if isinstance(weights, np.ndarray):
+            if weights.dtype != np.float32:
+                raise ValueError(f"edge weights must be float32, not {weights.dtype}")
+            weights = torch.from_numpy(np.ascontiguousarray(weights))
+        if not isinstance(weights, torch.Tensor):
+            raise ValueError(f"edge weights must be a float32 tensor or array, not {type(weights).__name__}")
+        if weights.dtype != torch.float32:
+            raise ValueError(f"edge weights must be float32, not {weights.dtype}")
+        if weights.dim() != 1 or weights.numel() != self.edge_num:
+            raise ValueError(f"edge weights must have one entry per edge ({self.edge_num}), not shape {tuple(weights.shape)}")
+        w = weights.to(self.col.device).contiguous()
+        if self._lib.legion_graph_set_edge_weights(self.handle, _stream_handle(stream), _ptr(w)) != 0:
+            raise RuntimeError("legion_graph_set_edge_weights: a weighted hop has been enqueued against this graph already")
+        self._weights = w                            # (alive until the build has run; replaced by the next call)
+
+    def edge_cdf(self):
+        """The prefix-sum table, float32[E] as a device view (indexed like col), or None before set_edge_weights."""
+        ptr = self._lib.legion_graph_edge_cdf(self.handle)
+        if not ptr:
+            return None
+        return device_view(ptr, (self.edge_num,), torch.float32, self.col.device)
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))
@@ -270,17 +297,21 @@ class MemoryPool:
             "agg_edge_ids": (14, torch.int64)}
 
     def __init__(self, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, pipeline_depth=1, feature_out_dtype="float32",
-                 replace=True, edge_ids=False):
+                 replace=True, edge_ids=False, weighted=False):
         """feature_out_dtype: dtype of the rows the pool's gathers write ("float32" or "bfloat16": bf16[rows, D], the float32 row
         rounded to nearest even, or a bf16 storage's rows verbatim), independent of the FeatureStorage's dtype.
         replace: as DGL's NeighborSampler keyword -- True samples with replacement (the reference's draw), False takes min(f, D)
         distinct neighbours of each frontier entry (fan-outs up to 256).
         edge_ids: True also records, per sampled edge, its position in the graph's column array (DGL's dgl.EID): buffer("agg_edge_ids"),
-        int64, indexed like agg_src_ids; read_batch returns it as "agg_edge_ids"."""
+        int64, indexed like agg_src_ids; read_batch returns it as "agg_edge_ids".
+        weighted: as DGL's prob= -- True picks each neighbour with probability proportional to its edge's weight
+        (GraphStorage.set_edge_weights, which must have run before the first batch); needs replace=True."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         if not isinstance(edge_ids, bool):
             raise ValueError(f"edge_ids must be True or False, not {edge_ids!r}")
+        if not isinstance(weighted, bool):
+            raise ValueError(f"weighted must be True or False, not {weighted!r}")
         self._lib = _libmod.load()
         self.dev_id = int(dev_id)
         self.device = _torch_device(self.dev_id)
@@ -297,6 +328,8 @@ class MemoryPool:
         self.set_replace(replace)
         if edge_ids:
             self.set_edge_ids(True)
+        if weighted:
+            self.set_weighted(True)
 
     @classmethod
     def _borrowed(cls, handle, dev_id, total_num_nodes, batch_size, fanout, float_feature_len, feature_rows):
@@ -333,7 +366,8 @@ class MemoryPool:
         if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
             raise ValueError(f"replace must be True or False, not {replace!r}")
         if self._lib.legion_pool_set_sample_replace(self.handle, int(bool(replace))) != 0:
-            raise RuntimeError("legion_pool_set_sample_replace: the pool has sampled already, or a fan-out is above 256 without replacement")
+            raise RuntimeError("legion_pool_set_sample_replace: the pool has sampled already, or a fan-out is above 256 without replacement, "
+                               "or the pool is weighted")
 
     @property
     def edge_ids(self):
@@ -346,6 +380,18 @@ class MemoryPool:
             raise ValueError(f"edge_ids must be True or False, not {on!r}")
         if self._lib.legion_pool_set_edge_ids(self.handle, int(on)) != 0:
             raise RuntimeError("legion_pool_set_edge_ids: the pool has sampled already")
+
+    @property
+    def weighted(self):
+        return int(self._lib.legion_pool_sample_weighted(self.handle)) == 1
+
+    def set_weighted(self, on):
+        """Only before the pool samples its first hop, and only with replace=True (the C ABI refuses it otherwise: RuntimeError).  A
+        Pipeline's lanes take the mode through Pipeline.set_weighted."""
+        if not isinstance(on, bool):
+            raise ValueError(f"weighted must be True or False, not {on!r}")
+        if self._lib.legion_pool_set_sample_weighted(self.handle, int(on)) != 0:
+            raise RuntimeError("legion_pool_set_sample_weighted: the pool has sampled already, or it samples without replacement")
 
     def alloc_features(self, rows):
         self.feature_rows = int(rows)
@@ -447,13 +493,15 @@ class Pipeline:
 
     def __init__(self, graph, feature, cache, dev_id, batch_size, fanout, group_size, feature_rows, use_graph=True,
                  slots=2, overlap=False, split=False, weave=False, arena=False,      # (split: accepted and ignored -- removed in round 5)
-                 feature_out_dtype="float32", replace=True, edge_ids=False):
+                 feature_out_dtype="float32", replace=True, edge_ids=False, weighted=False):
         """replace: MemoryPool's (every lane samples with / without replacement).  edge_ids: MemoryPool's (every lane records its
-        edges' ids)."""
+        edges' ids).  weighted: MemoryPool's (every lane picks by the graph's edge weights)."""
         if feature_out_dtype not in FEATURE_DTYPES:
             raise ValueError(f"feature_out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {feature_out_dtype!r}")
         if not isinstance(edge_ids, bool):
             raise ValueError(f"edge_ids must be True or False, not {edge_ids!r}")
+        if not isinstance(weighted, bool):
+            raise ValueError(f"weighted must be True or False, not {weighted!r}")
         self._lib = _libmod.load()
         self.group_size, self.slots = int(group_size), int(slots)
         self.fanout = [int(f) for f in fanout]
@@ -471,13 +519,16 @@ class Pipeline:
             self.set_replace(False)
         if edge_ids:
             self.set_edge_ids(True)
+        if weighted:
+            self.set_weighted(True)
 
     def set_replace(self, replace):
         """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
         if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
             raise ValueError(f"replace must be True or False, not {replace!r}")
         if self._lib.legion_pipeline_set_sample_replace(self.handle, int(bool(replace))) != 0:
-            raise RuntimeError("legion_pipeline_set_sample_replace: the pipeline has sampled already, or a fan-out is above 256 without replacement")
+            raise RuntimeError("legion_pipeline_set_sample_replace: the pipeline has sampled already, or a fan-out is above 256 without replacement, "
+                               "or the pipeline is weighted")
 
     @property
     def edge_ids(self):
@@ -489,6 +540,17 @@ class Pipeline:
             raise ValueError(f"edge_ids must be True or False, not {on!r}")
         if self._lib.legion_pipeline_set_edge_ids(self.handle, int(on)) != 0:
             raise RuntimeError("legion_pipeline_set_edge_ids: the pipeline has sampled already")
+
+    @property
+    def weighted(self):
+        return all(pool.weighted for lanes in self.pools for pool in lanes)
+
+    def set_weighted(self, on):
+        """Only before the first submit, and only with replace=True (the C ABI refuses it otherwise: RuntimeError)."""
+        if not isinstance(on, bool):
+            raise ValueError(f"weighted must be True or False, not {on!r}")
+        if self._lib.legion_pipeline_set_sample_weighted(self.handle, int(on)) != 0:
+            raise RuntimeError("legion_pipeline_set_sample_weighted: the pipeline has sampled already, or it samples without replacement")
 
     def submit(self, counter0, mode=TRAINMODE, n_active=None):
         if n_active is None or n_active >= self.group_size:

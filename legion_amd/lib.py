@@ -31,6 +31,8 @@ SIGNATURES = {
     "legion_graph_destroy": (None, [c_p]),
     "legion_graph_column_slots": (c_i32, [c_p, c_i32]),
     "legion_graph_cached_csr": (None, [c_p, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]),
+    "legion_graph_set_edge_weights": (c_i32, [c_p, c_p, c_p]),
+    "legion_graph_edge_cdf": (c_p, [c_p]),
     "legion_feature_create": (c_p, [c_i32, c_i32, c_i32, c_p]),
     "legion_feature_set_ids": (None, [c_p, c_i32, c_i32, c_p, c_p, c_i32]),
     "legion_feature_destroy": (None, [c_p]),
@@ -55,6 +57,8 @@ SIGNATURES = {
     "legion_pool_sample_replace": (c_i32, [c_p]),
     "legion_pool_set_edge_ids": (c_i32, [c_p, c_i32]),
     "legion_pool_edge_ids": (c_i32, [c_p]),
+    "legion_pool_set_sample_weighted": (c_i32, [c_p, c_i32]),
+    "legion_pool_sample_weighted": (c_i32, [c_p]),
     "legion_cache_create": (c_p, [c_i64, c_i32, c_i32, c_i32, c_i32]),
     "legion_cache_init_controller": (None, [c_p, c_i32]),
     "legion_cache_set_replica_memory": (None, [c_p, c_i64]),
@@ -113,6 +117,7 @@ SIGNATURES = {
     "legion_pipeline_create_ex": (c_p, [c_p, c_p, c_p, c_i32, c_i32, P_I32, c_i32, c_i32, c_i32, c_i64, c_i32, c_i32]),
     "legion_pipeline_set_sample_replace": (c_i32, [c_p, c_i32]),
     "legion_pipeline_set_edge_ids": (c_i32, [c_p, c_i32]),
+    "legion_pipeline_set_sample_weighted": (c_i32, [c_p, c_i32]),
     "legion_pipeline_submit": (c_i32, [c_p, c_i32, c_i32]),
     "legion_pipeline_submit_n": (c_i32, [c_p, c_i32, c_i32, c_i32]),
     "legion_enqueue_group_n": (None, [c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, P_I32, c_i32]),
@@ -135,6 +140,7 @@ SIGNATURES = {
     "legion_gather_rows": (None, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_i32]),
     "legion_draw_batch": (None, [c_p, c_p, c_p, c_p, c_i32]),
     "legion_draw_distinct_batch": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32]),
+    "legion_draw_weighted_batch": (None, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
