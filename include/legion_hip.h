@@ -383,7 +383,8 @@ LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatu
                                           LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
                                           const int32_t* fanout, int32_t hop_num, int32_t group_size,
                                           int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype);
-/* sampling mode of every lane (legion_pool_set_sample_replace).  Returns 0, or -1 (nothing changes) once the pipeline has
+/* The three setters below: where one succeeds, the pipeline's GPU is the calling thread's current device afterwards.
+ * sampling mode of every lane (legion_pool_set_sample_replace).  Returns 0, or -1 (nothing changes) once the pipeline has
  * submitted a group, for a value other than 0 / 1 or for 0 with a fan-out above LEGION_DISTINCT_MAX_FANOUT. */
 int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace);
 /* edge-id mode of every lane (legion_pool_set_edge_ids; a lane's ids: legion_pool_buffer(legion_pipeline_pool(..), 14)).  Returns

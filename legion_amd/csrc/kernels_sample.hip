@@ -102,7 +102,7 @@ void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, in
 }
 
 // ------------------------------------------------------------------------------------------
-// Sampling without replacement (HopParams.replace == 0, DGL's replace=False).  Frontier entry q of a hop with fan-out f owns
+// Sampling without replacement (SampleMode::replace == 0, DGL's replace=False).  Frontier entry q of a hop with fan-out f owns
 // slots q*f + k, k < f, as with replacement; its row of degree D yields min(f, D) picks:
 //   D <= f: position k (every neighbour in CSR order, no draw);
 //   D >  f: Floyd's algorithm in slot order -- t_k = draw(q*f + k, j_k + 1) with j_k = D - f + k, and pick_k = t_k unless one
@@ -147,7 +147,7 @@ void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_
 }
 
 // ------------------------------------------------------------------------------------------
-// Weighted sampling (HopParams.weighted == 1, DGL's prob=; with replacement).  cdf is the graph's prefix-sum table (kernels_weights.hip):
+// Weighted sampling (SampleMode::weighted == 1, DGL's prob=; with replacement).  cdf is the graph's prefix-sum table (kernels_weights.hip):
 // per row the inclusive sums of the sanitised weights, float32, indexed like the full CSR's column array.  Slot idx of a row
 // {s, D} with total T = cdf[s + D - 1]:  t = r * (double)T with the r of draw_from_x, and
 //   pick = #{ i in [0, D) : (double)cdf[s + i] <= t }
@@ -394,22 +394,24 @@ __device__ __forceinline__ HopGeom hop_geometry(const SampleArgs& a)
 // !SINGLE (256-bucket class): the kernel samples K super tiles (a partition tile), counts their claims per bucket and
 // reserves, with one atomic per bucket, that many places of each bucket's claim list (run_off: {first place, count} per
 // partition tile and bucket); place_kernel writes the pairs (see there).  SINGLE + STAGED (64-bucket class): below.
-// DISTINCT: sampling without replacement (see floyd_resolve): the slots' draws go to s_pick, indexed by slot - j0 * f (the super
+// DRAW (sample_mode.h): how a slot picks its adjacency position.  Uniform: draw_from_x.
+// Distinct: sampling without replacement (see floyd_resolve): the slots' draws go to s_pick, indexed by slot - j0 * f (the super
 // tile's slots and, for an entry that began in the previous super tile, its earlier ones); one thread per entry with D > f then
 // resolves them in place, and the slots read their picks from there.  Fan-outs up to LG_DISTINCT_MAX_FANOUT (the span of s_pick).
-// EIDS: edge-id mode (HopParams.edge_ids): the adjacency position a slot drew goes to slot_pick, next to slot_dst -- the same for a
-// row of the full CSR and for its copy in a cached topology (the fill copies a row in CSR order); compact_kernel<.., EIDS> adds the
-// full CSR's row start.  4 bytes per slot with an edge, no branch on where the row lives, no LDS.
-// WEIGHTED: weighted mode (HopParams.weighted, with replacement only): the pick is the upper-bound search of the row's prefix sums
+// Weighted (with replacement only: no such SampleDraw as weighted + distinct): the pick is the upper-bound search of the row's prefix sums
 // (weighted_step) in place of draw_from_x; nothing else differs.  The table is indexed like the FULL column array, so the row's base
 // is h.start for a row of the full CSR and indptr_full[frontier vertex] for a row read from a cached topology -- loaded per slot,
 // by those slots only: staging it with the headers would take 8 KB more LDS per workgroup (24 KB: 6 workgroups per CU instead
 // of 8) for a load that the f slots of an entry, on adjacent lanes, share anyway.  A lane's four searches advance together, so four
 // probes are in flight per lane as four column loads are; the first probes of an entry's f slots fall into the same lines.
-template <int BB, bool SINGLE, bool STAGED = false, bool DISTINCT = false, bool EIDS = false, bool WEIGHTED = false>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
+// EIDS: edge-id mode (SampleMode::edge_ids): the adjacency position a slot drew goes to slot_pick, next to slot_dst -- the same for a
+// row of the full CSR and for its copy in a cached topology (the fill copies a row in CSR order); compact_kernel<.., EIDS> adds the
+// full CSR's row start.  4 bytes per slot with an edge, no branch on where the row lives, no LDS.
+template <int BB, bool SINGLE, bool STAGED, SampleDraw DRAW, bool EIDS>      // 2^BB hash buckets per lane; SINGLE: partition tile = super tile; STAGED: see below
 __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_SGPRS))) void sample_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NB = 1 << BB;
+    constexpr bool DISTINCT = DRAW == SampleDraw::Distinct, WEIGHTED = DRAW == SampleDraw::Weighted;
     const int32_t K = SINGLE ? 1 : hp.lds_k;      // super tiles per partition tile
     static_assert(NB <= LG_TILE, "one thread per bucket in the prefix");
     const SampleArgs a = lane_args(hp, lanes);
@@ -417,7 +419,6 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
     __shared__ int32_t s_pick[DISTINCT ? LG_SUPER + LG_DISTINCT_MAX_FANOUT - 1 : 1];
     __shared__ int32_t s_bcnt[NB], s_boff[SINGLE ? NB : 1], s_list[STAGED ? NB : 1];
     static_assert(!STAGED || (SINGLE && NB <= 64), "the staged form scans its buckets with one wave");
-    static_assert(!(WEIGHTED && DISTINCT), "weighted sampling is with replacement only");
     static_assert(!WEIGHTED || LG_SLOTS_PER_LANE == 4, "the lock-step search below names its four slots");
 
     const HopGeom g = hop_geometry(a);
@@ -603,18 +604,10 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                         if (dst[u] >= 0) __builtin_nontemporal_store(pk[u], &a.slot_pick[idx]);                       // (read for slots with an edge only)
                 }
             }
-            if (SINGLE && STAGED) {
-                // 64 buckets: a super tile's ~450 claims are ~7 per bucket.  Written straight from the registers (as below) a wave's 64
-                // claims would go to ~40 different lists: 8-byte stores all over the lane's pair array, +60 % memory requests in a
-                // kernel that is bound by them.  So the claims are ranked and STAGED in LDS grouped by bucket -- in the row-header
-                // stage, which nobody reads any more once every pick has been loaded: no LDS added, the kernel keeps its 8 workgroups
-                // per CU -- and written out entry by entry: consecutive entries of a bucket go to consecutive places of its list, a
-                // wave's store covers ~9 runs instead of ~40.  One reservation per non-empty bucket and super tile.  (Round 4 did this
-                // with a second kernel over partition tiles of 8 super tiles, place_kernel: 93-107 us per 64-lane group of B = 8000
-                // for 250 MB of traffic; the 256-bucket class, where a bucket's share of a super tile is 1-2 claims, still does.)
+            if (SINGLE) {
+                // the super tile's claims, grouped by hash bucket: ranks by LDS atomics (the order inside a bucket does not matter)
                 int32_t rank[LG_SLOTS_PER_LANE], bkt[LG_SLOTS_PER_LANE];
-                unsigned long long* s_stage = reinterpret_cast<unsigned long long*>(s_hdr);      // LG_SUPER pairs = 8 KB of the 16 KB
-                __syncthreads();                                   // every thread has read its headers; s_bcnt zeroed
+                __syncthreads();                                   // s_bcnt zeroed by every wave's view; STAGED: every thread has read its headers (s_stage below)
 #pragma unroll
                 for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
                     bkt[u] = -1;
@@ -624,58 +617,56 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                     }
                 }
                 __syncthreads();
-                if (tid < 64) {                                    // wave 0: exclusive prefix of the bucket counts + the reservations
-                    const int32_t c = tid < NB ? s_bcnt[tid] : 0;
-                    int32_t inc = c;
-                    for (int d = 1; d < 64; d <<= 1) { const int32_t o = __shfl_up(inc, d); if (tid >= d) inc += o; }
+                if (STAGED) {
+                    // 64 buckets: a super tile's ~450 claims are ~7 per bucket.  Written straight from the registers (as below) a wave's 64
+                    // claims would go to ~40 different lists: 8-byte stores all over the lane's pair array, +60 % memory requests in a
+                    // kernel that is bound by them.  So the claims are ranked and STAGED in LDS grouped by bucket -- in the row-header
+                    // stage, which nobody reads any more once every pick has been loaded: no LDS added, the kernel keeps its 8 workgroups
+                    // per CU -- and written out entry by entry: consecutive entries of a bucket go to consecutive places of its list, a
+                    // wave's store covers ~9 runs instead of ~40.  One reservation per non-empty bucket and super tile.  (Round 4 did this
+                    // with a second kernel over partition tiles of 8 super tiles, place_kernel: 93-107 us per 64-lane group of B = 8000
+                    // for 250 MB of traffic; the 256-bucket class, where a bucket's share of a super tile is 1-2 claims, still does.)
+                    unsigned long long* s_stage = reinterpret_cast<unsigned long long*>(s_hdr);      // LG_SUPER pairs = 8 KB of the 16 KB
+                    if (tid < 64) {                                    // wave 0: exclusive prefix of the bucket counts + the reservations
+                        const int32_t c = tid < NB ? s_bcnt[tid] : 0;
+                        int32_t inc = c;
+                        for (int d = 1; d < 64; d <<= 1) { const int32_t o = __shfl_up(inc, d); if (tid >= d) inc += o; }
+                        if (tid < NB) {
+                            s_boff[tid] = inc - c;
+                            s_list[tid] = c > 0 ? __hip_atomic_fetch_add(a.claim_cnt + tid * LG_CLAIM_CNT_STRIDE, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+                        }
+                    }
+                    __syncthreads();
+#pragma unroll
+                    for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
+                        if (bkt[u] >= 0)
+                            s_stage[s_boff[bkt[u]] + rank[u]] = ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
+                    __syncthreads();
+                    const int32_t tot = s_boff[NB - 1] + s_bcnt[NB - 1];
+                    for (int32_t i = tid; i < tot; i += LG_TILE) {
+                        const unsigned long long pr = s_stage[i];
+                        const int32_t bk = (int32_t)(lg_tab_hash((int32_t)(pr >> 32)) & (NB - 1));
+                        const int32_t at = s_list[bk] + (i - s_boff[bk]);
+                        if (at < a.claim_cap) a.claim_pairs[lg_claim_at<NB>(bk, at)] = pr;
+                    }
+                } else {
+                    // one list per bucket: the super tile's claims of a bucket take the next places of that bucket's list (one
+                    // reservation per bucket and super tile).  A claim past the list's capacity is not written: the count says so, and
+                    // the bucket's de-duplication workgroup then reads the hop's slots instead of the list
                     if (tid < NB) {
-                        s_boff[tid] = inc - c;
-                        s_list[tid] = c > 0 ? __hip_atomic_fetch_add(a.claim_cnt + tid * LG_CLAIM_CNT_STRIDE, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
+                        const int32_t c = s_bcnt[tid];
+                        s_boff[tid] = c > 0 ? __hip_atomic_fetch_add(a.claim_cnt + tid * LG_CLAIM_CNT_STRIDE, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
                     }
-                }
-                __syncthreads();
+                    __syncthreads();
 #pragma unroll
-                for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
-                    if (bkt[u] >= 0)
-                        s_stage[s_boff[bkt[u]] + rank[u]] = ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
-                __syncthreads();
-                const int32_t tot = s_boff[NB - 1] + s_bcnt[NB - 1];
-                for (int32_t i = tid; i < tot; i += LG_TILE) {
-                    const unsigned long long pr = s_stage[i];
-                    const int32_t bk = (int32_t)(lg_tab_hash((int32_t)(pr >> 32)) & (NB - 1));
-                    const int32_t at = s_list[bk] + (i - s_boff[bk]);
-                    if (at < a.claim_cap) a.claim_pairs[lg_claim_at<NB>(bk, at)] = pr;
+                    for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
+                        if (bkt[u] >= 0) {
+                            const int32_t at = s_boff[bkt[u]] + rank[u];
+                            if (at < a.claim_cap)
+                                a.claim_pairs[lg_claim_at<NB>(bkt[u], at)] =
+                                    ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
+                        }
                 }
-            } else if (SINGLE) {
-                // the super tile's claims, grouped by hash bucket, into one run of the lane's pair array: ranks by LDS atomics
-                // (the order inside a bucket does not matter), ONE global reservation per super tile
-                int32_t rank[LG_SLOTS_PER_LANE], bkt[LG_SLOTS_PER_LANE];
-                __syncthreads();                                   // s_bcnt zeroed by every wave's view
-#pragma unroll
-                for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
-                    bkt[u] = -1;
-                    if (dst[u] >= 0) {
-                        bkt[u] = (int32_t)(lg_tab_hash(dst[u]) & (NB - 1));
-                        rank[u] = atomicAdd(&s_bcnt[bkt[u]], 1);
-                    }
-                }
-                __syncthreads();
-                // one list per bucket: the super tile's claims of a bucket take the next places of that bucket's list (one
-                // reservation per bucket and super tile).  A claim past the list's capacity is not written: the count says so, and
-                // the bucket's de-duplication workgroup then reads the hop's slots instead of the list
-                if (tid < NB) {
-                    const int32_t c = s_bcnt[tid];
-                    s_boff[tid] = c > 0 ? __hip_atomic_fetch_add(a.claim_cnt + tid * LG_CLAIM_CNT_STRIDE, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
-                }
-                __syncthreads();
-#pragma unroll
-                for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
-                    if (bkt[u] >= 0) {
-                        const int32_t at = s_boff[bkt[u]] + rank[u];
-                        if (at < a.claim_cap)
-                            a.claim_pairs[lg_claim_at<NB>(bkt[u], at)] =
-                                ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
-                    }
             }
 
             if (!SINGLE) {
@@ -1015,7 +1006,7 @@ __device__ __forceinline__ unsigned long long st_word(unsigned long long status,
 __device__ __forceinline__ int32_t st_edges(unsigned long long w) { return (int32_t)((w >> 31) & 0x7FFFFFFFull); }
 __device__ __forceinline__ int32_t st_nodes(unsigned long long w) { return (int32_t)(w & 0x7FFFFFFFull); }
 
-// EIDS (edge-id mode, HopParams.edge_ids): every edge e also gets agg_edge_ids[e] = indptr_full[vertex the slot sampled for] + the
+// EIDS (edge-id mode, SampleMode::edge_ids): every edge e also gets agg_edge_ids[e] = indptr_full[vertex the slot sampled for] + the
 // position the slot drew (slot_pick, sample_kernel<.., EIDS>): the edge's place in the FULL CSR's column array, also for a row that
 // was read from a cached topology.  Both loads depend on the slot index only and go out with the others of that kind (the row
 // pointer is one 8-byte load the f consecutive slots of a frontier entry share); int64 from the load to the store.  A template
@@ -1354,6 +1345,22 @@ static bool launch_dedup(hipStream_t s, const SampleHopPlan& plan, const HopPara
     return false;
 }
 
+// the sample_kernel instance of class BB for one draw rule, with or without edge ids (which also leave each slot's pick: slot_pick)
+template <int BB, SampleDraw DRAW>
+static void launch_sample(hipStream_t s, dim3 grid, const HopParams& q, const LanePtrs* d_lanes)
+{
+    constexpr SampleClassInfo ci = sample_class(BB);
+    if (q.mode.edge_ids) sample_kernel<BB, ci.single, ci.staged, DRAW, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    else sample_kernel<BB, ci.single, ci.staged, DRAW, false><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+}
+// the compact_kernel instance: edge-id mode's also turn slot_pick into agg_edge_ids
+template <bool EIDS>
+static void launch_compact(hipStream_t s, dim3 grid, const HopParams& p, const LanePtrs* d_lanes)
+{
+    if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS, EIDS><<<grid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+    else compact_kernel<false, LG_COMPACT_THREADS, EIDS><<<grid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
+}
+
 // one hop of class BB (sample_plan.h SAMPLE_CLASSES), as sample_hop_plan sized it: sample (+ place) -> de-duplicate -> compact (-> list)
 template <int BB>
 static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams& p, const LanePtrs* d_lanes, int32_t n_lanes)
@@ -1362,15 +1369,10 @@ static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams
     HopParams q = p;
     q.lds_k = plan.k;
     const dim3 grid(plan.sample_gx, n_lanes);
-    if (!p.edge_ids && !p.weighted) {
-        if (p.replace) sample_kernel<BB, ci.single, ci.staged><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-        else sample_kernel<BB, ci.single, ci.staged, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-    } else if (p.weighted) {      // weighted mode (with replacement: do_random_sample refuses anything else), with or without edge ids
-        if (!p.edge_ids) sample_kernel<BB, ci.single, ci.staged, false, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-        else sample_kernel<BB, ci.single, ci.staged, false, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-    } else {       // edge-id mode: the instances that also leave each slot's pick (slot_pick)
-        if (p.replace) sample_kernel<BB, ci.single, ci.staged, false, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
-        else sample_kernel<BB, ci.single, ci.staged, true, true><<<grid, LG_TILE, 0, s>>>(q, d_lanes);
+    switch (p.mode.draw()) {       // (a mode sample_mode_refusal names never gets here: do_random_sample)
+    case SampleDraw::Uniform: launch_sample<BB, SampleDraw::Uniform>(s, grid, q, d_lanes); break;
+    case SampleDraw::Distinct: launch_sample<BB, SampleDraw::Distinct>(s, grid, q, d_lanes); break;
+    case SampleDraw::Weighted: launch_sample<BB, SampleDraw::Weighted>(s, grid, q, d_lanes); break;
     }
     hipCheckError();
     if constexpr (!ci.single) {
@@ -1384,13 +1386,8 @@ static void launch_hop(hipStream_t s, const SampleHopPlan& plan, const HopParams
     }
     hipCheckError();
     const dim3 cgrid(plan.compact_gx, n_lanes);
-    if (!p.edge_ids) {
-        if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-        else compact_kernel<false, LG_COMPACT_THREADS><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-    } else {       // edge-id mode: ... and the instances that turn it into agg_edge_ids
-        if (p.last_hop) compact_kernel<true, LG_COMPACT_THREADS, true><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-        else compact_kernel<false, LG_COMPACT_THREADS, true><<<cgrid, LG_COMPACT_THREADS, 0, s>>>(p, d_lanes);
-    }
+    if (p.mode.edge_ids) launch_compact<true>(s, cgrid, p, d_lanes);
+    else launch_compact<false>(s, cgrid, p, d_lanes);
     hipCheckError();
     if (!p.last_hop) {       // later hops must recognise the nodes this one added: their buckets' lists
         list_known_kernel<BB><<<dim3(plan.known_chunks, n_lanes), LG_TILE, 0, s>>>(p, d_lanes);

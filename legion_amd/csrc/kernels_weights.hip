@@ -3,7 +3,7 @@
 //   edge_cdf[s + i] = (float)( sum_{j <= i} (double) w'[s + j] ),  s = indptr[v],  w'[e] = w[e] if w[e] is finite and > 0, else 0
 //
 // one pass over w: sanitise + a segmented inclusive scan, the sum carried in double and rounded once.  Set-up, once per graph; the
-// sampler (sample_kernel<.., WEIGHTED>) only reads the table.
+// sampler (sample_kernel<.., SampleDraw::Weighted, ..>) only reads the table.
 //   * rows of up to LG_W_LONG entries: a wave per row, 64 entries per step (one coalesced 256-byte load and store), a shuffle scan
 //     and a double carried from step to step.  A wave takes 64 CONSECUTIVE rows: their row pointers are one coalesced load, and
 //     the rows' entries are consecutive in memory;

@@ -23,6 +23,7 @@
 #include <vector>
 
 #include "../../include/legion_hip.h"
+#include "sample_mode.h"
 #include "sample_plan.h"
 
 #define INTERBATCH_CON LEGION_INTERBATCH_CON
@@ -132,7 +133,6 @@ enum HopScratch {
 #ifndef LG_CLAIM_CNT_STRIDE
 #define LG_CLAIM_CNT_STRIDE 32        // ints between the claim-list counts of two buckets: a line each (the 8 / 16 reservations of a super tile go to different lines)
 #endif
-#define LG_DISTINCT_MAX_FANOUT LEGION_DISTINCT_MAX_FANOUT   // largest fan-out of sampling without replacement (the sampler's LDS span of an entry's picks)
 
 // Per-vertex row header: where the adjacency of v lives (slot of the CSR pointer tables: P = the
 // full CSR, d < P = GPU d's cached CSR), its first edge and its degree.  One 16-byte read resolves
@@ -210,7 +210,7 @@ struct LanePtrs {
     float* float_features;
     int32_t feature_rows;
     int32_t max_slots;
-    // edge-id mode (MemoryPool::edge_ids), else both null: the adjacency position each slot drew (sample_kernel -> compact_kernel)
+    // edge-id mode (MemoryPool::mode.edge_ids), else both null: the adjacency position each slot drew (sample_kernel -> compact_kernel)
     // and, per edge of the batch, its position in the FULL CSR's column array -- indexed like agg_src_ids
     int32_t* slot_pick;                // [max_slots]
     int64_t* agg_edge_ids;             // [num_ids]
@@ -299,22 +299,17 @@ public:
     // legion_pool_alloc_features (features_allocated); the buffer's element size follows it, its capacity in rows does not
     int32_t feature_out_dtype = LEGION_FEATURE_F32;
     bool features_allocated = false;
-    // 1: the sampler draws with replacement (the reference's draw); 0: without (distinct adjacency positions per frontier entry, DGL's
-    // replace=False).  Fixed once the pool has sampled a hop, eagerly or into a captured graph (sample_used)
-    int32_t sample_replace = 1;
+    // the sampler's modes (sample_mode.h), each fixed once the pool has sampled a hop, eagerly or into a captured graph (sample_used):
+    // replace 0 takes distinct adjacency positions per frontier entry; edge_ids 1 also gives every sampled edge e agg_edge_ids[e] = its
+    // position in the full CSR's column array, next to agg_src_ids[e] -- the two arrays below exist only then (lg_pool_alloc_edge_ids:
+    // plain allocations of the pool, never part of a lane arena: the trainer-visible arrays and the wire do not change); weighted 1
+    // picks position i of a row with probability w'[i] / row total, by an upper-bound search of the graph's per-row prefix-sum table
+    // (GraphStorage::EdgeCdf, legion_graph_set_edge_weights) -- nothing is allocated in the pool: the table lives with the graph
+    SampleMode mode;
     bool sample_used = false;
     int32_t max_fanout = 0;            // largest fan-out the pool was sized for
-    // 1: every sampled edge e also gets agg_edge_ids[e] = its position in the full CSR's column array (DGL's dgl.EID), next to
-    // agg_src_ids[e].  The two arrays below exist only then (lg_pool_alloc_edge_ids: plain allocations of the pool, never part of a
-    // lane arena -- the trainer-visible arrays and the wire do not change).  Fixed once the pool has sampled a hop (sample_used)
-    int32_t edge_ids = 0;
     int32_t* slot_pick = nullptr;      // [max_slots] see LanePtrs
     int64_t* agg_edge_ids = nullptr;   // [num_ids]
-    // 1: weighted sampling (DGL's prob=): a slot picks adjacency position i of its row with probability w'[i] / row total, by an
-    // upper-bound search of the graph's per-row prefix-sum table (GraphStorage::EdgeCdf, legion_graph_set_edge_weights) in place of
-    // the uniform draw.  With replacement only (the setters refuse sample_replace == 0 beside it).  Nothing is allocated in the pool:
-    // the table lives with the graph.  Fixed once the pool has sampled a hop (sample_used)
-    int32_t sample_weighted = 0;
     int32_t lanes_epoch = 0;           // bumped when the pool's lane descriptor changes after creation (a lane group re-uploads its copy)
     int64_t grid_rows_hint = 0;        // > 0: rows a batch typically has (the Runner's pipe-slot pool holds the worst case: launches are sized for the usual one)
     int32_t dev_id = 0;
@@ -692,8 +687,11 @@ bool lg_is_local(int32_t dev);
 
 void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
                            const int32_t* fanout, int32_t hop_num, int32_t float_feature_len);
-// the two arrays of the edge-id mode (MemoryPool::edge_ids), part of the pool's private allocation: made when the mode is turned on
+// the two arrays of the edge-id mode (MemoryPool::mode.edge_ids), part of the pool's private allocation: made when the mode is turned on
 void lg_pool_alloc_edge_ids(MemoryPool* mp);
+// the one way a pool's mode changes (the three legion_pool_set_* of storage.hip, and legion_pipeline_set_* for every lane): refused
+// once the pool has sampled and for what sample_mode_refusal names; check_only: answer, change nothing
+bool lg_pool_try_set_mode(MemoryPool* mp, const SampleMode& mode, bool check_only = false);
 // how many pools of this shape the caller is about to keep in flight on the device (Pipeline: lanes x slots);
 // feeds the direct-vs-table choice of the position state (LEGION_DEDUP=auto).  Thread-local; 0 = one pool.
 // what PreSC saw of the LAST hop, the largest one: its edges (= the claims its de-duplication takes) and the batch's nodes
@@ -753,11 +751,10 @@ struct HopParams {                  // what every lane of a launch shares
     unsigned long long* edge_access_time;  // presample only (single lane), else null
     unsigned long long* topo_transactions; // presample only: 64-byte transactions the hop's topology reads amount to
     int32_t lds_k;                  // super tiles per partition tile in this hop (set by launch_random_sample)
-    int32_t replace;                // 1: draws with replacement (the reference's); 0: distinct positions per entry (MemoryPool::sample_replace)
-    int32_t edge_ids;               // 1: the hop also writes agg_edge_ids (MemoryPool::edge_ids): the flagged sample / compact instances
-    const int64_t* indptr_full;     // the full CSR's row pointers (slot P of the pointer tables): read by those instances only
-    int32_t weighted;               // 1: picks by the prefix-sum table instead of the uniform draw (MemoryPool::sample_weighted): the WEIGHTED instances
-    const float* edge_cdf;          // GraphStorage::EdgeCdf(), indexed like col_full; those instances also read indptr_full (cached rows)
+    const int64_t* indptr_full;     // the full CSR's row pointers (slot P of the pointer tables): read by the edge-id and weighted instances only
+    SampleMode mode;                // MemoryPool::mode: picks the sample / compact instances (launch_hop); no kernel reads it.  (It stands
+                                    // between the two pointers only so that they are not adjacent, as they never were)
+    const float* edge_cdf;          // GraphStorage::EdgeCdf(), indexed like col_full: the weighted instances, which also read indptr_full (cached rows)
 };
 // bucket_bits, last_hop_claims_hint: the pool's (MemoryPool); the launch follows sample_hop_plan (sample_plan.h)
 void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits, int64_t last_hop_claims_hint, const LanePtrs* d_lanes,

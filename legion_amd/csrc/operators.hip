@@ -93,6 +93,21 @@ static void do_batch_generate(hipStream_t s, FeatureStorage* feature, const Lane
     // cache->FindFeat(op 0) (operator_impl.cu:167-170) happens inside FeatureCacheLookup(op 1)
 }
 
+// May these lanes sample against this graph -- fanout > 0: a hop of that fan-out; 0: a batch as a whole, before its first hop (every
+// hop asks again with its own fan-out)?  The lanes of a launch share one HopParams, so they must agree; the rest is sample_mode.h's.
+// If not: says why, raises LG_ERR_SAMPLE_MODE on every one of the lanes and returns false -- the caller enqueues nothing
+static bool sample_allowed(const char* who, const char* outcome, MemoryPool* const* pools, int32_t n, GraphStorage* graph, int32_t fanout)
+{
+    SampleRefusal r = sample_launch_refusal(pools[0]->mode, fanout, graph->EdgeCdf() != nullptr);
+    for (int32_t i = 1; i < n; i++)
+        if (pools[i]->mode != pools[0]->mode) r = SampleRefusal::LanesDiffer;
+    if (r == SampleRefusal::Ok) return true;
+    if (r == SampleRefusal::Fanout) printf("%s: fan-out %d without replacement (at most %d)%s\n", who, fanout, LG_DISTINCT_MAX_FANOUT, outcome);   // (names the hop's fan-out)
+    else printf("%s: %s%s\n", who, sample_refusal_text(r), outcome);
+    for (int32_t i = 0; i < n; i++) pools[i]->RaiseError(LG_ERR_SAMPLE_MODE);
+    return false;
+}
+
 static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* cache, const LanePtrs* d_lanes,
                              int32_t n_lanes, MemoryPool* pool0, int32_t count, int32_t dev_id, int32_t op_id,
                              bool is_presc)
@@ -101,19 +116,10 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
         printf("Sampling Parameters Error\n");   // counter_update's complaint, operator_impl.cu:86-88
         return;
     }
-    if (!pool0->sample_replace && count > LG_DISTINCT_MAX_FANOUT) {
-        printf("Sampling Parameters Error: fan-out %d without replacement (at most %d)\n", count, LG_DISTINCT_MAX_FANOUT);
-        pool0->RaiseError(LG_ERR_SAMPLE_MODE);
-        return;
-    }
-    if (pool0->sample_weighted && (graph->EdgeCdf() == nullptr || !pool0->sample_replace)) {      // (enqueue_lanes has refused the batch already)
-        printf("Sampling Parameters Error: a weighted hop needs the graph's edge weights (legion_graph_set_edge_weights) and replacement\n");
-        pool0->RaiseError(LG_ERR_SAMPLE_MODE);
-        return;
-    }
+    if (!sample_allowed("Sampling Parameters Error", "", &pool0, 1, graph, count)) return;      // (the fan-out; enqueue_lanes' callers have asked the rest)
     lg::Range mark("op%d sample%s fanout=%d lanes=%d", op_id, is_presc ? " (presc)" : "", count, n_lanes);
-    pool0->sample_used = true;              // the mode is fixed from here on (legion_pool_set_sample_replace)
-    if (pool0->sample_weighted) graph->MarkWeightedUsed();      // ... and so is the graph's table (legion_graph_set_edge_weights)
+    pool0->sample_used = true;              // the mode is fixed from here on (lg_pool_try_set_mode)
+    if (pool0->mode.weighted) graph->MarkWeightedUsed();      // ... and so is the graph's table (legion_graph_set_edge_weights)
     lg::HopParams p;
     p.op_id = op_id;
     p.count = count;
@@ -133,10 +139,8 @@ static void do_random_sample(hipStream_t s, GraphStorage* graph, UnifiedCache* c
     p.edge_access_time = (is_presc && cache) ? cache->GetEdgeAccessedMap(dev_id) : nullptr;   // :473
     p.topo_transactions = (is_presc && cache) ? cache->Controller(dev_id)->GetTopoTransactions() : nullptr;
     p.lds_k = 1;                             // (launch_random_sample sets the hop's partition tile)
-    p.replace = pool0->sample_replace;
-    p.edge_ids = pool0->edge_ids;
+    p.mode = pool0->mode;
     p.indptr_full = graph->GetCSRNodeIndexCPU();
-    p.weighted = pool0->sample_weighted;
     p.edge_cdf = graph->EdgeCdf();
     lg::launch_random_sample(s, p, pool0->lds_bucket_bits, pool0->last_hop_claims_hint, d_lanes, n_lanes);
 }
@@ -438,11 +442,7 @@ extern "C" void legion_enqueue_batch(legion_stream_t strm_hdl, LegionGraphStorag
 {
     MemoryPool* mp = reinterpret_cast<MemoryPool*>(memorypool);
     if (!graph || !feature || !mp) { std::cout << "invalid storage ptr\n"; return; }
-    if (mp->sample_weighted && reinterpret_cast<GraphStorage*>(graph)->EdgeCdf() == nullptr) {      // nothing of the batch is enqueued
-        printf("legion_hip: a weighted pool against a graph without edge weights (legion_graph_set_edge_weights); nothing enqueued\n");
-        mp->RaiseError(LG_ERR_SAMPLE_MODE);
-        return;
-    }
+    if (!sample_allowed("legion_hip", "; nothing enqueued", &mp, 1, reinterpret_cast<GraphStorage*>(graph), 0)) return;
     enqueue_lanes(static_cast<hipStream_t>(strm_hdl), reinterpret_cast<GraphStorage*>(graph),
                   reinterpret_cast<FeatureStorage*>(feature), cache_of(cache), mp->DeviceLane(), 1, mp, mp->iter_state,
                   batch_size, counter, dev_id, mode, is_presc, fanout, hop_num);
@@ -504,7 +504,7 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
     if (!graph || !feature || !group || group->pools.empty()) { std::cout << "invalid storage ptr\n"; return; }
     if (n_active < 1 || n_active > (int32_t)group->pools.size()) n_active = (int32_t)group->pools.size();
     // every lane samples with lane 0's modes (HopParams is shared by the launch): lanes that disagree are refused, and every lane's
-    // modes are fixed from here on (legion_pool_set_sample_replace, legion_pool_set_edge_ids)
+    // modes are fixed from here on (lg_pool_try_set_mode)
     {
         bool stale = false;
         for (size_t i = 0; i < group->pools.size(); i++) stale |= group->epochs[i] != group->pools[i]->lanes_epoch;
@@ -517,20 +517,9 @@ extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraph
         }
         if (stale) legion_group_refresh(group);
     }
-    for (int32_t i = 0; i < n_active; i++)
-        if (group->pools[i]->sample_replace != group->pools[0]->sample_replace || group->pools[i]->edge_ids != group->pools[0]->edge_ids ||
-            group->pools[i]->sample_weighted != group->pools[0]->sample_weighted) {
-            printf("legion_hip: lanes of one group with different sampling modes; nothing enqueued\n");
-            for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
-            return;
-        }
-    if (group->pools[0]->sample_weighted && reinterpret_cast<GraphStorage*>(graph)->EdgeCdf() == nullptr) {
-        printf("legion_hip: weighted lanes against a graph without edge weights (legion_graph_set_edge_weights); nothing enqueued\n");
-        for (int32_t j = 0; j < n_active; j++) group->pools[j]->RaiseError(LG_ERR_SAMPLE_MODE);
-        return;
-    }
+    if (!sample_allowed("legion_hip", "; nothing enqueued", group->pools.data(), n_active, reinterpret_cast<GraphStorage*>(graph), 0)) return;
     for (int32_t i = 0; i < n_active; i++) group->pools[i]->sample_used = true;
-    if (group->pools[0]->sample_weighted) reinterpret_cast<GraphStorage*>(graph)->MarkWeightedUsed();
+    if (group->pools[0]->mode.weighted) reinterpret_cast<GraphStorage*>(graph)->MarkWeightedUsed();
     enqueue_lanes(static_cast<hipStream_t>(strm_hdl), reinterpret_cast<GraphStorage*>(graph),
                   reinterpret_cast<FeatureStorage*>(feature), cache_of(cache), group->d_lanes, n_active, group->pools[0],
                   group->iter_state, batch_size, counter0, dev_id, mode, false, fanout, hop_num, phase);

@@ -233,52 +233,32 @@ extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, Leg
                                      use_graph, LEGION_FEATURE_F32);
 }
 
-// every lane of every slot takes the mode; refused once any lane has sampled (a captured graph never mixes modes)
-extern "C" int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace)
+// Every lane of every slot takes the mode with one field changed (legion_pool_set_*), all or none: refused once any lane has sampled
+// (a captured graph never mixes modes) or where any lane's pool refuses.  Each slot's copy of its lanes' descriptors is written again
+// before anything is captured (only edge_ids changes a descriptor: a refresh with unchanged epochs copies nothing).  All three leave
+// the pipeline's GPU as the calling thread's current device (before, legion_pipeline_set_sample_replace did not)
+static int32_t pipeline_set_mode_field(LegionPipeline* p, int32_t SampleMode::*field, int32_t value)
 {
-    if (!p || (replace != 0 && replace != 1)) return -1;
-    for (Slot& sl : p->slots)
-        for (MemoryPool* mp : sl.pools)
-            if (mp->sample_used || (replace == 0 && (mp->max_fanout > LG_DISTINCT_MAX_FANOUT || mp->sample_weighted))) return -1;
-    for (Slot& sl : p->slots)
-        for (MemoryPool* mp : sl.pools)
-            if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(mp), replace) != 0) return -1;
+    if (!p) return -1;
+    auto each_pool = [&](bool check_only) {
+        for (Slot& sl : p->slots)
+            for (MemoryPool* mp : sl.pools) {
+                SampleMode mode = mp->mode;
+                mode.*field = value;
+                if (!lg_pool_try_set_mode(mp, mode, check_only)) return false;
+            }
+        return true;
+    };
+    if (!each_pool(true)) return -1;
+    SetGPUDevice(p->dev_id);
+    if (!each_pool(false)) return -1;
+    for (Slot& sl : p->slots) legion_group_refresh(sl.group);
     return 0;
 }
 
-// edge-id mode of every lane of every slot (legion_pool_set_edge_ids); refused once any lane has sampled
-extern "C" int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on)
-{
-    if (!p || (on != 0 && on != 1)) return -1;
-    for (Slot& sl : p->slots)
-        for (MemoryPool* mp : sl.pools)
-            if (mp->sample_used) return -1;
-    SetGPUDevice(p->dev_id);
-    for (Slot& sl : p->slots) {
-        for (MemoryPool* mp : sl.pools)
-            if (legion_pool_set_edge_ids(reinterpret_cast<LegionMemoryPool*>(mp), on) != 0) return -1;
-        legion_group_refresh(sl.group);          // the slot's copy of its lanes' descriptors, before anything is captured
-    }
-    return 0;
-}
-
-// weighted mode of every lane of every slot (legion_pool_set_sample_weighted); refused once any lane has sampled, or for 1 beside
-// sampling without replacement.  The lane descriptors are written again as legion_pipeline_set_edge_ids writes them (the mode itself
-// travels with each launch, not in the descriptor: the refresh is a no-op unless another mode changed them too)
-extern "C" int32_t legion_pipeline_set_sample_weighted(LegionPipeline* p, int32_t on)
-{
-    if (!p || (on != 0 && on != 1)) return -1;
-    for (Slot& sl : p->slots)
-        for (MemoryPool* mp : sl.pools)
-            if (mp->sample_used || (on == 1 && mp->sample_replace == 0)) return -1;
-    SetGPUDevice(p->dev_id);
-    for (Slot& sl : p->slots) {
-        for (MemoryPool* mp : sl.pools)
-            if (legion_pool_set_sample_weighted(reinterpret_cast<LegionMemoryPool*>(mp), on) != 0) return -1;
-        legion_group_refresh(sl.group);
-    }
-    return 0;
-}
+extern "C" int32_t legion_pipeline_set_sample_replace(LegionPipeline* p, int32_t replace) { return pipeline_set_mode_field(p, &SampleMode::replace, replace); }
+extern "C" int32_t legion_pipeline_set_edge_ids(LegionPipeline* p, int32_t on) { return pipeline_set_mode_field(p, &SampleMode::edge_ids, on); }
+extern "C" int32_t legion_pipeline_set_sample_weighted(LegionPipeline* p, int32_t on) { return pipeline_set_mode_field(p, &SampleMode::weighted, on); }
 
 static void slot_wait(LegionPipeline* p, Slot& sl)
 {

@@ -463,7 +463,7 @@ public:
                               float_feature_len_);
         num_ids_ = memorypool_->num_ids;
         if (legion_pool_set_sample_replace(reinterpret_cast<LegionMemoryPool*>(memorypool_), g_sample_replace) != 0) {
-            printf("legion_hip: sampling without replacement takes fan-outs up to %d\n", LG_DISTINCT_MAX_FANOUT);
+            printf("legion_hip: %s\n", sample_refusal_text(SampleRefusal::Fanout));
             exit(EXIT_FAILURE);
         }
         if (g_sample_replace == 0) std::cout << "Sampling: without replacement\n";
@@ -887,7 +887,7 @@ private:
                                           g_feature_out_dtype);
         lg_set_pool_arena(nullptr);
         if (pipe_ != nullptr && legion_pipeline_set_sample_replace(pipe_, g_sample_replace) != 0) {
-            printf("legion_hip: sampling without replacement takes fan-outs up to %d\n", LG_DISTINCT_MAX_FANOUT);
+            printf("legion_hip: %s\n", sample_refusal_text(SampleRefusal::Fanout));
             exit(EXIT_FAILURE);
         }
         for (int pp = 0; pp < interbatch_concurrency_ && pp < INTERBATCH_CON; pp++)

@@ -1291,60 +1291,44 @@ extern "C" int32_t legion_pool_feature_out_dtype(const LegionMemoryPool* p_)
     return mp ? mp->feature_out_dtype : -1;
 }
 
-// 1: sampling with replacement (default), 0: without (fan-outs up to LG_DISTINCT_MAX_FANOUT); only before the pool samples a hop
-extern "C" int32_t legion_pool_set_sample_replace(LegionMemoryPool* p_, int32_t replace)
+// The pool's sampling modes (sample_mode.h; include/legion_hip.h says what each means).  Only before the pool samples a hop.  Turning
+// edge ids on allocates their two arrays, which stay until the pool goes; a change of edge_ids also changes the lane descriptor.
+// Weighted mode allocates nothing: the table travels with the launch (HopParams)
+bool lg_pool_try_set_mode(MemoryPool* mp, const SampleMode& mode, bool check_only)
+{
+    if (!mp || mp->sample_used || sample_mode_refusal(mode, mp->max_fanout) != SampleRefusal::Ok) return false;
+    if (check_only) return true;
+    const bool lane_changes = mode.edge_ids != mp->mode.edge_ids;
+    if (mode.edge_ids) lg_pool_alloc_edge_ids(mp);
+    mp->mode = mode;
+    if (lane_changes) {
+        mp->lanes_epoch++;                 // (lane groups made before this re-upload their copy of the lane: operators.hip)
+        mp->InvalidateDeviceLanes();
+    }
+    return true;
+}
+
+// the pool's mode with one field changed, handed to lg_pool_try_set_mode
+static int32_t pool_set_mode_field(LegionMemoryPool* p_, int32_t SampleMode::*field, int32_t value)
 {
     MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
-    if (!mp || (replace != 0 && replace != 1) || mp->sample_used) return -1;
-    if (replace == 0 && mp->sample_weighted) return -1;      // weighted sampling is with replacement only
-    if (replace == 0 && mp->max_fanout > LG_DISTINCT_MAX_FANOUT) return -1;
-    mp->sample_replace = replace;
-    return 0;
+    if (!mp) return -1;
+    SampleMode mode = mp->mode;
+    mode.*field = value;
+    return lg_pool_try_set_mode(mp, mode) ? 0 : -1;
 }
-
-extern "C" int32_t legion_pool_sample_replace(const LegionMemoryPool* p_)
+static int32_t pool_mode_field(const LegionMemoryPool* p_, int32_t SampleMode::*field)
 {
     const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
-    return mp ? mp->sample_replace : -1;
+    return mp ? mp->mode.*field : -1;
 }
 
-// 1: every sampled edge also gets its position in the full CSR's column array (agg_edge_ids, DGL's dgl.EID); 0 (default): nothing
-// of that exists.  Only before the pool samples a hop; turning it on allocates the two arrays, which stay until the pool goes
-extern "C" int32_t legion_pool_set_edge_ids(LegionMemoryPool* p_, int32_t on)
-{
-    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
-    if (!mp || (on != 0 && on != 1) || mp->sample_used) return -1;
-    if (on == mp->edge_ids) return 0;
-    if (on) lg_pool_alloc_edge_ids(mp);
-    mp->edge_ids = on;
-    mp->lanes_epoch++;                     // (lane groups made before this re-upload their copy of the lane: operators.hip)
-    mp->InvalidateDeviceLanes();
-    return 0;
-}
-
-extern "C" int32_t legion_pool_edge_ids(const LegionMemoryPool* p_)
-{
-    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
-    return mp ? mp->edge_ids : -1;
-}
-
-// 1: weighted sampling -- a slot picks adjacency position i with probability w'[i] / row total, by the graph's prefix-sum table
-// (legion_graph_set_edge_weights); 0 (default): the uniform draw.  With replacement only; only before the pool samples a hop.
-// Nothing is allocated and the lane descriptor does not change: the table travels with the launch (HopParams)
-extern "C" int32_t legion_pool_set_sample_weighted(LegionMemoryPool* p_, int32_t on)
-{
-    MemoryPool* mp = reinterpret_cast<MemoryPool*>(p_);
-    if (!mp || (on != 0 && on != 1) || mp->sample_used) return -1;
-    if (on == 1 && mp->sample_replace == 0) return -1;
-    mp->sample_weighted = on;
-    return 0;
-}
-
-extern "C" int32_t legion_pool_sample_weighted(const LegionMemoryPool* p_)
-{
-    const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
-    return mp ? mp->sample_weighted : -1;
-}
+extern "C" int32_t legion_pool_set_sample_replace(LegionMemoryPool* p, int32_t replace) { return pool_set_mode_field(p, &SampleMode::replace, replace); }
+extern "C" int32_t legion_pool_sample_replace(const LegionMemoryPool* p) { return pool_mode_field(p, &SampleMode::replace); }
+extern "C" int32_t legion_pool_set_edge_ids(LegionMemoryPool* p, int32_t on) { return pool_set_mode_field(p, &SampleMode::edge_ids, on); }
+extern "C" int32_t legion_pool_edge_ids(const LegionMemoryPool* p) { return pool_mode_field(p, &SampleMode::edge_ids); }
+extern "C" int32_t legion_pool_set_sample_weighted(LegionMemoryPool* p, int32_t on) { return pool_set_mode_field(p, &SampleMode::weighted, on); }
+extern "C" int32_t legion_pool_sample_weighted(const LegionMemoryPool* p) { return pool_mode_field(p, &SampleMode::weighted); }
 
 extern "C" void legion_pool_set_current_pipe(LegionMemoryPool* p_, int32_t pipe)
 {
@@ -1383,7 +1367,7 @@ extern "C" void* legion_pool_buffer(LegionMemoryPool* p_, int32_t which)
         case 11: return mp->GetTmpPartOff();
         case 12: return mp->GetPositionMap();      // always null: no per-vertex state in this build
         case 13: return mp->node_slot;             // [num_ids] feature-cache slot carried per node (LG_FS_UNKNOWN = -3: look it up), or null
-        case 14: return mp->edge_ids ? mp->agg_edge_ids : nullptr;      // int64[num_ids], edge-id mode only (legion_pool_set_edge_ids)
+        case 14: return mp->mode.edge_ids ? mp->agg_edge_ids : nullptr;      // int64[num_ids], edge-id mode only (legion_pool_set_edge_ids)
         default: return nullptr;
     }
 }

@@ -287,6 +287,15 @@ class FeatureStorage:
             self.handle = None
 
 
+def _set_sample_mode(owner, c_name, what, value, types, refused):
+    """One sampling mode of a MemoryPool or a Pipeline (owner: its _lib and handle, touched only once the value is valid) through its
+    C setter, which refuses what sample_mode.h does not allow and every change after the first hop: RuntimeError."""
+    if not isinstance(value, types) or int(value) not in (0, 1):
+        raise ValueError(f"{what} must be True or False, not {value!r}")
+    if getattr(owner._lib, c_name)(owner.handle, int(value)) != 0:
+        raise RuntimeError(f"{c_name}: {refused}")
+
+
 class MemoryPool:
     _BUF = {"sampled_ids": (0, torch.int32), "float_features": (1, torch.float32),
             "labels": (2, torch.int32), "agg_src_off": (3, torch.int32), "agg_dst_off": (4, torch.int32),
@@ -363,11 +372,8 @@ class MemoryPool:
 
     def set_replace(self, replace):
         """Only before the pool samples its first hop (the C ABI refuses it after: RuntimeError)."""
-        if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
-            raise ValueError(f"replace must be True or False, not {replace!r}")
-        if self._lib.legion_pool_set_sample_replace(self.handle, int(bool(replace))) != 0:
-            raise RuntimeError("legion_pool_set_sample_replace: the pool has sampled already, or a fan-out is above 256 without replacement, "
-                               "or the pool is weighted")
+        _set_sample_mode(self, "legion_pool_set_sample_replace", "replace", replace, (bool, int),
+                         "the pool has sampled already, or a fan-out is above 256 without replacement, or the pool is weighted")
 
     @property
     def edge_ids(self):
@@ -376,10 +382,7 @@ class MemoryPool:
     def set_edge_ids(self, on):
         """Only before the pool samples its first hop (the C ABI refuses it after: RuntimeError).  A Pipeline's lanes take the mode
         through Pipeline.set_edge_ids."""
-        if not isinstance(on, bool):
-            raise ValueError(f"edge_ids must be True or False, not {on!r}")
-        if self._lib.legion_pool_set_edge_ids(self.handle, int(on)) != 0:
-            raise RuntimeError("legion_pool_set_edge_ids: the pool has sampled already")
+        _set_sample_mode(self, "legion_pool_set_edge_ids", "edge_ids", on, bool, "the pool has sampled already")
 
     @property
     def weighted(self):
@@ -388,10 +391,8 @@ class MemoryPool:
     def set_weighted(self, on):
         """Only before the pool samples its first hop, and only with replace=True (the C ABI refuses it otherwise: RuntimeError).  A
         Pipeline's lanes take the mode through Pipeline.set_weighted."""
-        if not isinstance(on, bool):
-            raise ValueError(f"weighted must be True or False, not {on!r}")
-        if self._lib.legion_pool_set_sample_weighted(self.handle, int(on)) != 0:
-            raise RuntimeError("legion_pool_set_sample_weighted: the pool has sampled already, or it samples without replacement")
+        _set_sample_mode(self, "legion_pool_set_sample_weighted", "weighted", on, bool,
+                         "the pool has sampled already, or it samples without replacement")
 
     def alloc_features(self, rows):
         self.feature_rows = int(rows)
@@ -524,11 +525,8 @@ class Pipeline:
 
     def set_replace(self, replace):
         """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
-        if not isinstance(replace, (bool, int)) or int(replace) not in (0, 1):
-            raise ValueError(f"replace must be True or False, not {replace!r}")
-        if self._lib.legion_pipeline_set_sample_replace(self.handle, int(bool(replace))) != 0:
-            raise RuntimeError("legion_pipeline_set_sample_replace: the pipeline has sampled already, or a fan-out is above 256 without replacement, "
-                               "or the pipeline is weighted")
+        _set_sample_mode(self, "legion_pipeline_set_sample_replace", "replace", replace, (bool, int),
+                         "the pipeline has sampled already, or a fan-out is above 256 without replacement, or the pipeline is weighted")
 
     @property
     def edge_ids(self):
@@ -536,10 +534,7 @@ class Pipeline:
 
     def set_edge_ids(self, on):
         """Only before the first submit (the C ABI refuses it after: RuntimeError)."""
-        if not isinstance(on, bool):
-            raise ValueError(f"edge_ids must be True or False, not {on!r}")
-        if self._lib.legion_pipeline_set_edge_ids(self.handle, int(on)) != 0:
-            raise RuntimeError("legion_pipeline_set_edge_ids: the pipeline has sampled already")
+        _set_sample_mode(self, "legion_pipeline_set_edge_ids", "edge_ids", on, bool, "the pipeline has sampled already")
 
     @property
     def weighted(self):
@@ -547,10 +542,8 @@ class Pipeline:
 
     def set_weighted(self, on):
         """Only before the first submit, and only with replace=True (the C ABI refuses it otherwise: RuntimeError)."""
-        if not isinstance(on, bool):
-            raise ValueError(f"weighted must be True or False, not {on!r}")
-        if self._lib.legion_pipeline_set_sample_weighted(self.handle, int(on)) != 0:
-            raise RuntimeError("legion_pipeline_set_sample_weighted: the pipeline has sampled already, or it samples without replacement")
+        _set_sample_mode(self, "legion_pipeline_set_sample_weighted", "weighted", on, bool,
+                         "the pipeline has sampled already, or it samples without replacement")
 
     def submit(self, counter0, mode=TRAINMODE, n_active=None):
         if n_active is None or n_active >= self.group_size:
