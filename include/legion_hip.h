@@ -455,6 +455,35 @@ int32_t legion_draw_distinct_batch(legion_stream_t stream, const int32_t* base, 
  * of cdf and has deg[i] entries; out[i] = pick, or -1 for deg[i] <= 0 or a row total of 0 */
 void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, const int64_t* row_start, const int32_t* deg,
                                 const float* cdf, int32_t* out, int32_t n);
+/* Random walks over the graph (DGL's dgl.sampling.random_walk), new in this build; no reference counterpart.
+ * num_walks walks of `length` steps: traces_out is int32[num_walks x (length + 1)], row-major, and edge_ids_out, if not NULL,
+ * int64[num_walks x length] (both device memory).  Everything is enqueued on `stream`, on the device current at the call; nothing
+ * synchronises with the host, and the call may be captured into a graph.  The walk reads the FULL CSR only (slot partition_count of
+ * the pointer tables: the arrays given to legion_graph_create), and edge_cdf when weighted; a GPU's cached topology and its column-slot
+ * copy are not read.
+ * Walk w:  traces[w][0] = seeds[w], copied as given.  For step j = 1 .. length let v = traces[w][j - 1], n = base + w * length + (j - 1)
+ * and minstd(k) = 48271^k mod (2^31 - 1), the power of the sampler's draw.  Then, in this order:
+ *   1. ended walk: v < 0 or v >= node_num (a bad seed too): traces[w][j] = -1, and so is every later entry -- no memory is read for v;
+ *   2. restart, only if restart_prob > 0: y = minstd((uint32)(n + 1) + 2^31), r2 = (double)(y - 1) / 2147483646.0; r2 < (double)restart_prob:
+ *      the walk ends before this transition (DGL's restart_prob).  With restart_prob == 0 nothing is drawn;
+ *   3. row: s = indptr[v], D = indptr[v + 1] - s; D == 0: the walk ends;
+ *   4. pick: x = minstd(n + 1), r = (double)(x - 1) / 2147483646.0.  Unweighted: pick = (int)(r * D), the sampler's uniform draw.
+ *      Weighted: the pick of legion_graph_set_edge_weights -- T = edge_cdf[s + D - 1]; T == 0: the walk ends; else t = r * (double)T and
+ *      pick = min(#{ i in [0, D) : (double)edge_cdf[s + i] <= t }, D - 1), by the same upper-bound search;
+ *   5. next vertex: u = col[s + pick]; u < 0 (a dead column entry): the walk ends; else traces[w][j] = u and edge_ids[w][j - 1] = s + pick;
+ *   6. wherever traces[w][j] == -1, edge_ids[w][j - 1] == -1.
+ * With all weights 1.0f (D < 2^24) the weighted walk is the unweighted one bit for bit.  Since 48271 generates the whole group,
+ * minstd(k + 2^31) == minstd(k + 2): the restart draw of index n is the number the pick of index n + 2 uses, so a
+ * walk that survives step j's restart draw picks at step j + 2 with r >= restart_prob: with restart_prob > 0 the picks from the third
+ * step on favour the later entries of a row.  The rule is kept as specified; DESIGN.md 4.11 says what would remove the dependence.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, seeds_devptr or traces_out; num_walks < 0; length < 1;
+ * base < 0; base + num_walks * length > 2^31 - 1 (the draw index, the restart offset included, stays where the power tables reach);
+ * weighted outside {0, 1}; weighted == 1 on a graph without a table; restart_prob NaN or outside [0, 1].  num_walks == 0 returns 0
+ * and enqueues nothing.  A weighted walk counts as a weighted hop for legion_graph_set_edge_weights: the table cannot be replaced
+ * afterwards.  Not offered: metapaths, node2vec's p / q bias, PinSAGE's visit counting; the server, the launcher and the wire. */
+int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
+                           int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
+                           int64_t* edge_ids_out /* may be NULL */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -860,6 +860,22 @@ void launch_draw_weighted_batch(hipStream_t s, const int32_t* idx, const int64_t
 int64_t lg_weights_long_rows_cap(int64_t num_edges);
 void build_edge_cdf(hipStream_t s, const int64_t* indptr, int32_t n_rows, const float* w, float* cdf, int32_t* long_rows, int32_t long_cap);
 
+// random walks over the full CSR (kernels_walk.hip; the rule: legion_random_walk in legion_hip.h)
+struct WalkParams {
+    const int64_t* indptr;          // the FULL CSR (slot P of the pointer tables), int64[node_num + 1]
+    const int32_t* col;
+    const float* edge_cdf;          // the graph's prefix table: a weighted walk; null: the uniform pick
+    const int32_t* seeds;           // int32[num_walks]
+    int32_t* traces;                // int32[num_walks x (length + 1)]
+    int64_t* edge_ids;              // int64[num_walks x length], or null
+    int32_t node_num;
+    int32_t num_walks;
+    int32_t length;
+    float restart_prob;             // > 0: the instances with the restart draw
+    int64_t base;                   // draw index of walk 0's first step
+};
+void launch_random_walk(hipStream_t s, const WalkParams& p);
+
 // a roctx range for the enclosing scope (markers.hip): visible to rocprofv3 --marker-trace, near-free otherwise
 struct Range {
     explicit Range(const char* fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -379,6 +379,37 @@ extern "C" int32_t legion_draw_distinct_batch(legion_stream_t stream, const int3
     return 0;
 }
 
+// Random walks over the full CSR (the rule and the refusals: legion_hip.h).  Every check comes before the launch: a refused call
+// enqueues nothing and touches no buffer.
+extern "C" int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_walks,
+                                      int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
+                                      int64_t* edge_ids_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !seeds_devptr || !traces_out) return -1;
+    if (num_walks < 0 || length < 1 || base < 0) return -1;
+    if (base + (int64_t)num_walks * (int64_t)length > (int64_t)0x7FFFFFFF) return -1;       // (each term < 2^62: no overflow once base is bounded below)
+    if (weighted != 0 && weighted != 1) return -1;
+    if (weighted == 1 && graph->EdgeCdf() == nullptr) return -1;
+    if (!(restart_prob >= 0.0f && restart_prob <= 1.0f)) return -1;                         // (NaN fails both comparisons)
+    if (num_walks == 0) return 0;
+    if (weighted == 1) graph->MarkWeightedUsed();       // the table stays as it is from here on, as after a weighted hop
+    lg::WalkParams p;
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
+    p.seeds = seeds_devptr;
+    p.traces = traces_out;
+    p.edge_ids = edge_ids_out;
+    p.node_num = graph->NodeNum();
+    p.num_walks = num_walks;
+    p.length = length;
+    p.restart_prob = restart_prob;
+    p.base = base;
+    lg::launch_random_walk(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
 // One whole mini-batch in the op order of GPURunner::RunOnce / RunPreSc (SS/engine/server.cu:285-332)
 // without the IPC hand-off: what a Runner enqueues per batch, exposed for callers that own the
 // buffers themselves (tests, bench.py, an in-process trainer).

@@ -202,6 +202,61 @@ class GraphStorage:
             return None
         return device_view(ptr, (self.edge_num,), torch.float32, self.col.device)
 
+    @staticmethod
+    def _check_walk(n, length, weighted, restart_prob, return_eids, base):
+        """random_walk's arguments by the rules of legion_random_walk, before anything touches a device: ValueError with the reason."""
+        for name, flag in (("weighted", weighted), ("return_eids", return_eids)):
+            if not isinstance(flag, bool):
+                raise ValueError(f"{name} must be True or False, not {flag!r}")
+        for name, value in (("length", length), ("base", base)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, not {value!r}")
+        if length < 1:
+            raise ValueError(f"length must be at least 1, not {length}")
+        if base < 0:
+            raise ValueError(f"base must not be negative, not {base}")
+        if base + n * length > 2 ** 31 - 1:
+            raise ValueError(f"base + num_walks * length = {base + n * length} is past the last draw index, 2^31 - 1")
+        if isinstance(restart_prob, bool) or not isinstance(restart_prob, (int, float, np.floating, np.integer)):
+            raise ValueError(f"restart_prob must be a number in [0, 1], not {restart_prob!r}")
+        if not 0.0 <= float(np.float32(restart_prob)) <= 1.0:      # (NaN fails; the library sees the float32)
+            raise ValueError(f"restart_prob must lie in [0, 1], not {restart_prob!r}")
+
+    def random_walk(self, seeds, length, *, weighted=False, restart_prob=0.0, return_eids=False, base=0, stream=None):
+        """Random walks over the full CSR (DGL's dgl.sampling.random_walk; the rule: legion_random_walk in legion_hip.h).  seeds: int32
+        vertex ids, a CUDA tensor or anything torch.as_tensor takes; walk w starts at seeds[w] and takes `length` steps.  Returns
+        traces, int32 [n, length + 1] with -1 from where a walk ended (no out-edge, a dead column entry, a restart, a seed outside
+        the graph), and with return_eids also eids, int64 [n, length], each step's position in col (-1 where the trace is).
+        weighted: steps pick by the edge weights (set_edge_weights must have run; the table is fixed afterwards, as after a weighted
+        hop).  restart_prob: each step first ends the walk with this probability.  base: draw index of the first walk's first step;
+        walks with the same seeds, flags and base are the same walks.  Enqueued on `stream` (default: the current one)."""
+        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
+            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.as_tensor(seeds, dtype=torch.int32)
+        if seeds.dim() != 1:
+            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        n = int(seeds.numel())
+        self._check_walk(n, length, weighted, restart_prob, return_eids, base)
+        if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
+            raise ValueError("a weighted walk needs the graph's edge weights (set_edge_weights)")
+        dev = self.col.device
+        seeds = seeds.to(dev).contiguous()
+        traces = torch.empty((n, int(length) + 1), dtype=torch.int32, device=dev)
+        eids = torch.empty((n, int(length)), dtype=torch.int64, device=dev) if return_eids else None
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return (traces, eids) if return_eids else traces
+        with torch.cuda.device(dev):
+            rc = self._lib.legion_random_walk(_stream_handle(stream), self.handle, _ptr(seeds), n, int(length), int(weighted),
+                                              float(restart_prob), int(base), _ptr(traces), _ptr(eids))
+        if rc != 0:
+            raise RuntimeError("legion_random_walk refused arguments that random_walk had accepted")
+        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
+            for x in (seeds, traces, eids):
+                if x is not None:
+                    x.record_stream(stream)
+        return (traces, eids) if return_eids else traces
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))
