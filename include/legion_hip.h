@@ -480,10 +480,39 @@ void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, cons
  * base < 0; base + num_walks * length > 2^31 - 1 (the draw index, the restart offset included, stays where the power tables reach);
  * weighted outside {0, 1}; weighted == 1 on a graph without a table; restart_prob NaN or outside [0, 1].  num_walks == 0 returns 0
  * and enqueues nothing.  A weighted walk counts as a weighted hop for legion_graph_set_edge_weights: the table cannot be replaced
- * afterwards.  Not offered: metapaths, node2vec's p / q bias, PinSAGE's visit counting; the server, the launcher and the wire. */
+ * afterwards.  Not offered: metapaths, node2vec's p / q bias; the server, the launcher and the wire. */
 int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
                            int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
                            int64_t* edge_ids_out /* may be NULL */);
+/* PinSAGE's neighbour sampler (DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous graph), new in this build;
+ * no reference counterpart.  For each of num_seeds seeds: num_walks_per_seed (R) walks of walk_length (T) steps, the visited vertices
+ * counted, and the num_neighbors (k) most visited returned with their counts.  neighbors_out and counts_out are int32[num_seeds x k],
+ * row-major, device memory.  Everything is enqueued on `stream`, on the device current at the call; nothing synchronises with the host,
+ * and the call may be captured into a graph.  It reads the FULL CSR only, and edge_cdf when weighted, as legion_random_walk does.  No
+ * traces are written anywhere.
+ * Walks.  Walk r of seed i is global walk w = i * R + r and starts at seeds[i].  Step j = 1 .. T has draw index
+ * n = base + w * T + (j - 1) and is exactly steps 1-5 of legion_random_walk's rule (ended-walk test before any load, restart, row, uniform
+ * or weighted pick, dead column entry) with restart_prob = termination_prob -- except that step j = 1 takes NO restart draw, whatever
+ * termination_prob is: DGL passes restart_prob = 0 for the first traversal.  Steps j >= 2 take the restart draw of their index
+ * (y = minstd((uint32)(n + 1) + 2^31), r2 < (double)termination_prob ends the walk) when termination_prob > 0.  With termination_prob == 0
+ * the walks are, bit for bit, those of legion_random_walk over seeds with each entry repeated R times, length T, the same base.
+ * Visits.  The visits of seed i are the multiset of the vertices its R walks reach at steps j = 1 .. T (trace entries >= 0).  The seed
+ * position j = 0 is not a visit; the seed's own id is one whenever a walk returns to it, as in DGL.
+ * Result.  The distinct visited vertices of a seed are ordered by visit count descending, ties by vertex id ascending (a total order;
+ * DGL leaves ties open).  neighbors[i][m], counts[i][m] for m < k are the m-th of them; slots past the number of distinct vertices hold
+ * -1 / 0.  A seed outside [0, node_num), a seed without out-edges and a seed whose walks all end at step 1 give a row of -1 / 0.
+ * The rule of the walk is shared, and so is its weakness: the restart draw of index n is the number the pick of index n + 2 uses (see
+ * legion_random_walk), so with termination_prob > 0 a walk that survives step j's restart draw picks at step j + 2 with r >= termination_prob.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, seeds_devptr, neighbors_out or counts_out; num_seeds < 0;
+ * R < 1, T < 1 or k < 1; R * T > LEGION_PINSAGE_MAX_VISITS or k > LEGION_PINSAGE_MAX_VISITS; base < 0;
+ * base + num_seeds * R * T > 2^31 - 1 (in 64 bits); weighted outside {0, 1}; weighted == 1 on a graph without a table; termination_prob
+ * NaN or outside [0, 1].  num_seeds == 0 returns 0 and enqueues nothing.  A weighted call counts as a weighted hop for
+ * legion_graph_set_edge_weights, like a weighted walk.  Not offered: metapaths (heterogeneous graphs); the server, the launcher, the wire. */
+#define LEGION_PINSAGE_MAX_VISITS 1024
+int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_seeds,
+                                 int32_t num_walks_per_seed, int32_t walk_length, int32_t num_neighbors, int32_t weighted,
+                                 float termination_prob, int64_t base, int32_t* neighbors_out /* int32[n x k] */,
+                                 int32_t* counts_out /* int32[n x k] */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -876,6 +876,17 @@ struct WalkParams {
 };
 void launch_random_walk(hipStream_t s, const WalkParams& p);
 
+// PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
+struct PinsageParams {
+    WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the
+                                    // termination probability; num_walks = n (one row of results per seed); traces, edge_ids unused
+    int32_t walks_per_seed;         // R
+    int32_t num_neighbors;          // k
+    int32_t* neighbors;             // int32[n x k]
+    int32_t* counts;                // int32[n x k]
+};
+void launch_pinsage_neighbors(hipStream_t s, const PinsageParams& p);
+
 // a roctx range for the enclosing scope (markers.hip): visible to rocprofv3 --marker-trace, near-free otherwise
 struct Range {
     explicit Range(const char* fmt, ...) __attribute__((format(printf, 2, 3)));

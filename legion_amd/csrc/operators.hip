@@ -410,6 +410,42 @@ extern "C" int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage
     return 0;
 }
 
+// PinSAGE's neighbour sampler (the rule and the refusals: legion_hip.h).  As above: every check comes before the launch.
+extern "C" int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_seeds,
+                                            int32_t num_walks_per_seed, int32_t walk_length, int32_t num_neighbors, int32_t weighted,
+                                            float termination_prob, int64_t base, int32_t* neighbors_out, int32_t* counts_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !seeds_devptr || !neighbors_out || !counts_out) return -1;
+    if (num_seeds < 0 || num_walks_per_seed < 1 || walk_length < 1 || num_neighbors < 1 || base < 0) return -1;
+    const int64_t visits = (int64_t)num_walks_per_seed * (int64_t)walk_length;
+    if (visits > LEGION_PINSAGE_MAX_VISITS || num_neighbors > LEGION_PINSAGE_MAX_VISITS) return -1;
+    if (base > (int64_t)0x7FFFFFFF || base + (int64_t)num_seeds * visits > (int64_t)0x7FFFFFFF) return -1;      // (num_seeds * visits < 2^41)
+    if (weighted != 0 && weighted != 1) return -1;
+    if (weighted == 1 && graph->EdgeCdf() == nullptr) return -1;
+    if (!(termination_prob >= 0.0f && termination_prob <= 1.0f)) return -1;                 // (NaN fails both comparisons)
+    if (num_seeds == 0) return 0;
+    if (weighted == 1) graph->MarkWeightedUsed();
+    lg::PinsageParams p;
+    p.walk.indptr = graph->GetCSRNodeIndexCPU();
+    p.walk.col = graph->GetCSRNodeMatrixCPU();
+    p.walk.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
+    p.walk.seeds = seeds_devptr;
+    p.walk.traces = nullptr;
+    p.walk.edge_ids = nullptr;
+    p.walk.node_num = graph->NodeNum();
+    p.walk.num_walks = num_seeds;
+    p.walk.length = walk_length;
+    p.walk.restart_prob = termination_prob;
+    p.walk.base = base;
+    p.walks_per_seed = num_walks_per_seed;
+    p.num_neighbors = num_neighbors;
+    p.neighbors = neighbors_out;
+    p.counts = counts_out;
+    lg::launch_pinsage_neighbors(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
 // One whole mini-batch in the op order of GPURunner::RunOnce / RunPreSc (SS/engine/server.cu:285-332)
 // without the IPC hand-off: what a Runner enqueues per batch, exposed for callers that own the
 // buffers themselves (tests, bench.py, an in-process trainer).

@@ -257,6 +257,72 @@ class GraphStorage:
                     x.record_stream(stream)
         return (traces, eids) if return_eids else traces
 
+    PINSAGE_MAX_VISITS = 1024                        # LEGION_PINSAGE_MAX_VISITS
+
+    @staticmethod
+    def _check_pinsage(n, num_random_walks, walk_length, num_neighbors, termination_prob, weighted, base):
+        """pinsage_neighbors' arguments by the rules of legion_pinsage_neighbors, before anything touches a device: ValueError with
+        the reason."""
+        cap = GraphStorage.PINSAGE_MAX_VISITS
+        if not isinstance(weighted, bool):
+            raise ValueError(f"weighted must be True or False, not {weighted!r}")
+        for name, value in (("num_random_walks", num_random_walks), ("walk_length", walk_length), ("num_neighbors", num_neighbors),
+                            ("base", base)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, not {value!r}")
+        for name, value in (("num_random_walks", num_random_walks), ("walk_length", walk_length), ("num_neighbors", num_neighbors)):
+            if value < 1:
+                raise ValueError(f"{name} must be at least 1, not {value}")
+        if num_random_walks * walk_length > cap:
+            raise ValueError(f"num_random_walks * walk_length = {num_random_walks * walk_length} visits per seed, at most {cap}")
+        if num_neighbors > cap:
+            raise ValueError(f"num_neighbors must be at most {cap}, not {num_neighbors}")
+        if base < 0:
+            raise ValueError(f"base must not be negative, not {base}")
+        if base + n * num_random_walks * walk_length > 2 ** 31 - 1:
+            raise ValueError(f"base + num_seeds * num_random_walks * walk_length = {base + n * num_random_walks * walk_length} "
+                             f"is past the last draw index, 2^31 - 1")
+        if isinstance(termination_prob, bool) or not isinstance(termination_prob, (int, float, np.floating, np.integer)):
+            raise ValueError(f"termination_prob must be a number in [0, 1], not {termination_prob!r}")
+        if not 0.0 <= float(np.float32(termination_prob)) <= 1.0:      # (NaN fails; the library sees the float32)
+            raise ValueError(f"termination_prob must lie in [0, 1], not {termination_prob!r}")
+
+    def pinsage_neighbors(self, seeds, num_random_walks, walk_length, num_neighbors, *, termination_prob=0.5, weighted=False, base=0,
+                          stream=None):
+        """PinSAGE's importance neighbourhoods (DGL's RandomWalkNeighborSampler / PinSAGESampler on a homogeneous graph; the rule:
+        legion_pinsage_neighbors in legion_hip.h).  From each seed num_random_walks walks of walk_length steps over the full CSR; after
+        its first step a walk ends before each step with termination_prob.  Returns (neighbors, counts), both int32
+        [n, num_neighbors]: per seed the most visited vertices, by visit count descending and vertex id ascending, and their counts;
+        -1 / 0 past the number of distinct visited vertices.  seeds, weighted, base and stream as in random_walk; no traces are
+        written.  A DGL block: mask = neighbors >= 0, src = neighbors[mask], dst = seeds repeated per row under the mask, edge weight
+        counts[mask]."""
+        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
+            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.as_tensor(seeds, dtype=torch.int32)
+        if seeds.dim() != 1:
+            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        n = int(seeds.numel())
+        self._check_pinsage(n, num_random_walks, walk_length, num_neighbors, termination_prob, weighted, base)
+        if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
+            raise ValueError("weighted walks need the graph's edge weights (set_edge_weights)")
+        dev = self.col.device
+        seeds = seeds.to(dev).contiguous()
+        neighbors = torch.empty((n, int(num_neighbors)), dtype=torch.int32, device=dev)
+        counts = torch.empty((n, int(num_neighbors)), dtype=torch.int32, device=dev)
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return neighbors, counts
+        with torch.cuda.device(dev):
+            rc = self._lib.legion_pinsage_neighbors(_stream_handle(stream), self.handle, _ptr(seeds), n, int(num_random_walks),
+                                                    int(walk_length), int(num_neighbors), int(weighted), float(termination_prob),
+                                                    int(base), _ptr(neighbors), _ptr(counts))
+        if rc != 0:
+            raise RuntimeError("legion_pinsage_neighbors refused arguments that pinsage_neighbors had accepted")
+        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
+            for x in (seeds, neighbors, counts):
+                x.record_stream(stream)
+        return neighbors, counts
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))

@@ -142,6 +142,7 @@ SIGNATURES = {
     "legion_draw_distinct_batch": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32]),
     "legion_draw_weighted_batch": (None, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
     "legion_random_walk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
+    "legion_pinsage_neighbors": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
