@@ -41,9 +41,9 @@ def visits(indptr, col, seeds, R, T, table=None, termination_prob=0.5, base=0, r
     return out.reshape(n, R * T)
 
 
-def topk(vis, k):
+def topk_loop(vis, k):
     """(neighbors, counts), int32 [n, k], of visit rows (entries < 0 are no visits): distinct vertices by count descending, id ascending;
-    -1 / 0 past their number."""
+    -1 / 0 past their number.  Row by row: the definition of topk."""
     n = vis.shape[0]
     nb = np.full((n, k), -1, dtype=np.int32)
     ct = np.zeros((n, k), dtype=np.int32)
@@ -54,6 +54,36 @@ def topk(vis, k):
         ids, c = np.unique(row, return_counts=True)               # ids ascending
         order = np.lexsort((ids, -c))[:k]
         nb[i, :order.size], ct[i, :order.size] = ids[order], c[order]
+    return nb, ct
+
+
+def topk(vis, k):
+    """topk_loop over all rows at once: the rows sorted, run lengths from the run heads, one flat sort by (row, -count, id)
+    packed in an int64."""
+    vis = np.asarray(vis)
+    n, V = vis.shape
+    nb = np.full((n, k), -1, dtype=np.int32)
+    ct = np.zeros((n, k), dtype=np.int32)
+    if n == 0 or V == 0:
+        return nb, ct
+    s = np.sort(np.where(vis < 0, np.int64(2 ** 31), vis.astype(np.int64)), axis=1)      # no visit sorts last
+    valid = (s < 2 ** 31).sum(axis=1)
+    head = s < 2 ** 31
+    head[:, 1:] &= s[:, 1:] != s[:, :-1]
+    row, pos = np.nonzero(head)                                    # row-major: a row's heads are consecutive, positions ascending
+    if row.size == 0:
+        return nb, ct
+    end = np.append(pos[1:], 0)
+    last = np.append(row[1:] != row[:-1], True)                    # a row's last run ends where its visits do
+    end[last] = valid[row[last]]
+    count, ids = end - pos, s[row, pos]
+    assert n < 2 ** 21 and V < 2 ** 11                              # one int64 key: row, V - count and id in 21, 11 and 31 bits
+    key = np.sort((row.astype(np.int64) << 42) | ((V - count).astype(np.int64) << 31) | ids)
+    row, count, ids = key >> 42, V - ((key >> 31) & 2047), key & (2 ** 31 - 1)
+    first = np.nonzero(np.append(True, row[1:] != row[:-1]))[0]
+    rank = np.arange(row.size) - np.repeat(first, np.diff(np.append(first, row.size)))
+    keep = rank < k
+    nb[row[keep], rank[keep]], ct[row[keep], rank[keep]] = ids[keep], count[keep]
     return nb, ct
 
 

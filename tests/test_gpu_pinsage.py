@@ -132,6 +132,23 @@ def test_base(world, base):
         _same(got, want, f"base {base} weighted {weighted} termination {p}")
 
 
+def test_a_call_on_another_stream_is_the_default_streams(world):
+    """stream=: the launch goes to a stream that is not current (and the call's tensors are recorded on it); same neighbourhoods."""
+    seeds = torch.from_numpy(walk_ref.seeds_for(257)).to(DEV)
+    shapes = [(10, 2, 3), (64, 16, 10)]
+    want = [world["graph"].pinsage_neighbors(seeds, *shape, weighted=True, termination_prob=0.3, base=5) for shape in shapes]
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    assert s != torch.cuda.current_stream()
+    got = [world["graph"].pinsage_neighbors(seeds, *shape, weighted=True, termination_prob=0.3, base=5, stream=s) for shape in shapes]
+    host = world["graph"].pinsage_neighbors(walk_ref.seeds_for(257), *shapes[0], weighted=True, termination_prob=0.3, base=5, stream=s)
+    s.synchronize()
+    for a, b in zip(got + [host], want + [want[0]]):
+        assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
+    _same(got[0], ref.neighbors(world["indptr"], world["col"], seeds.cpu().numpy(), *shapes[0], table=world["table"], termination_prob=0.3,
+                                base=5), "stream=")
+
+
 def test_empty_call_returns_empty_arrays(world):
     nb, ct = world["graph"].pinsage_neighbors(np.zeros(0, np.int32), 10, 2, 3)
     assert nb.shape == ct.shape == (0, 3) and nb.dtype == ct.dtype == torch.int32

@@ -115,6 +115,22 @@ def test_base(world, base):
         _same(got, want, f"base {base} weighted {weighted} restart {restart}")
 
 
+def test_a_walk_on_another_stream_is_the_default_streams(world):
+    """stream=: the launch goes to a stream that is not current (and the call's tensors are recorded on it); same walks."""
+    seeds = torch.from_numpy(ref.seeds_for(5000)).to(DEV)
+    want = world["graph"].random_walk(seeds, 17, weighted=True, restart_prob=0.3, return_eids=True, base=5)
+    plain = world["graph"].random_walk(seeds, 17, base=5)
+    torch.cuda.synchronize()
+    s = torch.cuda.Stream()
+    assert s != torch.cuda.current_stream()
+    got = world["graph"].random_walk(seeds, 17, weighted=True, restart_prob=0.3, return_eids=True, base=5, stream=s)
+    only = world["graph"].random_walk(seeds, 17, base=5, stream=s)
+    host = world["graph"].random_walk(ref.seeds_for(5000), 17, base=5, stream=s)      # seeds from the host: copied, then walked on s
+    s.synchronize()
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(only, plain) and torch.equal(host, plain)
+    _same(got, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), 17, table=world["table"], restart_prob=0.3, base=5), "stream=")
+
+
 def test_empty_call_returns_empty_arrays(world):
     traces, eids = world["graph"].random_walk(np.zeros(0, np.int32), 3, return_eids=True)
     assert traces.shape == (0, 4) and eids.shape == (0, 3) and traces.dtype == torch.int32 and eids.dtype == torch.int64

@@ -21,19 +21,30 @@ def refused(num_walks, length, weighted, restart_prob, base, has_table):
     return not (p >= 0 and p <= 1)
 
 
+def draws_slow(first, count, offset=0):
+    """The definition of draws: one pow per draw index, nothing shared."""
+    return np.array([minstd(((k + 1) & 0xFFFFFFFF) + offset) for k in range(first, first + count)], dtype=np.uint64)
+
+
 _DRAWS = {}                                                       # (first, offset) -> the longest run computed so far
 
 
 def draws(first, count, offset=0):
     """minstd(k + offset) for k = first + 1 .. first + count as uint64: the x of draw indices first .. first + count - 1 (offset 0) or
-    their restart draws (offset 2^31, on the uint32 of k).  A run is computed once and shared: shorter runs are its prefixes."""
-    have = _DRAWS.get((first, offset), np.zeros(0, dtype=np.uint64))
-    if have.size < count:
-        more = [minstd(((k + 1) & 0xFFFFFFFF) + offset) for k in range(first + have.size, first + count)]
-        have = np.concatenate([have, np.array(more, dtype=np.uint64)])
+    their restart draws (offset 2^31, on the uint32 of k).  A run is computed once and shared: shorter runs are its prefixes.
+    The exponents of a legal call are consecutive integers (first + count <= 2^31 - 1: nothing wraps inside a run), so a run grows by
+    doubling: a run of length m, then the same run times 48271^m -- in uint64, products below 2^62.  draws_slow is the definition."""
+    have = _DRAWS.get((first, offset))
+    if have is None and count > 0:
+        have = np.array([minstd(first + 1 + offset)], dtype=np.uint64)
+    if have is not None and have.size < count:
+        assert first >= 0 and first + count <= M31 and offset in (0, 2 ** 31), (first, count, offset)
+        while have.size < count:
+            m = min(have.size, count - have.size)
+            have = np.concatenate([have, have[:m] * np.uint64(minstd(have.size)) % np.uint64(M31)])
         have.setflags(write=False)
         _DRAWS[(first, offset)] = have
-    return have[:count]
+    return have[:count] if have is not None else np.zeros(0, dtype=np.uint64)
 
 
 def unit_of(x):
