@@ -683,21 +683,19 @@ unsigned long long int* UnifiedCache::GetEdgeAccessedMap(int32_t dev_id)
 }
 
 // SS/cache/cache.cu:726-748 -- lookup (FindFeat) fused into the gather
-void UnifiedCache::FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id,
-                                   hipStream_t strm_hdl, int32_t max_rows, bool use_snapshot, int32_t first_op_id, bool last_op,
-                                   bool skip_remote, int32_t grid_rows, int32_t out_dtype)
+void UnifiedCache::FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t dev_id, hipStream_t strm_hdl, const GatherCall& call)
 {
-    lg::GatherParams g = GatherParamsOf(dev_id, op_id, max_rows, use_snapshot, first_op_id, last_op);
-    g.skip_remote = skip_remote;
-    g.grid_rows = grid_rows;
-    g.out_dtype = out_dtype;
+    lg::GatherParams g = GatherParamsOf(dev_id, call.op_id, call.max_rows, call.use_snapshot, call.first_op_id, call.last_op);
+    g.skip_remote = call.skip_remote;
+    g.grid_rows = call.grid_rows;
+    g.out_dtype = call.out_dtype;
     lg::launch_gather(strm_hdl, g, d_lanes, n_lanes);
 }
 
-void UnifiedCache::BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id, hipStream_t s, int32_t max_rows,
+void UnifiedCache::BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, const BatchOp& whole, int32_t dev_id, hipStream_t s, int32_t max_rows,
                               const lg::BulkLists& lists, const char* arena_base)
 {
-    const lg::GatherParams g = GatherParamsOf(dev_id, op_id, max_rows, true, 1, true);
+    const lg::GatherParams g = GatherParamsOf(dev_id, whole.op_id, max_rows, true, whole.first_op_id, true);
     lg::launch_bulk_bucket(s, g, d_lanes, n_lanes, lists, arena_base);
 }
 
@@ -716,7 +714,6 @@ lg::GatherParams UnifiedCache::GatherParamsOf(int32_t dev_id, int32_t op_id, int
 {
     const bool filled = !node_capacity_.empty() && d_float_feature_cache_ptr_[dev_id] != nullptr &&
                         cache_controller_[dev_id]->NodeMap() != nullptr;
-    (void)op_id;
     lg::GatherParams g;
     g.replica = (filled && dev_id < (int32_t)replica_.size()) ? replica_[dev_id] : nullptr;
     g.replica_rows = g.replica ? replica_rows_[dev_id] : 0;

@@ -114,15 +114,10 @@ enum HopScratch {
 #define LG_G __attribute__((address_space(1)))
 #define LG_GPTR(T, p) ((LG_G T*)(p))
 
-// phases of a whole-batch enqueue (legion_enqueue_group_phase)
-#define LG_PHASE_ALL 0      // reference op order: gather right after the op that produced its rows
-#define LG_PHASE_SAMPLE 1   // BatchGenerate + every RandomSample + IOComplete
-#define LG_PHASE_GATHER 2   // every FeatureCacheLookup, from the per-op range snapshots
-// "weave" arrangement (pipeline.hip): the group cut where its character changes
-#define LG_PHASE_HEAD 3     // BatchGenerate + every hop but the last, complete: small, latency-bound kernels
-#define LG_PHASE_REST 4     // the last hop (sample .. localise) + IOComplete + every gather, in that order
-#define LG_PHASE_REST_SAMPLE 5   // LG_PHASE_REST without the gathers (GPURunner serving a trainer end that gets its rows gathered
-                                 // batch by batch straight into a pipe slot)
+// phases of a whole-batch enqueue (legion_enqueue_group_phase): LG_PHASE_* and the ops each of them issues, in order, are
+// batch_ops.h's (batch_op_list)
+#include "batch_ops.h"
+static_assert(BATCH_OP_STRIDE == INTRABATCH_CON, "batch_ops.h numbers the ops of a batch as the counters do");
 
 // Feature-cache slot of a sampled neighbour, carried from the sampler to the gather (see "column slots", GraphStorage):
 // a value >= 0 or CACHEMISS_FLAG is what node_map[id] holds; LG_FS_UNKNOWN means "not carried: look it up"
@@ -517,12 +512,20 @@ public:
     void LastHopMax(int32_t dev_id, int32_t out[2]);   // PreSC maxima {edges of the last hop, nodes before it}; {0, 0} before PreSC
     unsigned long long int* GetEdgeAccessedMap(int32_t dev_id);
     // the gather over a group of lanes (the reference's per-array arguments live in LanePtrs)
-    // first_op_id < op_id: one launch also covers the new-node ranges of the earlier ops first_op_id, +3, ...
-    void FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id,
-                         hipStream_t strm_hdl, int32_t max_rows, bool use_snapshot, int32_t first_op_id = -1, bool last_op = true,
-                         bool skip_remote = false, int32_t grid_rows = 0, int32_t out_dtype = LEGION_FEATURE_F32);
-    // peer_gather = bulk (lg::BulkLists): the requester's bucket pass over every row of its group's batches, and the owner's push
-    void BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, int32_t op_id, int32_t dev_id, hipStream_t s, int32_t max_rows,
+    struct GatherCall {
+        int32_t op_id;
+        int32_t first_op_id = -1;       // < op_id: one launch also covers the new-node ranges of the earlier ops first_op_id, +3, ...
+        bool use_snapshot = true;       // the rows' range from the snapshot the op's producer left (false: from the live counters)
+        bool last_op = true;            // the batch's last gather: what it leaves in cache_search_buffer is what the batch hands over
+        bool skip_remote = false;       // peer_gather = bulk: rows of other members' stripes are the owners' to push
+        int32_t max_rows = 0;           // rows the lanes' feature buffers hold
+        int32_t grid_rows = 0;          // rows a lane typically has (sizes the grid); 0: max_rows
+        int32_t out_dtype = LEGION_FEATURE_F32;
+    };
+    void FeatCacheLookup(const LanePtrs* d_lanes, int32_t n_lanes, int32_t dev_id, hipStream_t strm_hdl, const GatherCall& call);
+    // peer_gather = bulk (lg::BulkLists): the requester's bucket pass over every row of its group's batches (whole: batch_whole_gather),
+    // and the owner's push
+    void BulkBucket(const LanePtrs* d_lanes, int32_t n_lanes, const BatchOp& whole, int32_t dev_id, hipStream_t s, int32_t max_rows,
                     const lg::BulkLists& lists, const char* arena_base);
     lg::GatherParams GatherParamsOf(int32_t dev_id, int32_t op_id, int32_t max_rows, bool use_snapshot, int32_t first_op_id, bool last_op);
     void BulkPush(int32_t owner_dev, hipStream_t s, const int32_t* fidx, const int64_t* dst, const unsigned long long* cnt,

@@ -157,20 +157,20 @@ static void do_feature_lookup(hipStream_t s, UnifiedCache* cache, const LanePtrs
         return;
     }
     lg::Range mark("op%d gather lanes=%d first_op=%d", op_id, n_lanes, first_op_id);
-    int64_t max_rows = pool0->feature_rows;
-    if (max_rows > pool0->num_ids) max_rows = pool0->num_ids;
-    const size_t hop = (size_t)(op_id / INTRABATCH_CON);          // grid bound: new nodes of op 3h <= B f1..fh
-    int64_t bound = 0;                                            // + the earlier ops that ride along
-    for (size_t h = (use_snapshot && first_op_id >= 0 && first_op_id < op_id) ? (size_t)(first_op_id / INTRABATCH_CON) : hop;
-         h <= hop && h < pool0->max_new.size(); h++)
-        bound += pool0->max_new[h];
-    if (hop < pool0->max_new.size() && bound < max_rows) max_rows = bound;
+    const int64_t max_rows = gather_row_bound(pool0->max_new.data(), (int32_t)pool0->max_new.size(), op_id, first_op_id, use_snapshot,
+                                              pool0->feature_rows, pool0->num_ids);
     MemoryPool* pp = pool0;
     const bool prof = pp->prof_on && (size_t)(2 * pp->prof_used + 1) < pp->prof_events.size();
     if (prof) HIP_CALL(hipEventRecord(pp->prof_events[2 * pp->prof_used], s));
-    cache->FeatCacheLookup(d_lanes, n_lanes, op_id, dev_id, s, (int32_t)max_rows, use_snapshot, first_op_id,
-                           hop + 1 >= pool0->max_new.size(), false, (int32_t)std::min<int64_t>(pool0->grid_rows_hint, max_rows),
-                           pool0->feature_out_dtype);
+    UnifiedCache::GatherCall call;
+    call.op_id = op_id;
+    call.first_op_id = first_op_id;
+    call.use_snapshot = use_snapshot;
+    call.last_op = (size_t)(op_id / INTRABATCH_CON) + 1 >= pool0->max_new.size();
+    call.max_rows = (int32_t)max_rows;
+    call.grid_rows = (int32_t)std::min<int64_t>(pool0->grid_rows_hint, max_rows);
+    call.out_dtype = pool0->feature_out_dtype;
+    cache->FeatCacheLookup(d_lanes, n_lanes, dev_id, s, call);
     if (prof) {
         HIP_CALL(hipEventRecord(pp->prof_events[2 * pp->prof_used + 1], s));
         pp->prof_op[pp->prof_used] = op_id;
@@ -460,46 +460,30 @@ static void enqueue_lanes(hipStream_t s, GraphStorage* graph, FeatureStorage* fe
     }
     if (cache && feature && cache->FeatureTable() == nullptr)
         cache->BindFeatureTable(feature);
-    // inside a whole-batch enqueue every gather reads the {offset, count} snapshot its producer left in
-    // hop_scratch[HS_RANGE + 2h] (not overwritten by later hops), so the gathers may also run as a
-    // phase of their own after the whole sampler (LG_PHASE_GATHER, on another stream: pipeline.hip)
-    const bool seeds_ride = hop_num >= 2;
-    if (phase >= LG_PHASE_HEAD) {          // the two pieces of the weave arrangement (serve mode only)
-        const int32_t last = hop_num - 1;
-        // (every gather stays on the heavy stream, behind the last hop: the seeds' and earlier hops' gathers on the light stream
-        // under the previous group's last gather were measured in round 4 -- no gain -- and removed)
-        if (phase == LG_PHASE_HEAD) {
+    const bool profile = is_presc && mode == TRAINMODE && cache != nullptr;
+    const BatchOpList ops = batch_op_list(hop_num, phase, is_presc, profile);     // batch_ops.h: the order, the op ids, which gathers share a launch
+    const bool weave = phase >= LG_PHASE_HEAD;                                     // (serve mode only)
+    for (int32_t i = 0; i < ops.n; i++) {
+        const BatchOp& op = ops.op[i];
+        switch (op.kind) {
+        case BatchOpKind::Seeds:
             do_batch_generate(s, feature, d_lanes, n_lanes, pool0, batch_size, counter, dev_id, mode, hop_num, iter_state);
-            for (int32_t h = 0; h < last; h++)
-                do_random_sample(s, graph, cache, d_lanes, n_lanes, pool0, fanout[h], dev_id, INTRABATCH_CON * (h + 1), false);
-        } else {
-            if (last >= 0) do_random_sample(s, graph, cache, d_lanes, n_lanes, pool0, fanout[last], dev_id, INTRABATCH_CON * (last + 1), false);
+            break;
+        case BatchOpKind::Sample:
+            do_random_sample(s, graph, cache, d_lanes, n_lanes, pool0, fanout[op.hop], dev_id, op.op_id, !weave && is_presc);
+            break;
+        case BatchOpKind::Gather:
+            do_feature_lookup(s, cache, d_lanes, n_lanes, pool0, op.op_id, dev_id, true, op.first_op_id);
+            break;
+        case BatchOpKind::Profile:      // CacheProfiling (one lane only in PreSC)
+            cache->CacheProfiling(pool0->GetSampledIds(), pool0->GetAggSrcId(), pool0->GetAggDstId(), pool0->GetAggSrcOf(),
+                                  pool0->GetAggDstOf(), pool0->GetNodeCounter(), pool0->GetEdgeCounter(), s, dev_id);
+            break;
+        case BatchOpKind::EndOfBatch:
             lg::launch_end_of_batch(s, d_lanes, n_lanes, iter_state);
-            if (phase == LG_PHASE_REST_SAMPLE) return;
-            if (!seeds_ride) do_feature_lookup(s, cache, d_lanes, n_lanes, pool0, 1, dev_id, true);
-            for (int32_t h = 0; h <= last; h++)
-                do_feature_lookup(s, cache, d_lanes, n_lanes, pool0, INTRABATCH_CON * (h + 1) + 1, dev_id, true,
-                                  (h == 0 && seeds_ride) ? 1 : -1);
+            break;
         }
-        return;
     }
-    const bool sampler = phase != LG_PHASE_GATHER, gathers = phase != LG_PHASE_SAMPLE && !is_presc;
-    if (sampler) do_batch_generate(s, feature, d_lanes, n_lanes, pool0, batch_size, counter, dev_id, mode, hop_num, iter_state);
-    // The seeds' rows (op 1) are few and directly in front of hop 1's: when a later gather follows (so that
-    // what FindFeat leaves in cache_search_buffer is the last op's either way), one launch fetches both.
-    const bool seeds_ride_along = hop_num >= 2;
-    if (gathers && !seeds_ride_along) do_feature_lookup(s, cache, d_lanes, n_lanes, pool0, 1, dev_id, true);
-    for (int32_t h = 0; h < hop_num; h++) {
-        const int32_t op = INTRABATCH_CON * (h + 1);
-        if (sampler) do_random_sample(s, graph, cache, d_lanes, n_lanes, pool0, fanout[h], dev_id, op, is_presc);
-        if (gathers) do_feature_lookup(s, cache, d_lanes, n_lanes, pool0, op + 1, dev_id, true,
-                                       (h == 0 && seeds_ride_along) ? 1 : -1);
-    }
-    if (!sampler) return;
-    if (is_presc && mode == TRAINMODE && cache != nullptr)     // CacheProfiling (one lane only in PreSC)
-        cache->CacheProfiling(pool0->GetSampledIds(), pool0->GetAggSrcId(), pool0->GetAggDstId(), pool0->GetAggSrcOf(),
-                              pool0->GetAggDstOf(), pool0->GetNodeCounter(), pool0->GetEdgeCounter(), s, dev_id);
-    lg::launch_end_of_batch(s, d_lanes, n_lanes, iter_state);
 }
 
 extern "C" void legion_enqueue_batch(legion_stream_t strm_hdl, LegionGraphStorage* graph, LegionFeatureStorage* feature,
@@ -617,7 +601,7 @@ extern "C" void legion_enqueue_group_last_gather(legion_stream_t strm_hdl, Legio
     if (!cache || !group || group->pools.empty() || hop_num < 1) { std::cout << "invalid cache/group ptr\n"; return; }
     if (n_active < 1 || n_active > (int32_t)group->pools.size()) n_active = (int32_t)group->pools.size();
     do_feature_lookup(static_cast<hipStream_t>(strm_hdl), cache_of(cache), group->d_lanes, n_active, group->pools[0],
-                      INTRABATCH_CON * hop_num + 1, dev_id, true, -1);
+                      batch_whole_gather(hop_num).op_id, dev_id, true, -1);
 }
 
 // ---- gather-op timing (HIP events recorded on the op's stream around the gather launch) -------

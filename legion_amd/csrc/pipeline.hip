@@ -15,7 +15,7 @@
 //   * `slots` groups are in flight (default 2): while the consumer reads slot s, slot s+1 runs;
 //   * weave (use_graph bit 4, what bench.py and the Runner use): a group is cut where its character changes -- the
 //     HEAD (seeds + every hop but the last) of group k+1 runs on a low-priority stream under the heavy kernels of group k
-//     (see submit).  The plain two-stream split (every sampler on one stream, every gather on another, with CU masks and
+//     (see phases_of).  The plain two-stream split (every sampler on one stream, every gather on another, with CU masks and
 //     priorities) was measured against it in rounds 2-4 and removed in round 5: DESIGN_HISTORY.md 4.5.
 #include "legion_core.h"
 
@@ -97,7 +97,7 @@ struct LegionPipeline {
     std::vector<Slot> slots;
     bool use_graph;
     bool overlap = false;   // let kernels of different slots run concurrently (default: chained)
-    bool weave = false;     // head of group k+1 on a second stream under the heavy kernels of group k (see submit)
+    bool weave = false;     // head of group k+1 on a second stream under the heavy kernels of group k (see phases_of)
     bool gathers = true;        // weave: false = the REST phase stops before the gathers (legion_pipeline_set_gathers)
     bool sample_only = false;   // only the sampler phase runs here; the owner gathers each lane itself (GPURunner: straight
                                 // into a trainer-visible pipe slot)
@@ -316,6 +316,42 @@ static int32_t checked_batch_size(const LegionPipeline* p, int32_t batch_size)
     return batch_size;
 }
 
+// Which phases (batch_ops.h) a group runs on a slot, in order, and on which stream.
+// Weave: the group is cut where its character changes.  HEAD (seeds + every hop but the last: a dozen small,
+// latency-bound kernels that cannot fill the chip) runs on the light stream Y; REST (the last hop -- scattered
+// atomics at ~2 TB/s of sector traffic -- and every gather) runs on the heavy stream X:
+//     X:  rest(k)                | rest(k+1)                 | ...
+//     Y:      head(k+1)          |      head(k+2)            |
+// The head of the next group hides under the current group's heavy kernels, which lose nothing measurable to it
+// (the dominant gather keeps 0.78 of the HBM peak); the two heavy kinds of traffic never share the machine, which
+// is what costs the plain two-stream split (sampler || gathers) a quarter of the gather's bandwidth.
+// Measured (RMAT-26, B = 1024, 256 lanes): 4.25-4.31 G edges/s against 4.06-4.15 G on one stream.  Running the
+// last hop's compaction kernels on Y beside the early gathers as well was measured too: no gain, gather at 0.75.
+struct SlotPhases {
+    int32_t n;
+    struct { hipStream_t stream; int32_t phase; } at[2];
+};
+static SlotPhases phases_of(const LegionPipeline* p, const Slot& sl)
+{
+    if (p->weave) return {2, {{p->sample_stream, LG_PHASE_HEAD}, {sl.stream, p->gathers ? LG_PHASE_REST : LG_PHASE_REST_SAMPLE}}};
+    return {1, {{sl.stream, p->sample_only ? LG_PHASE_SAMPLE : LG_PHASE_ALL}}};
+}
+
+// The next slot (round robin), idle -- this waits for its previous group, which must have been consumed -- with lane g set to
+// batch counter0 + g of `mode`
+static int32_t acquire_slot(LegionPipeline* p, int32_t counter0, int32_t mode)
+{
+    const int32_t si = p->rr;
+    p->rr = (p->rr + 1) % p->slots_n;
+    Slot& sl = p->slots[si];
+    slot_wait(p, sl);
+    for (int32_t g = 0; g < p->group_size; g++) {
+        sl.pools[g]->SetCurrentMode(mode);
+        sl.pools[g]->SetIter(counter0 + g);
+    }
+    return si;
+}
+
 // Captures and instantiates, on EVERY slot, the graph(s) a later submit of (mode, n_active, batch_size) will replay, without
 // launching anything.  A server calls this for every group shape of its schedule before it starts serving: stream capture
 // and graph instantiation then never run beside another thread's HIP calls (GPURunner's poster polls events; a capture
@@ -326,16 +362,11 @@ extern "C" void legion_pipeline_prepare(LegionPipeline* p, int32_t mode, int32_t
     if (n_active < 1 || n_active > p->group_size) n_active = p->group_size;
     batch_size = checked_batch_size(p, batch_size);
     SetGPUDevice(p->dev_id);
-    const int32_t first_phase = p->sample_only ? LG_PHASE_SAMPLE : LG_PHASE_ALL;
     for (Slot& sl : p->slots) {
         slot_wait(p, sl);
         legion_group_set_iter_state(sl.group, sl.d_iter);
-        if (p->weave) {
-            (void)graph_of(p, sl, p->sample_stream, LG_PHASE_HEAD, mode, n_active, batch_size);
-            (void)graph_of(p, sl, sl.stream, p->gathers ? LG_PHASE_REST : LG_PHASE_REST_SAMPLE, mode, n_active, batch_size);
-            continue;
-        }
-        (void)graph_of(p, sl, sl.stream, first_phase, mode, n_active, batch_size);
+        const SlotPhases ph = phases_of(p, sl);
+        for (int32_t i = 0; i < ph.n; i++) (void)graph_of(p, sl, ph.at[i].stream, ph.at[i].phase, mode, n_active, batch_size);
     }
 }
 
@@ -368,15 +399,9 @@ extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0
     if (n_active < 1 || n_active > p->group_size) n_active = p->group_size;
     batch_size = checked_batch_size(p, batch_size);
     SetGPUDevice(p->dev_id);
-    const int32_t si = p->rr;
-    p->rr = (p->rr + 1) % p->slots_n;
+    lg::Range mark("group slot=%d first=%d lanes=%d mode=%d B=%d", p->rr, counter0, n_active, mode, batch_size);
+    const int32_t si = acquire_slot(p, counter0, mode);
     Slot& sl = p->slots[si];
-    lg::Range mark("group slot=%d first=%d lanes=%d mode=%d B=%d", si, counter0, n_active, mode, batch_size);
-    slot_wait(p, sl);
-    for (int32_t g = 0; g < p->group_size; g++) {
-        sl.pools[g]->SetCurrentMode(mode);
-        sl.pools[g]->SetIter(counter0 + g);
-    }
     sl.pools[0]->prof_used = 0;
     // Chain the slots: this group starts on the GPU when the previously submitted one has finished.
     // The launch (and its host latency) still happens while that group runs, but kernels of different
@@ -384,67 +409,30 @@ extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0
     // and a gather that runs alone streams at ~73% of HBM peak instead of ~52%.
     // (chained slots share one stream, so the order is the stream's own)
     p->last_slot = si;
-    LegionGraphStorage* gr = reinterpret_cast<LegionGraphStorage*>(p->graph);
-    LegionFeatureStorage* f = reinterpret_cast<LegionFeatureStorage*>(p->feature);
-    if (p->weave) {
-        // Weave: the group is cut where its character changes.  HEAD (seeds + every hop but the last: a dozen small,
-        // latency-bound kernels that cannot fill the chip) runs on the light stream Y; REST (the last hop -- scattered
-        // atomics at ~2 TB/s of sector traffic -- and every gather) runs on the heavy stream X:
-        //     X:  rest(k)                | rest(k+1)                 | ...
-        //     Y:      head(k+1)          |      head(k+2)            |
-        // The head of the next group hides under the current group's heavy kernels, which lose nothing measurable to it
-        // (the dominant gather keeps 0.78 of the HBM peak); the two heavy kinds of traffic never share the machine, which
-        // is what costs the plain two-stream split (sampler || gathers) a quarter of the gather's bandwidth.
-        // Measured (RMAT-26, B = 1024, 256 lanes): 4.25-4.31 G edges/s against 4.06-4.15 G on one stream.  Running the
-        // last hop's compaction kernels on Y beside the early gathers as well was measured too: no gain, gather at 0.75.
-        hipStream_t X = sl.stream, Y = p->sample_stream;
-        const bool eager = !p->use_graph || p->profiling;
-        legion_group_set_iter_state(sl.group, eager ? nullptr : sl.d_iter);
-        if (!eager && sl.next_iter != counter0) {
-            sl.h_iter[0] = counter0;
-            sl.h_iter[1] = p->group_size * p->slots_n;
-            HIP_CALL(hipMemcpyAsync(sl.d_iter, sl.h_iter, 2 * sizeof(int32_t), hipMemcpyHostToDevice, Y));
-        }
-        auto run = [&](hipStream_t strm, int32_t phase) {
-            if (eager)
-                legion_enqueue_group_phase(strm, gr, f, p->cache_handle, sl.group, n_active, batch_size, counter0, p->dev_id, mode,
-                                           p->fanout.data(), p->hop_num, phase);
-            else
-                HIP_CALL(hipGraphLaunch(graph_of(p, sl, strm, phase, mode, n_active, batch_size), strm));
-        };
-        run(Y, LG_PHASE_HEAD);
-        HIP_CALL(hipEventRecord(sl.sampled, Y));
-        HIP_CALL(hipStreamWaitEvent(X, sl.sampled, 0));
-        run(X, p->gathers ? LG_PHASE_REST : LG_PHASE_REST_SAMPLE);
-        if (eager) {
-            sl.next_iter = -1;
-            sl.prof_pairs = sl.pools[0]->prof_used;
-        } else {
-            sl.next_iter = n_active == p->group_size ? counter0 + p->group_size * p->slots_n : -1;
-        }
-        HIP_CALL(hipEventRecord(sl.done, X));
-        sl.busy = true;
-        return si;
+    const SlotPhases ph = phases_of(p, sl);
+    const bool eager = !p->use_graph || p->profiling;            // HIP cannot time events recorded by graph nodes
+    legion_group_set_iter_state(sl.group, eager ? nullptr : sl.d_iter);      // eager: iteration by value
+    if (!eager && sl.next_iter != counter0) {                    // (re)position the device-resident iteration
+        sl.h_iter[0] = counter0;
+        sl.h_iter[1] = p->group_size * p->slots_n;
+        HIP_CALL(hipMemcpyAsync(sl.d_iter, sl.h_iter, 2 * sizeof(int32_t), hipMemcpyHostToDevice, ph.at[0].stream));
     }
-    hipStream_t s1 = sl.stream;
-    const int32_t first_phase = p->sample_only ? LG_PHASE_SAMPLE : LG_PHASE_ALL;
-    if (!p->use_graph || p->profiling) {            // HIP cannot time events recorded by graph nodes
-        legion_group_set_iter_state(sl.group, nullptr);     // eager: iteration by value
-        legion_enqueue_group_phase(s1, gr, f, p->cache_handle, sl.group, n_active, batch_size, counter0,
-                                   p->dev_id, mode, p->fanout.data(), p->hop_num, first_phase);
-        sl.next_iter = -1;
-        sl.prof_pairs = sl.pools[0]->prof_used;
-    } else {
-        legion_group_set_iter_state(sl.group, sl.d_iter);
-        if (sl.next_iter != counter0) {                     // (re)position the device-resident iteration
-            sl.h_iter[0] = counter0;
-            sl.h_iter[1] = p->group_size * p->slots_n;
-            HIP_CALL(hipMemcpyAsync(sl.d_iter, sl.h_iter, 2 * sizeof(int32_t), hipMemcpyHostToDevice, s1));
+    for (int32_t i = 0; i < ph.n; i++) {
+        const hipStream_t strm = ph.at[i].stream;
+        if (i > 0 && strm != ph.at[i - 1].stream) {              // another stream: it starts behind the phase before
+            HIP_CALL(hipEventRecord(sl.sampled, ph.at[i - 1].stream));
+            HIP_CALL(hipStreamWaitEvent(strm, sl.sampled, 0));
         }
-        HIP_CALL(hipGraphLaunch(graph_of(p, sl, s1, first_phase, mode, n_active, batch_size), s1));
-        // what the last kernel leaves in d_iter[0] (a partial group breaks the regular stride)
-        sl.next_iter = n_active == p->group_size ? counter0 + p->group_size * p->slots_n : -1;
+        if (eager)
+            legion_enqueue_group_phase(strm, reinterpret_cast<LegionGraphStorage*>(p->graph), reinterpret_cast<LegionFeatureStorage*>(p->feature),
+                                       p->cache_handle, sl.group, n_active, batch_size, counter0, p->dev_id, mode, p->fanout.data(),
+                                       p->hop_num, ph.at[i].phase);
+        else
+            HIP_CALL(hipGraphLaunch(graph_of(p, sl, strm, ph.at[i].phase, mode, n_active, batch_size), strm));
     }
+    // what the last kernel of a replay leaves in d_iter[0] (a partial group breaks the regular stride; eager launches leave it alone)
+    sl.next_iter = (!eager && n_active == p->group_size) ? counter0 + p->group_size * p->slots_n : -1;
+    if (eager) sl.prof_pairs = sl.pools[0]->prof_used;
     HIP_CALL(hipEventRecord(sl.done, sl.stream));
     sl.busy = true;
     return si;
@@ -745,15 +733,9 @@ extern "C" int32_t legion_pipeline_bulk_phase_a(LegionPipeline* p, int32_t count
     if (n_active < 1 || n_active > p->group_size) n_active = p->group_size;
     batch_size = checked_batch_size(p, batch_size);
     SetGPUDevice(p->dev_id);
-    const int32_t si = p->rr;
-    p->rr = (p->rr + 1) % p->slots_n;
+    lg::Range mark("bulk group A slot=%d first=%d lanes=%d", p->rr, counter0, n_active);
+    const int32_t si = acquire_slot(p, counter0, mode);      // (the gathers' timing is submit_ex's: prof_used stays)
     Slot& sl = p->slots[si];
-    lg::Range mark("bulk group A slot=%d first=%d lanes=%d", si, counter0, n_active);
-    slot_wait(p, sl);
-    for (int32_t g = 0; g < p->group_size; g++) {
-        sl.pools[g]->SetCurrentMode(mode);
-        sl.pools[g]->SetIter(counter0 + g);
-    }
     hipStream_t X = sl.stream;
     LegionGraphStorage* gr = reinterpret_cast<LegionGraphStorage*>(p->graph);
     LegionFeatureStorage* f = reinterpret_cast<LegionFeatureStorage*>(p->feature);
@@ -765,15 +747,19 @@ extern "C" int32_t legion_pipeline_bulk_phase_a(LegionPipeline* p, int32_t count
     HIP_CALL(hipMemsetAsync(mine.cnt, 0, 256, X));
     const LanePtrs* d_lanes = static_cast<const LanePtrs*>(legion_group_lane_desc(sl.group, 0));
     const int32_t max_rows = (int32_t)std::min<int64_t>(p->feature_rows, sl.pools[0]->num_ids);
-    const int32_t last_op = INTRABATCH_CON * p->hop_num + 1;
-    cache->BulkBucket(d_lanes, n_active, last_op, p->dev_id, X, max_rows, mine, p->arena.base);
-    // the gathers in the op order of a whole-batch enqueue (operators.hip enqueue_lanes: the seeds ride along with hop 1 when a
-    // later gather follows), each skipping the rows of other members' stripes
-    const bool seeds_ride = p->hop_num >= 2;
-    if (!seeds_ride) cache->FeatCacheLookup(d_lanes, n_active, 1, p->dev_id, X, max_rows, true, -1, p->hop_num == 0, true, 0, p->feature_out_dtype);
-    for (int32_t h = 0; h < p->hop_num; h++)
-        cache->FeatCacheLookup(d_lanes, n_active, INTRABATCH_CON * (h + 1) + 1, p->dev_id, X, max_rows, true, (h == 0 && seeds_ride) ? 1 : -1,
-                               h + 1 == p->hop_num, /*skip_remote=*/true, 0, p->feature_out_dtype);
+    cache->BulkBucket(d_lanes, n_active, batch_whole_gather(p->hop_num), p->dev_id, X, max_rows, mine, p->arena.base);
+    // the gathers of a whole-batch enqueue, in its order (batch_ops.h), each skipping the rows of other members' stripes
+    const BatchOpList ops = batch_op_list(p->hop_num, LG_PHASE_GATHER, false, false);
+    for (int32_t i = 0; i < ops.n; i++) {
+        UnifiedCache::GatherCall call;
+        call.op_id = ops.op[i].op_id;
+        call.first_op_id = ops.op[i].first_op_id;
+        call.last_op = ops.op[i].hop + 1 == p->hop_num;
+        call.skip_remote = true;
+        call.max_rows = max_rows;
+        call.out_dtype = p->feature_out_dtype;
+        cache->FeatCacheLookup(d_lanes, n_active, p->dev_id, X, call);
+    }
     HIP_CALL(hipStreamSynchronize(X));
     sl.next_iter = -1;
     p->last_slot = si;

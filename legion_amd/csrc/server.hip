@@ -650,8 +650,7 @@ public:
             if (float_feature_len_ > 0 && batch_rows > lane_feature_rows_ && overflow_[p] != nullptr) {
                 UnifiedCache* cache = (UnifiedCache*)(params->cache);
                 const LanePtrs* desc = d_overflow_desc_ + ((size_t)p * slots_ + g.slot) * lanes_ + lane;
-                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, overflow_stream_, memorypool_->num_ids, true, 1,
-                                       true, false, 0, memorypool_->feature_out_dtype);
+                cache->FeatCacheLookup(desc, 1, local_dev_id_, overflow_stream_, WholeBatchGather(memorypool_->num_ids, 0));
                 HIP_CALL(hipStreamSynchronize(overflow_stream_));
                 off[1] = (char*)overflow_[p] - arena_.base;
                 if (lp->err_host != nullptr) *(volatile int32_t*)lp->err_host &= ~LG_ERR_FEATURE_ROWS;      // this batch is whole again; the lane's next batch starts clean
@@ -671,8 +670,7 @@ public:
             const LanePtrs* desc = d_desc_ + ((size_t)p * slots_ + g.slot) * lanes_ + lane;     // lane -> pipe slot p
             UnifiedCache* cache = (UnifiedCache*)(params->cache);
             if (float_feature_len_ > 0 && max_rows > 0)   // one launch: gather of every row of the batch + the hand-over copies
-                cache->FeatCacheLookup(desc, 1, INTRABATCH_CON * hop_num_ + 1, local_dev_id_, s, (int32_t)max_rows, true, 1, true, false, lane_rule_rows_,
-                                       memorypool_->feature_out_dtype);
+                cache->FeatCacheLookup(desc, 1, local_dev_id_, s, WholeBatchGather((int32_t)max_rows, lane_rule_rows_));
             else
                 lg::launch_deliver(s, desc, deliver_[p]);
             HIP_CALL(hipEventRecord(batch_done_[p], s));
@@ -1030,6 +1028,19 @@ private:
     void SubmitWhatFits(IPCEnv* env, int32_t k)
     {
         while (sched_.next_first < max_step_ && sched_.may_submit(k)) SubmitNext(env);
+    }
+
+    // a hand-over gathers every row of its batch in one launch (batch_ops.h), into max_rows rows of a pipe slot
+    UnifiedCache::GatherCall WholeBatchGather(int32_t max_rows, int32_t grid_rows) const
+    {
+        const BatchOp whole = batch_whole_gather(hop_num_);
+        UnifiedCache::GatherCall call;
+        call.op_id = whole.op_id;
+        call.first_op_id = whole.first_op_id;
+        call.max_rows = max_rows;
+        call.grid_rows = grid_rows;
+        call.out_dtype = memorypool_->feature_out_dtype;
+        return call;
     }
 
     int32_t num_ids_ = 0;

@@ -731,3 +731,36 @@ def test_owner_bucketed_bulk_transfer_matches_direct_peer_loads(hip, monkeypatch
     for pl in pipes:
         pl.close()
     gpu.close(); cpu.close()
+
+
+@pytest.mark.parametrize("use_graph,weave,fanout", [(False, False, [3]), (True, False, [3]), (False, True, [3]), (True, True, [3]),
+                                                    (False, False, [3, 2]), (False, True, [3, 2]), (True, True, [3, 2])],
+                         ids=["eager-1hop", "replay-1hop", "weave-eager-1hop", "weave-replay-1hop",
+                              "eager-2hops", "weave-eager-2hops", "weave-replay-2hops"])
+def test_every_submit_arrangement_at_one_and_two_hops_with_a_partial_last_group(hip, use_graph, weave, fanout):
+    """The four ways a pipeline submits a group (eager or hipGraph replay, one stream or the weave's two) on both sides of the rule
+    that lets the seeds' rows ride along with hop 1's gather (two hops and more; with one hop the seeds' gather is a launch of its
+    own): 7 batches in groups of 3 on 2 slots, so the last group runs with one active lane, two epochs (the second re-positions the
+    device-resident iteration).  Every batch against the oracle.  test_pipeline_groups_and_graph_replay runs the four arrangements
+    at two hops with whole groups only and test_pipeline_partial_group the plain replay with partial ones (the pair left out
+    here); nothing ran a pipeline at one hop."""
+    from legion_amd import engine
+    wl = Workload(scale=9, edge_factor=8, dim=8, n_seeds=100)
+    batch, group, slots, n_batches = 8, 3, 2, 7
+    gpu, cpu = GpuSide(wl, batch, fanout), CpuSide(wl, batch, fanout)
+    want = [cpu.run(0, k, 0) for k in range(n_batches)]
+    pipe = engine.Pipeline(gpu.graph, gpu.feature, gpu.cache, 0, batch, fanout, group, gpu.pools[0].num_ids, use_graph, slots, weave=weave)
+    for rep in range(2):
+        pending = []
+        for first in range(0, n_batches, group):
+            n_active = min(group, n_batches - first)
+            pending.append((first, n_active, pipe.submit(first, 0, n_active)))
+            if len(pending) == slots or first + n_active == n_batches:
+                for f, n, sl in pending:
+                    pipe.wait(sl)
+                    for lane in range(n):
+                        compare_batches(engine.read_batch(pipe.pools[sl][lane]), want[f + lane], f"rep {rep} batch {f + lane}: ")
+                        assert pipe.pools[sl][lane].error() == 0
+                pending = []
+    pipe.close()
+    gpu.close(); cpu.close()

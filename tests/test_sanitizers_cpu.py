@@ -53,6 +53,12 @@ def test_runner_schedule_simulation_under_asan_ubsan(san):
     assert res.returncode == 0 and "VIOLATION" not in res.stdout, res.stdout[-3000:]
 
 
+def test_batch_op_lists_under_asan_ubsan(san):
+    """batch_ops.h fills fixed-size lists: its literal table once more, with every write checked."""
+    res = subprocess.run([os.path.join(san, "batch_ops_test")], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert res.returncode == 0 and " 0 failed" in res.stdout and "runtime error" not in res.stdout, res.stdout[-3000:]
+
+
 # ---- the wire protocol's server end, played in Python for tools/boundary_consumer.c ------------------------------------------------
 MAX_DEVICE, INTERBATCH_CON, MEMORY_USAGE = 8, 2, 7
 SHM_BYTES = 12 + MAX_DEVICE * INTERBATCH_CON * MEMORY_USAGE * 64                       # simpleIPCshm (SS/engine/ipc_service.cu:28-31)
