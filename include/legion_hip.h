@@ -122,6 +122,11 @@ void legion_graph_cached_csr(const LegionGraphStorage* g, int32_t dev, const int
  * weighted hop has been enqueued against this graph.  legion_graph_edge_cdf: the table, or null before that call (introspection). */
 int32_t legion_graph_set_edge_weights(LegionGraphStorage* g, legion_stream_t stream, const float* w_devptr);
 const float* legion_graph_edge_cdf(const LegionGraphStorage* g);
+/* Are the rows of the full CSR sorted: col[e - 1] <= col[e], as int32, for every two adjacent entries of one row?  (Dead entries, -1,
+ * then come first in their row; parallel edges are fine.)  One pass over the full CSR on the device current at the call, enqueued on
+ * `stream`; the result is read back -- set-up: the call synchronises that stream -- and remembered in the graph, so a repeat call
+ * returns it without work.  1: sorted, 0: not, -1: a null graph.  legion_node2vec_walk asks for a remembered 1. */
+int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g, legion_stream_t stream);
 
 /* FeatureStorage: SS/storage/feature_storage.cu:18-90.  ids/labels are HOST arrays copied to
  * device `dev_id`; mode selects the training / validation / testing set. */
@@ -480,10 +485,45 @@ void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, cons
  * base < 0; base + num_walks * length > 2^31 - 1 (the draw index, the restart offset included, stays where the power tables reach);
  * weighted outside {0, 1}; weighted == 1 on a graph without a table; restart_prob NaN or outside [0, 1].  num_walks == 0 returns 0
  * and enqueues nothing.  A weighted walk counts as a weighted hop for legion_graph_set_edge_weights: the table cannot be replaced
- * afterwards.  Not offered: metapaths, node2vec's p / q bias; the server, the launcher and the wire. */
+ * afterwards.  node2vec's p / q bias is legion_node2vec_walk, below.  Not offered: metapaths; the server, the launcher and the wire. */
 int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
                            int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
                            int64_t* edge_ids_out /* may be NULL */);
+/* node2vec walks over the graph (DGL's dgl.sampling.node2vec_random_walk), new in this build; no reference counterpart.  A second-order
+ * walk: the step from v depends on the vertex t the walk came from, by rejection sampling -- candidates are drawn as legion_random_walk
+ * draws its step and accepted with probability wt / Mx, wt = 1/p for a return to t, 1 for a neighbour of t, 1/q for any other vertex.
+ * Buffers, stream, capture and what is read (the FULL CSR, edge_cdf when weighted) as in legion_random_walk.  "u is a neighbour of t" is
+ * a binary search of t's row, so the graph's rows must have been checked sorted (legion_graph_check_rows_sorted == 1).
+ * Walk w:  traces[w][0] = seeds[w], copied as given.  Step j = 1 .. length has v = traces[w][j - 1], t = traces[w][j - 2] (none at j = 1),
+ * draw index n = base + w * length + (j - 1), minstd(k) = 48271^k mod (2^31 - 1), and a = 1.0 / (double)p, b = 1.0 / (double)q,
+ * Mx = max(a, 1.0, b) (IEEE double, computed once on the host).  Then, in this order:
+ *   1. ended walk: v < 0 or v >= node_num (a bad seed too): traces[w][j] = -1, and so is every later entry -- no memory is read for v;
+ *   2. row: s = indptr[v], D = indptr[v + 1] - s; D == 0: the walk ends.  Weighted: T = edge_cdf[s + D - 1]; T == 0: the walk ends;
+ *   3. tries i = 0, 1, .. max_tries - 1:
+ *        candidate draw: x = minstd((uint32)(n + 1) + i * 2^23), r = (double)(x - 1) / 2147483646.0;
+ *        pick: unweighted pick = (int)(r * D); weighted t' = r * (double)T and pick = min(#{ e in [0, D) : (double)edge_cdf[s + e] <= t' }, D - 1),
+ *          the upper-bound search of legion_random_walk;
+ *        candidate: u = col[s + pick]; u < 0 (a dead column entry): the walk ends at once;
+ *        unconditional accept: at j == 1, or at i == max_tries - 1 (the last try), u is accepted without an accept draw;
+ *        class: else wt = a if u == t; else 1.0 if u occurs in col[indptr[t] .. indptr[t + 1]); else b -- the paper's d(t, u) = 0 / 1 / 2; on
+ *          the symmetric graphs node2vec is used on it equals DGL's test;
+ *        accept draw: y = minstd((uint32)(n + 1) + i * 2^23 + 2^22), ry = (double)(y - 1) / 2147483646.0;
+ *        accept test: u is accepted iff ry * Mx < wt, in double (wt == Mx always accepts: ry < 1);
+ *   4. on acceptance traces[w][j] = u and edge_ids[w][j - 1] = s + pick; wherever traces[w][j] == -1, edge_ids[w][j - 1] == -1.
+ * With p == q == 1 (every wt == Mx), or with max_tries == 1 (the first try is the last), the walk is legion_random_walk's with
+ * restart_prob = 0, bit for bit.  Within a step the 2 * 256 draw indices are distinct (255 * 2^23 + 2^22 < 2^31 - 2, the order of 48271);
+ * they coincide only with draws of steps whose index differs by a multiple of 2^22, walks four million steps away: accepted.  The forced
+ * acceptance at the last try has probability at most (15/16)^255, about 7e-8, per step at the default max_tries and the worst legal bias.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, seeds_devptr or traces_out; num_walks < 0; length < 1;
+ * base < 0; base + num_walks * length > 2^31 - 1; weighted outside {0, 1}; weighted == 1 on a graph without a table; max_tries outside
+ * [1, LEGION_NODE2VEC_MAX_TRIES]; p or q NaN, infinite or <= 0; min(a, 1, b) * LEGION_NODE2VEC_MAX_BIAS < max(a, 1, b); a graph whose rows
+ * legion_graph_check_rows_sorted has not checked, or has found unsorted.  num_walks == 0 returns 0 and enqueues nothing.  A weighted call
+ * counts as a weighted hop for legion_graph_set_edge_weights.  Not offered: the server, the launcher and the wire. */
+#define LEGION_NODE2VEC_MAX_TRIES 256
+#define LEGION_NODE2VEC_MAX_BIAS  16
+int32_t legion_node2vec_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
+                             int32_t length, float p, float q, int32_t weighted, int32_t max_tries, int64_t base,
+                             int32_t* traces_out /* int32[n x (length + 1)] */, int64_t* edge_ids_out /* int64[n x length], or NULL */);
 /* PinSAGE's neighbour sampler (DGL's dgl.sampling.RandomWalkNeighborSampler / PinSAGESampler on a homogeneous graph), new in this build;
  * no reference counterpart.  For each of num_seeds seeds: num_walks_per_seed (R) walks of walk_length (T) steps, the visited vertices
  * counted, and the num_neighbors (k) most visited returned with their counts.  neighbors_out and counts_out are int32[num_seeds x k],

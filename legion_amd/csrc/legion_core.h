@@ -367,6 +367,11 @@ public:
     virtual int32_t SetEdgeWeights(hipStream_t s, const float* w) = 0;
     virtual const float* EdgeCdf() const = 0;                         // null before SetEdgeWeights
     virtual void MarkWeightedUsed() = 0;
+    // Sorted rows (new): are the column entries of every row of the full CSR non-decreasing as int32?  CheckRowsSorted counts on the
+    // device current at the call (kernels_node2vec.hip), reads the answer back through `s` (set-up: it synchronises s) and remembers
+    // it; RowsSorted: 1 / 0, or -1 before any check.  node2vec's membership test is a binary search of a row (legion_node2vec_walk).
+    virtual int32_t CheckRowsSorted(hipStream_t s) = 0;
+    virtual int32_t RowsSorted() const = 0;
     // "Column slots" (new): a copy of the full column array in which every entry is the pair {neighbour id, feature-cache
     // slot of that neighbour = node_map[id]} (8 bytes).  The sampler's scattered 4-byte pick costs a whole 64-byte sector
     // either way; read as 8 bytes it brings the neighbour's cache slot along for free, and the gather no longer fetches a
@@ -878,6 +883,19 @@ struct WalkParams {
     int64_t base;                   // draw index of walk 0's first step
 };
 void launch_random_walk(hipStream_t s, const WalkParams& p);
+
+// node2vec walks over the full CSR (kernels_node2vec.hip; the rule: legion_node2vec_walk in legion_hip.h)
+struct Node2vecParams {
+    WalkParams walk;                // as for launch_random_walk; restart_prob unused
+    double a, b, mx;                // 1 / p, 1 / q and max(1 / p, 1, 1 / q) (node2vec_rule.h)
+    double lo, hi;                  // min(1, 1 / q), max(1, 1 / q): the weights of a candidate u != t, whichever class the search finds
+    int32_t max_tries;
+};
+void launch_node2vec_walk(hipStream_t s, const Node2vecParams& p);
+// counts[0] += #{ e in [1, E) : col[e - 1] > col[e] }, counts[1] += the same inversions at e = indptr[v] of rows v with entries and
+// e > 0: the rows are sorted iff the two agree (every inversion lies across a row boundary)
+void launch_row_inversion_counts(hipStream_t s, const int64_t* indptr, const int32_t* col, int32_t n_rows, int64_t num_edges,
+                                 unsigned long long* counts);
 
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {

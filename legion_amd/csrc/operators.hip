@@ -15,6 +15,7 @@
 //   * there is no accessed bitmap and no position map: first touches keep no per-vertex state (see
 //     legion_core.h), so BatchGenerate has nothing to memset and IOComplete nothing to restore.
 #include "legion_core.h"
+#include "node2vec_rule.h"
 
 #include <iostream>
 
@@ -407,6 +408,42 @@ extern "C" int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage
     p.restart_prob = restart_prob;
     p.base = base;
     lg::launch_random_walk(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// node2vec walks (the rule: legion_hip.h; the refusals and the bias in double: node2vec_rule.h).  As above: every check comes before
+// the launch.  p == q == 1 runs the node2vec kernel too: it is that kernel's pin against random_walk_kernel.
+extern "C" int32_t legion_node2vec_walk(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_walks,
+                                        int32_t length, float p, float q, int32_t weighted, int32_t max_tries, int64_t base,
+                                        int32_t* traces_out, int64_t* edge_ids_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !seeds_devptr || !traces_out) return -1;
+    if (node2vec_refusal(num_walks, length, base, weighted, graph->EdgeCdf() != nullptr, max_tries, p, q, graph->RowsSorted()) !=
+        Node2vecRefusal::Ok)
+        return -1;
+    if (num_walks == 0) return 0;
+    if (weighted == 1) graph->MarkWeightedUsed();
+    const Node2vecBias bias = node2vec_bias(p, q);
+    lg::Node2vecParams k;
+    k.walk.indptr = graph->GetCSRNodeIndexCPU();
+    k.walk.col = graph->GetCSRNodeMatrixCPU();
+    k.walk.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
+    k.walk.seeds = seeds_devptr;
+    k.walk.traces = traces_out;
+    k.walk.edge_ids = edge_ids_out;
+    k.walk.node_num = graph->NodeNum();
+    k.walk.num_walks = num_walks;
+    k.walk.length = length;
+    k.walk.restart_prob = 0.0f;
+    k.walk.base = base;
+    k.a = bias.a;
+    k.b = bias.b;
+    k.mx = bias.mx;
+    k.lo = bias.lo;
+    k.hi = bias.hi;
+    k.max_tries = max_tries;
+    lg::launch_node2vec_walk(static_cast<hipStream_t>(stream), k);
     return 0;
 }
 

@@ -690,6 +690,24 @@ public:
     const float* EdgeCdf() const override { return edge_cdf_; }
     void MarkWeightedUsed() override { weighted_used_ = true; }
 
+    // sorted rows (legion_core.h): two counts on the current device, read back once and remembered
+    int32_t CheckRowsSorted(hipStream_t s) override
+    {
+        if (rows_sorted_ >= 0) return rows_sorted_;
+        unsigned long long h[2] = {0, 0};
+        if (edge_num_ > 1) {
+            unsigned long long* d = (unsigned long long*)d_alloc_space(2 * sizeof(unsigned long long));
+            HIP_CALL(hipMemsetAsync(d, 0, 2 * sizeof(unsigned long long), s));
+            lg::launch_row_inversion_counts(s, csr_node_index_cpu_, csr_dst_node_ids_cpu_, node_num_, edge_num_, d);
+            HIP_CALL(hipMemcpyAsync(h, d, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+            HIP_CALL(hipStreamSynchronize(s));
+            d_free_space(d);
+        }
+        rows_sorted_ = h[0] == h[1] ? 1 : 0;
+        return rows_sorted_;
+    }
+    int32_t RowsSorted() const override { return rows_sorted_; }
+
     void Finalize() override
     {
         if (edge_cdf_ != nullptr) {
@@ -753,6 +771,7 @@ private:
     int32_t* cdf_long_rows_ = nullptr;   // scratch of its build: {count, rows longer than a wave scans}
     int32_t cdf_long_cap_ = 0;
     int edge_cdf_dev_ = 0;
+    int32_t rows_sorted_ = -1;           // CheckRowsSorted's answer, -1 before the first check
     bool weighted_used_ = false;         // a weighted hop has been enqueued against this graph: the table stays as it is
 };
 
@@ -1125,6 +1144,13 @@ extern "C" const float* legion_graph_edge_cdf(const LegionGraphStorage* g_)
 {
     const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
     return g ? g->EdgeCdf() : nullptr;
+}
+
+// are the full CSR's rows sorted?  counted on `stream` once (it synchronises that stream), remembered in the graph
+extern "C" int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g_, legion_stream_t stream)
+{
+    GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
+    return g ? g->CheckRowsSorted(static_cast<hipStream_t>(stream)) : -1;
 }
 
 extern "C" void legion_graph_destroy(LegionGraphStorage* g_)

@@ -257,6 +257,78 @@ class GraphStorage:
                     x.record_stream(stream)
         return (traces, eids) if return_eids else traces
 
+    NODE2VEC_MAX_TRIES = 256                         # LEGION_NODE2VEC_MAX_TRIES
+    NODE2VEC_MAX_BIAS = 16                           # LEGION_NODE2VEC_MAX_BIAS
+
+    def rows_sorted(self, stream=None):
+        """Are the column entries of every row non-decreasing (as int32: dead entries, -1, first; parallel edges are fine)?  Counted
+        on the device at the first call (legion_graph_check_rows_sorted: it synchronises `stream`, default the current one) and
+        remembered: node2vec_random_walk searches rows and needs True."""
+        if getattr(self, "_rows_sorted", None) is None:
+            with torch.cuda.device(self.col.device):
+                rc = self._lib.legion_graph_check_rows_sorted(self.handle, _stream_handle(stream))
+            if rc not in (0, 1):
+                raise RuntimeError("legion_graph_check_rows_sorted refused the graph")
+            self._rows_sorted = bool(rc)
+        return self._rows_sorted
+
+    @staticmethod
+    def _check_node2vec(n, p, q, length, weighted, return_eids, max_tries, base):
+        """node2vec_random_walk's arguments by the rules of legion_node2vec_walk, before anything touches a device: ValueError with the
+        reason."""
+        GraphStorage._check_walk(n, length, weighted, 0.0, return_eids, base)
+        if isinstance(max_tries, bool) or not isinstance(max_tries, (int, np.integer)):
+            raise ValueError(f"max_tries must be an integer, not {max_tries!r}")
+        if not 1 <= max_tries <= GraphStorage.NODE2VEC_MAX_TRIES:
+            raise ValueError(f"max_tries must lie in [1, {GraphStorage.NODE2VEC_MAX_TRIES}], not {max_tries}")
+        for name, value in (("p", p), ("q", q)):
+            if isinstance(value, bool) or not isinstance(value, (int, float, np.floating, np.integer)):
+                raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+            with np.errstate(over="ignore"):
+                f = float(np.float32(value))             # (the library sees the float32)
+            if not (f > 0.0 and np.isfinite(f)):         # (NaN fails)
+                raise ValueError(f"{name} must be a finite number > 0, not {value!r}")
+        with np.errstate(over="ignore"):
+            a, b = 1.0 / float(np.float32(p)), 1.0 / float(np.float32(q))
+        if min(a, 1.0, b) * GraphStorage.NODE2VEC_MAX_BIAS < max(a, 1.0, b):
+            raise ValueError(f"the bias of p = {p!r}, q = {q!r} is too strong: the largest of 1/p, 1, 1/q may be at most "
+                             f"{GraphStorage.NODE2VEC_MAX_BIAS} times the smallest")
+
+    def node2vec_random_walk(self, seeds, p, q, length, *, weighted=False, return_eids=False, max_tries=256, base=0, stream=None):
+        """node2vec walks over the full CSR (DGL's dgl.sampling.node2vec_random_walk; the rule: legion_node2vec_walk in legion_hip.h).
+        From v, having come from t, a candidate neighbour u is drawn as random_walk draws its step and accepted with probability
+        proportional to 1/p if u == t, 1 if u is a neighbour of t, 1/q otherwise; the first step, and the max_tries-th candidate of a
+        step, are taken as drawn.  p = q = 1 is random_walk's walk bit for bit.  Needs sorted rows (rows_sorted(), asked here:
+        ValueError if not).  seeds, weighted, return_eids, base, stream and what is returned: as in random_walk."""
+        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
+            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
+        if not isinstance(seeds, torch.Tensor):
+            seeds = torch.as_tensor(seeds, dtype=torch.int32)
+        if seeds.dim() != 1:
+            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        n = int(seeds.numel())
+        self._check_node2vec(n, p, q, length, weighted, return_eids, max_tries, base)
+        if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
+            raise ValueError("a weighted walk needs the graph's edge weights (set_edge_weights)")
+        if not self.rows_sorted(stream):
+            raise ValueError("node2vec_random_walk needs a graph whose rows are sorted (rows_sorted() is False)")
+        dev = self.col.device
+        seeds = seeds.to(dev).contiguous()
+        traces = torch.empty((n, int(length) + 1), dtype=torch.int32, device=dev)
+        eids = torch.empty((n, int(length)), dtype=torch.int64, device=dev) if return_eids else None
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return (traces, eids) if return_eids else traces
+        with torch.cuda.device(dev):
+            rc = self._lib.legion_node2vec_walk(_stream_handle(stream), self.handle, _ptr(seeds), n, int(length), float(p), float(q),
+                                                int(weighted), int(max_tries), int(base), _ptr(traces), _ptr(eids))
+        if rc != 0:
+            raise RuntimeError("legion_node2vec_walk refused arguments that node2vec_random_walk had accepted")
+        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
+            for x in (seeds, traces, eids):
+                if x is not None:
+                    x.record_stream(stream)
+        return (traces, eids) if return_eids else traces
+
     PINSAGE_MAX_VISITS = 1024                        # LEGION_PINSAGE_MAX_VISITS
 
     @staticmethod

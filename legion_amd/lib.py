@@ -33,6 +33,7 @@ SIGNATURES = {
     "legion_graph_cached_csr": (None, [c_p, c_i32, ctypes.POINTER(c_p), ctypes.POINTER(c_p)]),
     "legion_graph_set_edge_weights": (c_i32, [c_p, c_p, c_p]),
     "legion_graph_edge_cdf": (c_p, [c_p]),
+    "legion_graph_check_rows_sorted": (c_i32, [c_p, c_p]),
     "legion_feature_create": (c_p, [c_i32, c_i32, c_i32, c_p]),
     "legion_feature_set_ids": (None, [c_p, c_i32, c_i32, c_p, c_p, c_i32]),
     "legion_feature_destroy": (None, [c_p]),
@@ -142,6 +143,7 @@ SIGNATURES = {
     "legion_draw_distinct_batch": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32]),
     "legion_draw_weighted_batch": (None, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
     "legion_random_walk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
+    "legion_node2vec_walk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_i64, c_p, c_p]),
     "legion_pinsage_neighbors": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
