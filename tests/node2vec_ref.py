@@ -166,19 +166,20 @@ ZERO_ROW = 10                                                      # every weigh
 EMPTY = (7, 40, 41, 1234, 3000, 5998)                              # rows without entries (nothing points at them either)
 
 
-def sym_graph():
+def sym_graph(node_num=NODE_NUM, hubs=HUBS, empty=EMPTY, chords=3000):
     """About 6 000 vertices, every edge in both directions so that all three classes are common: a ring lattice v +- 1 .. 3 over the
     vertices that have rows, 3 000 random chords, hub rows of 63-65, 255-257 and 4 097 entries, a few empty rows, parallel edges and
     self-loops; rows sorted; then the first entry of a few rows made dead (-1, still first).  Weights are walk_ref's multiples of 1/8
-    with leading, inner and trailing runs of zeros and one all-zero row."""
+    with leading, inner and trailing runs of zeros and one all-zero row.  node_num, hubs, empty and chords: the same graph at another
+    size (tests/far_rows.py); the defaults are the graph of the node2vec tests."""
     rng = np.random.RandomState(22)
-    ring = np.array([v for v in range(NODE_NUM) if v not in EMPTY], dtype=np.int64)
+    ring = np.array([v for v in range(node_num) if v not in empty], dtype=np.int64)
     src, dst = [], []
     for d in (1, 2, 3):
         src.append(ring)
         dst.append(np.roll(ring, -d))
-    plain = ring[ring > max(HUBS)]                                 # the hubs get their chords below, counted
-    c = rng.choice(plain, (3000, 2))
+    plain = ring[ring > max(hubs)]                                 # the hubs get their chords below, counted
+    c = rng.choice(plain, (chords, 2))
     c = c[c[:, 0] != c[:, 1]]
     src.append(c[:, 0])
     dst.append(c[:, 1])
@@ -187,9 +188,9 @@ def sym_graph():
     dst.append(twice[:, 1])
     src, dst = np.concatenate(src), np.concatenate(dst)
     loops = plain[::7]                                             # self-loops: one entry each
-    deg = np.bincount(np.concatenate([src, dst, loops]), minlength=NODE_NUM)
+    deg = np.bincount(np.concatenate([src, dst, loops]), minlength=node_num)
     hs, hd = [], []
-    for h, want in HUBS.items():
+    for h, want in hubs.items():
         near = set(dst[src == h].tolist()) | set(src[dst == h].tolist())
         pool = np.array([x for x in plain if x not in near], dtype=np.int64)
         more = rng.choice(pool, want - int(deg[h]), replace=False)
@@ -200,14 +201,14 @@ def sym_graph():
     cols = np.concatenate([dst, src, loops])
     order = np.lexsort((cols, rows))
     rows, col = rows[order], cols[order].astype(np.int32)
-    deg = np.bincount(rows, minlength=NODE_NUM).astype(np.int64)
+    deg = np.bincount(rows, minlength=node_num).astype(np.int64)
     indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
-    assert all(deg[h] == want for h, want in HUBS.items()) and all(deg[v] == 0 for v in EMPTY)
-    for v in list(range(50, NODE_NUM, 211)) + [3]:                 # dead entries: first in their rows, so the rows stay sorted
+    assert all(deg[h] == want for h, want in hubs.items()) and all(deg[v] == 0 for v in empty)
+    for v in list(range(50, node_num, 211)) + [3]:                 # dead entries: first in their rows, so the rows stay sorted
         col[indptr[v]] = -1
     E = col.size
     w = (rng.randint(1, 33, E) / 8).astype(np.float32)
-    for v in range(NODE_NUM):
+    for v in range(node_num):
         s, D = int(indptr[v]), int(deg[v])
         if D >= 2 and v % 2 == 0:
             w[s:s + max(D // 5, 1)] = 0                            # a leading run of zeros

@@ -21,8 +21,9 @@ def refused(num_seeds, R, T, k, weighted, termination_prob, base, has_table):
     return not (p >= 0 and p <= 1)
 
 
-def visits(indptr, col, seeds, R, T, table=None, termination_prob=0.5, base=0, reads=None):
-    """int32 [n, R * T]: entry [i, r * T + j - 1] is the vertex walk r of seed i reaches at step j, or -1 once the walk has ended."""
+def visits(indptr, col, seeds, R, T, table=None, termination_prob=0.5, base=0, reads=None, eids=None):
+    """int32 [n, R * T]: entry [i, r * T + j - 1] is the vertex walk r of seed i reaches at step j, or -1 once the walk has ended.
+    eids, if a list, collects per step the int64 [n * R] edge ids of the traversals (-1: no traversal; walk w = i * R + r)."""
     indptr = np.asarray(indptr, dtype=np.int64)
     col = np.asarray(col, dtype=np.int32)
     seeds = np.asarray(seeds, dtype=np.int32)
@@ -34,9 +35,11 @@ def visits(indptr, col, seeds, R, T, table=None, termination_prob=0.5, base=0, r
     out = np.full((W, T), -1, dtype=np.int32)
     for j in range(1, T + 1):
         if j == 1 or y is None:                                    # the first traversal takes no restart draw
-            v, _ = walk_ref.step(indptr, col, node_num, v, x[:, j - 1], table=table, reads=reads)
+            v, e = walk_ref.step(indptr, col, node_num, v, x[:, j - 1], table=table, reads=reads)
         else:
-            v, _ = walk_ref.step(indptr, col, node_num, v, x[:, j - 1], y[:, j - 1], table, termination_prob, reads)
+            v, e = walk_ref.step(indptr, col, node_num, v, x[:, j - 1], y[:, j - 1], table, termination_prob, reads)
+        if eids is not None:
+            eids.append(e)
         out[:, j - 1] = v
     return out.reshape(n, R * T)
 
@@ -87,5 +90,5 @@ def topk(vis, k):
     return nb, ct
 
 
-def neighbors(indptr, col, seeds, R, T, k, table=None, termination_prob=0.5, base=0, reads=None):
-    return topk(visits(indptr, col, seeds, R, T, table, termination_prob, base, reads), k)
+def neighbors(indptr, col, seeds, R, T, k, table=None, termination_prob=0.5, base=0, reads=None, eids=None):
+    return topk(visits(indptr, col, seeds, R, T, table, termination_prob, base, reads, eids), k)
