@@ -553,6 +553,63 @@ int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphStorage* gra
                                  int32_t num_walks_per_seed, int32_t walk_length, int32_t num_neighbors, int32_t weighted,
                                  float termination_prob, int64_t base, int32_t* neighbors_out /* int32[n x k] */,
                                  int32_t* counts_out /* int32[n x k] */);
+/* The seeds of a link-prediction batch (DGL's as_edge_prediction_sampler with a negative sampler: find_edges, negatives,
+ * compact_graphs), new in this build; no reference counterpart.  Three ops: the endpoints of B seed edges, k negative endpoints per edge
+ * that are no neighbours, and the list of the distinct ids among the B (2 + k) with local indices into it -- the distinct list is what
+ * legion_feature_set_ids / BatchGenerate need, whose de-duplication assumes no duplicate among a batch's seeds.  All buffers are device
+ * memory.  Each op is enqueued on `stream`, on the device current at the call; nothing synchronises with the host, and each call may be
+ * captured into a graph.  The two graph ops read the FULL CSR only (the arrays given to legion_graph_create).  A CSR row is the sampler's
+ * dst side and a column entry its src side (col[agg_edge_ids[e]] == agg_src_ids[e]): hence `row` and `col`, not src and dst.
+ *
+ * legion_find_edges (DGL's g.find_edges).  With N = node_num, E = the number of column entries, for i in [0, n), e = eids[i]:
+ *   1. e < 0 or e >= E: row_out[i] = col_out[i] = -1 -- no memory is read for e;
+ *   2. c = col[e]; c < 0 (a dead column entry): row_out[i] = col_out[i] = -1, as everywhere else in the library;
+ *   3. row_out[i] = #{ v in [0, N] : indptr[v] <= e } - 1, an upper-bound search over the N + 1 row pointers in int64: the one row v with
+ *      indptr[v] <= e < indptr[v + 1], rows without entries skipped; col_out[i] = c.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for a null graph, eids_devptr, row_out or col_out, or n < 0.  n == 0
+ * returns 0 and enqueues nothing. */
+int32_t legion_find_edges(legion_stream_t stream, LegionGraphStorage* graph, const int64_t* eids_devptr /* int64[n] */, int32_t n,
+                          int32_t* row_out /* int32[n] */, int32_t* col_out /* int32[n] */);
+/* legion_negative_sample (exclude == 0: DGL's negative_sampler.Uniform(k); with bit 1: PyG's structured_negative_sampling).  neg_out is
+ * int32[n x k], row-major.  Slot m = i * k + j (i in [0, n), j in [0, k)) belongs to row r = rows[i] and has draw index nn = base + m;
+ * minstd(e) = 48271^e mod (2^31 - 1), the power of the sampler's draw.  Then, in this order:
+ *   1. r < 0 or r >= N: neg_out[m] = -1 -- no memory is read for r;
+ *   2. tries t = 0, 1, .. max_tries - 1:
+ *        draw: x = minstd((uint32)(nn + 1) + t * 2^23), r01 = (double)(x - 1) / 2147483646.0, u = (int)(r01 * N): the sampler's uniform
+ *          draw over N (legion_node2vec_walk's try stepping: x of try t + 1 = x of try t * 48271^(2^23));
+ *        u is rejected if exclude & 1 and u == r;
+ *        u is rejected if exclude & 2 and u occurs in col[indptr[r] .. indptr[r + 1]) (a binary search of the sorted row; the pair
+ *          {indptr[r], indptr[r + 1]} is loaded once per slot);
+ *        the first u not rejected is neg_out[m];
+ *   3. every try rejected: neg_out[m] = -1.
+ * With exclude == 0 the first draw is taken and nothing but rows is read.  The index of try t coincides with try 0 of the slot t * 2^23
+ * further on (as node2vec's tries coincide with steps four million steps away): accepted.  A row whose every vertex is excluded gives -1
+ * at any max_tries.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, rows_devptr or neg_out; n < 0; k < 1; base < 0;
+ * base + n * k > 2^31 - 1 (in 64 bits); exclude outside [0, 3]; max_tries outside [1, LEGION_NEGATIVE_MAX_TRIES] (255 * 2^23 + 2^31 < 2^32,
+ * the reach of the power tables); exclude & 2 on a graph whose rows legion_graph_check_rows_sorted has not checked, or has found
+ * unsorted.  n == 0 returns 0 and enqueues nothing.  Not offered: degree-biased negatives. */
+#define LEGION_NEGATIVE_MAX_TRIES 256
+int32_t legion_negative_sample(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                               int32_t k, int32_t exclude, int32_t max_tries, int64_t base, int32_t* neg_out /* int32[n x k] */);
+/* legion_unique_ids (compact_graphs' relabelling, in order of first appearance).  No graph is involved.  For i in [0, m):
+ *   1. ids[i] < 0: local_out[i] = -1; the entry is no seed;
+ *   2. else first(i) = min{ j : ids[j] == ids[i] }.  The entries with first(i) == i are numbered rank = 0 .. U - 1 in index order;
+ *      unique_out[rank(i)] = ids[i] for each of them, local_out[i] = rank(first(i)) for every i of 2., count_out[0] = U;
+ *   3. unique_out[U .. m) = -1: the whole buffer is defined.
+ * unique_out and local_out are int32[m], count_out int32[1].  scratch: device memory, 4-byte aligned, of at least
+ * legion_unique_ids_scratch_bytes(m) bytes (-1 for m < 0 or m > LEGION_UNIQUE_MAX_IDS); the call clears what it needs of it on `stream`
+ * itself, and two calls in flight on different streams need scratch of their own.  The result does not depend on the order in which the
+ * device takes the ids.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null ids_devptr, unique_out, local_out, count_out or scratch; m < 0;
+ * m > LEGION_UNIQUE_MAX_IDS; scratch_bytes below legion_unique_ids_scratch_bytes(m); unique_out, local_out or count_out overlapping
+ * ids.  m == 0 returns 0 and writes count_out[0] = 0 only.
+ * Not offered by these three: excluding the seed edges from the sampled neighbourhood (a consumer masks by agg_edge_ids); device-resident
+ * seed sets for BatchGenerate (legion_feature_set_ids still takes host arrays); the server, the launcher and the wire. */
+#define LEGION_UNIQUE_MAX_IDS 1048576
+int64_t legion_unique_ids_scratch_bytes(int32_t m);
+int32_t legion_unique_ids(legion_stream_t stream, const int32_t* ids_devptr /* int32[m] */, int32_t m, int32_t* unique_out /* int32[m] */,
+                          int32_t* local_out /* int32[m] */, int32_t* count_out /* int32[1] */, void* scratch, int64_t scratch_bytes);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

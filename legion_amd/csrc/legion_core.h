@@ -897,6 +897,26 @@ void launch_node2vec_walk(hipStream_t s, const Node2vecParams& p);
 void launch_row_inversion_counts(hipStream_t s, const int64_t* indptr, const int32_t* col, int32_t n_rows, int64_t num_edges,
                                  unsigned long long* counts);
 
+// the seeds of a link-prediction batch (kernels_link.hip; the rules: legion_find_edges, legion_negative_sample and legion_unique_ids in
+// legion_hip.h).  The arguments are the caller's to check (link_rule.h).
+void launch_find_edges(hipStream_t s, const int64_t* indptr, const int32_t* col, int32_t node_num, int64_t num_edges, const int64_t* eids,
+                       int32_t n, int32_t* row_out, int32_t* col_out);
+struct NegativeParams {
+    const int64_t* indptr;          // the FULL CSR; read only with exclude & 2
+    const int32_t* col;
+    const int32_t* rows;            // int32[n]
+    int32_t* neg;                   // int32[n x k]
+    int32_t node_num;
+    int32_t n, k;
+    int32_t exclude;                // bit 0: the row itself, bit 1: the entries of its row
+    int32_t max_tries;
+    int64_t base;                   // draw index of slot 0
+};
+void launch_negative_sample(hipStream_t s, const NegativeParams& p);
+// slots, n_tiles: unique_ids_table_slots(m), unique_ids_tiles(m); scratch: unique_ids_scratch_bytes(m) bytes, cleared here on s
+void launch_unique_ids(hipStream_t s, const int32_t* ids, int32_t m, int32_t* unique, int32_t* local, int32_t* count, void* scratch,
+                       int64_t slots, int64_t n_tiles);
+
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {
     WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the

@@ -16,6 +16,7 @@
 //     legion_core.h), so BatchGenerate has nothing to memset and IOComplete nothing to restore.
 #include "legion_core.h"
 #include "node2vec_rule.h"
+#include "link_rule.h"
 
 #include <iostream>
 
@@ -480,6 +481,59 @@ extern "C" int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphS
     p.neighbors = neighbors_out;
     p.counts = counts_out;
     lg::launch_pinsage_neighbors(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// The seeds of a link-prediction batch (the rules: legion_hip.h; the refusals and the scratch size: link_rule.h).  As above: every check
+// comes before the launch.
+extern "C" int32_t legion_find_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int64_t* eids_devptr, int32_t n,
+                                     int32_t* row_out, int32_t* col_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !eids_devptr || !row_out || !col_out) return -1;
+    if (find_edges_refusal(n) != LinkRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    lg::launch_find_edges(static_cast<hipStream_t>(stream), graph->GetCSRNodeIndexCPU(), graph->GetCSRNodeMatrixCPU(), graph->NodeNum(),
+                          graph->EdgeNum(), eids_devptr, n, row_out, col_out);
+    return 0;
+}
+
+extern "C" int32_t legion_negative_sample(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n, int32_t k,
+                                          int32_t exclude, int32_t max_tries, int64_t base, int32_t* neg_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !neg_out) return -1;
+    if (negative_sample_refusal(n, k, base, exclude, max_tries, graph->RowsSorted()) != LinkRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    lg::NegativeParams p;
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.rows = rows_devptr;
+    p.neg = neg_out;
+    p.node_num = graph->NodeNum();
+    p.n = n;
+    p.k = k;
+    p.exclude = exclude;
+    p.max_tries = max_tries;
+    p.base = base;
+    lg::launch_negative_sample(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int64_t legion_unique_ids_scratch_bytes(int32_t m)
+{
+    return unique_ids_scratch_bytes(m);
+}
+
+extern "C" int32_t legion_unique_ids(legion_stream_t stream, const int32_t* ids_devptr, int32_t m, int32_t* unique_out, int32_t* local_out,
+                                     int32_t* count_out, void* scratch, int64_t scratch_bytes)
+{
+    if (!ids_devptr || !unique_out || !local_out || !count_out || !scratch) return -1;
+    if (unique_ids_refusal(m, scratch_bytes, (uint64_t)(uintptr_t)ids_devptr, (uint64_t)(uintptr_t)unique_out, (uint64_t)(uintptr_t)local_out,
+                           (uint64_t)(uintptr_t)count_out) != LinkRefusal::Ok)
+        return -1;
+    lg::launch_unique_ids(static_cast<hipStream_t>(stream), ids_devptr, m, unique_out, local_out, count_out, scratch,
+                          unique_ids_table_slots(m), unique_ids_tiles(m));
     return 0;
 }
 

@@ -161,6 +161,56 @@ def _i32_array(values):
     return arr
 
 
+def _as_1d(x, dtype, name):
+    """x as a one-dimensional tensor of dtype: a tensor of another dtype or shape is a ValueError, anything else goes through
+    torch.as_tensor."""
+    short = str(dtype).replace("torch.", "")
+    if isinstance(x, torch.Tensor) and x.dtype != dtype:
+        raise ValueError(f"{name} must be {short}, not {x.dtype}")
+    if not isinstance(x, torch.Tensor):
+        x = torch.as_tensor(x, dtype=dtype)
+    if x.dim() != 1:
+        raise ValueError(f"{name} must be one-dimensional, not shape {tuple(x.shape)}")
+    return x
+
+
+UNIQUE_MAX_IDS = 2 ** 20                             # LEGION_UNIQUE_MAX_IDS
+
+
+def _check_unique(m):
+    if m > UNIQUE_MAX_IDS:
+        raise ValueError(f"{m} ids in one call, at most {UNIQUE_MAX_IDS}")
+
+
+def unique_ids(ids, stream=None):
+    """The distinct ids in order of first appearance, and where each id sits among them (compact_graphs' relabelling; the rule:
+    legion_unique_ids in legion_hip.h).  ids: int32, a CUDA tensor (its device is used) or anything torch.as_tensor takes (the current
+    device); at most UNIQUE_MAX_IDS of them.  Returns (unique, local, count): unique int32 [m], the distinct non-negative ids and -1
+    from count on; local int32 [m], each id's index in unique, -1 for a negative id; count, a one-element int32 device tensor (no
+    sync).  The scratch is allocated here.  Enqueued on `stream` (default: the current one)."""
+    ids = _as_1d(ids, torch.int32, "ids")
+    m = int(ids.numel())
+    _check_unique(m)
+    L = _libmod.load()
+    dev = ids.device if ids.is_cuda else torch.device("cuda", torch.cuda.current_device())
+    ids = ids.to(dev).contiguous()
+    unique = torch.empty((m,), dtype=torch.int32, device=dev)
+    local = torch.empty((m,), dtype=torch.int32, device=dev)
+    if m == 0:                                       # (nothing to enqueue; an empty tensor has no address to hand over)
+        return unique, local, torch.zeros((1,), dtype=torch.int32, device=dev)
+    count = torch.empty((1,), dtype=torch.int32, device=dev)
+    nbytes = int(L.legion_unique_ids_scratch_bytes(m))
+    scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        rc = L.legion_unique_ids(_stream_handle(stream), _ptr(ids), m, _ptr(unique), _ptr(local), _ptr(count), _ptr(scratch), nbytes)
+    if rc != 0:
+        raise RuntimeError("legion_unique_ids refused arguments that unique_ids had accepted")
+    if stream is not None:                           # (tensors of this call, used on a stream that is not the allocator's)
+        for x in (ids, unique, local, count, scratch):
+            x.record_stream(stream)
+    return unique, local, count
+
+
 class GraphStorage:
     """Full CSR (slot P of the pointer tables) from device tensors: indptr int64[N+1], col int32[E]."""
 
@@ -394,6 +444,101 @@ class GraphStorage:
             for x in (seeds, neighbors, counts):
                 x.record_stream(stream)
         return neighbors, counts
+
+    NEGATIVE_MAX_TRIES = 256                         # LEGION_NEGATIVE_MAX_TRIES
+
+    def find_edges(self, eids, stream=None):
+        """The endpoints of edges (DGL's g.find_edges; the rule: legion_find_edges in legion_hip.h).  eids: int64 positions in col, a
+        CUDA tensor or anything torch.as_tensor takes.  Returns (row, col), both int32 [n]: the CSR row that holds position e -- the
+        sampler's dst side -- and col[e], its src side; -1 / -1 for an e outside [0, E) and for a dead (negative) column entry.
+        Enqueued on `stream` (default: the current one)."""
+        eids = _as_1d(eids, torch.int64, "eids")
+        n = int(eids.numel())
+        dev = self.col.device
+        eids = eids.to(dev).contiguous()
+        row = torch.empty((n,), dtype=torch.int32, device=dev)
+        col = torch.empty((n,), dtype=torch.int32, device=dev)
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return row, col
+        with torch.cuda.device(dev):
+            rc = self._lib.legion_find_edges(_stream_handle(stream), self.handle, _ptr(eids), n, _ptr(row), _ptr(col))
+        if rc != 0:
+            raise RuntimeError("legion_find_edges refused arguments that find_edges had accepted")
+        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
+            for x in (eids, row, col):
+                x.record_stream(stream)
+        return row, col
+
+    @staticmethod
+    def _check_negative(n, k, exclude_self, exclude_edges, max_tries, base):
+        """negative_sample's arguments by the rules of legion_negative_sample, before anything touches a device: ValueError with the
+        reason."""
+        for name, flag in (("exclude_self", exclude_self), ("exclude_edges", exclude_edges)):
+            if not isinstance(flag, bool):
+                raise ValueError(f"{name} must be True or False, not {flag!r}")
+        for name, value in (("k", k), ("max_tries", max_tries), ("base", base)):
+            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+                raise ValueError(f"{name} must be an integer, not {value!r}")
+        if k < 1:
+            raise ValueError(f"k must be at least 1, not {k}")
+        if not 1 <= max_tries <= GraphStorage.NEGATIVE_MAX_TRIES:
+            raise ValueError(f"max_tries must lie in [1, {GraphStorage.NEGATIVE_MAX_TRIES}], not {max_tries}")
+        if base < 0:
+            raise ValueError(f"base must not be negative, not {base}")
+        if base + n * k > 2 ** 31 - 1:
+            raise ValueError(f"base + n * k = {base + n * k} is past the last draw index, 2^31 - 1")
+
+    def negative_sample(self, rows, k, *, exclude_self=True, exclude_edges=True, max_tries=256, base=0, stream=None):
+        """k uniform negative endpoints for each of rows (the rule: legion_negative_sample in legion_hip.h; with both exclusions off DGL's
+        negative_sampler.Uniform(k), with exclude_edges PyG's structured_negative_sampling).  rows: int32 vertex ids, a CUDA tensor or
+        anything torch.as_tensor takes.  Returns int32 [n, k]: vertices drawn uniformly over the graph, redrawn up to max_tries times
+        while they are the row itself (exclude_self) or occur in its row of the CSR (exclude_edges: needs sorted rows, rows_sorted() is
+        asked here, ValueError if not); -1 where every try was rejected and for a row outside the graph.  base: draw index of the first
+        slot; the same rows, flags and base give the same negatives.  Enqueued on `stream` (default: the current one)."""
+        rows = _as_1d(rows, torch.int32, "rows")
+        n = int(rows.numel())
+        self._check_negative(n, k, exclude_self, exclude_edges, max_tries, base)
+        if exclude_edges and not self.rows_sorted(stream):
+            raise ValueError("negative_sample with exclude_edges needs a graph whose rows are sorted (rows_sorted() is False)")
+        dev = self.col.device
+        rows = rows.to(dev).contiguous()
+        neg = torch.empty((n, int(k)), dtype=torch.int32, device=dev)
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return neg
+        with torch.cuda.device(dev):
+            rc = self._lib.legion_negative_sample(_stream_handle(stream), self.handle, _ptr(rows), n, int(k),
+                                                  int(exclude_self) | int(exclude_edges) << 1, int(max_tries), int(base), _ptr(neg))
+        if rc != 0:
+            raise RuntimeError("legion_negative_sample refused arguments that negative_sample had accepted")
+        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
+            for x in (rows, neg):
+                x.record_stream(stream)
+        return neg
+
+    def edge_prediction_seeds(self, eids, k, *, exclude_self=True, exclude_edges=True, max_tries=256, base=0, stream=None):
+        """The seeds of a link-prediction batch from B seed edges (DGL's as_edge_prediction_sampler with a negative sampler): find_edges,
+        negative_sample with k negatives per edge's row, and unique_ids over [rows | cols | negatives, row-major].  Returns (seeds,
+        num_seeds, pos_row, pos_col, neg_col): seeds int32 [B (2 + k)], the distinct vertices in order of first appearance, -1 from
+        num_seeds (a one-element device tensor: no sync) on; pos_row, pos_col int32 [B] and neg_col int32 [B, k], indices into seeds
+        (-1 where the edge or the negative is -1).  Hand seeds[:num_seeds] to FeatureStorage.set_ids: a batch's sampled_ids start with
+        them in this order, so the indices address the batch's rows.  At k = 1 the thirds of a link-prediction loss are h[pos_row],
+        h[pos_col], h[neg_col[:, 0]].  Keywords and stream as in negative_sample."""
+        eids = _as_1d(eids, torch.int64, "eids")
+        B = int(eids.numel())
+        self._check_negative(B, k, exclude_self, exclude_edges, max_tries, base)
+        _check_unique(B * (2 + int(k)))
+        if exclude_edges and not self.rows_sorted(stream):
+            raise ValueError("edge_prediction_seeds with exclude_edges needs a graph whose rows are sorted (rows_sorted() is False)")
+        row, col = self.find_edges(eids, stream=stream)
+        neg = self.negative_sample(row, k, exclude_self=exclude_self, exclude_edges=exclude_edges, max_tries=max_tries, base=base,
+                                   stream=stream)
+        if stream is None:
+            ids = torch.cat([row, col, neg.reshape(-1)])
+        else:
+            with torch.cuda.stream(stream):
+                ids = torch.cat([row, col, neg.reshape(-1)])
+        seeds, local, count = unique_ids(ids, stream=stream)
+        return seeds, count, local[:B], local[B:2 * B], local[2 * B:].reshape(B, int(k))
 
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""

@@ -145,6 +145,10 @@ SIGNATURES = {
     "legion_random_walk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
     "legion_node2vec_walk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, ctypes.c_float, ctypes.c_float, c_i32, c_i32, c_i64, c_p, c_p]),
     "legion_pinsage_neighbors": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i32, ctypes.c_float, c_i64, c_p, c_p]),
+    "legion_find_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_p]),
+    "legion_negative_sample": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i64, c_p]),
+    "legion_unique_ids_scratch_bytes": (c_i64, [c_i32]),
+    "legion_unique_ids": (c_i32, [c_p, c_p, c_i32, c_p, c_p, c_p, c_p, c_i64]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
