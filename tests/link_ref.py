@@ -191,3 +191,105 @@ def ring_graph(n=8):
     """The n-ring: row v holds v - 1 and v + 1 (mod n), sorted."""
     col = np.array([sorted(((v - 1) % n, (v + 1) % n)) for v in range(n)], dtype=np.int32).reshape(-1)
     return np.arange(n + 1, dtype=np.int64) * 2, col
+
+
+# ---- the table of unique_ids, restated to say what an input does to it ------------------------------------------------------------
+HASH = 2654435769                                                  # the multiplicative hash of kernels_link.hip; odd: a bijection mod 2^32
+HASH_INV = pow(HASH, -1, 2 ** 32)
+
+
+def ids_with_home(m, homes, per):
+    """`per` distinct non-negative int32 ids for each home slot in `homes` of the table of m ids, home by home: the hash inverted.
+    y = id * HASH mod 2^32 has home y >> shift, so the ids of a home are y * HASH_INV mod 2^32 over y in [home << shift,
+    (home + 1) << shift), those below 2^31 kept, the first `per` in order of y taken."""
+    slots = table_slots(m)
+    shift = 32 - (slots.bit_length() - 1)
+    out = []
+    for home in homes:
+        assert 0 <= home < slots, (home, slots)
+        y = np.arange(home << shift, min((home + 1) << shift, (home << shift) + 4 * per + 4096), dtype=np.uint64)      # (half are kept)
+        ids = (y * np.uint64(HASH_INV)) & np.uint64(0xFFFFFFFF)
+        ids = ids[ids < 2 ** 31][:per]
+        assert ids.size == per, f"home {home} of {slots} slots has {ids.size} non-negative ids, {per} asked for"
+        out.append(ids.astype(np.int64))
+    out = np.concatenate(out) if out else np.zeros(0, dtype=np.int64)
+    assert np.array_equal(home_slots(out, m), np.repeat(np.asarray(homes, dtype=np.int64), per)) and np.unique(out).size == out.size
+    return out.astype(np.int32)
+
+
+def probe_table(ids, m, order, wrap=True):
+    """The insert of unique_ids done one id at a time in the arrival order `order` (a permutation of the indices): linear probing from
+    home_slots over table_slots(m) slots.  Returns (slot int64 [len(ids)], -1 for a negative id; the longest probe run, in slots looked
+    at; how many distinct ids sit in a slot below their home: a wrap).  wrap=False is a wrong table, one that stops probing at its last
+    slot: an id that finds no place gets slot -1.  Only a statement about inputs: which slot a key lands in depends on arrival order,
+    so no GPU result is compared with this."""
+    ids = np.asarray(ids, dtype=np.int64)
+    slots = table_slots(m)
+    homes = home_slots(np.maximum(ids, 0), m)
+    nxt = np.arange(slots + 1, dtype=np.int64)                     # nxt[s]: a free slot at or after s, found by path halving; slots: none
+
+    def free(s):
+        while nxt[s] != s:
+            nxt[s] = nxt[nxt[s]]
+            s = nxt[s]
+        return int(s)
+
+    where, slot = {}, np.full(ids.size, -1, dtype=np.int64)
+    longest = wraps = 0
+    for i in np.asarray(order).tolist():
+        v = int(ids[i])
+        if v < 0:
+            continue
+        if v not in where:
+            h = int(homes[i])
+            s = free(h)
+            if s == slots:                                         # nothing free up to the table's end
+                s = free(0) if wrap else -1
+            where[v] = s
+            if s >= 0:
+                nxt[s] = s + 1
+                wraps += int(s < h)
+                longest = max(longest, (s - h) % slots + 1)
+            else:
+                longest = max(longest, slots - h)
+        slot[i] = where[v]
+    return slot, longest, wraps
+
+
+# ---- small graphs for find_edges --------------------------------------------------------------------------------------------------
+def _graph_of_degrees(deg, seed, dead=0):
+    deg = np.asarray(deg, dtype=np.int64)
+    indptr = np.concatenate([[0], np.cumsum(deg)]).astype(np.int64)
+    rng = np.random.RandomState(seed)
+    col = rng.randint(0, deg.size, int(indptr[-1])).astype(np.int32)
+    if dead:
+        col[rng.choice(col.size, dead, replace=False)] = -1
+    return indptr, col
+
+
+def small_graphs():
+    """name -> (indptr, col): one vertex with a self-loop; two and three vertices with empty rows first, in the middle and last; 254 to
+    257 vertices of degree 0 .. 3 (N + 1 row pointers: a power of two and one or two either side) with three dead entries each; a
+    graph whose first three and last three rows are empty; 64 rows with every edge in row 17."""
+    g = {"loop": (np.array([0, 1], dtype=np.int64), np.array([0], dtype=np.int32)),
+         "two-first-empty": _graph_of_degrees([0, 2], 1),
+         "two-last-empty": _graph_of_degrees([2, 0], 2),
+         "three-middle-empty": _graph_of_degrees([1, 0, 2], 3),
+         "three-two-empty": _graph_of_degrees([0, 0, 3], 4),
+         "ends-empty": _graph_of_degrees([0, 0, 0, 2, 1, 0, 3, 1, 0, 0, 2, 0, 0, 0], 5),
+         "one-row": _graph_of_degrees([0] * 17 + [40] + [0] * 46, 6)}
+    for n in (254, 255, 256, 257):
+        g[f"degrees-{n}"] = _graph_of_degrees(np.random.RandomState(100 + n).randint(0, 4, n), 200 + n, dead=3)
+    return g
+
+
+def find_edges_lower_bound(indptr, col, eids):
+    """A wrong find_edges: the row by a lower bound over the row pointers -- the first v with indptr[v] >= e, one less where that
+    pointer is past e.  Right except where e starts a row that follows empty rows: there it names the first of the empty rows."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    row, c = find_edges(indptr, col, eids)
+    e = np.asarray(eids, dtype=np.int64)
+    live = row >= 0
+    pos = np.searchsorted(indptr, e[live], side="left")
+    row[live] = np.where(indptr[np.minimum(pos, indptr.size - 1)] == e[live], pos, pos - 1)
+    return row, c

@@ -1,7 +1,8 @@
 """GraphStorage.negative_sample / legion_negative_sample on the GPU, bit for bit against tests/link_ref.py: on the symmetric graph of
 tests/node2vec_ref.py over every workgroup boundary in the row count, three k, the four exclusions, four max_tries and the whole range
 of the draw index; and on two graphs of eight vertices, where the self-rejection (1 in 6 000 on the big graph) and the exhausted slot are
-the rule rather than the exception.
+the rule rather than the exception; on one vertex; and over 2^24 + 3 and 2^25 + 3 vertices, where the candidate floor(r * N) in double is
+not what a float32 product gives.
 
 The grid is the product thinned: case number c of the 18 (rows, k) pairs takes exclude c mod 4, max_tries number (c + c div 4) mod 4
 and base number (c div 2) mod 3, so every exclusion meets every max_tries.  The references are computed once, with the counters that
@@ -134,6 +135,87 @@ def test_a_ring_rejects_the_row_itself(world, tries):
     torch.cuda.synchronize()
     _same(got, want, f"ring exclude 1 tries {tries}")
     _same(both, ref.negative_sample(ip, c, rows, 5, 3, tries, 0), f"ring exclude 3 tries {tries}")
+
+
+def test_one_vertex(hip):
+    """N = 1, a self-loop: the only candidate is 0.  Excluding the row itself (or its edges) every slot is -1; excluding nothing, 0."""
+    from legion_amd import engine
+    ip, c = np.array([0, 1], dtype=np.int64), np.array([0], dtype=np.int32)
+    rows = np.array([0] * 300 + [-1, 1], dtype=np.int32)
+    want = {e: ref.negative_sample(ip, c, rows, 5, e, 3, 9) for e in range(4)}
+    assert np.all(want[0][:300] == 0) and all(np.all(want[e] == -1) for e in (1, 2, 3)) and np.all(want[0][300:] == -1)
+    g = engine.GraphStorage(1, torch.from_numpy(ip).to(DEV), torch.from_numpy(c).to(DEV))
+    try:
+        for e in range(4):
+            got = g.negative_sample(rows, 5, exclude_self=bool(e & 1), exclude_edges=bool(e & 2), max_tries=3, base=9)
+            torch.cuda.synchronize()
+            _same(got, want[e], f"one vertex, exclude {e}")
+    finally:
+        torch.cuda.synchronize()
+        g.close()
+
+
+BIG = [2 ** 24 + 3, 2 ** 25 + 3]
+BIG_N, BIG_K, BIG_BASE, HUB_ENTRIES, HUB_FROM_DRAWS = 5000, 5, 77, 1000, 300
+
+
+def draw_in_float32(rows, k, base, node_num):
+    """A wrong draw with no exclusion: the unit and the product in float32, floor(float(r) * float(N)), capped at N - 1."""
+    x = walk_ref.draws(base, rows.size * k)
+    u = np.floor(walk_ref.unit_of(x).astype(np.float32) * np.float32(node_num)).astype(np.int64)
+    out = np.where(np.repeat((rows >= 0) & (rows < node_num), k), np.minimum(u, node_num - 1), -1)
+    return out.reshape(rows.size, k).astype(np.int32)
+
+
+def big_case(node_num):
+    """(indptr, col, rows, {exclude: reference}) over node_num vertices whose rows are empty except one sorted hub of 1 000 entries, 300
+    of them what the hub's own slots draw first (so its search is hit: uniform chance, 1 000 in 2^24, would not) and 2^24 + 1 and
+    2^24 + 2 among the rest.  Checked from the reference: the hub's search is hit, a float32 draw differs in at least 100 slots, and
+    -- over 2^25 + 3 vertices; over 2^24 + 3 the only such value is 2^24 + 1, drawn once in 16 million -- at least 100 expected values
+    are odd and above 2^24, which no float32 holds."""
+    hub = 2 ** 24 + 1
+    rows = (np.arange(BIG_N, dtype=np.int64) * 2654435761 % node_num).astype(np.int32)
+    rows[::5] = hub
+    rows[1], rows[2], rows[3] = -1, node_num, node_num - 1
+    indptr = np.zeros(node_num + 1, dtype=np.int64)
+    free = ref.negative_sample(indptr, np.zeros(0, dtype=np.int32), rows, BIG_K, 0, 1, BIG_BASE)      # no exclusion: try 0 of every slot
+    drawn = np.unique(free[rows == hub].reshape(-1))[:HUB_FROM_DRAWS]
+    rest = np.concatenate([[0, hub, 2 ** 24 + 2, node_num - 1], np.random.RandomState(5).randint(0, node_num, 2 * HUB_ENTRIES)])
+    rest = rest[np.sort(np.unique(rest, return_index=True)[1])]                                     # distinct, the four named ones first
+    rest = rest[~np.isin(rest, drawn)]
+    col = np.sort(np.concatenate([drawn, rest[:HUB_ENTRIES - drawn.size]])).astype(np.int32)
+    assert col.size == HUB_ENTRIES and drawn.size == HUB_FROM_DRAWS and np.unique(col).size == col.size and (col > 2 ** 24).any()
+    indptr[hub + 1:] = HUB_ENTRIES
+    want = {}
+    for exclude in (0, 3):
+        reads, stats = {}, ref.new_stats(node_num)
+        want[exclude] = ref.negative_sample(indptr, col, rows, BIG_K, exclude, 256, BIG_BASE, reads=reads, stats=stats)
+        walk_ref.assert_reads_in_bounds(reads, node_num, col.size)
+        assert np.all(want[exclude][1:3] == -1) and want[exclude].max() < node_num
+        if exclude:
+            assert stats["hits_of_row"][hub] >= HUB_FROM_DRAWS and stats["exhausted"] == 0 and stats["self"] == 0
+            assert int((want[3] != want[0]).sum()) >= HUB_FROM_DRAWS
+    assert np.array_equal(want[0], free)
+    odd_high = int(((want[0] > 2 ** 24) & (want[0] % 2 == 1)).sum())
+    off = int((draw_in_float32(rows, BIG_K, BIG_BASE, node_num) != want[0]).sum())
+    print(f"N {node_num}: {odd_high} expected values odd and above 2^24, a float32 draw differs in {off} of {want[0].size} slots")
+    assert off >= 100 and (node_num < 2 ** 25 or odd_high >= 100)
+    return indptr, col, rows, want
+
+
+@pytest.mark.parametrize("node_num", BIG, ids=["2^24+3", "2^25+3"])
+def test_the_draw_over_more_than_2_24_vertices(hip, node_num):
+    from legion_amd import engine
+    indptr, col, rows, want = big_case(node_num)
+    g = engine.GraphStorage(1, torch.from_numpy(indptr).to(DEV), torch.from_numpy(col).to(DEV))
+    try:
+        for exclude in (0, 3):
+            got = g.negative_sample(rows, BIG_K, exclude_self=bool(exclude & 1), exclude_edges=bool(exclude & 2), base=BIG_BASE)
+            torch.cuda.synchronize()
+            _same(got, want[exclude], f"N {node_num}, exclude {exclude}")
+    finally:
+        torch.cuda.synchronize()
+        g.close()
 
 
 def test_an_empty_call_returns_an_empty_array(world):

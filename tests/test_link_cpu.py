@@ -12,6 +12,12 @@ import pytest
 from legion_amd import engine, lib
 from tests import link_ref as ref
 from tests import node2vec_ref, walk_ref
+# the inputs of the GPU files come from their own builders: what is proven here is what they launch
+from tests import test_gpu_link_find_edges as gpu_find
+from tests import test_gpu_link_fuzz as gpu_fuzz
+from tests import test_gpu_link_negative as gpu_negative
+from tests import test_gpu_link_stride as gpu_stride
+from tests import test_gpu_link_table as gpu_table
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 HEADER = os.path.join(ROOT, "include", "legion_hip.h")
@@ -290,3 +296,191 @@ def test_negatives_are_uniform_over_the_non_neighbours(world):
     worst = float(np.abs(counts[~banned] - n * prob).max() / sd)
     print(f"{cells} cells, expected {n * prob:.1f} each, worst {worst:.2f} sd")
     assert n * prob >= 50 and worst <= 5.0, worst
+
+
+# ---- what the GPU tests of the second pass assert before they launch, and four wrong kernels that they catch ----------------------
+def unique_without_wrap(ids, order):
+    """Wrong kernel 1: a probe that stops at the table's last slot.  An id that finds no place there has no slot: local = -1, and it is
+    no seed."""
+    ids = np.asarray(ids, dtype=np.int32)
+    slot = ref.probe_table(ids, ids.size, order, wrap=False)[0]
+    return ref.unique_ids(np.where(slot < 0, -1, ids))
+
+
+def unique_by_first_claimer(ids, order):
+    """Wrong kernel 2: the slot remembers the index of the lane that claimed it, not the minimum over its lanes.  With `order` the
+    arrival order, the claimer of an id is its first index in that order; the later launches are the library's: index i is a first
+    touch if it is its id's remembered index, first touches are ranked in index order, local[i] is the rank of the remembered index."""
+    ids = np.asarray(ids, dtype=np.int32)
+    m = ids.size
+    claimed = {}
+    for i in np.asarray(order).tolist():
+        if ids[i] >= 0:
+            claimed.setdefault(int(ids[i]), i)
+    flag = np.zeros(m, dtype=bool)
+    flag[list(claimed.values())] = True
+    rank = np.cumsum(flag) - 1
+    unique, local = np.full(m, -1, dtype=np.int32), np.full(m, -1, dtype=np.int32)
+    unique[:int(flag.sum())] = ids[flag]
+    live = np.nonzero(ids >= 0)[0]
+    local[live] = [rank[claimed[int(v)]] for v in ids[live]]
+    return unique, local, int(flag.sum())
+
+
+def _differs(a, b):
+    return any(not np.array_equal(x, y) for x, y in zip(a[:2], b[:2])) or a[2] != b[2]
+
+
+def test_ids_with_home_inverts_the_hash():
+    assert ref.HASH * ref.HASH_INV % 2 ** 32 == 1
+    for m, homes in ((2, [0, 255]), (1000, [2047]), (70001, range(262144 - 64, 262144)), (2 ** 20, [0, 2 ** 21 - 1])):
+        ids = ref.ids_with_home(m, homes, 50)
+        assert ids.dtype == np.int32 and ids.min() >= 0 and np.unique(ids).size == ids.size == 50 * len(homes)
+        assert np.array_equal(ref.home_slots(ids, m), np.repeat(np.asarray(homes), 50))
+    with pytest.raises(AssertionError):
+        ref.ids_with_home(2 ** 20, [5], 2000)                      # a home of 2^21 slots has 2 048 values of y, half of them ids
+
+
+def test_probe_table_is_linear_probing():
+    """Against the loop over slots on a table small enough to fill by hand."""
+    ids = np.array([5, -1, 9, 5, 14, 9, 3, 22], dtype=np.int32)
+    homes = ref.home_slots(np.maximum(ids, 0), ids.size)
+    for order in (np.arange(8), np.arange(8)[::-1]):
+        table, want, longest, wraps = {}, np.full(8, -1), 0, 0
+        for i in order:
+            if ids[i] < 0:
+                continue
+            s, n = int(homes[i]), 1
+            while s in table and table[s] != ids[i]:
+                s, n = (s + 1) % 256, n + 1
+            wraps += int(s not in table and s < homes[i])
+            table[s] = ids[i]
+            want[i], longest = s, max(longest, n)
+        got = ref.probe_table(ids, 8, order)
+        assert np.array_equal(got[0], want) and got[1:] == (longest, wraps)
+    one = ref.ids_with_home(8, [255], 8)
+    slot, longest, wraps = ref.probe_table(one, 8, np.arange(8))
+    assert slot.tolist() == [255, 0, 1, 2, 3, 4, 5, 6] and (longest, wraps) == (8, 7)
+    slot, longest, wraps = ref.probe_table(one, 8, np.arange(8), wrap=False)
+    assert slot.tolist() == [255] + [-1] * 7 and wraps == 0
+
+
+@pytest.mark.parametrize("interleaved", [False, True])
+@pytest.mark.parametrize("m", gpu_table.ONE_HOME)
+def test_one_home_inputs_wrap_and_probe_far(m, interleaved):
+    ids = gpu_table.one_home(m, interleaved)
+    gpu_table.one_home_conditions(ids, m)
+    want = ref.unique_ids(ids)
+    for order in gpu_table.orders(ids.size):
+        wrong = unique_without_wrap(ids, order)
+        assert wrong[2] == 1 and want[2] == m and _differs(wrong, want)
+        assert int((wrong[1] == -1).sum()) - int((want[1] == -1).sum()) == (ids >= 0).sum() * (m - 1) // m      # every id but one: no slot
+    if interleaved:                                                # descending arrival: the claimer is an id's LAST appearance
+        wrong = unique_by_first_claimer(ids, np.arange(ids.size)[::-1])
+        assert wrong[2] == want[2] and _differs(wrong, want)
+        assert int((wrong[1] != want[1]).sum()) >= m and not np.array_equal(wrong[0], want[0])
+        assert not _differs(unique_by_first_claimer(ids, np.arange(ids.size)), want)      # in index order the claimer IS the minimum
+
+
+def test_cluster_inputs_wrap():
+    for m in gpu_table.CLUSTERS:
+        ids, at = gpu_table.cluster(m)
+        least = gpu_table.cluster_conditions(ids, at, m)
+        want = ref.unique_ids(ids)
+        if m > 70001:                                              # (the pigeonhole alone: the model takes seconds at 2^20)
+            continue
+        for order in gpu_table.orders(m):
+            _, longest, wraps = ref.probe_table(ids, m, order)
+            print(f"m {m}: {wraps} ids wrap, longest run {longest}")
+            assert wraps >= least and longest > gpu_table.CLUSTER_PER
+        wrong = unique_without_wrap(ids, np.arange(m))
+        assert want[2] - wrong[2] >= least and int((wrong[1] == -1).sum()) >= least
+
+
+def test_the_hot_key():
+    ids = gpu_table.hot_key()
+    unique, local, count = ref.unique_ids(ids)
+    assert ids.size == 2 ** 20 and count == 2 and np.all(local[:-1] == 0) and local[-1] == 1 and np.all(unique[2:] == -1)
+
+
+def test_find_edges_stride_case_and_a_stale_second_trip():
+    eids, want, named = gpu_stride.find_case()
+    assert eids.size == 2048 * 1024 + 1024 + 1 and set(named) >= {"-1", "E", "E + 5", "dead entry", "after two empty rows"}
+    for w in want:                                                 # wrong kernel 3
+        stale = gpu_stride.stale_second_trip(w, gpu_stride.FIND_STRIDE)
+        assert np.array_equal(stale[:gpu_stride.FIND_STRIDE], w[:gpu_stride.FIND_STRIDE]) and (stale != w).sum() >= 900
+    indptr, col = gpu_stride.graph()                               # wrong kernel 4, on the id placed for it
+    i = named["after two empty rows"][0]
+    assert ref.find_edges_lower_bound(indptr, col, eids[i:i + 1])[0][0] == 40 and want[0][i] == 42
+
+
+@pytest.mark.parametrize("shape", gpu_stride.NEG_SHAPES, ids=lambda s: f"{s['n']}x{s['k']}")
+def test_negative_stride_cases_and_a_stale_second_trip(shape):
+    rows, want, stats = gpu_stride.negative_case(shape)
+    print({k: v for k, v in stats.items() if not hasattr(v, "shape")}, "second-trip -1s", int((want.reshape(-1)[gpu_stride.NEG_STRIDE:] < 0).sum()))
+    stale = gpu_stride.stale_second_trip(want, gpu_stride.NEG_STRIDE)
+    late = want.size - gpu_stride.NEG_STRIDE
+    assert (stale != want).sum() * 2 >= late, "half of the second trip's slots at least"
+    if shape["exclude"] == 3:
+        assert shape["tries"] == 3 and (want.reshape(-1)[gpu_stride.NEG_STRIDE:] < 0).sum() == 128 + stats["exhausted"]
+
+
+@pytest.mark.parametrize("kind", gpu_stride.UNIQUE_KINDS)
+@pytest.mark.parametrize("m", gpu_stride.UNIQUE_COUNTS)
+def test_unique_stride_cases_and_a_stale_second_trip(m, kind):
+    ids = gpu_stride.stride_ids(kind, m)
+    want, firsts, repeats = gpu_stride.unique_conditions(kind, ids)
+    if (kind, m) == ("mix", 524545):
+        assert (firsts, repeats, int((ids[gpu_stride.UNIQUE_STRIDE:] == -1).sum())) == (51, 155, 51)
+    if m > gpu_stride.UNIQUE_STRIDE:
+        stale = gpu_stride.stale_second_trip(want[1], gpu_stride.UNIQUE_STRIDE)
+        assert not np.array_equal(stale, want[1])
+        if kind == "mix":                                          # the model of the claimer on an input with repeats all over
+            assert _differs(unique_by_first_claimer(ids, np.arange(m)[::-1]), want)
+    else:                                                          # the scan: per = 1 at 256 tiles, 2 from 257 on; 2 050 tiles: runs of 9, the last of 7
+        per = lambda tiles: (tiles + 255) // 256
+        assert (per((m + 255) // 256), (m + 255) // 256) in ((1, 256), (2, 257))
+        assert per(2050) == 9 and 2050 - 9 * (2050 // 9) == 7 and (524545 + 255) // 256 == 2050
+
+
+@pytest.mark.parametrize("name", sorted(ref.small_graphs()))
+def test_small_graphs_against_the_loop_and_a_lower_bound(name):
+    indptr, col, eids, want = gpu_find.small_case(name)
+    assert eids[0] == -2 and eids[-1] == col.size + 2
+    for i, e in enumerate(eids.tolist()):                          # the definition: the row whose range holds e
+        rows = [v for v in range(indptr.size - 1) if indptr[v] <= e < indptr[v + 1]] if 0 <= e < col.size and col[e] >= 0 else []
+        assert (want[0][i], want[1][i]) == ((rows[0], col[e]) if rows else (-1, -1)), (name, e)
+
+
+def test_the_small_graphs_are_what_they_are_called():
+    g = ref.small_graphs()
+    assert {ip.size - 1 for ip, _ in g.values()} >= {1, 2, 3, 254, 255, 256, 257, 64}
+    assert g["loop"][1].tolist() == [0] and np.diff(g["ends-empty"][0])[:3].tolist() == [0, 0, 0] == np.diff(g["ends-empty"][0])[-3:].tolist()
+    deg = np.diff(g["one-row"][0])
+    assert deg[17] == deg.sum() == 40 and deg.size == 64
+    for n in (254, 255, 256, 257):
+        d = np.diff(g[f"degrees-{n}"][0])
+        assert set(d.tolist()) == {0, 1, 2, 3} and (g[f"degrees-{n}"][1] < 0).sum() == 3
+    wrong = sum(int((ref.find_edges_lower_bound(ip, c, np.arange(c.size))[0] != ref.find_edges(ip, c, np.arange(c.size))[0]).sum()) for ip, c in g.values())
+    assert wrong >= 100                                            # wrong kernel 4 over all of them
+
+
+def test_the_find_edges_counts_split_a_lanes_four_ids():
+    """A lane's ids j = 0 .. 3 sit at lane + 256 j: id j is dead for every lane at n <= 256 j, for some at 256 j < n < 256 (j + 1)."""
+    for j in (1, 2, 3):
+        assert {256 * j, 256 * j + 1} <= set(gpu_find.COUNTS)
+    assert {1023, 1024, 1025, 2049, 5000} <= set(gpu_find.COUNTS)
+
+
+def test_one_vertex_and_the_big_draw():
+    ip, c = np.array([0, 1], dtype=np.int64), np.array([0], dtype=np.int32)
+    rows = np.zeros(50, dtype=np.int32)
+    assert np.all(ref.negative_sample(ip, c, rows, 5, 1, 3) == -1) and np.all(ref.negative_sample(ip, c, rows, 5, 0, 3) == 0)
+    indptr, col, rows, want = gpu_negative.big_case(gpu_negative.BIG[0])      # (its conditions are asserted inside)
+    assert indptr.size == 2 ** 24 + 4 and col.size == 1000 and np.all(np.diff(col) > 0) and rows.size == 5000 and want[3].shape == (5000, 5)
+
+
+def test_the_fuzz_seed_set_holds_its_conditions():
+    made = {}
+    gpu_fuzz.seed_set_conditions(lambda seed: made.setdefault(seed, gpu_fuzz.link_shape(seed)))
+    assert len(made) == 24
