@@ -448,6 +448,25 @@ void legion_gather_rows(legion_stream_t stream, const float* full_table, const f
                         const int32_t* node_map, int32_t node_capacity, int32_t float_feature_len,
                         int32_t total_num_nodes, const int32_t* sampled_ids, int32_t* cache_index_out,
                         const int32_t* range_devptr, float* dst, int32_t max_rows);
+/* legion_gather_rows with every argument of a gather launch, so that each instance of the gather kernel can be run alone.
+ *   dtype, out_dtype  LEGION_FEATURE_*: the row format of full_table and of every cache table, and that of dst.  bf16 source rows are
+ *                     round_up(float_feature_len, 8) elements apart (legion_feature_row_bytes), their pad elements are never stored;
+ *                     dst rows are float_feature_len elements of out_dtype, no pad.
+ *   node_slot         NULL, or int32 indexed like sampled_ids: the feature-cache slot carried for each row (what node_map[id] would
+ *                     give: a slot >= 0 or -2 for a miss), or -3 for "look it up".  Read only with a node_map.
+ *   dst_rows          rows dst holds: rows range[0] + r >= dst_rows are not written (a lane's feature buffer; legion_gather_rows
+ *                     passes INT32_MAX)
+ *   grid_rows         the rows the grid is sized for, 0 = max_rows (a lane with more rows is still gathered whole: workgroups walk tiles)
+ *   last_op           0 / 1: the kernel instance of a batch's early gathers / of its last one (legion_gather_rows runs the last one's)
+ *   plan_out          NULL, or host int32[3] filled before the call returns with what was launched: {row format 0 .. 5 = F32, F32Tail,
+ *                     F32Scalar, Bf16x8, Bf16Copy, F32Narrow; rows per tile; grid x}, {-1, 0, 0} where there was nothing to launch
+ *                     (float_feature_len <= 0 or max_rows <= 0).  LEGION_GATHER_ROWS (LegionTuning.gather_rows_per_wg) applies as in a batch.
+ * Returns 0, or -1 with nothing enqueued and plan_out untouched for a dtype or out_dtype that is no LEGION_FEATURE_*. */
+int32_t legion_gather_rows_fmt(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                               const void* const* cache_tables, const int32_t* node_map, int32_t node_capacity,
+                               int32_t float_feature_len, int32_t total_num_nodes, const int32_t* sampled_ids,
+                               const int32_t* node_slot, int32_t* cache_index_out, const int32_t* range_devptr, void* dst,
+                               int32_t max_rows, int32_t dst_rows, int32_t grid_rows, int32_t last_op, int32_t* plan_out);
 /* the draw of SS/engine/operator_impl.cu:235-238 evaluated on the GPU for n (idx, deg) pairs */
 void legion_draw_batch(legion_stream_t stream, const int32_t* idx, const int32_t* deg, int32_t* out,
                        int32_t n);

@@ -51,7 +51,8 @@ static inline GatherPlan gather_plan(int32_t dtype, int32_t out_dtype, int32_t D
     } else {
         // The tile whose SOURCE payload is 16 KB for rows of 512 bytes and more, 32 KB below: measured for float32 rows in round 3
         // (DESIGN.md 4.1); the bf16 formats take the same rule over their source rows, measured only against float32 at the headline
-        // shapes, not against other tile sizes (tools/feature_dtype_ab.py --rows R is the sweep still to run).
+        // shapes, not against other tile sizes (tools/feature_dtype_ab.py --rows R is the timing sweep still to run; every format is
+        // CHECKED at every tile size, tests/test_gpu_gather_formats.py).
         const int64_t row_bytes = gather_info(p.format).src_bf16 ? (int64_t)pitch * 2 : (int64_t)D * 4;
         const int64_t payload = row_bytes >= 512 ? 16384 : 32768;
         p.rows = 16;

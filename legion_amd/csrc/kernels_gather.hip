@@ -534,39 +534,54 @@ static inline int32_t gather_grid_x(int32_t max_rows, int32_t rows_per_tile, int
 }
 
 // the instance of format F with the plan's tile size (walking ROWS = 16, 32, ... 256 over the sizes gather_info(F).tiles has); the
-// LASTOP instance for the gather of a batch's last op
+// LASTOP instance for the gather of a batch's last op.  Returns the launch's grid x (0: the format has no such tile size).
 template <typename VecT, GatherFormat F, int ROWS = 16>
-static void launch_format(hipStream_t s, int32_t rows, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
+static int32_t launch_format(hipStream_t s, int32_t rows, const GatherParams& gk, int32_t grid_rows, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
 {
     constexpr GatherFormatInfo fi = gather_info(F);
     if constexpr ((fi.tiles & ROWS) != 0) {
-        const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
-        if (rows == ROWS && gk.last_op) gather_kernel<VecT, ROWS, fi.unroll, fi.tail, true><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
-        else if (rows == ROWS) gather_kernel<VecT, ROWS, fi.unroll, fi.tail, false><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
+        if (rows == ROWS) {
+            const dim3 grid(gather_grid_x(grid_rows, ROWS, n_lanes), n_lanes);
+            if (gk.last_op) gather_kernel<VecT, ROWS, fi.unroll, fi.tail, true><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
+            else gather_kernel<VecT, ROWS, fi.unroll, fi.tail, false><<<grid, LG_GATHER_THREADS, 0, s>>>(gk, d_lanes, copy_range);
+            return (int32_t)grid.x;
+        }
     }
-    if constexpr (ROWS < 256) launch_format<VecT, F, ROWS * 2>(s, rows, gk, grid_rows, d_lanes, n_lanes, copy_range);
+    if constexpr (ROWS < 256) return launch_format<VecT, F, ROWS * 2>(s, rows, gk, grid_rows, d_lanes, n_lanes, copy_range);
+    return 0;
 }
 
-// gk: what the kernel gets (max_rows = the clamp); grid_rows: what sizes the launch, the rows a lane typically has (GatherParams.grid_rows)
-static void launch_gather_impl(hipStream_t s, GatherParams gk, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range)
+// the plan of a gather launch over n_lanes lanes; grid_rows: what sizes the launch, the rows a lane typically has (GatherParams.grid_rows)
+static GatherPlan plan_of_launch(const GatherParams& gk, int32_t n_lanes, int32_t& grid_rows)
 {
-    if (gk.D <= 0 || gk.max_rows <= 0) return;      // :256 float_feature_len > 0
+    grid_rows = gk.grid_rows > 0 && gk.grid_rows < gk.max_rows ? gk.grid_rows : gk.max_rows;
+    return gather_plan(gk.dtype, gk.out_dtype, gk.D, gk.pitch, grid_rows, n_lanes, tuning().gather_rows_per_wg);
+}
+
+// gk: what the kernel gets (max_rows = the clamp).  Returns the plan it launched and sets grid_x to the launch's grid x (0: nothing to
+// launch).
+static GatherPlan launch_gather_impl(hipStream_t s, GatherParams gk, const LanePtrs* d_lanes, int32_t n_lanes, bool copy_range, int32_t* grid_x = nullptr)
+{
+    if (grid_x != nullptr) *grid_x = 0;
+    if (gk.D <= 0 || gk.max_rows <= 0) return {GatherPlan::OK, GatherFormat::F32, 0};      // :256 float_feature_len > 0
     if (gk.node_capacity < 1) gk.node_capacity = 1;
-    const int32_t grid_rows = gk.grid_rows > 0 && gk.grid_rows < gk.max_rows ? gk.grid_rows : gk.max_rows;
-    const GatherPlan p = gather_plan(gk.dtype, gk.out_dtype, gk.D, gk.pitch, grid_rows, n_lanes, tuning().gather_rows_per_wg);
+    int32_t grid_rows, gx = 0;
+    const GatherPlan p = plan_of_launch(gk, n_lanes, grid_rows);
     if (p.error == GatherPlan::BAD_DTYPE) printf("gather: unknown feature dtype %d or output dtype %d\n", gk.dtype, gk.out_dtype);
     if (p.error == GatherPlan::BAD_PITCH) printf("gather: bf16 rows need a pitch that is a multiple of 8 and at least D (pitch %d, D %d)\n", gk.pitch, gk.D);
     if (p.error != GatherPlan::OK) exit(EXIT_FAILURE);
     typedef GatherFormat GF;
     switch (p.format) {     // the row type of each format
-        case GF::F32:       launch_format<f32x4, GF::F32>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case GF::F32Tail:   launch_format<f32x4, GF::F32Tail>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case GF::F32Scalar: launch_format<float, GF::F32Scalar>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case GF::Bf16x8:    launch_format<Bf16x8, GF::Bf16x8>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case GF::Bf16Copy:  launch_format<Bf16Copy, GF::Bf16Copy>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
-        case GF::F32Narrow: launch_format<F32Narrow, GF::F32Narrow>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32:       gx = launch_format<f32x4, GF::F32>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Tail:   gx = launch_format<f32x4, GF::F32Tail>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Scalar: gx = launch_format<float, GF::F32Scalar>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::Bf16x8:    gx = launch_format<Bf16x8, GF::Bf16x8>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::Bf16Copy:  gx = launch_format<Bf16Copy, GF::Bf16Copy>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
+        case GF::F32Narrow: gx = launch_format<F32Narrow, GF::F32Narrow>(s, p.rows, gk, grid_rows, d_lanes, n_lanes, copy_range); break;
     }
     hipCheckError();
+    if (grid_x != nullptr) *grid_x = gx;
+    return p;
 }
 
 void launch_gather(hipStream_t s, const GatherParams& g, const LanePtrs* d_lanes, int32_t n_lanes)
@@ -574,25 +589,35 @@ void launch_gather(hipStream_t s, const GatherParams& g, const LanePtrs* d_lanes
     launch_gather_impl(s, g, d_lanes, n_lanes, true);
 }
 
-// stand-alone form (tests, probes): explicit arrays; a one-lane descriptor is staged on the stream
-void launch_gather_explicit(hipStream_t s, const GatherParams& g, const int32_t* sampled_ids,
-                            int32_t* cache_index_out, const int32_t* range, float* dst, int32_t dst_rows)
+// stand-alone form (tests, probes): explicit arrays; a one-lane descriptor is staged on the stream.  node_slot: the lane's carried
+// slots or null; g.last_op picks the instance; plan_out: null, or host {format, rows per tile, grid x} of the launch made ({-1, 0, 0}
+// where there was nothing to launch).  Returns 0, or -1 with nothing enqueued for a dtype or pitch the plan refuses.
+int32_t launch_gather_explicit(hipStream_t s, const GatherParams& g, const int32_t* sampled_ids, const int32_t* node_slot,
+                               int32_t* cache_index_out, const int32_t* range, void* dst, int32_t dst_rows, int32_t* plan_out)
 {
+    int32_t grid_rows, gx = 0;
+    if (plan_of_launch(g, 1, grid_rows).error != GatherPlan::OK) return -1;
     static thread_local LanePtrs* d_lane = nullptr;
     if (d_lane == nullptr) HIP_CALL(hipMalloc(&d_lane, sizeof(LanePtrs)));
     LanePtrs h;
     memset(&h, 0, sizeof(h));
     h.sampled_ids = const_cast<int32_t*>(sampled_ids);
+    h.node_slot = const_cast<int32_t*>(node_slot);
     h.cache_search_buffer = cache_index_out;
     h.node_counter = const_cast<int32_t*>(range);
-    h.float_features = dst;
+    h.float_features = static_cast<float*>(dst);
     h.feature_rows = dst_rows;
     GatherParams ge = g;
     ge.hop = -1;
     ge.first_hop = -1;
-    ge.last_op = true;
     HIP_CALL(hipMemcpyAsync(d_lane, &h, sizeof(h), hipMemcpyHostToDevice, s));   // pageable source: staged before return
-    launch_gather_impl(s, ge, d_lane, 1, false);
+    const GatherPlan p = launch_gather_impl(s, ge, d_lane, 1, false, &gx);
+    if (plan_out != nullptr) {
+        plan_out[0] = gx > 0 ? (int32_t)p.format : -1;
+        plan_out[1] = gx > 0 ? p.rows : 0;
+        plan_out[2] = gx;
+    }
+    return 0;
 }
 
 }  // namespace lg

@@ -834,9 +834,9 @@ void launch_bulk_push(hipStream_t s, const float* stripe, int32_t D, const int32
 void launch_gather(hipStream_t s, const GatherParams& g, const LanePtrs* d_lanes, int32_t n_lanes);
 void launch_deliver(hipStream_t s, const LanePtrs* d_lane, const DeliverParams& d);
 // the whole finished batch of a lane -- ids, feature rows, labels, both edge arrays, counters -- copied into a pipe slot
-// stand-alone form for tests / probes: explicit arrays, one lane
-void launch_gather_explicit(hipStream_t s, const GatherParams& g, const int32_t* sampled_ids,
-                            int32_t* cache_index_out, const int32_t* range, float* dst, int32_t dst_rows);
+// stand-alone form for tests / probes: explicit arrays, one lane (node_slot, plan_out may be null); -1 = refused by the plan, nothing enqueued
+int32_t launch_gather_explicit(hipStream_t s, const GatherParams& g, const int32_t* sampled_ids, const int32_t* node_slot,
+                               int32_t* cache_index_out, const int32_t* range, void* dst, int32_t dst_rows, int32_t* plan_out);
 
 struct SeedParams {
     int32_t batch_size;

@@ -328,11 +328,11 @@ private:
 Operator* NewSSDIOCompleteOP(int op_id) { return new SSDIOCompleteOP(op_id); }
 
 // ---- kernel-level C entry points ----------------------------------------------------------
-extern "C" void legion_gather_rows(legion_stream_t stream, const float* full_table,
-                                   const float* const* cache_tables, const int32_t* node_map,
-                                   int32_t node_capacity, int32_t float_feature_len, int32_t total_num_nodes,
-                                   const int32_t* sampled_ids, int32_t* cache_index_out,
-                                   const int32_t* range_devptr, float* dst, int32_t max_rows)
+extern "C" int32_t legion_gather_rows_fmt(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                                          const void* const* cache_tables, const int32_t* node_map, int32_t node_capacity,
+                                          int32_t float_feature_len, int32_t total_num_nodes, const int32_t* sampled_ids,
+                                          const int32_t* node_slot, int32_t* cache_index_out, const int32_t* range_devptr, void* dst,
+                                          int32_t max_rows, int32_t dst_rows, int32_t grid_rows, int32_t last_op, int32_t* plan_out)
 {
     lg::GatherParams g;
     g.replica = nullptr;
@@ -341,24 +341,36 @@ extern "C" void legion_gather_rows(legion_stream_t stream, const float* full_tab
     g.member = 0;
     g.striped = true;               // the caller's node_map may address several tables: always decode (owner, row)
     g.stats = nullptr;
-    g.full_table = full_table;
-    g.cache_tables = cache_tables;
+    g.full_table = static_cast<const float*>(full_table);
+    g.cache_tables = reinterpret_cast<const float* const*>(cache_tables);
     g.local_table = nullptr;
     g.node_map = node_map;
     g.node_capacity = node_capacity;
     g.D = float_feature_len;
     g.skip_remote = false;
-    g.grid_rows = 0;
+    g.grid_rows = grid_rows;
+    g.last_op = last_op != 0;
     g.hybrid = false;
     g.hybrid_cpu_cap = g.hybrid_gpu_cap = 0;
     g.hybrid_cpu_cache = nullptr;
     g.total_num_nodes = total_num_nodes;
     g.max_rows = max_rows;
-    g.dtype = LEGION_FEATURE_F32;
-    g.pitch = float_feature_len;
-    g.out_dtype = LEGION_FEATURE_F32;
-    lg::launch_gather_explicit(static_cast<hipStream_t>(stream), g, sampled_ids, cache_index_out, range_devptr, dst,
-                               0x7FFFFFFF);
+    g.dtype = dtype;
+    g.pitch = lg_feature_pitch(dtype, float_feature_len);
+    g.out_dtype = out_dtype;
+    return lg::launch_gather_explicit(static_cast<hipStream_t>(stream), g, sampled_ids, node_slot, cache_index_out, range_devptr, dst,
+                                      dst_rows, plan_out);
+}
+
+extern "C" void legion_gather_rows(legion_stream_t stream, const float* full_table,
+                                   const float* const* cache_tables, const int32_t* node_map,
+                                   int32_t node_capacity, int32_t float_feature_len, int32_t total_num_nodes,
+                                   const int32_t* sampled_ids, int32_t* cache_index_out,
+                                   const int32_t* range_devptr, float* dst, int32_t max_rows)
+{
+    legion_gather_rows_fmt(stream, LEGION_FEATURE_F32, LEGION_FEATURE_F32, full_table, reinterpret_cast<const void* const*>(cache_tables),
+                           node_map, node_capacity, float_feature_len, total_num_nodes, sampled_ids, nullptr, cache_index_out,
+                           range_devptr, dst, max_rows, 0x7FFFFFFF, 0, 1, nullptr);
 }
 
 extern "C" void legion_draw_batch(legion_stream_t stream, const int32_t* idx, const int32_t* deg, int32_t* out,

@@ -139,6 +139,7 @@ SIGNATURES = {
     "legion_pipeline_regather_last": (c_i32, [c_p, c_i32, c_i32, c_i32, ctypes.POINTER(ctypes.c_double)]),
     # 4. kernel-level
     "legion_gather_rows": (None, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_i32]),
+    "legion_gather_rows_fmt": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, P_I32]),
     "legion_draw_batch": (None, [c_p, c_p, c_p, c_p, c_i32]),
     "legion_draw_distinct_batch": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32]),
     "legion_draw_weighted_batch": (None, [c_p, c_p, c_p, c_p, c_p, c_p, c_i32]),
