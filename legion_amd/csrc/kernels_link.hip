@@ -4,10 +4,10 @@
 //
 // The rules are the contracts in include/legion_hip.h (legion_find_edges, legion_negative_sample, legion_unique_ids).  The layout:
 //   * find_edges, negative_sample: one lane per output (find_edges: per four), 256 lanes per workgroup, a grid of at most 2 048 workgroups that strides over
-//     tiles (the walks' cap, kernels_walk.hip); consecutive lanes write consecutive outputs.  Every offset into indptr and col is 64
+//     tiles (the walks' cap, walk_step.h); consecutive lanes write consecutive outputs.  Every offset into indptr and col is 64
 //     bits wide.  negative_sample is a flat loop over tries with the two exclusions as template flags: the instance without either
 //     loads nothing but rows, the row pair {s, e} of the edge exclusion is loaded once per slot, and try t + 1 is try t times the
-//     constant 48271^(2^23) -- node2vec's stepping (kernels_node2vec.hip): one table look-up per slot;
+//     constant 48271^(2^23) -- node2vec's stepping and row search (kPow23, row_has: walk_step.h): one table look-up per slot;
 //   * find_edges: a lane searches for four edge ids at once, 256 apart, their chains of dependent loads interleaved -- the op is bound
 //     by latency times loads in flight.  Measured against one and two ids per lane and against the top eight levels of the search
 //     staged in LDS, which gained nothing beside it and is not built;
@@ -29,16 +29,9 @@
 namespace lg {
 
 #define LG_LINK_THREADS 256
-#define LG_LINK_MAX_WG 2048      // 256 CUs x 8 resident workgroups: every further tile is a stride of the grid
 #define LG_FIND_EDGES_ILP 4      // edge ids per lane, searched for at once (1, 2 and 4 measured: DESIGN.md 4.14)
 
-static constexpr uint32_t kLinkPow23 = make_pow_tables().t2[2];      // 48271^(2^23): from a try's draw to the next try's
-
-static inline dim3 link_grid(int64_t outputs)
-{
-    const int64_t tiles = (outputs + LG_LINK_THREADS - 1) / LG_LINK_THREADS;
-    return dim3((uint32_t)(tiles < LG_LINK_MAX_WG ? tiles : LG_LINK_MAX_WG));
-}
+static_assert(LG_LINK_THREADS == LG_WALK_THREADS, "the grids below are walk_grid's: a tile of 256 outputs, the walks' cap");
 
 // a tile is 256 x ILP edge ids; a lane's ILP ids lie 256 apart, so consecutive lanes read and write consecutive entries
 __global__ __launch_bounds__(LG_LINK_THREADS, 8) void find_edges_kernel(const int64_t* indptr, const int32_t* col, int32_t node_num,
@@ -94,7 +87,7 @@ void launch_find_edges(hipStream_t s, const int64_t* indptr, const int32_t* col,
                        int32_t n, int32_t* row_out, int32_t* col_out)
 {
     if (n <= 0) return;
-    const dim3 grid = link_grid(((int64_t)n + LG_FIND_EDGES_ILP - 1) / LG_FIND_EDGES_ILP);
+    const dim3 grid = walk_grid(((int64_t)n + LG_FIND_EDGES_ILP - 1) / LG_FIND_EDGES_ILP);
     find_edges_kernel<<<grid, LG_LINK_THREADS, 0, s>>>(indptr, col, node_num, num_edges, eids, n, row_out, col_out);
     hipCheckError();
 }
@@ -117,19 +110,9 @@ __global__ __launch_bounds__(LG_LINK_THREADS, 8) void negative_sample_kernel(Neg
             uint32_t x = minstd_pow((uint32_t)(p.base + m) + 1u);
             for (int32_t t = 0; t < p.max_tries; t++) {
                 const int32_t u = draw_from_x(x, p.node_num);         // r01 < 1: u <= node_num - 1
-                bool reject = SELF && u == r;
-                if (EDGES && !reject) {                               // is u in r's row?  (s + D <= E: probes inside col)
-                    const int32_t* c = p.col + s;
-                    int32_t lo = 0, len = D;
-                    while (len > 0) {
-                        const int32_t half = len >> 1, cv = c[lo + half];
-                        if (cv == u) { reject = true; break; }
-                        if (cv < u) { lo += half + 1; len -= half + 1; }
-                        else len = half;
-                    }
-                }
+                const bool reject = (SELF && u == r) || (EDGES && row_has(p.col + s, D, u));      // (s + D <= E: probes inside col)
                 if (!reject) { out = u; break; }
-                x = mulmod31(x, kLinkPow23);
+                x = mulmod31(x, kPow23);
             }
         }
         p.neg[m] = out;
@@ -141,7 +124,7 @@ void launch_negative_sample(hipStream_t s, const NegativeParams& p)
 {
     const int64_t total = (int64_t)p.n * p.k;
     if (total <= 0) return;
-    const dim3 grid = link_grid(total);
+    const dim3 grid = walk_grid(total);
     switch (p.exclude & 3) {
     case 0: negative_sample_kernel<false, false><<<grid, LG_LINK_THREADS, 0, s>>>(p); break;
     case 1: negative_sample_kernel<true, false><<<grid, LG_LINK_THREADS, 0, s>>>(p); break;
@@ -293,14 +276,14 @@ void launch_unique_ids(hipStream_t s, const int32_t* ids, int32_t m, int32_t* un
     while (((int64_t)1 << bits) < slots) bits++;
     p.shift = 32 - bits;                                              // slots in [2^8, 2^21]
     if (m > 0) {
-        const dim3 grid = link_grid(m);
-        unique_clear_kernel<<<link_grid(2 * slots), LG_LINK_THREADS, 0, s>>>(reinterpret_cast<uint32_t*>(p.keys), 2 * slots);
+        const dim3 grid = walk_grid(m);
+        unique_clear_kernel<<<walk_grid(2 * slots), LG_LINK_THREADS, 0, s>>>(reinterpret_cast<uint32_t*>(p.keys), 2 * slots);
         unique_insert_kernel<<<grid, LG_LINK_THREADS, 0, s>>>(p);
         unique_count_kernel<<<grid, LG_LINK_THREADS, 0, s>>>(p);
     }
     unique_scan_kernel<<<1, LG_LINK_THREADS, 0, s>>>(p);              // (m == 0: no tiles, count = 0)
     if (m > 0) {
-        const dim3 grid = link_grid(m);
+        const dim3 grid = walk_grid(m);
         unique_apply_kernel<<<grid, LG_LINK_THREADS, 0, s>>>(p);
         unique_scatter_kernel<<<grid, LG_LINK_THREADS, 0, s>>>(p);
     }

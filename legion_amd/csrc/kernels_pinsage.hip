@@ -38,7 +38,6 @@ namespace lg {
 
 #define LG_PINSAGE_THREADS 256
 #define LG_PINSAGE_SLOTS 2048        // visit slots of a tile: S * VPAD
-#define LG_PINSAGE_MAX_WG 2048       // 256 CUs x 8 resident workgroups: every further tile is a stride of the grid
 #define LG_PINSAGE_EMPTY 0x7FFFFFFF  // no vertex (ids are below node_num <= INT32_MAX) and no key (keys are below 2^20)
 
 static_assert(LEGION_PINSAGE_MAX_VISITS == 1024, "the key holds 1024 - count and a position in 10 bits each");
@@ -217,7 +216,7 @@ static void launch_pinsage_class(hipStream_t s, const PinsageParams& p)
 {
     constexpr int64_t S = LG_PINSAGE_SLOTS / VPAD;
     const int64_t n_tiles = ((int64_t)p.walk.num_walks + S - 1) / S;
-    const dim3 grid((uint32_t)(n_tiles < LG_PINSAGE_MAX_WG ? n_tiles : LG_PINSAGE_MAX_WG));
+    const dim3 grid((uint32_t)(n_tiles < LG_WALK_MAX_WG ? n_tiles : LG_WALK_MAX_WG));
     const bool weighted = p.walk.edge_cdf != nullptr, restart = p.walk.restart_prob > 0.0f;
     if (weighted) {
         if (restart) pinsage_neighbors_kernel<VPAD, true, true><<<grid, LG_PINSAGE_THREADS, 0, s>>>(p);

@@ -7,6 +7,13 @@
 #include <cstdint>
 
 #include "../../include/legion_hip.h"
+// The checks every walk op shares, beside this file.  The second path exists for one caller only: tests/test_node2vec_rule_cpu.py
+// compiles a COPY of this header alone from a temporary directory with -I <repository>/include, where the first is not found.
+#if __has_include("walk_rule.h")
+#include "walk_rule.h"
+#else
+#include "../legion_amd/csrc/walk_rule.h"
+#endif
 
 struct Node2vecBias {
     double a, b, mx;                // the acceptance weights of "return" (u == t) and "other" (u no neighbour of t), and the envelope
@@ -28,9 +35,9 @@ constexpr Node2vecRefusal node2vec_refusal(int32_t num_walks, int32_t length, in
                                            int32_t max_tries, float p, float q, int32_t rows_sorted)
 {
     if (num_walks < 0 || length < 1 || base < 0) return Node2vecRefusal::Count;
-    if (base + (int64_t)num_walks * (int64_t)length > (int64_t)0x7FFFFFFF) return Node2vecRefusal::DrawIndex;      // (each term < 2^62)
-    if (weighted != 0 && weighted != 1) return Node2vecRefusal::Weighted;
-    if (weighted == 1 && !graph_has_table) return Node2vecRefusal::NoTable;
+    if (walk_draw_index_past(base, num_walks, length)) return Node2vecRefusal::DrawIndex;
+    if (!walk_flag(weighted)) return Node2vecRefusal::Weighted;
+    if (walk_lacks_table(weighted, graph_has_table)) return Node2vecRefusal::NoTable;
     if (max_tries < 1 || max_tries > LEGION_NODE2VEC_MAX_TRIES) return Node2vecRefusal::Tries;
     if (!(p > 0.0f) || !(q > 0.0f) || p > 3.402823466e+38f || q > 3.402823466e+38f) return Node2vecRefusal::Bias;      // (NaN fails p > 0)
     const Node2vecBias w = node2vec_bias(p, q);

@@ -15,6 +15,7 @@
 //   * there is no accessed bitmap and no position map: first touches keep no per-vertex state (see
 //     legion_core.h), so BatchGenerate has nothing to memset and IOComplete nothing to restore.
 #include "legion_core.h"
+#include "walk_rule.h"
 #include "node2vec_rule.h"
 #include "link_rule.h"
 
@@ -393,34 +394,27 @@ extern "C" int32_t legion_draw_distinct_batch(legion_stream_t stream, const int3
     return 0;
 }
 
-// Random walks over the full CSR (the rule and the refusals: legion_hip.h).  Every check comes before the launch: a refused call
-// enqueues nothing and touches no buffer.
+// Random walks over the full CSR (the rule: legion_hip.h; the refusals: walk_rule.h).  Every check comes before the launch: a refused
+// call enqueues nothing and touches no buffer.
+static lg::WalkParams walk_params(GraphStorage* graph, const int32_t* seeds, int32_t num_walks, int32_t length, int32_t weighted,
+                                  float restart_prob, int64_t base, int32_t* traces, int64_t* edge_ids)
+{
+    return lg::WalkParams{.indptr = graph->GetCSRNodeIndexCPU(), .col = graph->GetCSRNodeMatrixCPU(),
+                          .edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr, .seeds = seeds, .traces = traces, .edge_ids = edge_ids,
+                          .node_num = graph->NodeNum(), .num_walks = num_walks, .length = length, .restart_prob = restart_prob, .base = base};
+}
+
 extern "C" int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_walks,
                                       int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
                                       int64_t* edge_ids_out)
 {
     GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
     if (!graph || !seeds_devptr || !traces_out) return -1;
-    if (num_walks < 0 || length < 1 || base < 0) return -1;
-    if (base + (int64_t)num_walks * (int64_t)length > (int64_t)0x7FFFFFFF) return -1;       // (each term < 2^62: no overflow once base is bounded below)
-    if (weighted != 0 && weighted != 1) return -1;
-    if (weighted == 1 && graph->EdgeCdf() == nullptr) return -1;
-    if (!(restart_prob >= 0.0f && restart_prob <= 1.0f)) return -1;                         // (NaN fails both comparisons)
+    if (walk_refusal(num_walks, length, base, weighted, graph->EdgeCdf() != nullptr, restart_prob) != WalkRefusal::Ok) return -1;
     if (num_walks == 0) return 0;
     if (weighted == 1) graph->MarkWeightedUsed();       // the table stays as it is from here on, as after a weighted hop
-    lg::WalkParams p;
-    p.indptr = graph->GetCSRNodeIndexCPU();
-    p.col = graph->GetCSRNodeMatrixCPU();
-    p.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
-    p.seeds = seeds_devptr;
-    p.traces = traces_out;
-    p.edge_ids = edge_ids_out;
-    p.node_num = graph->NodeNum();
-    p.num_walks = num_walks;
-    p.length = length;
-    p.restart_prob = restart_prob;
-    p.base = base;
-    lg::launch_random_walk(static_cast<hipStream_t>(stream), p);
+    lg::launch_random_walk(static_cast<hipStream_t>(stream),
+                           walk_params(graph, seeds_devptr, num_walks, length, weighted, restart_prob, base, traces_out, edge_ids_out));
     return 0;
 }
 
@@ -438,60 +432,27 @@ extern "C" int32_t legion_node2vec_walk(legion_stream_t stream, LegionGraphStora
     if (num_walks == 0) return 0;
     if (weighted == 1) graph->MarkWeightedUsed();
     const Node2vecBias bias = node2vec_bias(p, q);
-    lg::Node2vecParams k;
-    k.walk.indptr = graph->GetCSRNodeIndexCPU();
-    k.walk.col = graph->GetCSRNodeMatrixCPU();
-    k.walk.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
-    k.walk.seeds = seeds_devptr;
-    k.walk.traces = traces_out;
-    k.walk.edge_ids = edge_ids_out;
-    k.walk.node_num = graph->NodeNum();
-    k.walk.num_walks = num_walks;
-    k.walk.length = length;
-    k.walk.restart_prob = 0.0f;
-    k.walk.base = base;
-    k.a = bias.a;
-    k.b = bias.b;
-    k.mx = bias.mx;
-    k.lo = bias.lo;
-    k.hi = bias.hi;
-    k.max_tries = max_tries;
+    const lg::Node2vecParams k{.walk = walk_params(graph, seeds_devptr, num_walks, length, weighted, 0.0f, base, traces_out, edge_ids_out),
+                               .a = bias.a, .b = bias.b, .mx = bias.mx, .lo = bias.lo, .hi = bias.hi, .max_tries = max_tries};
     lg::launch_node2vec_walk(static_cast<hipStream_t>(stream), k);
     return 0;
 }
 
-// PinSAGE's neighbour sampler (the rule and the refusals: legion_hip.h).  As above: every check comes before the launch.
+// PinSAGE's neighbour sampler (the rule: legion_hip.h; the refusals: walk_rule.h).  As above: every check comes before the launch.
 extern "C" int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_seeds,
                                             int32_t num_walks_per_seed, int32_t walk_length, int32_t num_neighbors, int32_t weighted,
                                             float termination_prob, int64_t base, int32_t* neighbors_out, int32_t* counts_out)
 {
     GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
     if (!graph || !seeds_devptr || !neighbors_out || !counts_out) return -1;
-    if (num_seeds < 0 || num_walks_per_seed < 1 || walk_length < 1 || num_neighbors < 1 || base < 0) return -1;
-    const int64_t visits = (int64_t)num_walks_per_seed * (int64_t)walk_length;
-    if (visits > LEGION_PINSAGE_MAX_VISITS || num_neighbors > LEGION_PINSAGE_MAX_VISITS) return -1;
-    if (base > (int64_t)0x7FFFFFFF || base + (int64_t)num_seeds * visits > (int64_t)0x7FFFFFFF) return -1;      // (num_seeds * visits < 2^41)
-    if (weighted != 0 && weighted != 1) return -1;
-    if (weighted == 1 && graph->EdgeCdf() == nullptr) return -1;
-    if (!(termination_prob >= 0.0f && termination_prob <= 1.0f)) return -1;                 // (NaN fails both comparisons)
+    if (pinsage_refusal(num_seeds, num_walks_per_seed, walk_length, num_neighbors, base, weighted, graph->EdgeCdf() != nullptr,
+                        termination_prob) != WalkRefusal::Ok)
+        return -1;
     if (num_seeds == 0) return 0;
     if (weighted == 1) graph->MarkWeightedUsed();
-    lg::PinsageParams p;
-    p.walk.indptr = graph->GetCSRNodeIndexCPU();
-    p.walk.col = graph->GetCSRNodeMatrixCPU();
-    p.walk.edge_cdf = weighted == 1 ? graph->EdgeCdf() : nullptr;
-    p.walk.seeds = seeds_devptr;
-    p.walk.traces = nullptr;
-    p.walk.edge_ids = nullptr;
-    p.walk.node_num = graph->NodeNum();
-    p.walk.num_walks = num_seeds;
-    p.walk.length = walk_length;
-    p.walk.restart_prob = termination_prob;
-    p.walk.base = base;
-    p.walks_per_seed = num_walks_per_seed;
-    p.num_neighbors = num_neighbors;
-    p.neighbors = neighbors_out;
-    p.counts = counts_out;
+    const lg::PinsageParams p{.walk = walk_params(graph, seeds_devptr, num_seeds, walk_length, weighted, termination_prob, base, nullptr, nullptr),
+                              .walks_per_seed = num_walks_per_seed, .num_neighbors = num_neighbors, .neighbors = neighbors_out,
+                              .counts = counts_out};
     lg::launch_pinsage_neighbors(static_cast<hipStream_t>(stream), p);
     return 0;
 }

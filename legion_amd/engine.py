@@ -174,6 +174,45 @@ def _as_1d(x, dtype, name):
     return x
 
 
+def _need_bool(name, flag):
+    if not isinstance(flag, bool):
+        raise ValueError(f"{name} must be True or False, not {flag!r}")
+
+
+def _need_int(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
+        raise ValueError(f"{name} must be an integer, not {value!r}")
+
+
+def _need_prob(name, value):
+    if isinstance(value, bool) or not isinstance(value, (int, float, np.floating, np.integer)):
+        raise ValueError(f"{name} must be a number in [0, 1], not {value!r}")
+    if not 0.0 <= float(np.float32(value)) <= 1.0:       # (NaN fails; the library sees the float32)
+        raise ValueError(f"{name} must lie in [0, 1], not {value!r}")
+
+
+def _need_draw_indices(base, count, what):
+    """The draw indices base .. base + count - 1 (count spelled `what`) exist: the last one is 2^31 - 2."""
+    if base < 0:
+        raise ValueError(f"base must not be negative, not {base}")
+    if base + count > 2 ** 31 - 1:
+        raise ValueError(f"base + {what} = {base + count} is past the last draw index, 2^31 - 1")
+
+
+def _enqueue(lib, c_name, op, dev, stream, args, tensors):
+    """The tail of every op over the graph: the C call on dev with `stream` (default: the current one) in front of args, a refusal the
+    op's own checks should have caught as a RuntimeError, and the call's tensors (None: not used) recorded on a stream that is not the
+    allocator's."""
+    with torch.cuda.device(dev):
+        rc = getattr(lib, c_name)(_stream_handle(stream), *args)
+    if rc != 0:
+        raise RuntimeError(f"{c_name} refused arguments that {op} had accepted")
+    if stream is not None:
+        for x in tensors:
+            if x is not None:
+                x.record_stream(stream)
+
+
 UNIQUE_MAX_IDS = 2 ** 20                             # LEGION_UNIQUE_MAX_IDS
 
 
@@ -201,13 +240,8 @@ def unique_ids(ids, stream=None):
     count = torch.empty((1,), dtype=torch.int32, device=dev)
     nbytes = int(L.legion_unique_ids_scratch_bytes(m))
     scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
-    with torch.cuda.device(dev):
-        rc = L.legion_unique_ids(_stream_handle(stream), _ptr(ids), m, _ptr(unique), _ptr(local), _ptr(count), _ptr(scratch), nbytes)
-    if rc != 0:
-        raise RuntimeError("legion_unique_ids refused arguments that unique_ids had accepted")
-    if stream is not None:                           # (tensors of this call, used on a stream that is not the allocator's)
-        for x in (ids, unique, local, count, scratch):
-            x.record_stream(stream)
+    _enqueue(L, "legion_unique_ids", "unique_ids", dev, stream,
+             (_ptr(ids), m, _ptr(unique), _ptr(local), _ptr(count), _ptr(scratch), nbytes), (ids, unique, local, count, scratch))
     return unique, local, count
 
 
@@ -255,22 +289,14 @@ class GraphStorage:
     @staticmethod
     def _check_walk(n, length, weighted, restart_prob, return_eids, base):
         """random_walk's arguments by the rules of legion_random_walk, before anything touches a device: ValueError with the reason."""
-        for name, flag in (("weighted", weighted), ("return_eids", return_eids)):
-            if not isinstance(flag, bool):
-                raise ValueError(f"{name} must be True or False, not {flag!r}")
-        for name, value in (("length", length), ("base", base)):
-            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-                raise ValueError(f"{name} must be an integer, not {value!r}")
+        _need_bool("weighted", weighted)
+        _need_bool("return_eids", return_eids)
+        _need_int("length", length)
+        _need_int("base", base)
         if length < 1:
             raise ValueError(f"length must be at least 1, not {length}")
-        if base < 0:
-            raise ValueError(f"base must not be negative, not {base}")
-        if base + n * length > 2 ** 31 - 1:
-            raise ValueError(f"base + num_walks * length = {base + n * length} is past the last draw index, 2^31 - 1")
-        if isinstance(restart_prob, bool) or not isinstance(restart_prob, (int, float, np.floating, np.integer)):
-            raise ValueError(f"restart_prob must be a number in [0, 1], not {restart_prob!r}")
-        if not 0.0 <= float(np.float32(restart_prob)) <= 1.0:      # (NaN fails; the library sees the float32)
-            raise ValueError(f"restart_prob must lie in [0, 1], not {restart_prob!r}")
+        _need_draw_indices(base, n * length, "num_walks * length")
+        _need_prob("restart_prob", restart_prob)
 
     def random_walk(self, seeds, length, *, weighted=False, restart_prob=0.0, return_eids=False, base=0, stream=None):
         """Random walks over the full CSR (DGL's dgl.sampling.random_walk; the rule: legion_random_walk in legion_hip.h).  seeds: int32
@@ -280,12 +306,7 @@ class GraphStorage:
         weighted: steps pick by the edge weights (set_edge_weights must have run; the table is fixed afterwards, as after a weighted
         hop).  restart_prob: each step first ends the walk with this probability.  base: draw index of the first walk's first step;
         walks with the same seeds, flags and base are the same walks.  Enqueued on `stream` (default: the current one)."""
-        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
-            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
-        if not isinstance(seeds, torch.Tensor):
-            seeds = torch.as_tensor(seeds, dtype=torch.int32)
-        if seeds.dim() != 1:
-            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        seeds = _as_1d(seeds, torch.int32, "seeds")
         n = int(seeds.numel())
         self._check_walk(n, length, weighted, restart_prob, return_eids, base)
         if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
@@ -296,15 +317,9 @@ class GraphStorage:
         eids = torch.empty((n, int(length)), dtype=torch.int64, device=dev) if return_eids else None
         if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
             return (traces, eids) if return_eids else traces
-        with torch.cuda.device(dev):
-            rc = self._lib.legion_random_walk(_stream_handle(stream), self.handle, _ptr(seeds), n, int(length), int(weighted),
-                                              float(restart_prob), int(base), _ptr(traces), _ptr(eids))
-        if rc != 0:
-            raise RuntimeError("legion_random_walk refused arguments that random_walk had accepted")
-        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
-            for x in (seeds, traces, eids):
-                if x is not None:
-                    x.record_stream(stream)
+        _enqueue(self._lib, "legion_random_walk", "random_walk", dev, stream,
+                 (self.handle, _ptr(seeds), n, int(length), int(weighted), float(restart_prob), int(base), _ptr(traces), _ptr(eids)),
+                 (seeds, traces, eids))
         return (traces, eids) if return_eids else traces
 
     NODE2VEC_MAX_TRIES = 256                         # LEGION_NODE2VEC_MAX_TRIES
@@ -327,8 +342,7 @@ class GraphStorage:
         """node2vec_random_walk's arguments by the rules of legion_node2vec_walk, before anything touches a device: ValueError with the
         reason."""
         GraphStorage._check_walk(n, length, weighted, 0.0, return_eids, base)
-        if isinstance(max_tries, bool) or not isinstance(max_tries, (int, np.integer)):
-            raise ValueError(f"max_tries must be an integer, not {max_tries!r}")
+        _need_int("max_tries", max_tries)
         if not 1 <= max_tries <= GraphStorage.NODE2VEC_MAX_TRIES:
             raise ValueError(f"max_tries must lie in [1, {GraphStorage.NODE2VEC_MAX_TRIES}], not {max_tries}")
         for name, value in (("p", p), ("q", q)):
@@ -350,12 +364,7 @@ class GraphStorage:
         proportional to 1/p if u == t, 1 if u is a neighbour of t, 1/q otherwise; the first step, and the max_tries-th candidate of a
         step, are taken as drawn.  p = q = 1 is random_walk's walk bit for bit.  Needs sorted rows (rows_sorted(), asked here:
         ValueError if not).  seeds, weighted, return_eids, base, stream and what is returned: as in random_walk."""
-        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
-            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
-        if not isinstance(seeds, torch.Tensor):
-            seeds = torch.as_tensor(seeds, dtype=torch.int32)
-        if seeds.dim() != 1:
-            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        seeds = _as_1d(seeds, torch.int32, "seeds")
         n = int(seeds.numel())
         self._check_node2vec(n, p, q, length, weighted, return_eids, max_tries, base)
         if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
@@ -368,15 +377,9 @@ class GraphStorage:
         eids = torch.empty((n, int(length)), dtype=torch.int64, device=dev) if return_eids else None
         if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
             return (traces, eids) if return_eids else traces
-        with torch.cuda.device(dev):
-            rc = self._lib.legion_node2vec_walk(_stream_handle(stream), self.handle, _ptr(seeds), n, int(length), float(p), float(q),
-                                                int(weighted), int(max_tries), int(base), _ptr(traces), _ptr(eids))
-        if rc != 0:
-            raise RuntimeError("legion_node2vec_walk refused arguments that node2vec_random_walk had accepted")
-        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
-            for x in (seeds, traces, eids):
-                if x is not None:
-                    x.record_stream(stream)
+        _enqueue(self._lib, "legion_node2vec_walk", "node2vec_random_walk", dev, stream,
+                 (self.handle, _ptr(seeds), n, int(length), float(p), float(q), int(weighted), int(max_tries), int(base), _ptr(traces),
+                  _ptr(eids)), (seeds, traces, eids))
         return (traces, eids) if return_eids else traces
 
     PINSAGE_MAX_VISITS = 1024                        # LEGION_PINSAGE_MAX_VISITS
@@ -386,12 +389,10 @@ class GraphStorage:
         """pinsage_neighbors' arguments by the rules of legion_pinsage_neighbors, before anything touches a device: ValueError with
         the reason."""
         cap = GraphStorage.PINSAGE_MAX_VISITS
-        if not isinstance(weighted, bool):
-            raise ValueError(f"weighted must be True or False, not {weighted!r}")
+        _need_bool("weighted", weighted)
         for name, value in (("num_random_walks", num_random_walks), ("walk_length", walk_length), ("num_neighbors", num_neighbors),
                             ("base", base)):
-            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-                raise ValueError(f"{name} must be an integer, not {value!r}")
+            _need_int(name, value)
         for name, value in (("num_random_walks", num_random_walks), ("walk_length", walk_length), ("num_neighbors", num_neighbors)):
             if value < 1:
                 raise ValueError(f"{name} must be at least 1, not {value}")
@@ -399,15 +400,8 @@ class GraphStorage:
             raise ValueError(f"num_random_walks * walk_length = {num_random_walks * walk_length} visits per seed, at most {cap}")
         if num_neighbors > cap:
             raise ValueError(f"num_neighbors must be at most {cap}, not {num_neighbors}")
-        if base < 0:
-            raise ValueError(f"base must not be negative, not {base}")
-        if base + n * num_random_walks * walk_length > 2 ** 31 - 1:
-            raise ValueError(f"base + num_seeds * num_random_walks * walk_length = {base + n * num_random_walks * walk_length} "
-                             f"is past the last draw index, 2^31 - 1")
-        if isinstance(termination_prob, bool) or not isinstance(termination_prob, (int, float, np.floating, np.integer)):
-            raise ValueError(f"termination_prob must be a number in [0, 1], not {termination_prob!r}")
-        if not 0.0 <= float(np.float32(termination_prob)) <= 1.0:      # (NaN fails; the library sees the float32)
-            raise ValueError(f"termination_prob must lie in [0, 1], not {termination_prob!r}")
+        _need_draw_indices(base, n * num_random_walks * walk_length, "num_seeds * num_random_walks * walk_length")
+        _need_prob("termination_prob", termination_prob)
 
     def pinsage_neighbors(self, seeds, num_random_walks, walk_length, num_neighbors, *, termination_prob=0.5, weighted=False, base=0,
                           stream=None):
@@ -418,12 +412,7 @@ class GraphStorage:
         -1 / 0 past the number of distinct visited vertices.  seeds, weighted, base and stream as in random_walk; no traces are
         written.  A DGL block: mask = neighbors >= 0, src = neighbors[mask], dst = seeds repeated per row under the mask, edge weight
         counts[mask]."""
-        if isinstance(seeds, torch.Tensor) and seeds.dtype != torch.int32:
-            raise ValueError(f"seeds must be int32, not {seeds.dtype}")
-        if not isinstance(seeds, torch.Tensor):
-            seeds = torch.as_tensor(seeds, dtype=torch.int32)
-        if seeds.dim() != 1:
-            raise ValueError(f"seeds must be one-dimensional, not shape {tuple(seeds.shape)}")
+        seeds = _as_1d(seeds, torch.int32, "seeds")
         n = int(seeds.numel())
         self._check_pinsage(n, num_random_walks, walk_length, num_neighbors, termination_prob, weighted, base)
         if weighted and not self._lib.legion_graph_edge_cdf(self.handle):
@@ -434,15 +423,9 @@ class GraphStorage:
         counts = torch.empty((n, int(num_neighbors)), dtype=torch.int32, device=dev)
         if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
             return neighbors, counts
-        with torch.cuda.device(dev):
-            rc = self._lib.legion_pinsage_neighbors(_stream_handle(stream), self.handle, _ptr(seeds), n, int(num_random_walks),
-                                                    int(walk_length), int(num_neighbors), int(weighted), float(termination_prob),
-                                                    int(base), _ptr(neighbors), _ptr(counts))
-        if rc != 0:
-            raise RuntimeError("legion_pinsage_neighbors refused arguments that pinsage_neighbors had accepted")
-        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
-            for x in (seeds, neighbors, counts):
-                x.record_stream(stream)
+        _enqueue(self._lib, "legion_pinsage_neighbors", "pinsage_neighbors", dev, stream,
+                 (self.handle, _ptr(seeds), n, int(num_random_walks), int(walk_length), int(num_neighbors), int(weighted),
+                  float(termination_prob), int(base), _ptr(neighbors), _ptr(counts)), (seeds, neighbors, counts))
         return neighbors, counts
 
     NEGATIVE_MAX_TRIES = 256                         # LEGION_NEGATIVE_MAX_TRIES
@@ -460,33 +443,23 @@ class GraphStorage:
         col = torch.empty((n,), dtype=torch.int32, device=dev)
         if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
             return row, col
-        with torch.cuda.device(dev):
-            rc = self._lib.legion_find_edges(_stream_handle(stream), self.handle, _ptr(eids), n, _ptr(row), _ptr(col))
-        if rc != 0:
-            raise RuntimeError("legion_find_edges refused arguments that find_edges had accepted")
-        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
-            for x in (eids, row, col):
-                x.record_stream(stream)
+        _enqueue(self._lib, "legion_find_edges", "find_edges", dev, stream, (self.handle, _ptr(eids), n, _ptr(row), _ptr(col)),
+                 (eids, row, col))
         return row, col
 
     @staticmethod
     def _check_negative(n, k, exclude_self, exclude_edges, max_tries, base):
         """negative_sample's arguments by the rules of legion_negative_sample, before anything touches a device: ValueError with the
         reason."""
-        for name, flag in (("exclude_self", exclude_self), ("exclude_edges", exclude_edges)):
-            if not isinstance(flag, bool):
-                raise ValueError(f"{name} must be True or False, not {flag!r}")
+        _need_bool("exclude_self", exclude_self)
+        _need_bool("exclude_edges", exclude_edges)
         for name, value in (("k", k), ("max_tries", max_tries), ("base", base)):
-            if isinstance(value, bool) or not isinstance(value, (int, np.integer)):
-                raise ValueError(f"{name} must be an integer, not {value!r}")
+            _need_int(name, value)
         if k < 1:
             raise ValueError(f"k must be at least 1, not {k}")
         if not 1 <= max_tries <= GraphStorage.NEGATIVE_MAX_TRIES:
             raise ValueError(f"max_tries must lie in [1, {GraphStorage.NEGATIVE_MAX_TRIES}], not {max_tries}")
-        if base < 0:
-            raise ValueError(f"base must not be negative, not {base}")
-        if base + n * k > 2 ** 31 - 1:
-            raise ValueError(f"base + n * k = {base + n * k} is past the last draw index, 2^31 - 1")
+        _need_draw_indices(base, n * k, "n * k")
 
     def negative_sample(self, rows, k, *, exclude_self=True, exclude_edges=True, max_tries=256, base=0, stream=None):
         """k uniform negative endpoints for each of rows (the rule: legion_negative_sample in legion_hip.h; with both exclusions off DGL's
@@ -505,14 +478,9 @@ class GraphStorage:
         neg = torch.empty((n, int(k)), dtype=torch.int32, device=dev)
         if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
             return neg
-        with torch.cuda.device(dev):
-            rc = self._lib.legion_negative_sample(_stream_handle(stream), self.handle, _ptr(rows), n, int(k),
-                                                  int(exclude_self) | int(exclude_edges) << 1, int(max_tries), int(base), _ptr(neg))
-        if rc != 0:
-            raise RuntimeError("legion_negative_sample refused arguments that negative_sample had accepted")
-        if stream is not None:                       # (tensors of this call, used on a stream that is not the allocator's)
-            for x in (rows, neg):
-                x.record_stream(stream)
+        _enqueue(self._lib, "legion_negative_sample", "negative_sample", dev, stream,
+                 (self.handle, _ptr(rows), n, int(k), int(exclude_self) | int(exclude_edges) << 1, int(max_tries), int(base), _ptr(neg)),
+                 (rows, neg))
         return neg
 
     def edge_prediction_seeds(self, eids, k, *, exclude_self=True, exclude_edges=True, max_tries=256, base=0, stream=None):

@@ -1,5 +1,5 @@
 """One stride of the grid and a bit for the link seed ops: every kernel of kernels_link.hip caps its grid at 2 048 workgroups
-(LG_LINK_MAX_WG) and strides over tiles, so only a call of more than 2 048 tiles sends a workgroup through its loop a second time --
+(LG_WALK_MAX_WG) and strides over tiles, so only a call of more than 2 048 tiles sends a workgroup through its loop a second time --
 find_edges past 2 048 x 1 024 edge ids, negative_sample past 524 288 slots, the kernels of unique_ids past 524 288 ids (and its
 one-workgroup scan changes shape at 256 tiles: a thread takes a run of tiles from 257 on, and the last run is short at 2 050).  Whole
 arrays bit for bit against tests/link_ref.py, unique_ids twice.
@@ -33,7 +33,7 @@ from tests.test_gpu_link_unique import _check, ids_of
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-MAX_WG = 2048                                                      # LG_LINK_MAX_WG
+MAX_WG = 2048                                                      # LG_WALK_MAX_WG
 M31 = 2 ** 31 - 1
 N = node2vec_ref.NODE_NUM
 

@@ -119,6 +119,31 @@ def test_walks_are_the_reference_bit_for_bit(world, num_walks, length):
     assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), str(c) + ": traces without edge ids"
 
 
+# trace rows of 8, 9, 16, 17 and 32 positions: one chunk of the staging tile exactly and one position into the next, for the chunk of 8
+# (edge ids) and of 16 (plain), at one walk and around one tile of 256.  (15, 1), (15, 257), (16, 1) and (16, 257) are cases of
+# test_walks_are_the_reference_bit_for_bit above.
+CHUNK_EDGES = [(n, length) for length in (7, 8, 15, 16, 31) for n in (1, 255, 256, 257) if not (n in NUM_WALKS and length in LENGTHS)]
+
+
+@pytest.mark.parametrize("num_walks, length", CHUNK_EDGES)
+def test_chunk_edges_of_the_staging_tile(world, num_walks, length):
+    """With edge ids and without; case number c takes the biased (p, q) number c mod 4 and is weighted when c is odd."""
+    assert len(CHUNK_EDGES) == 16
+    c = CHUNK_EDGES.index((num_walks, length))
+    pq, weighted = PQ[1 + c % 4], c % 2 == 1
+    seeds = ref.seeds_for(num_walks)
+    reads = {}
+    want = ref.walk(world["indptr"], world["col"], seeds, length, *pq, table=world["table"] if weighted else None, base=77, reads=reads)
+    walk_ref.assert_reads_in_bounds(reads, ref.NODE_NUM, world["col"].size)
+    d_seeds = torch.from_numpy(seeds).to(DEV)
+    got = world["graph"].node2vec_random_walk(d_seeds, *pq, length, weighted=weighted, return_eids=True, base=77)
+    only = world["graph"].node2vec_random_walk(d_seeds, *pq, length, weighted=weighted, base=77)
+    torch.cuda.synchronize()
+    ctx = f"{num_walks} x {length}, (p, q) = {pq}, {'weighted' if weighted else 'uniform'}"
+    _same(got, want, ctx)
+    assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), ctx + ": traces without edge ids"
+
+
 @pytest.mark.parametrize("weighted", [False, True], ids=["uniform", "weighted"])
 @pytest.mark.parametrize("num_walks, length", [(5000, 17), (257, 100), (65, 1)])
 def test_unbiased_walks_are_the_random_walk_kernels(world, num_walks, length, weighted):

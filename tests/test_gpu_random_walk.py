@@ -76,6 +76,19 @@ def test_walks_are_the_reference_bit_for_bit(world, num_walks, length):
         assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), ctx + ": traces without edge ids"
 
 
+# trace rows of 8, 9, 16, 17 and 32 positions: one chunk of the staging tile exactly and one position into the next, for the chunk of 8
+# (edge ids) and of 16 (plain), at one walk and around one tile of 256.  (15, 1), (15, 257), (16, 1) and (16, 257) are cases of
+# test_walks_are_the_reference_bit_for_bit above, which this test runs at the rest.
+CHUNK_EDGES = [(n, length) for length in (7, 8, 15, 16, 31) for n in (1, 255, 256, 257) if not (n in NUM_WALKS and length in LENGTHS)]
+
+
+@pytest.mark.parametrize("num_walks, length", CHUNK_EDGES)
+def test_chunk_edges_of_the_staging_tile(world, num_walks, length):
+    """Uniform and weighted, with edge ids and without, as the grid above."""
+    assert len(CHUNK_EDGES) == 16
+    test_walks_are_the_reference_bit_for_bit(world, num_walks, length)
+
+
 @pytest.mark.parametrize("restart", [0.0, 0.3, 1.0])
 @pytest.mark.parametrize("weighted", [False, True], ids=["uniform", "weighted"])
 @pytest.mark.parametrize("eids", [False, True], ids=["plain", "edge-ids"])

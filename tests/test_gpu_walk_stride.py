@@ -1,4 +1,4 @@
-"""One stride of the grid and a bit: random_walk_kernel and pinsage_neighbors_kernel cap their grids at 2 048 workgroups, so a call of
+"""One stride of the grid and a bit: random_walk_kernel, node2vec_walk_kernel and pinsage_neighbors_kernel cap their grids at 2 048 workgroups, so a call of
 more than 2 048 tiles sends workgroups 0 and 1 through the tile loop a second time -- the staging arrays reused, the visit array
 refilled, `live` and the per-trip n1 / w0 formed again.  Here every instance family runs 2 050 tiles (the last with one live row) on
 the hand-built graph of tests/walk_ref.py, whole arrays bit for bit against the references.
@@ -17,6 +17,7 @@ import pytest
 import torch
 
 from tests import functional_ref
+from tests import node2vec_ref
 from tests import pinsage_ref
 from tests import walk_ref
 from tests import weighted_ref
@@ -24,7 +25,7 @@ from tests import weighted_ref
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-MAX_WG = 2048                                                      # LG_WALK_MAX_WG, LG_PINSAGE_MAX_WG
+MAX_WG = 2048                                                      # LG_WALK_MAX_WG
 BASE = 40
 # what goes into tile 2048 from its slot 1 on, in this order, as far as the second trip has room before its last seed: the seeds
 # outside the graph first (slot 1 of tile 0 is vertex 1, one entry: R visits), then the special rows, the empty ones (0; 10 when
@@ -115,6 +116,71 @@ def test_walks_over_one_grid_stride_and_a_bit(world, length, weighted):
         got = world["graph"].random_walk(seeds, length, base=BASE)
         torch.cuda.synchronize()
         _assert_same((got,), want[:1], 256, (ctx, ("traces",)))
+
+
+# ---- node2vec: the same tile code, on the world with every row sorted ---------------------------------------------------------------
+N2V_WALKS = (MAX_WG + 2) * 256                                     # 2 050 full tiles
+N2V_TILES = (0, MAX_WG - 1, MAX_WG, MAX_WG + 1)                    # a first trip's first and last tile, both second-trip tiles
+
+
+@pytest.fixture(scope="module")
+def sorted_world(hip):
+    """The hand-built graph with the entries of every row (and their weights) in ascending order, dead entries first: what node2vec's
+    search of a row needs."""
+    from legion_amd import engine
+    indptr, col, w = walk_ref.hand_graph()
+    rows = np.repeat(np.arange(walk_ref.NODE_NUM), np.diff(indptr))
+    order = np.lexsort((col, rows))
+    col, w = col[order], w[order]
+    assert node2vec_ref.rows_sorted(indptr, col)
+    g = engine.GraphStorage(1, torch.from_numpy(indptr).to(DEV), torch.from_numpy(col).to(DEV))
+    g.set_edge_weights(w)
+    torch.cuda.synchronize()
+    table = weighted_ref.cdf(indptr, w)
+    assert np.array_equal(g.edge_cdf().cpu().numpy().view(np.uint32), table.view(np.uint32)), "edge_cdf"
+    seeds = (np.arange(N2V_WALKS, dtype=np.int64) * 2654435761 % walk_ref.NODE_NUM).astype(np.int32)
+    for t in N2V_TILES:                                            # the special rows lead each checked tile; the long rows often: walks
+        seeds[t * 256:t * 256 + 12] = np.arange(12)                # leave them and search them on the step after
+        seeds[t * 256 + 12:(t + 1) * 256:5] = [9, 8, 7, 6, 5][t % 5]
+    seeds[MAX_WG * 256 + 1:MAX_WG * 256 + 3] = [-1, walk_ref.NODE_NUM]
+    yield dict(graph=g, indptr=indptr, col=col, table=table, seeds=seeds)
+    g.close()
+
+
+@pytest.mark.parametrize("length, full", [(2, False), (17, True)], ids=["2-uniform-plain", "17-weighted-edge-ids"])
+def test_node2vec_walks_over_one_grid_stride_and_a_bit(sorted_world, length, full):
+    """2 050 tiles of 256 walks through node2vec_walk_kernel.  p = q = 1: every walk is random_walk's (the rule says so), whole arrays
+    against walk_ref.  p = 0.25, q = 4: the walks of four tiles against node2vec_ref, computed for those walks alone at their own
+    draw indices (a walk depends only on its seed and its draw indices)."""
+    w = sorted_world
+    g, indptr, col, seeds = w["graph"], w["indptr"], w["col"], w["seeds"]
+    table = w["table"] if full else None
+    assert seeds.size == 524800 and seeds.size // 256 == MAX_WG + 2
+    plain = walk_ref.walk(indptr, col, seeds, length, table=table, base=BASE)
+    for t, r0, live in _second_trip(seeds.size, 256):
+        old = r0 - MAX_WG * 256
+        assert not np.array_equal(plain[0][r0:r0 + live], plain[0][old:old + live]), f"tile {t} expects what tile {t - MAX_WG} does"
+    stats, reads, biased = node2vec_ref.new_stats(), {}, {}
+    for t in N2V_TILES:
+        r0 = t * 256
+        biased[t] = node2vec_ref.walk(indptr, col, seeds[r0:r0 + 256], length, 0.25, 4.0, table=table, base=BASE + r0 * length, reads=reads,
+                                      stats=stats)
+    walk_ref.assert_reads_in_bounds(reads, walk_ref.NODE_NUM, col.size)
+    print("rejected", stats["rejected"], "searches", stats["searches"])
+    assert sum(stats["rejected"]) > 0 and stats["searches"] > 0, "no walk of the four tiles rejects a candidate, or none searches a row"
+    kw = dict(weighted=full, return_eids=full, base=BASE)
+    what = ("traces", "edge ids") if full else ("traces",)
+    got = g.node2vec_random_walk(seeds, 1.0, 1.0, length, **kw)
+    torch.cuda.synchronize()
+    _assert_same(got if full else (got,), plain[:len(what)], 256, (f"{seeds.size} walks x {length}, p = q = 1", what))
+    got = g.node2vec_random_walk(seeds, 0.25, 4.0, length, **kw)
+    torch.cuda.synchronize()
+    got = got if full else (got,)
+    for t in N2V_TILES:
+        for x, want, name in zip(got, biased[t], what):
+            x = x[t * 256:(t + 1) * 256].cpu().numpy()
+            assert x.dtype == want.dtype and np.array_equal(x, want), \
+                f"p = 0.25, q = 4, length {length}: {name} of tile {t} differ in rows {np.nonzero((x != want).any(axis=1))[0][:8]}"
 
 
 # ---- PinSAGE ----------------------------------------------------------------------------------------------------------------------
