@@ -35,7 +35,7 @@ __global__ void find_range_kernel(const int32_t* __restrict__ sampled_ids,
 }
 
 // max_ids[0]: nodes of a batch (cache.cu:55-61); [1], [2]: edges of its LAST hop and nodes before it -- the claims and the
-// known vertices of the largest de-duplication (lg_set_pool_claims_hint)
+// known vertices of the largest de-duplication (PoolSource::claims_hint)
 __global__ void track_max_kernel(const int32_t* __restrict__ nc, const int32_t* __restrict__ ec, int32_t* __restrict__ max_ids)
 {
     atomicMax(max_ids, nc[INTRABATCH_CON * 2 + 1]);
@@ -842,7 +842,6 @@ extern "C" void legion_cache_candidate_selection(LegionUnifiedCache* c, int32_t 
 // One process per GPU: all-reduce (RCCL, the process-wide communicator of legion_collective_init_rank) of GPU dev_id's two
 // access-counter arrays in place; returns the world size the collective ran over (0: no communicator).  Afterwards call
 // legion_cache_candidate_selection(..., world_reduced = 1).
-extern "C" int32_t legion_collective_allreduce_u64(void* devptr, int64_t count, double* ms_out);
 extern "C" int32_t legion_cache_allreduce_hotness(LegionUnifiedCache* c, int32_t dev_id, double* ms_out)
 {
     UnifiedCache* u = as_cache(c);

@@ -48,9 +48,6 @@ static_assert(offsetof(shmStruct, memHandle) == 12 && sizeof(shmStruct) == 12 + 
 // sem_post; from then on a hand-over is no GPU work at all: the server writes, per (device, pipe slot), where the five
 // trainer-visible arrays of the batch start inside the arena and posts sem_w -- same semaphores, same two-slot order, and
 // the reference-sized slab above stays valid for a trainer that knows nothing of this (it gets copies in the slot buffers).
-extern "C" int64_t lg_scattered_info(void* ptr, int32_t* n_chunks);
-extern "C" int lg_scattered_export_fd(void* ptr, int32_t index);
-extern "C" int32_t lg_scattered_serve(void* ptr, const char* name);
 typedef struct shmExt_st {
     int32_t ext_magic;                                         // LEGION_SHM_EXT_MAGIC once the mirror below is live
     int32_t ext_version;                                       // >= 2: the fields behind `counters` exist; 3: those behind `view` too

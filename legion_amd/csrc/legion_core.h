@@ -25,6 +25,7 @@
 #include "../../include/legion_hip.h"
 #include "sample_mode.h"
 #include "sample_plan.h"
+#include "pool_plan.h"
 
 #define INTERBATCH_CON LEGION_INTERBATCH_CON
 #define INTRABATCH_CON LEGION_INTRABATCH_CON
@@ -73,8 +74,6 @@ static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
 {
     return dtype == LEGION_FEATURE_BF16 ? (int64_t)lg_feature_pitch(dtype, D) * 2 : (int64_t)D * 4;
 }
-// bytes of one element of a row handed to the caller (a pool's feature output dtype, LEGION_FEATURE_*)
-static inline int64_t lg_feature_out_bytes(int32_t out_dtype) { return out_dtype == LEGION_FEATURE_BF16 ? 2 : 4; }
 __host__ __device__ inline uint32_t lg_tab_hash(int32_t id)
 {
     uint32_t x = (uint32_t)id;
@@ -98,6 +97,7 @@ enum HopScratch {
     HS_RANGE = 10,         // [HS_RANGE + 2h], [+1]: {offset, count} of the new nodes of op 3h, kept for its gather
     HS_WORDS = 32
 };
+static_assert(HS_WORDS == POOL_HOP_SCRATCH_WORDS, "pool_plan.h sizes hop_scratch");
 
 // error bits a kernel can raise for its lane (MemoryPool::ErrorBits / legion_pool_error)
 #define LG_ERR_TABLE_FULL 1       // a de-duplication bucket did not fit its LDS table even in 2^14 sub-bucket passes (not a hash problem: cannot happen)
@@ -125,9 +125,6 @@ static_assert(BATCH_OP_STRIDE == INTRABATCH_CON, "batch_ops.h numbers the ops of
 // slot_dst[slot] of a hop: -1 no edge; v >= 0 the sampled neighbour; v < -1 the neighbour -2 - v, marked by the de-duplication as
 // NOT the first touch of a new vertex (an involution: the same expression marks and unmarks; every int32 vertex id fits)
 #define LG_SLOT_LOSER(v) (-2 - (v))
-#ifndef LG_CLAIM_CNT_STRIDE
-#define LG_CLAIM_CNT_STRIDE 32        // ints between the claim-list counts of two buckets: a line each (the 8 / 16 reservations of a super tile go to different lines)
-#endif
 
 // Per-vertex row header: where the adjacency of v lives (slot of the CSR pointer tables: P = the
 // full CSR, d < P = GPU d's cached CSR), its first edge and its degree.  One 16-byte read resolves
@@ -138,6 +135,7 @@ struct alignas(16) RowHdr {
     int32_t deg;
     int32_t slot;
 };
+static_assert(sizeof(RowHdr) == POOL_ROW_HDR_BYTES, "pool_plan.h sizes fh_edge");
 
 struct BuildInfo {  // SS/include/buildinfo.h (only the fields of the in-memory path)
     int32_t partition_count = 0;
@@ -211,6 +209,32 @@ struct LanePtrs {
     int64_t* agg_edge_ids;             // [num_ids]
 };
 
+// Where a pool's memory comes from.  Default (all null): one allocation per array.  `arena`: the trainer-visible arrays (sampled_ids,
+// features, labels, agg_src_off, agg_dst_off, the two counter blocks) of a pool of depth 1 are carved from it -- GPURunner's and an
+// arena pipeline's ONE exportable allocation for every lane, so that a trainer end opens it once and takes a batch as views of its
+// lane -- and the counters are mirrored to its host-visible block.  `priv`: the lane-private arrays (pool_plan.h) are carved from one
+// block of shuffled chunks as well (measured: +0.9 % on the whole job, +4 % on the sampler chain, against both separate allocations
+// and one plain block); never freed one by one: the block goes when its pipeline goes.  claims_hint: what PreSC saw of the LAST hop,
+// the largest one -- its edges (= the claims its de-duplication takes) and the batch's nodes before it, maxima over the PreSC
+// batches; 0, 0 = unknown -- picks the small class's bucket count (sample_plan.h).
+struct PoolArena {
+    char* base = nullptr;
+    int64_t bytes = 0, used = 0;
+    int32_t* mirror_host = nullptr;    // [mirror_lanes][32] mapped pinned host memory ...
+    int32_t* mirror_dev = nullptr;     // ... and its device address
+    int32_t mirror_lanes = 0, mirror_used = 0;
+};
+struct PrivateBlock { char* base = nullptr; int64_t bytes = 0, used = 0; };
+struct PoolSource {
+    PoolArena* arena = nullptr;
+    PrivateBlock* priv = nullptr;
+    int64_t claims_hint[2] = {0, 0};
+};
+PrivateBlock* lg_private_block_create(int64_t bytes, int32_t scatter_mb);
+void lg_private_block_destroy(PrivateBlock* b);
+// `bytes` (rounded up to 256) from the block, or from d_alloc_space where there is none; a block too small is fatal
+void* lg_private_take(PrivateBlock* b, int64_t bytes);
+
 // ---------------------------------------------------------------------------------------------
 class MemoryPool {
 public:
@@ -278,9 +302,13 @@ public:
     int32_t* err_dev = nullptr;
     int32_t ErrorBits() const { return err_host ? *(volatile int32_t*)err_host : 0; }
     void RaiseError(int32_t bits) { if (err_host) __atomic_fetch_or(err_host, bits, __ATOMIC_SEQ_CST); }
-    // lanes of a GPURunner group (lg_set_pool_arena): the trainer-visible arrays live in the runner's arena (not freed
+    // lanes of a GPURunner group or an arena pipeline (source.arena): the trainer-visible arrays live in the arena (not freed
     // here) and the counters are mirrored to host-visible memory by the end-of-batch kernel
     bool arena_backed = false;
+    PoolSource source;                 // kept for the pool's later feature allocation
+    PoolPrivatePlan private_plan;      // the private arrays' list (pool_plan.h) and, entry by entry, what lg_pool_alloc_private's walk of it took
+    std::vector<void*> private_arrays;
+    bool private_carved = false;       // ... from source.priv: Finalize frees none of them
     int32_t* counter_mirror_dev = nullptr;
     int32_t* counter_mirror_host = nullptr;
     int32_t num_ids = 0;
@@ -694,35 +722,17 @@ extern "C" void legion_set_local_device(int32_t dev);
 bool lg_is_local(int32_t dev);
 
 void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
-                           const int32_t* fanout, int32_t hop_num, int32_t float_feature_len);
+                           const int32_t* fanout, int32_t hop_num, int32_t float_feature_len, const PoolSource& source = PoolSource());
+// legion_pool_create with a source (the extern "C" function passes an empty one)
+MemoryPool* lg_pool_create(int32_t dev_id, int32_t total_num_nodes, int32_t batch_size, const int32_t* fanout, int32_t hop_num,
+                           int32_t float_feature_len, int32_t pipeline_depth, const PoolSource& source);
+// the private plan of a pool of this shape under the tuning as it stands (what lg_pool_alloc_private walks)
+PoolPrivatePlan lg_pool_private_plan(const PoolShape& shape, const PoolSource& source);
 // the two arrays of the edge-id mode (MemoryPool::mode.edge_ids), part of the pool's private allocation: made when the mode is turned on
 void lg_pool_alloc_edge_ids(MemoryPool* mp);
 // the one way a pool's mode changes (the three legion_pool_set_* of storage.hip, and legion_pipeline_set_* for every lane): refused
 // once the pool has sampled and for what sample_mode_refusal names; check_only: answer, change nothing
 bool lg_pool_try_set_mode(MemoryPool* mp, const SampleMode& mode, bool check_only = false);
-// how many pools of this shape the caller is about to keep in flight on the device (Pipeline: lanes x slots);
-// feeds the direct-vs-table choice of the position state (LEGION_DEDUP=auto).  Thread-local; 0 = one pool.
-// what PreSC saw of the LAST hop, the largest one: its edges (= the claims its de-duplication takes) and the batch's nodes
-// before it (= what that de-duplication must recognise), maxima over the PreSC batches; 0, 0 = unknown.  Pools created
-// afterwards by this thread pick the small class's bucket count from it (8, or 16 where a bucket would need two passes).
-void lg_set_pool_claims_hint(int64_t last_hop_edges, int64_t nodes_before_last_hop);
-
-// Where the pools a thread is about to create put their trainer-visible arrays (sampled_ids, features, labels, agg_src_off,
-// agg_dst_off, the two counter blocks).  Default (null): one allocation each.  GPURunner sets an arena -- ONE exportable device
-// allocation for every lane of its groups, so that a trainer end can open it with a single IPC handle and take a batch as
-// views of its lane (no copy into a pipe slot) -- and a host-visible block for the lanes' counters.  Thread-local.
-struct PoolArena {
-    char* base = nullptr;
-    int64_t bytes = 0, used = 0;
-    int32_t* mirror_host = nullptr;    // [mirror_lanes][32] mapped pinned host memory ...
-    int32_t* mirror_dev = nullptr;     // ... and its device address
-    int32_t mirror_lanes = 0, mirror_used = 0;
-};
-void lg_set_pool_arena(PoolArena* arena);
-PoolArena* lg_get_pool_arena();
-int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len,
-                            int32_t feature_out_dtype = LEGION_FEATURE_F32);
-
 // alloc helpers, SS/engine/server_imp.cuh:2-51
 extern "C" void* d_alloc_space(int64_t num_bytes);
 extern "C" void d_free_space(void* d_ptr);
@@ -733,6 +743,41 @@ extern "C" int32_t GetGPUDevice();
 // 'invalid argument' for a fresh, valid allocation and succeeds a moment later; a persistent failure is fatal as before
 void lg_ipc_export(void* handle64, void* dev_ptr, const char* file, int line);
 void* lg_alloc_exported(int64_t num_bytes, void* handle64, const char* file, int line);   // fresh buffer + its handle; tries other blocks
+
+// ---- extern "C" functions one source file of the library calls in another and include/legion_hip.h does not list (the public ones
+//      come from that header): declared once, here, so that the compiler checks every caller against the definition ---------------
+// storage.hip: device memory built from shuffled physical chunks, and its hand-over to other GPUs and processes
+extern "C" void* d_alloc_scattered(int64_t num_bytes, int32_t chunk_mb);
+extern "C" void* d_alloc_scattered_exportable(int64_t num_bytes, int32_t chunk_mb);
+extern "C" int64_t lg_scattered_info(void* ptr, int32_t* n_chunks);
+extern "C" int32_t lg_scattered_grant(void* ptr, const int32_t* logical_devs, int32_t n);
+extern "C" int32_t lg_scattered_serve(void* ptr, const char* name);
+extern "C" int32_t lg_scattered_exportable(void* ptr);
+extern "C" void* lg_scattered_map_remote(const char* name, int32_t n_chunks, int64_t chunk_bytes);
+extern "C" void lg_scattered_unmap_remote(void* base);
+extern "C" int lg_scattered_export_fd(void* ptr, int32_t index);
+// operators.hip: lane groups
+LegionLaneGroup* lg_group_create(LegionMemoryPool** pools, int32_t n, PrivateBlock* priv);      // legion_group_create with its lanes' copy carved from `priv`
+extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                           LegionUnifiedCache* cache, LegionLaneGroup* group, int32_t n_active,
+                                           int32_t batch_size, int32_t counter0, int32_t dev_id, int32_t mode,
+                                           const int32_t* fanout, int32_t hop_num, int32_t phase);
+extern "C" const void* legion_group_lane_desc(LegionLaneGroup* g, int32_t lane);
+extern "C" void legion_group_refresh(LegionLaneGroup* g);
+extern "C" void legion_enqueue_group_last_gather(legion_stream_t strm_hdl, LegionUnifiedCache* cache, LegionLaneGroup* group,
+                                                 int32_t n_active, int32_t dev_id, int32_t hop_num);
+// pipeline.hip: what GPURunner needs beyond the public pipeline API
+LegionPipeline* lg_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature, LegionUnifiedCache* cache, int32_t dev_id,
+                                   int32_t batch_size, const int32_t* fanout, int32_t hop_num, int32_t group_size, int32_t slots,
+                                   int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype, PoolArena* caller_arena);
+extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
+extern "C" void legion_pipeline_prepare(LegionPipeline* p, int32_t mode, int32_t n_active, int32_t batch_size);
+extern "C" legion_stream_t legion_pipeline_stream(LegionPipeline* p);
+extern "C" void* legion_pipeline_slot_done_event(LegionPipeline* p, int32_t slot);
+extern "C" void legion_pipeline_wait_sleeping(LegionPipeline* p, int32_t slot, int32_t spin_us);
+extern "C" void legion_pipeline_set_gathers(LegionPipeline* p, int32_t on);
+extern "C" int32_t legion_pipeline_bulk_enable_shared(LegionPipeline* p, const PoolArena* arena);
+extern "C" int32_t legion_pipeline_submit_bulk_inproc(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
 
 // ---------------------------------------------------------------------------------------------
 // kernel launchers (kernels_*.hip)

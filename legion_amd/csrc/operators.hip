@@ -21,13 +21,6 @@
 
 #include <iostream>
 
-extern "C" void BatchGenerate(legion_stream_t strm_hdl, LegionFeatureStorage* feature_,
-                              LegionUnifiedCache* cache_, LegionMemoryPool* memorypool_,
-                              int32_t batch_size, int32_t counter, int32_t part_id, int32_t dev_id,
-                              int32_t mode, bool is_presc, int32_t hop_num);
-extern "C" void RandomSample(legion_stream_t strm_hdl, LegionGraphStorage* graph_, LegionUnifiedCache* cache_,
-                             LegionMemoryPool* memorypool_, int32_t count, int32_t dev_id, int32_t op_id,
-                             bool is_presc);
 
 // The C handles are the C++ objects themselves, except the cache, whose handle boxes the
 // UnifiedCache as its first member (cache.hip: LegionCacheBox).
@@ -38,6 +31,7 @@ struct LegionLaneGroup {
     std::vector<MemoryPool*> pools;
     std::vector<int32_t> epochs;      // each pool's lanes_epoch when d_lanes was written
     LanePtrs* d_lanes = nullptr;      // contiguous device copy of every pool's current lane
+    bool lanes_carved = false;        // ... taken from a pipeline's private block: goes with the block
     int32_t* iter_state = nullptr;    // device {next iteration of lane 0, stride} for graph replay, or null
 };
 
@@ -564,7 +558,8 @@ extern "C" void legion_enqueue_batch(legion_stream_t strm_hdl, LegionGraphStorag
 }
 
 // ---- lane groups: G independent mini-batches served by every launch ---------------------------
-extern "C" LegionLaneGroup* legion_group_create(LegionMemoryPool** pools, int32_t n)
+// `priv`: the block the group's copy of its lanes is carved from (an arena pipeline's, behind its lanes' private arrays), or null
+LegionLaneGroup* lg_group_create(LegionMemoryPool** pools, int32_t n, PrivateBlock* priv)
 {
     LegionLaneGroup* g = new LegionLaneGroup();
     std::vector<LanePtrs> h;
@@ -575,10 +570,12 @@ extern "C" LegionLaneGroup* legion_group_create(LegionMemoryPool** pools, int32_
         h.push_back(mp->HostLane(mp->GetCurrentPipe()));
     }
     SetGPUDevice(g->pools[0]->dev_id);
-    g->d_lanes = (LanePtrs*)d_alloc_space((int64_t)n * sizeof(LanePtrs));
+    g->d_lanes = (LanePtrs*)lg_private_take(priv, (int64_t)n * sizeof(LanePtrs));
+    g->lanes_carved = priv != nullptr;
     HIP_CALL(hipMemcpy(g->d_lanes, h.data(), h.size() * sizeof(LanePtrs), hipMemcpyHostToDevice));
     return g;
 }
+extern "C" LegionLaneGroup* legion_group_create(LegionMemoryPool** pools, int32_t n) { return lg_group_create(pools, n, nullptr); }
 
 // a pool whose lane descriptor changed after the group was made (legion_pool_set_edge_ids: possible only before the pool has
 // sampled, so never between the replays of a captured graph): its entry of d_lanes is written again
@@ -605,7 +602,7 @@ extern "C" const void* legion_group_lane_desc(LegionLaneGroup* g, int32_t lane)
 extern "C" void legion_group_destroy(LegionLaneGroup* g)
 {
     if (!g) return;
-    d_free_space(g->d_lanes);
+    if (!g->lanes_carved) d_free_space(g->d_lanes);
     delete g;
 }
 

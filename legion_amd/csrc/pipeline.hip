@@ -28,34 +28,6 @@
 #include <map>
 #include <tuple>
 
-struct LegionLaneGroup;
-extern "C" void* d_alloc_scattered(int64_t num_bytes, int32_t chunk_mb);
-extern "C" void* d_alloc_scattered_exportable(int64_t num_bytes, int32_t chunk_mb);
-extern "C" int64_t lg_scattered_info(void* ptr, int32_t* n_chunks);
-extern "C" int32_t lg_scattered_grant(void* ptr, const int32_t* logical_devs, int32_t n);
-extern "C" int32_t lg_scattered_serve(void* ptr, const char* name);
-extern "C" int32_t lg_scattered_exportable(void* ptr);
-extern "C" void* lg_scattered_map_remote(const char* name, int32_t n_chunks, int64_t chunk_bytes);
-extern "C" void lg_scattered_unmap_remote(void* base);
-extern "C" void* lg_private_arena_begin(int64_t bytes, int32_t scatter_mb);
-extern "C" void lg_private_arena_end();
-extern "C" void lg_private_arena_free(void* handle);
-extern "C" void lg_alloc_count_begin();
-extern "C" int64_t lg_alloc_count_end();
-extern "C" LegionLaneGroup* legion_group_create(LegionMemoryPool** pools, int32_t n);
-extern "C" void legion_group_set_iter_state(LegionLaneGroup* g, int32_t* iter_state_devptr);
-extern "C" void legion_group_destroy(LegionLaneGroup* g);
-extern "C" void legion_enqueue_group_n(legion_stream_t strm_hdl, LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                       LegionUnifiedCache* cache, LegionLaneGroup* group, int32_t n_active,
-                                       int32_t batch_size, int32_t counter0, int32_t dev_id, int32_t mode,
-                                       const int32_t* fanout, int32_t hop_num);
-extern "C" void legion_enqueue_group_phase(legion_stream_t strm_hdl, LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                           LegionUnifiedCache* cache, LegionLaneGroup* group, int32_t n_active,
-                                           int32_t batch_size, int32_t counter0, int32_t dev_id, int32_t mode,
-                                           const int32_t* fanout, int32_t hop_num, int32_t phase);
-extern "C" void legion_pool_profile_begin(LegionMemoryPool* p_, int32_t max_ops);
-extern "C" const void* legion_group_lane_desc(LegionLaneGroup* g, int32_t lane);
-extern "C" void legion_group_refresh(LegionLaneGroup* g);
 
 struct Slot {
     std::vector<MemoryPool*> pools;           // G lanes
@@ -109,16 +81,16 @@ struct LegionPipeline {
     std::map<int32_t, int64_t> prof_cnt;
     PoolArena arena;                          // use_graph bit 5: the lanes' trainer-visible arrays live in ONE exportable allocation
     BulkState* bulk = nullptr;
-    void* priv_arena = nullptr;               // the block of shuffled chunks the lanes' private arrays were carved from (arena pipelines)
+    PrivateBlock* priv = nullptr;             // the block of shuffled chunks the lanes' private arrays were carved from (arena pipelines)
     bool arena_borrowed = false;              // the arena belongs to the caller (legion_pipeline_bulk_enable_shared)
     int64_t feature_rows = 0;
     int32_t feature_out_dtype = LEGION_FEATURE_F32;      // of every lane (legion_pool_set_feature_out_dtype)
 };
 
-extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                                     LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
-                                                     const int32_t* fanout, int32_t hop_num, int32_t group_size,
-                                                     int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype)
+// caller_arena: the lanes' trainer-visible arrays are carved from an arena the CALLER owns (GPURunner's lane arena), or null
+LegionPipeline* lg_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature, LegionUnifiedCache* cache, int32_t dev_id,
+                                   int32_t batch_size, const int32_t* fanout, int32_t hop_num, int32_t group_size, int32_t slots,
+                                   int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype, PoolArena* caller_arena)
 {
     if (!graph || !feature || !cache) { printf("invalid storage ptr\n"); return nullptr; }
     if (feature_out_dtype != LEGION_FEATURE_F32 && feature_out_dtype != LEGION_FEATURE_BF16) {
@@ -155,11 +127,12 @@ extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, 
     }
     p->slots.resize(p->slots_n);
     p->feature_rows = feature_rows;
+    const int32_t D = p->feature->GetFloatFeatureLen();
+    const PoolShape shape = pool_shape(batch_size, fanout, hop_num);
+    PoolSource source;
+    source.arena = caller_arena;
     if ((use_graph & 32) != 0) {       // one arena for every lane (peer_gather = bulk: the owners push rows into it)
-        const int32_t D = p->feature->GetFloatFeatureLen();
-        int64_t num_ids = batch_size, per = batch_size;
-        for (int32_t h = 0; h < hop_num; h++) { per *= fanout[h]; num_ids += per; }
-        p->arena.bytes = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, D, feature_out_dtype) * p->group_size * p->slots_n;
+        p->arena.bytes = pool_visible_bytes(batch_size, shape.num_ids, feature_rows, D, feature_out_dtype) * p->group_size * p->slots_n;
         // The arena is built from shuffled physical chunks (storage.hip d_alloc_scattered; LegionTuning.arena_scatter_mb = 0: one plain
         // allocation).  use_graph bit 6: it must be reachable from another process or GPU (peer_gather = bulk: owners push rows into
         // it) -- then its chunks are created exportable, other GPUs of this process are granted access when they are linked
@@ -169,44 +142,41 @@ extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, 
         p->arena.base = (char*)(chunk_mb <= 0 ? d_alloc_space(p->arena.bytes)
                                               : ((use_graph & 64) != 0 ? d_alloc_scattered_exportable(p->arena.bytes, std::max(chunk_mb, 16))
                                                                        : d_alloc_scattered(p->arena.bytes, chunk_mb)));
-        lg_set_pool_arena(&p->arena);
+        source.arena = &p->arena;
     }
-    {   // what PreSC saw of the largest hop decides the small class's bucket count (8 or 16, storage.hip)
+    // what PreSC saw of the largest hop decides the small class's bucket count (8 or 16, sample_plan.h)
+    if (p->cache_handle != nullptr) {       // (the handle boxes the UnifiedCache as its first member, cache.hip)
         int32_t last_hop[2] = {0, 0};
-        if (p->cache_handle != nullptr)     // (the handle boxes the UnifiedCache as its first member, cache.hip)
-            reinterpret_cast<UnifiedCache*>(p->cache_handle)->LastHopMax(dev_id, last_hop);
-        lg_set_pool_claims_hint(last_hop[0], last_hop[1]);
+        reinterpret_cast<UnifiedCache*>(p->cache_handle)->LastHopMax(dev_id, last_hop);
+        source.claims_hint[0] = last_hop[0];
+        source.claims_hint[1] = last_hop[1];
     }
     // Arena pipelines (own arena or the caller's -- the server's) also carve their lanes' PRIVATE arrays from one block of shuffled
-    // chunks (storage.hip): one lane is created with plain allocations first, only to add up what a lane asks for.
-    if (lg_get_pool_arena() != nullptr && lg::tuning().arena_scatter_mb > 0) {
-        PoolArena* trainer_arena = lg_get_pool_arena();
-        lg_set_pool_arena(nullptr);
-        lg_alloc_count_begin();
-        LegionMemoryPool* probe = legion_pool_create(dev_id, p->feature->TotalNodeNum(), batch_size, fanout, hop_num, p->feature->GetFloatFeatureLen(), 1);
-        legion_pool_set_feature_out_dtype(probe, feature_out_dtype);
-        if (feature_rows > 0) legion_pool_alloc_features(probe, feature_rows);
-        const int64_t asked = lg_alloc_count_end();
-        legion_pool_destroy(probe);
-        lg_set_pool_arena(trainer_arena);
-        int64_t num_ids = batch_size, per = batch_size;
-        for (int32_t h = 0; h < hop_num; h++) { per *= fanout[h]; num_ids += per; }
-        const int64_t visible = lg_pool_arena_bytes(batch_size, num_ids, feature_rows, p->feature->GetFloatFeatureLen(), feature_out_dtype);
-        const int64_t lane = std::max<int64_t>(asked - visible, 0) + (64 << 10);
-        p->priv_arena = lg_private_arena_begin(lane * p->group_size * p->slots_n + ((int64_t)8 << 20), lg::tuning().arena_scatter_mb);
+    // chunks (storage.hip): per lane what its plan adds up to (pool_plan.h) plus 64 KiB, and 8 MiB on top.  Behind each slot's lanes
+    // the block also holds the slot's copy of their descriptors and its iteration state.
+    const int64_t lane_private = shape.over_limit ? 0 : lg_pool_private_plan(shape, source).sum;      // (over the limit: the first pool says so and exits)
+    if (source.arena != nullptr && lg::tuning().arena_scatter_mb > 0) {
+        p->priv = lg_private_block_create((lane_private + (64 << 10)) * p->group_size * p->slots_n + ((int64_t)8 << 20), lg::tuning().arena_scatter_mb);
+        source.priv = p->priv;
     }
     for (Slot& sl : p->slots) {
         std::vector<LegionMemoryPool*> handles;
         for (int32_t g = 0; g < p->group_size; g++) {
-            LegionMemoryPool* h = legion_pool_create(dev_id, p->feature->TotalNodeNum(), batch_size, fanout, hop_num,
-                                                     p->feature->GetFloatFeatureLen(), 1);
+            const int64_t before = p->priv ? p->priv->used : 0;
+            MemoryPool* mp = lg_pool_create(dev_id, p->feature->TotalNodeNum(), batch_size, fanout, hop_num, D, 1, source);
+            if (p->priv && p->priv->used - before != lane_private) {      // the plan and the allocations are one list, or nothing runs
+                printf("legion_hip: a lane took %lld bytes of the private block, its plan says %lld\n", (long long)(p->priv->used - before),
+                       (long long)lane_private);
+                exit(EXIT_FAILURE);
+            }
+            LegionMemoryPool* h = reinterpret_cast<LegionMemoryPool*>(mp);
             legion_pool_set_feature_out_dtype(h, feature_out_dtype);
             if (feature_rows > 0) legion_pool_alloc_features(h, feature_rows);
             handles.push_back(h);
-            sl.pools.push_back(reinterpret_cast<MemoryPool*>(h));
+            sl.pools.push_back(mp);
         }
-        sl.group = legion_group_create(handles.data(), p->group_size);
-        sl.d_iter = (int32_t*)d_alloc_space(2 * sizeof(int32_t));
+        sl.group = lg_group_create(handles.data(), p->group_size, p->priv);
+        sl.d_iter = (int32_t*)lg_private_take(p->priv, 2 * sizeof(int32_t));
         HIP_CALL(hipMemset(sl.d_iter, 0, 2 * sizeof(int32_t)));
         HIP_CALL(hipHostMalloc((void**)&sl.h_iter, 2 * sizeof(int32_t), hipHostMallocDefault));
         // chained slots share one in-order stream (back-to-back graph launches, no event round trip);
@@ -218,10 +188,16 @@ extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, 
         HIP_CALL(hipEventCreateWithFlags(&sl.done, hipEventDisableTiming));
         HIP_CALL(hipEventCreateWithFlags(&sl.sampled, hipEventDisableTiming));
     }
-    lg_set_pool_claims_hint(0, 0);
-    lg_set_pool_arena(nullptr);
-    if (p->priv_arena) lg_private_arena_end();
     return p;
+}
+
+extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
+                                                     LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
+                                                     const int32_t* fanout, int32_t hop_num, int32_t group_size,
+                                                     int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype)
+{
+    return lg_pipeline_create(graph, feature, cache, dev_id, batch_size, fanout, hop_num, group_size, slots, feature_rows, use_graph,
+                              feature_out_dtype, nullptr);
 }
 
 extern "C" LegionPipeline* legion_pipeline_create(LegionGraphStorage* graph, LegionFeatureStorage* feature,
@@ -373,8 +349,6 @@ extern "C" void legion_pipeline_prepare(LegionPipeline* p, int32_t mode, int32_t
 // Enqueues the group of batches counter0 .. counter0 + G - 1 of `mode` on the next slot (round robin)
 // and returns the slot index.  The slot's previous group must have been consumed: this call waits
 // for its completion first.
-extern "C" int32_t legion_pipeline_submit_n(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active);
-extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
 extern "C" int32_t legion_pipeline_submit(LegionPipeline* p, int32_t counter0, int32_t mode)
 {
     return legion_pipeline_submit_n(p, counter0, mode, p ? p->group_size : 0);
@@ -441,8 +415,6 @@ extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0
 // Diagnostics: the last op's gather of the group sitting in `slot`, launched `repeats` more times over the lanes as they stand
 // (a caller may have rewritten the lanes' ids in between: bench.py's cold-row figure), each launch between two HIP events on the
 // slot's stream; ms_each[i] = its duration.  Returns the launches timed.
-extern "C" void legion_enqueue_group_last_gather(legion_stream_t strm_hdl, LegionUnifiedCache* cache, LegionLaneGroup* group,
-                                                 int32_t n_active, int32_t dev_id, int32_t hop_num);
 extern "C" int32_t legion_pipeline_regather_last(LegionPipeline* p, int32_t slot, int32_t n_active, int32_t repeats, double* ms_each)
 {
     if (!p || slot < 0 || slot >= p->slots_n || repeats < 1 || !ms_each) return 0;
@@ -523,7 +495,7 @@ extern "C" void legion_pipeline_destroy(LegionPipeline* p)
         HIP_CALL(hipStreamSynchronize(sl.stream));
         for (auto& kv : sl.exec) HIP_CALL(hipGraphExecDestroy(kv.second));
         legion_group_destroy(sl.group);
-        d_free_space(sl.d_iter);
+        if (p->priv == nullptr) d_free_space(sl.d_iter);
         HIP_CALL(hipHostFree(sl.h_iter));
         for (MemoryPool* mp : sl.pools) legion_pool_destroy(reinterpret_cast<LegionMemoryPool*>(mp));
         HIP_CALL(hipEventDestroy(sl.done));
@@ -544,7 +516,7 @@ extern "C" void legion_pipeline_destroy(LegionPipeline* p)
         delete p->bulk;
     }
     if (p->arena.base && !p->arena_borrowed) d_free_space(p->arena.base);
-    if (p->priv_arena) lg_private_arena_free(p->priv_arena);
+    lg_private_block_destroy(p->priv);
     delete p;
 }
 
@@ -619,7 +591,7 @@ extern "C" int32_t legion_pipeline_bulk_enable(LegionPipeline* p)
     return 1;
 }
 
-// the lanes were carved from an arena the CALLER owns (GPURunner's lane arena, lg_set_pool_arena before legion_pipeline_create):
+// the lanes were carved from an arena the CALLER owns (GPURunner's lane arena, handed to lg_pipeline_create):
 // bulk transfers address it, the pipeline does not free it
 extern "C" int32_t legion_pipeline_bulk_enable_shared(LegionPipeline* p, const PoolArena* arena)
 {

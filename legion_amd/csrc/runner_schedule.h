@@ -57,3 +57,28 @@ struct RunnerSchedule {
         while (!groups.empty() && k >= groups.front().first + groups.front().n) groups.pop_front();
     }
 };
+
+// The group that starts at global batch `first`: consecutive batches of one mode with consecutive local ids (ipc_service.cu:213-253),
+// at most `cap` of them and none past `max_step`.  mode_of(k), local_of(k): the schedule's mode and local batch id of global batch k.
+template <class ModeOf, class LocalOf>
+static inline int32_t runner_group_at(int32_t first, int32_t cap, int32_t max_step, ModeOf mode_of, LocalOf local_of, int32_t& mode, int32_t& local0)
+{
+    mode = mode_of(first);
+    local0 = local_of(first);
+    int32_t n = 1;
+    while (n < cap && first + n < max_step && mode_of(first + n) == mode && local_of(first + n) == local0 + n) n++;
+    return n;
+}
+// the largest group the schedule ever forms under that cap
+template <class ModeOf, class LocalOf>
+static inline int32_t runner_largest_group(int32_t cap, int32_t max_step, ModeOf mode_of, LocalOf local_of)
+{
+    int32_t best = 1;
+    for (int32_t first = 0; first < max_step;) {
+        int32_t mode = 0, local0 = 0;
+        const int32_t n = runner_group_at(first, cap, max_step, mode_of, local_of, mode, local0);
+        if (n > best) best = n;
+        first += n;
+    }
+    return best;
+}

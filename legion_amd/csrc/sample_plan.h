@@ -12,7 +12,7 @@
 // slots per lane (B = 1024-class batches), 64 up to 2^22 (B = 8000 with [25,10]), 256 beyond (B = 8000 with [15,10,5] has 6 M,
 // with [25,10,10] 20 M; larger hops run more passes per bucket).  The kernels are instantiated for the four classes.
 #define LG_LDS_BITS_SMALL 3
-#define LG_LDS_BITS_SMALL16 4                    // the same class with 16 buckets: dense graphs, see lg_set_pool_claims_hint
+#define LG_LDS_BITS_SMALL16 4                    // the same class with 16 buckets: dense graphs, see PoolSource::claims_hint
 #ifndef LG_LDS_BITS_MEDIUM
 #define LG_LDS_BITS_MEDIUM 6
 #endif
@@ -85,7 +85,7 @@ struct SamplePoolPlan {
 };
 
 // slots: the pool's largest hop (B f1..fH); listed_nodes: the nodes hops 1 .. H-1 can add; hint_*: PreSC's maxima of the last hop's
-// edges and of the nodes before it (lg_set_pool_claims_hint; 0: unknown); the rest: LegionTuning's fields of these names
+// edges and of the nodes before it (PoolSource::claims_hint; 0: unknown); the rest: LegionTuning's fields of these names
 static inline SamplePoolPlan sample_pool_plan(int64_t slots, int64_t listed_nodes, int64_t hint_last_hop_edges, int64_t hint_nodes_before,
                                               int32_t lds_small_buckets, int32_t lds_claim_cap, int32_t lds_known_cap)
 {

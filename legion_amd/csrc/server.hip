@@ -15,7 +15,7 @@
 #include "legion_core.h"
 
 #include <pthread.h>
-extern "C" void* d_alloc_scattered_exportable(int64_t num_bytes, int32_t chunk_mb);
+#include "runner_plan.h"
 #include "runner_schedule.h"
 
 #include <fcntl.h>
@@ -399,22 +399,6 @@ private:
 };
 
 // =============================================================================================
-struct LegionPipeline;
-extern "C" LegionPipeline* legion_pipeline_create_ex(LegionGraphStorage* graph, LegionFeatureStorage* feature,
-                                                     LegionUnifiedCache* cache, int32_t dev_id, int32_t batch_size,
-                                                     const int32_t* fanout, int32_t hop_num, int32_t group_size,
-                                                     int32_t slots, int64_t feature_rows, int32_t use_graph, int32_t feature_out_dtype);
-extern "C" int32_t legion_pipeline_submit_ex(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
-extern "C" void legion_pipeline_prepare(LegionPipeline* p, int32_t mode, int32_t n_active, int32_t batch_size);
-extern "C" legion_stream_t legion_pipeline_stream(LegionPipeline* p);
-extern "C" void* legion_pipeline_slot_done_event(LegionPipeline* p, int32_t slot);
-extern "C" LegionMemoryPool* legion_pipeline_pool(LegionPipeline* p, int32_t slot, int32_t lane);
-extern "C" void legion_pipeline_destroy(LegionPipeline* p);
-extern "C" void legion_pipeline_wait(LegionPipeline* p, int32_t slot);
-extern "C" void legion_pipeline_wait_sleeping(LegionPipeline* p, int32_t slot, int32_t spin_us);
-extern "C" void legion_pipeline_set_gathers(LegionPipeline* p, int32_t on);
-extern "C" int32_t legion_pipeline_bulk_enable_shared(LegionPipeline* p, const PoolArena* arena);
-extern "C" int32_t legion_pipeline_submit_bulk_inproc(LegionPipeline* p, int32_t counter0, int32_t mode, int32_t n_active, int32_t batch_size);
 
 class GPURunner : public Runner {
 public:
@@ -507,27 +491,14 @@ public:
         HIP_CALL(hipDeviceSynchronize());
         ReportErrors(memorypool_);          // a PreSC epoch over corrupt batches would size the caches from garbage: stop here
         UnifiedCache* cache = (UnifiedCache*)(params->cache);
-        int32_t num_ids = int32_t((cache->MaxIdNum(local_dev_id_)) * 1.2);
-        // MaxIdNum was measured on training batches; validation/test batches can be larger than the
-        // raw batch (see Initialize): scale the reference's 1.2x rule by that ratio, never beyond num_ids
-        IPCEnv* env_ = (IPCEnv*)(params->env);
-        int64_t scaled = (int64_t)num_ids * ((memorypool_->batch_size + env_->GetRawBatchsize() - 1) / env_->GetRawBatchsize());
-        if (scaled > memorypool_->num_ids) scaled = memorypool_->num_ids;
-        num_ids = (int32_t)scaled;
-        if (num_ids < 1) num_ids = 1;
         IPCEnv* env = (IPCEnv*)(params->env);
-        // The 1.2 x rule sizes the LANES (hundreds of them).  The two pipe-slot buffers -- what a trainer end that does not take views
-        // reads its rows from, and what the operator-by-operator Runner gathers into -- take the worst case of a batch, num_ids rows,
-        // whenever the pair costs less than a tenth of the free HBM: no batch is ever truncated there (the reference sizes them by the
-        // rule and overruns, server.cu:277).  LegionTuning.runner_overflow = 0 keeps the rule for them too.
-        lane_rule_rows_ = num_ids;
-        int64_t slot_rows = num_ids;
-        {
-            size_t free_b = 0, total_b = 0;
-            HIP_CALL(hipMemGetInfo(&free_b, &total_b));
-            const int64_t worst_bytes = (int64_t)memorypool_->num_ids * float_feature_len_ * lg_feature_out_bytes(g_feature_out_dtype);
-            if (lg::tuning().runner_overflow != 0 && (int64_t)interbatch_concurrency_ * worst_bytes <= (int64_t)(free_b / 10)) slot_rows = memorypool_->num_ids;
-        }
+        // the lanes by the reference's 1.2 x rule, the two pipe-slot buffers by the worst case of a batch where that is cheap (runner_plan.h)
+        size_t free_b = 0, total_b = 0;
+        HIP_CALL(hipMemGetInfo(&free_b, &total_b));
+        const RunnerRows rows = runner_rows(cache->MaxIdNum(local_dev_id_), memorypool_->batch_size, env->GetRawBatchsize(), memorypool_->num_ids,
+                                            float_feature_len_, g_feature_out_dtype, (int64_t)free_b, interbatch_concurrency_, lg::tuning().runner_overflow);
+        lane_rule_rows_ = rows.lane_rule_rows;
+        const int64_t slot_rows = rows.slot_rows;
         if (g_feature_out_dtype != LEGION_FEATURE_F32 && (!use_groups_ || env->GetCounterMirror(local_dev_id_, 0) == nullptr)) {
             // the dtype reaches the trainer end through the shared extension (shmExt version 4), published by the lane-group path only
             std::cout << "bf16 feature output needs the lane-group runner (LEGION_RUNNER_GRAPH) and the shared counter mirror "
@@ -539,7 +510,7 @@ public:
         for (int i = 0; i < interbatch_concurrency_; i++)
             memorypool_->SetFloatFeatures(env->GetFloatFeatures(local_dev_id_, i), i);
         memorypool_->feature_rows = slot_rows;
-        memorypool_->grid_rows_hint = num_ids;      // launches into the pipe slots are sized for the usual batch, not for the buffers' worst case
+        memorypool_->grid_rows_hint = lane_rule_rows_;      // launches into the pipe slots are sized for the usual batch, not for the buffers' worst case
         // from here on every batch's counters are also written to the slab's host-visible mirror (lane-group path)
         if (use_groups_ && env->GetCounterMirror(local_dev_id_, 0) != nullptr) env->PublishMirror();
     }
@@ -581,41 +552,12 @@ public:
         SetGPUDevice(local_dev_id_);
         IPCEnv* env = (IPCEnv*)(params->env);
         const int32_t batch_id = params->global_batch_id;
-        if (!use_groups_) {
-            mode_ = env->GetCurrentMode(batch_id);
-            memorypool_->SetCurrentMode(mode_);
-            memorypool_->SetIter(env->GetLocalBatchId(batch_id));
-            env->IPCWait(local_dev_id_, current_pipe_);
-            for (int i = 0; i < op_num_; i++) {
-                op_params_[i]->is_presc = false;
-                op_factory_[i]->run(op_params_[i]);
-            }
-            HIP_CALL(hipEventSynchronize(op_params_[op_num_ - 1]->event));   // every op is on this stream
-            ReportErrors(memorypool_);
-            env->IPCPost(local_dev_id_, current_pipe_);
-            if (batch_id % 1000 == 0 && local_dev_id_ == 0) std::cout << "batch id: " << batch_id << "\n";
-            current_pipe_ = (current_pipe_ + 1) % interbatch_concurrency_;
-            memorypool_->SetCurrentPipe(current_pipe_);
-            return;
-        }
+        if (!use_groups_) { RunOnceByOperators(env, batch_id); return; }
         if (pipe_ == nullptr) PrepareServing(params);
         const int32_t k = batch_id;
         const int p = current_pipe_;
         const auto t_a = std::chrono::steady_clock::now();
-        {   // the trainer has released this slot?  Poll for a short while (a futex wake costs more than a small batch's
-            // GPU time) before blocking: ~20000 polls with the gather hand-over, where the per-batch round trip IS the rate;
-            // LegionTuning.runner_spin_us (20 us by default) once batches go out as views -- the trainer then sets the pace and a
-            // group completes every few ms, so the thread sleeps instead of holding a core
-            bool got = env->IPCTryWait(local_dev_id_, p);
-            if (!got && kind_ == KIND_VIEWS && spin_us_ >= 0) {
-                const auto t0 = std::chrono::steady_clock::now();
-                while (!got && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < spin_us_)
-                    got = env->IPCTryWait(local_dev_id_, p);
-            } else {
-                for (int spin = 0; spin < 20000 && !got; spin++) got = env->IPCTryWait(local_dev_id_, p);
-            }
-            if (!got) env->IPCWait(local_dev_id_, p);
-        }
+        WaitForSlot(env, p);
         const auto t_b = std::chrono::steady_clock::now();
         if (kind_ == KIND_UNDECIDED) DecideHandover(env);       // the trainer end said what it is before its first sem_post
         sched_.retire_before(k);
@@ -762,6 +704,45 @@ public:
 private:
     struct Pending { hipEvent_t ev; int pipe; MemoryPool* lane; std::chrono::steady_clock::time_point enqueued; };
     enum { KIND_UNDECIDED = 0, KIND_VIEWS, KIND_GATHER };
+    // the schedule as runner_schedule.h's group rule reads it: mode and local id of global batch k
+    static auto ModeOf(IPCEnv* env) { return [env](int32_t k) { return env->GetCurrentMode(k); }; }
+    static auto LocalOf(IPCEnv* env) { return [env](int32_t k) { return env->GetLocalBatchId(k); }; }
+
+    // LEGION_RUNNER_GRAPH=0: the operator-by-operator path of the reference, one batch per call, eager launches
+    void RunOnceByOperators(IPCEnv* env, int32_t batch_id)
+    {
+        mode_ = env->GetCurrentMode(batch_id);
+        memorypool_->SetCurrentMode(mode_);
+        memorypool_->SetIter(env->GetLocalBatchId(batch_id));
+        env->IPCWait(local_dev_id_, current_pipe_);
+        for (int i = 0; i < op_num_; i++) {
+            op_params_[i]->is_presc = false;
+            op_factory_[i]->run(op_params_[i]);
+        }
+        HIP_CALL(hipEventSynchronize(op_params_[op_num_ - 1]->event));   // every op is on this stream
+        ReportErrors(memorypool_);
+        env->IPCPost(local_dev_id_, current_pipe_);
+        if (batch_id % 1000 == 0 && local_dev_id_ == 0) std::cout << "batch id: " << batch_id << "\n";
+        current_pipe_ = (current_pipe_ + 1) % interbatch_concurrency_;
+        memorypool_->SetCurrentPipe(current_pipe_);
+    }
+
+    // The trainer has released pipe slot p?  Poll for a short while (a futex wake costs more than a small batch's GPU time) before
+    // blocking: ~20000 polls with the gather hand-over, where the per-batch round trip IS the rate; LegionTuning.runner_spin_us (20 us
+    // by default) once batches go out as views -- the trainer then sets the pace and a group completes every few ms, so the thread
+    // sleeps instead of holding a core
+    void WaitForSlot(IPCEnv* env, int p)
+    {
+        bool got = env->IPCTryWait(local_dev_id_, p);
+        if (!got && kind_ == KIND_VIEWS && spin_us_ >= 0) {
+            const auto t0 = std::chrono::steady_clock::now();
+            while (!got && std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now() - t0).count() < spin_us_)
+                got = env->IPCTryWait(local_dev_id_, p);
+        } else {
+            for (int spin = 0; spin < 20000 && !got; spin++) got = env->IPCTryWait(local_dev_id_, p);
+        }
+        if (!got) env->IPCWait(local_dev_id_, p);
+    }
 
     // as_view: the batch is about to be handed over as views of its lane
     void ReportErrors(MemoryPool* mp, bool as_view = false)
@@ -808,21 +789,6 @@ private:
                   << ", " << lanes_ << " lanes per group, " << slots_ << " groups in flight\n" << std::flush;
     }
 
-    // the largest group the schedule ever forms (consecutive batches of one mode with consecutive local ids)
-    int32_t LargestGroup(IPCEnv* env, int32_t cap)
-    {
-        int32_t best = 1, keep = lanes_;
-        lanes_ = cap;
-        for (int32_t first = 0; first < max_step_;) {
-            int32_t mode = 0, local0 = 0;
-            const int32_t n = PlanGroup(env, first, mode, local0);
-            best = std::max(best, n);
-            first += n;
-        }
-        lanes_ = keep;
-        return best;
-    }
-
     // lanes x groups in flight, their arena, the hand-over descriptors of every (pipe slot, group slot, lane), the poster
     void CreateGroups(RunnerParams* params)
     {
@@ -831,38 +797,19 @@ private:
         max_step_ = env->GetMaxStep();
         std::vector<int32_t> fanout(params->fanout.begin(), params->fanout.end());
         const LegionTuning tune = lg::tuning();
-        const int64_t feature_rows = std::max<int64_t>(1, std::min<int64_t>(lane_rule_rows_, memorypool_->num_ids));     // the lanes: 1.2 x the PreSC maximum
-        // groups as large as bench.py's (524288 / B rounded down to a power of two, at most 512: the launch tails and the
-        // per-kernel floors are paid once per group), never larger than the schedule can fill, halved while the lanes of
-        // the groups in flight would take more than 0.6 of the HBM that is free now (tables and caches are in place).
-        // Three groups in flight: one being handed over, one running, one queued behind it -- with two, the GPU could only
-        // start group g+2 after the trainer had taken the first batch of g+1, and the next group's head never ran under the
-        // current group's heavy kernels (measured at RMAT-26, views: 132 k batches/s with two)
-        slots_ = tune.runner_slots >= 2 ? std::min(tune.runner_slots, 4) : 3;
-        lanes_ = 1;
-        while (lanes_ * 2 <= 512 && (int64_t)lanes_ * 2 * memorypool_->batch_size <= 524288) lanes_ *= 2;
-        if (tune.runner_lanes > 0) lanes_ = tune.runner_lanes;
-        lanes_ = std::min(lanes_, LargestGroup(env, lanes_));
-        const bool lane_features = handover_ != 1 && float_feature_len_ > 0;        // forced `gather`: rows never land in a lane
-        lane_features_ = lane_features;
-        const int64_t arena_lane = lg_pool_arena_bytes(memorypool_->batch_size, memorypool_->num_ids, lane_features ? feature_rows : 0, float_feature_len_,
-                                                       g_feature_out_dtype);
-        const int64_t lane_bytes = arena_lane + (int64_t)memorypool_->num_ids * 40 + (int64_t)memorypool_->max_slots * 28;
+        // how many lanes, how many groups in flight, what their arena holds (runner_plan.h), against the HBM that is free now
         size_t free_b = 0, total_b = 0;
         HIP_CALL(hipMemGetInfo(&free_b, &total_b));
-        while (lanes_ > 1 && (int64_t)lanes_ * slots_ * lane_bytes > (int64_t)(free_b / 10 * 6)) lanes_ /= 2;
-        arena_.bytes = arena_lane * lanes_ * slots_;
-        lane_feature_rows_ = lane_features ? (int32_t)feature_rows : 0;
-        // one overflow buffer per pipe slot behind the lanes, inside the arena (a trainer end that takes views maps the whole arena): the
-        // worst case of a batch, num_ids rows -- unless two of them would not leave the lanes their memory (then an oversized batch
-        // stops the server as before)
-        int64_t overflow_bytes = 0;
-        if (lane_features && handover_ == 0 && feature_rows < memorypool_->num_ids && tune.runner_overflow != 0) {
-            overflow_bytes = (((int64_t)memorypool_->num_ids * float_feature_len_ * lg_feature_out_bytes(g_feature_out_dtype)) + 4095) & ~(int64_t)4095;
-            if (interbatch_concurrency_ * overflow_bytes > (int64_t)(free_b / 10) || (int64_t)lanes_ * slots_ * lane_bytes + interbatch_concurrency_ * overflow_bytes > (int64_t)(free_b / 10 * 7))
-                overflow_bytes = 0;
-        }
-        arena_.bytes += interbatch_concurrency_ * overflow_bytes;
+        const RunnerGroupPlan plan = runner_group_plan(
+            memorypool_->batch_size, memorypool_->num_ids, memorypool_->max_slots, float_feature_len_, g_feature_out_dtype, lane_rule_rows_, (int64_t)free_b,
+            handover_, tune.runner_slots, tune.runner_lanes, tune.runner_overflow,
+            [&](int32_t cap) { return runner_largest_group(cap, max_step_, ModeOf(env), LocalOf(env)); }, interbatch_concurrency_);
+        slots_ = plan.slots;
+        lanes_ = plan.lanes;
+        const bool lane_features = lane_features_ = plan.lane_features;
+        lane_feature_rows_ = plan.lane_feature_rows;
+        const int64_t overflow_bytes = plan.overflow_bytes;
+        arena_.bytes = plan.arena_bytes;
         // The arena is built from physical chunks mapped in shuffled order unless another GPU must reach it (peer_gather = bulk):
         // 128 MB chunks -- a trainer end receives them as file descriptors (IPCEnv::PublishArena) -- against the 2 MB of an arena
         // nobody else maps; LegionTuning.arena_scatter_mb = 0: one plain allocation, handed over as a hipIpcMemHandle.
@@ -877,13 +824,11 @@ private:
         HIP_CALL(hipHostMalloc((void**)&arena_.mirror_host, (size_t)arena_.mirror_lanes * 32 * sizeof(int32_t), hipHostMallocMapped));
         memset(arena_.mirror_host, 0, (size_t)arena_.mirror_lanes * 32 * sizeof(int32_t));
         HIP_CALL(hipHostGetDevicePointer((void**)&arena_.mirror_dev, arena_.mirror_host, 0));
-        lg_set_pool_arena(&arena_);
         // use_graph bits: 1 graph replay, 16 weave (the next group's head on a second stream under this group's heavy kernels)
-        pipe_ = legion_pipeline_create_ex((LegionGraphStorage*)params->graph, (LegionFeatureStorage*)params->feature,
-                                          (LegionUnifiedCache*)params->cache, local_dev_id_, memorypool_->batch_size,
-                                          fanout.data(), hop_num_, lanes_, slots_, lane_features ? feature_rows : 0, 1 | 16,
-                                          g_feature_out_dtype);
-        lg_set_pool_arena(nullptr);
+        pipe_ = lg_pipeline_create((LegionGraphStorage*)params->graph, (LegionFeatureStorage*)params->feature,
+                                   (LegionUnifiedCache*)params->cache, local_dev_id_, memorypool_->batch_size,
+                                   fanout.data(), hop_num_, lanes_, slots_, lane_feature_rows_, 1 | 16,
+                                   g_feature_out_dtype, &arena_);
         if (pipe_ != nullptr && legion_pipeline_set_sample_replace(pipe_, g_sample_replace) != 0) {
             printf("legion_hip: %s\n", sample_refusal_text(SampleRefusal::Fanout));
             exit(EXIT_FAILURE);
@@ -932,32 +877,11 @@ private:
         d_deliver_ = (lg::DeliverParams*)d_alloc_space(sizeof(deliver_));
         HIP_CALL(hipMemcpy(d_deliver_, deliver_, sizeof(deliver_), hipMemcpyHostToDevice));
         // `gather` hand-over descriptors [pipe slot][group slot][lane]: the lane's own buffers as the source, the pipe slot's
-        // feature buffer as the gather's destination, its other arrays as deliver_slice's
-        std::vector<LanePtrs> h((size_t)interbatch_concurrency_ * slots_ * lanes_);
-        for (int p = 0; p < interbatch_concurrency_; p++)
-            for (int sl = 0; sl < slots_; sl++)
-                for (int g = 0; g < lanes_; g++) {
-                    MemoryPool* lp = reinterpret_cast<MemoryPool*>(legion_pipeline_pool(pipe_, sl, g));
-                    LanePtrs d = lp->HostLane(0);
-                    d.float_features = env->GetFloatFeatures(local_dev_id_, p);
-                    d.feature_rows = (int32_t)std::min<int64_t>(memorypool_->feature_rows, memorypool_->num_ids);
-                    d.deliver = d_deliver_ + p;
-                    // counters stay the lane's: deliver_slice reads them there and writes the slot's (incl. [2..3])
-                    h[((size_t)p * slots_ + sl) * lanes_ + g] = d;
-                }
-        d_desc_ = (LanePtrs*)d_alloc_space((int64_t)h.size() * sizeof(LanePtrs));
-        HIP_CALL(hipMemcpy(d_desc_, h.data(), h.size() * sizeof(LanePtrs), hipMemcpyHostToDevice));
-        if (overflow_[0] != nullptr) {      // the same lanes with the pipe slot's overflow buffer as the gather's destination, nothing delivered
-            for (int p = 0; p < interbatch_concurrency_; p++)
-                for (size_t i = 0; i < (size_t)slots_ * lanes_; i++) {
-                    LanePtrs& d = h[(size_t)p * slots_ * lanes_ + i];
-                    d.float_features = overflow_[p];
-                    d.feature_rows = memorypool_->num_ids;
-                    d.deliver = nullptr;
-                }
-            d_overflow_desc_ = (LanePtrs*)d_alloc_space((int64_t)h.size() * sizeof(LanePtrs));
-            HIP_CALL(hipMemcpy(d_overflow_desc_, h.data(), h.size() * sizeof(LanePtrs), hipMemcpyHostToDevice));
-        }
+        // feature buffer as the gather's destination, its other arrays as deliver_slice's (the counters stay the lane's: deliver_slice
+        // reads them there and writes the slot's, incl. [2..3]); and the same lanes with the pipe slot's overflow buffer as the
+        // gather's destination, nothing delivered
+        d_desc_ = UploadDescriptors(env, false);
+        if (overflow_[0] != nullptr) d_overflow_desc_ = UploadDescriptors(env, true);
         poster_ = std::thread([this, env] {
             // The poster polls (the reference's runner thread polls cudaEventQuery the same way, server.cu:319-324): one core
             // per GPU buys a hand-over latency of about a microsecond instead of a condition-variable wake-up.
@@ -995,17 +919,29 @@ private:
         });
     }
 
+    // every lane's descriptor with a pipe slot's buffer as its gather's destination: the slot's feature buffer, or its overflow buffer
+    LanePtrs* UploadDescriptors(IPCEnv* env, bool to_overflow)
+    {
+        std::vector<LanePtrs> h((size_t)interbatch_concurrency_ * slots_ * lanes_);
+        for (int p = 0; p < interbatch_concurrency_; p++)
+            for (int sl = 0; sl < slots_; sl++)
+                for (int g = 0; g < lanes_; g++) {
+                    LanePtrs d = reinterpret_cast<MemoryPool*>(legion_pipeline_pool(pipe_, sl, g))->HostLane(0);
+                    d.float_features = to_overflow ? overflow_[p] : env->GetFloatFeatures(local_dev_id_, p);
+                    d.feature_rows = to_overflow ? memorypool_->num_ids : (int32_t)std::min<int64_t>(memorypool_->feature_rows, memorypool_->num_ids);
+                    d.deliver = to_overflow ? nullptr : d_deliver_ + p;
+                    h[((size_t)p * slots_ + sl) * lanes_ + g] = d;
+                }
+        LanePtrs* dev = (LanePtrs*)d_alloc_space((int64_t)h.size() * sizeof(LanePtrs));
+        HIP_CALL(hipMemcpy(dev, h.data(), h.size() * sizeof(LanePtrs), hipMemcpyHostToDevice));
+        return dev;
+    }
+
     // the group that starts at global batch `first`: consecutive batches of one mode with consecutive local ids
     // (ipc_service.cu:213-253), at most `lanes_`
     int32_t PlanGroup(IPCEnv* env, int32_t first, int32_t& mode, int32_t& local0)
     {
-        mode = env->GetCurrentMode(first);
-        local0 = env->GetLocalBatchId(first);
-        int32_t n = 1;
-        while (n < lanes_ && first + n < max_step_ && env->GetCurrentMode(first + n) == mode &&
-               env->GetLocalBatchId(first + n) == local0 + n)
-            n++;
-        return n;
+        return runner_group_at(first, lanes_, max_step_, ModeOf(env), LocalOf(env), mode, local0);
     }
 
     // enqueues the next group of the schedule on the pipeline's next slot

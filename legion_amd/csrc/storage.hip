@@ -373,56 +373,38 @@ static bool d_free_scattered(void* ptr)
     return true;
 }
 
-// ---- a pipeline's lane-PRIVATE arrays (slot arrays, claim lists, frontier headers ...) from one block of shuffled chunks as well: while a
-//      thread has a private arena set, its d_alloc_space calls are carved from it (never freed one by one: the block goes when the pipeline
-//      goes).  Measured: +0.9 % on the whole job, +4 % on the sampler chain, against both separate allocations and one plain block -----------
-namespace {
-struct PrivArena { char* base; int64_t bytes, used; };
-thread_local PrivArena* g_priv = nullptr;
-thread_local int64_t g_count_bytes = -1;          // >= 0: d_alloc_space adds up what this thread asks for (lg_alloc_count_begin / _end)
-std::mutex g_priv_mu;
-std::vector<std::pair<char*, int64_t>> g_priv_ranges;
-}
-extern "C" void* lg_private_arena_begin(int64_t bytes, int32_t scatter_mb)
+// ---- a pipeline's lane-PRIVATE arrays (slot arrays, claim lists, frontier headers ...) from one block of shuffled chunks as well
+//      (PoolSource, legion_core.h): carved in the order they are asked for, never freed one by one ----------------------------------
+PrivateBlock* lg_private_block_create(int64_t bytes, int32_t scatter_mb)
 {
-    PrivArena* a = new PrivArena();
-    a->base = (char*)(scatter_mb > 0 ? d_alloc_scattered(bytes, scatter_mb) : nullptr);
-    if (a->base == nullptr) HIP_CALL(hipMalloc((void**)&a->base, (size_t)bytes));
-    a->bytes = bytes;
-    a->used = 0;
-    { std::lock_guard<std::mutex> lk(g_priv_mu); g_priv_ranges.push_back({a->base, bytes}); }
-    g_priv = a;
-    return a;
+    PrivateBlock* b = new PrivateBlock();
+    b->base = (char*)(scatter_mb > 0 ? d_alloc_scattered(bytes, scatter_mb) : nullptr);
+    if (b->base == nullptr) HIP_CALL(hipMalloc((void**)&b->base, (size_t)bytes));
+    b->bytes = bytes;
+    return b;
 }
-extern "C" void lg_private_arena_end() { g_priv = nullptr; }
-extern "C" void lg_alloc_count_begin() { g_count_bytes = 0; }
-extern "C" int64_t lg_alloc_count_end() { const int64_t v = g_count_bytes; g_count_bytes = -1; return v; }
-extern "C" void lg_private_arena_free(void* handle)
+void lg_private_block_destroy(PrivateBlock* b)
 {
-    PrivArena* a = (PrivArena*)handle;
-    if (!a) return;
-    {
-        std::lock_guard<std::mutex> lk(g_priv_mu);
-        for (size_t i = 0; i < g_priv_ranges.size(); i++)
-            if (g_priv_ranges[i].first == a->base) { g_priv_ranges.erase(g_priv_ranges.begin() + (long)i); break; }
+    if (!b) return;
+    d_free_space(b->base);
+    delete b;
+}
+void* lg_private_take(PrivateBlock* b, int64_t bytes)
+{
+    if (b == nullptr) return d_alloc_space(bytes);
+    const int64_t need = pool_round(bytes);
+    if (b->used + need > b->bytes) {
+        printf("legion_hip: private block of %lld bytes is too small (%lld in use, %lld more asked for)\n", (long long)b->bytes,
+               (long long)b->used, (long long)need);
+        exit(EXIT_FAILURE);
     }
-    if (!d_free_scattered(a->base)) HIP_CALL(hipFree(a->base));
-    delete a;
-}
-static bool in_private_arena(void* p)
-{
-    std::lock_guard<std::mutex> lk(g_priv_mu);
-    for (auto& r : g_priv_ranges) if ((char*)p >= r.first && (char*)p < r.first + r.second) return true;
-    return false;
+    void* p = b->base + b->used;
+    b->used += need;
+    return p;
 }
 
 extern "C" void* d_alloc_space(int64_t num_bytes)
 {
-    if (g_count_bytes >= 0) g_count_bytes += ((num_bytes > 0 ? num_bytes : 16) + 255) & ~(int64_t)255;
-    if (g_priv != nullptr) {
-        const int64_t need = ((num_bytes > 0 ? num_bytes : 16) + 255) & ~(int64_t)255;
-        if (g_priv->used + need <= g_priv->bytes) { void* p = g_priv->base + g_priv->used; g_priv->used += need; return p; }
-    }
     void* ret = nullptr;
     HIP_CALL(hipMalloc(&ret, num_bytes > 0 ? (size_t)num_bytes : 16));
     return ret;
@@ -483,7 +465,7 @@ void* lg_alloc_exported(int64_t num_bytes, void* handle64, const char* file, int
 
 extern "C" void d_free_space(void* d_ptr)
 {
-    if (d_ptr && !in_private_arena(d_ptr) && !d_free_scattered(d_ptr)) HIP_CALL(hipFree(d_ptr));
+    if (d_ptr && !d_free_scattered(d_ptr)) HIP_CALL(hipFree(d_ptr));
 }
 
 extern "C" void* host_alloc_space(int64_t num_bytes)
@@ -947,46 +929,47 @@ const LanePtrs* MemoryPool::DeviceLane()
     return d_lanes_ + current_pipe_;
 }
 
+// one private array of the pool (pool_plan.h) takes `p`: the one list of which member is which (null: the array is gone)
+static void pool_set_array(MemoryPool* mp, PoolArray what, void* p)
+{
+    switch (what) {
+        case PA_CACHE_SEARCH: mp->SetCacheSearchBuffer((int32_t*)p); break;
+        case PA_CLAIM_PAIRS: mp->claim_pairs = (unsigned long long*)p; break;
+        case PA_CLAIM_CNT: mp->claim_cnt = (int32_t*)p; break;
+        case PA_RUN_OFF: mp->run_off = (int32_t*)p; break;
+        case PA_KNOWN_PAIRS: mp->known_pairs = (unsigned long long*)p; break;
+        case PA_KNOWN_CNT: mp->known_cnt = (int32_t*)p; break;
+        case PA_AGG_SRC_IDS: mp->SetAggSrcId((int32_t*)p); break;
+        case PA_AGG_DST_IDS: mp->SetAggDstId((int32_t*)p); break;
+        case PA_TMP_PART_IND: mp->SetTmpPartIdx((char*)p); break;
+        case PA_TMP_PART_OFF: mp->SetTmpPartOff((int32_t*)p); break;
+        case PA_SLOT_DST: mp->slot_dst = (int32_t*)p; break;
+        case PA_SLOT_POS: mp->slot_pos = (int32_t*)p; break;
+        case PA_SLOT_FS: mp->slot_fs = (int32_t*)p; break;
+        case PA_NODE_SLOT: mp->node_slot = (int32_t*)p; break;
+        case PA_TILE_STATE: mp->tile_state = (unsigned long long*)p; break;
+        case PA_FH_EDGE: mp->fh_edge = (RowHdr*)p; break;
+        case PA_HOP_SCRATCH: mp->hop_scratch = (int32_t*)p; break;
+        case PA_COUNT: break;
+    }
+}
+
 void MemoryPool::Finalize()
 {
     SetGPUDevice(dev_id);
     d_free_space(d_lanes_);
     d_lanes_ = nullptr;
-    d_free_space(cache_search_buffer_);
-    d_free_space(claim_pairs);
-    d_free_space(run_off);
-    d_free_space(claim_cnt);
-    claim_cnt = nullptr;
-    d_free_space(known_pairs);
-    d_free_space(known_cnt);
-    known_pairs = nullptr;
-    known_cnt = nullptr;
-    claim_pairs = nullptr;
-    run_off = nullptr;
+    for (size_t i = 0; i < private_arrays.size(); i++) {       // (carved ones go with their block)
+        if (!private_carved) d_free_space(private_arrays[i]);
+        pool_set_array(this, private_plan.entries[i].what, nullptr);
+    }
+    private_arrays.clear();
     if (err_host) HIP_CALL(hipHostFree(err_host));
     err_host = err_dev = nullptr;
-    d_free_space(agg_src_ids_);
-    d_free_space(agg_dst_ids_);
-    d_free_space(tmp_part_ind_);
-    d_free_space(tmp_part_off_);
-    d_free_space(slot_dst);
-    d_free_space(slot_pos);
-    slot_pos = nullptr;
-    d_free_space(slot_fs);
-    d_free_space(node_slot);
-    slot_fs = node_slot = nullptr;
-    d_free_space(tile_state);
-    d_free_space(hop_scratch);
-    d_free_space(fh_edge);
-    fh_edge = nullptr;
     d_free_space(slot_pick);
     d_free_space(agg_edge_ids);
     slot_pick = nullptr;
     agg_edge_ids = nullptr;
-    cache_search_buffer_ = agg_src_ids_ = agg_dst_ids_ = tmp_part_off_ = nullptr;
-    tmp_part_ind_ = nullptr;
-    slot_dst = hop_scratch = nullptr;
-    tile_state = nullptr;
     if (owns_buffers) {
         for (int i = 0; i < pipeline_depth_; i++) {
             d_free_space(float_features_[i]);
@@ -1003,60 +986,57 @@ void MemoryPool::Finalize()
     }
 }
 
-static thread_local int64_t g_pool_claims_hint[2] = {0, 0};
-void lg_set_pool_claims_hint(int64_t last_hop_edges, int64_t nodes_before_last_hop)
+PoolPrivatePlan lg_pool_private_plan(const PoolShape& shape, const PoolSource& source)
 {
-    g_pool_claims_hint[0] = last_hop_edges;
-    g_pool_claims_hint[1] = nodes_before_last_hop;
+    const LegionTuning tune = lg::tuning();
+    return pool_private_plan(shape, source.claims_hint, tune.lds_small_buckets, tune.lds_claim_cap, tune.lds_known_cap, tune.col_slots);
 }
 
 // server-private scratch of one GPU: SS/engine/server.cu:216-234 plus the compaction scratch
 void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
-                           const int32_t* fanout, int32_t hop_num, int32_t float_feature_len)
+                           const int32_t* fanout, int32_t hop_num, int32_t float_feature_len, const PoolSource& source)
 {
     SetGPUDevice(dev_id);
     lg::tuning_refresh();
-    const LegionTuning& tune = lg::tuning();
-    int64_t num_ids = batch_size, per = batch_size;         // server.cu:187-199
-    mp->max_new.assign(1, batch_size);
-    for (int i = 0; i < hop_num; i++) { per *= fanout[i]; num_ids += per; mp->max_new.push_back(per); }
-    mp->max_fanout = 0;
-    for (int i = 0; i < hop_num; i++) mp->max_fanout = std::max(mp->max_fanout, fanout[i]);
-    if (num_ids >= ((int64_t)1 << 31) - 16384) {          // positions and slot indices are int32, as in the reference (operator_impl.cu:208)
-        printf("legion_hip: batch %d with this fan-out needs %lld slots / %lld ids; the limit is 2^31\n", batch_size, (long long)per,
-               (long long)num_ids);
+    const PoolShape shape = pool_shape(batch_size, fanout, hop_num);
+    if (shape.over_limit) {
+        printf("legion_hip: batch %d with this fan-out needs %lld slots / %lld ids; the limit is 2^31\n", batch_size, (long long)shape.max_slots,
+               (long long)shape.num_ids);
         exit(EXIT_FAILURE);
     }
+    mp->max_new = shape.max_new;
+    mp->max_fanout = shape.max_fanout;
     mp->dev_id = dev_id;
-    mp->num_ids = (int32_t)num_ids;
-    mp->max_slots = (int32_t)(hop_num > 0 ? per : batch_size);
+    mp->num_ids = (int32_t)shape.num_ids;
+    mp->max_slots = (int32_t)shape.max_slots;
     mp->total_num_nodes = total_num_nodes;
     mp->batch_size = batch_size;
     mp->float_feature_len = float_feature_len;
-    mp->SetCacheSearchBuffer((int32_t*)d_alloc_space(num_ids * sizeof(int32_t)));
-    {
-        // first touches (legion_core.h): no per-vertex state; one claim list and one known list per hash bucket, sized by the plan
-        // (sample_plan.h; PreSC's maxima when this thread's creator passed them on, lg_set_pool_claims_hint)
-        int64_t listed = 0;
-        for (int i = 1; i < hop_num; i++) listed += mp->max_new[i];
-        const SamplePoolPlan plan = sample_pool_plan(hop_num > 0 ? per : batch_size, listed, g_pool_claims_hint[0], g_pool_claims_hint[1],
-                                                     tune.lds_small_buckets, tune.lds_claim_cap, tune.lds_known_cap);
-        mp->lds_bucket_bits = plan.bucket_bits;
-        mp->last_hop_claims_hint = g_pool_claims_hint[0];
-        const int64_t n_buckets = (int64_t)1 << plan.bucket_bits;
-        mp->claim_cap = plan.claim_cap;
-        mp->claim_pairs = (unsigned long long*)d_alloc_space(n_buckets * plan.claim_chunks * LG_CLAIM_CHUNK * sizeof(unsigned long long));      // (interleaved by chunk: LanePtrs)
-        mp->claim_cnt = (int32_t*)d_alloc_space(n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t));
-        HIP_CALL(hipMemset(mp->claim_cnt, 0, n_buckets * LG_CLAIM_CNT_STRIDE * sizeof(int32_t)));
-        if (plan.run_off_parts > 0)      // 256 buckets: {first place, count} per partition tile and bucket (sample_kernel -> place_kernel)
-            mp->run_off = (int32_t*)d_alloc_space(plan.run_off_parts * n_buckets * 2 * sizeof(int32_t));
-        if (plan.known_cap > 0) {        // per-bucket lists of the nodes hops 1 .. H-1 add
-            mp->known_cap = plan.known_cap;
-            mp->known_pairs = (unsigned long long*)d_alloc_space(n_buckets * mp->known_cap * sizeof(unsigned long long));
-            mp->known_cnt = (int32_t*)d_alloc_space(n_buckets * sizeof(int32_t));
-            HIP_CALL(hipMemset(mp->known_cnt, 0, n_buckets * sizeof(int32_t)));
+    mp->source = source;
+    // first touches (legion_core.h): one claim list and one known list per hash bucket, sized by the plan (sample_plan.h; PreSC's
+    // maxima when the creator passed them on, PoolSource::claims_hint)
+    const PoolPrivatePlan plan = mp->private_plan = lg_pool_private_plan(shape, source);
+    mp->lds_bucket_bits = plan.sample.bucket_bits;
+    mp->last_hop_claims_hint = source.claims_hint[0];
+    mp->claim_cap = plan.sample.claim_cap;
+    mp->known_cap = plan.sample.known_cap;
+    mp->private_carved = source.priv != nullptr;
+    for (int32_t i = 0; i < plan.n; i++) {
+        const PoolPrivatePlan::Entry& e = plan.entries[i];
+        void* p = lg_private_take(source.priv, e.bytes);
+        mp->private_arrays.push_back(p);
+        pool_set_array(mp, e.what, p);
+        switch (e.what) {
+            case PA_CLAIM_CNT: case PA_KNOWN_CNT: case PA_TILE_STATE: case PA_HOP_SCRATCH:
+                HIP_CALL(hipMemset(p, 0, (size_t)e.bytes));
+                break;
+            case PA_SLOT_FS: case PA_NODE_SLOT:       // nothing carried yet
+                lg::fill_value_i32(nullptr, (int32_t*)p, LG_FS_UNKNOWN, e.bytes / 4);
+                break;
+            default: break;
         }
     }
+    if (mp->node_slot != nullptr) HIP_CALL(hipDeviceSynchronize());
     {   // host-visible error word (kernels OR LG_ERR_* into it; reading it costs the host nothing)
         void* h = nullptr;
         void* dptr = nullptr;
@@ -1066,25 +1046,6 @@ void lg_pool_alloc_private(MemoryPool* mp, int32_t dev_id, int32_t total_num_nod
         mp->err_host = (int32_t*)h;
         mp->err_dev = (int32_t*)dptr;
     }
-    mp->SetAggSrcId((int32_t*)d_alloc_space(num_ids * sizeof(int32_t)));
-    mp->SetAggDstId((int32_t*)d_alloc_space(num_ids * sizeof(int32_t)));
-    mp->SetTmpPartIdx((char*)d_alloc_space(num_ids * sizeof(char)));
-    mp->SetTmpPartOff((int32_t*)d_alloc_space(num_ids * sizeof(int32_t)));
-    const int64_t max_tiles = (mp->max_slots + LG_TILE - 1) / LG_TILE + 1;
-    mp->slot_dst = (int32_t*)d_alloc_space((int64_t)mp->max_slots * sizeof(int32_t));
-    mp->slot_pos = (int32_t*)d_alloc_space((int64_t)mp->max_slots * sizeof(int32_t));
-    if (tune.col_slots != 0) {       // carried feature-cache slots (column slots): per slot of a hop, per node of the batch
-        mp->slot_fs = (int32_t*)d_alloc_space((int64_t)mp->max_slots * sizeof(int32_t));
-        mp->node_slot = (int32_t*)d_alloc_space(num_ids * sizeof(int32_t));
-        lg::fill_value_i32(nullptr, mp->node_slot, LG_FS_UNKNOWN, num_ids);
-        lg::fill_value_i32(nullptr, mp->slot_fs, LG_FS_UNKNOWN, mp->max_slots);
-        HIP_CALL(hipDeviceSynchronize());
-    }
-    mp->tile_state = (unsigned long long*)d_alloc_space((max_tiles / LG_SLOTS_PER_LANE + 2) * sizeof(unsigned long long));
-    HIP_CALL(hipMemset(mp->tile_state, 0, (size_t)(max_tiles / LG_SLOTS_PER_LANE + 2) * sizeof(unsigned long long)));
-    mp->fh_edge = (RowHdr*)d_alloc_space(num_ids * sizeof(RowHdr));
-    mp->hop_scratch = (int32_t*)d_alloc_space(HS_WORDS * sizeof(int32_t));
-    HIP_CALL(hipMemset(mp->hop_scratch, 0, HS_WORDS * sizeof(int32_t)));
 }
 
 // edge-id mode: the per-slot picks and the per-edge ids, sized like slot_dst and agg_src_ids.  Plain allocations of the pool even
@@ -1226,19 +1187,9 @@ extern "C" void legion_feature_destroy(LegionFeatureStorage* f_)
 }
 
 // ---- output arena (legion_core.h PoolArena) ---------------------------------------------------
-static thread_local PoolArena* g_pool_arena = nullptr;
-void lg_set_pool_arena(PoolArena* arena) { g_pool_arena = arena; }
-PoolArena* lg_get_pool_arena() { return g_pool_arena; }
-static inline int64_t arena_round(int64_t b) { return (b + 255) & ~(int64_t)255; }
-int64_t lg_pool_arena_bytes(int64_t batch_size, int64_t num_ids, int64_t feature_rows, int64_t float_feature_len, int32_t feature_out_dtype)
+static void* arena_take(PoolArena* a, int64_t bytes)
 {
-    return 3 * arena_round(num_ids * 4) + arena_round(batch_size * 4) + 2 * arena_round(64) +
-           arena_round(feature_rows * float_feature_len * lg_feature_out_bytes(feature_out_dtype));
-}
-static void* arena_take(int64_t bytes)
-{
-    PoolArena* a = g_pool_arena;
-    const int64_t need = arena_round(bytes);
+    const int64_t need = (bytes + 255) & ~(int64_t)255;
     if (a->used + need > a->bytes) {
         printf("legion_hip: lane arena of %lld bytes is too small (%lld in use, %lld more asked for)\n", (long long)a->bytes,
                (long long)a->used, (long long)need);
@@ -1249,21 +1200,21 @@ static void* arena_take(int64_t bytes)
     return p;
 }
 
-extern "C" LegionMemoryPool* legion_pool_create(int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
-                                                const int32_t* fanout, int32_t hop_num,
-                                                int32_t float_feature_len, int32_t pipeline_depth)
+MemoryPool* lg_pool_create(int32_t dev_id, int32_t total_num_nodes, int32_t batch_size, const int32_t* fanout, int32_t hop_num,
+                           int32_t float_feature_len, int32_t pipeline_depth, const PoolSource& source)
 {
     if (pipeline_depth < 1) pipeline_depth = 1;
     MemoryPool* mp = new MemoryPool(pipeline_depth);
-    lg_pool_alloc_private(mp, dev_id, total_num_nodes, batch_size, fanout, hop_num, float_feature_len);
-    const bool in_arena = g_pool_arena != nullptr && pipeline_depth == 1;
+    lg_pool_alloc_private(mp, dev_id, total_num_nodes, batch_size, fanout, hop_num, float_feature_len, source);
+    PoolArena* arena = source.arena;
+    const bool in_arena = arena != nullptr && pipeline_depth == 1;
     mp->owns_buffers = !in_arena;
     mp->arena_backed = in_arena;
-    auto take = [&](int64_t bytes) { return in_arena ? arena_take(bytes) : d_alloc_space(bytes); };
-    if (in_arena && g_pool_arena->mirror_dev != nullptr && g_pool_arena->mirror_used < g_pool_arena->mirror_lanes) {
-        mp->counter_mirror_dev = g_pool_arena->mirror_dev + 32 * (int64_t)g_pool_arena->mirror_used;
-        mp->counter_mirror_host = g_pool_arena->mirror_host + 32 * (int64_t)g_pool_arena->mirror_used;
-        g_pool_arena->mirror_used++;
+    auto take = [&](int64_t bytes) { return in_arena ? arena_take(arena, bytes) : d_alloc_space(bytes); };
+    if (in_arena && arena->mirror_dev != nullptr && arena->mirror_used < arena->mirror_lanes) {
+        mp->counter_mirror_dev = arena->mirror_dev + 32 * (int64_t)arena->mirror_used;
+        mp->counter_mirror_host = arena->mirror_host + 32 * (int64_t)arena->mirror_used;
+        arena->mirror_used++;
     }
     for (int i = 0; i < pipeline_depth; i++) {            // ipc_service.cu:134-161 without the handles
         mp->SetSampledIds((int32_t*)take((int64_t)mp->num_ids * 4), i);
@@ -1277,7 +1228,15 @@ extern "C" LegionMemoryPool* legion_pool_create(int32_t dev_id, int32_t total_nu
         HIP_CALL(hipMemset(mp->GetEdgeCounter(), 0, 64));
     }
     mp->SetCurrentPipe(0);
-    return reinterpret_cast<LegionMemoryPool*>(mp);
+    return mp;
+}
+
+extern "C" LegionMemoryPool* legion_pool_create(int32_t dev_id, int32_t total_num_nodes, int32_t batch_size,
+                                                const int32_t* fanout, int32_t hop_num,
+                                                int32_t float_feature_len, int32_t pipeline_depth)
+{
+    return reinterpret_cast<LegionMemoryPool*>(lg_pool_create(dev_id, total_num_nodes, batch_size, fanout, hop_num, float_feature_len,
+                                                              pipeline_depth, PoolSource()));
 }
 
 extern "C" void legion_pool_alloc_features(LegionMemoryPool* p_, int64_t rows)
@@ -1291,8 +1250,7 @@ extern "C" void legion_pool_alloc_features(LegionMemoryPool* p_, int64_t rows)
     for (int i = 0; i < mp->PipelineDepth(); i++) {
         mp->SetCurrentPipe(i);
         if (mp->arena_backed) {           // (once per pool: the arena is sized for exactly one feature buffer per lane)
-            if (g_pool_arena == nullptr) { printf("legion_hip: arena-backed pool without its arena\n"); exit(EXIT_FAILURE); }
-            mp->SetFloatFeatures((float*)arena_take(rows * row_bytes), i);
+            mp->SetFloatFeatures((float*)arena_take(mp->source.arena, rows * row_bytes), i);
             continue;
         }
         d_free_space(mp->GetFloatFeatures());
@@ -1417,8 +1375,8 @@ extern "C" int64_t legion_pool_state_bytes(const LegionMemoryPool* p_)
 {
     const MemoryPool* mp = reinterpret_cast<const MemoryPool*>(p_);
     if (!mp) return 0;
-    // one hop's claim lists + the known lists (nothing that scales with the graph)
-    return ((((int64_t)mp->claim_cap + LG_CLAIM_CHUNK - 1) / LG_CLAIM_CHUNK * LG_CLAIM_CHUNK) << mp->lds_bucket_bits) * 8 + ((int64_t)mp->known_cap << mp->lds_bucket_bits) * 8;
+    // one hop's claim lists + the known lists (nothing that scales with the graph), as the pool's plan sized them
+    return mp->private_plan.bytes_of(PA_CLAIM_PAIRS) + mp->private_plan.bytes_of(PA_KNOWN_PAIRS);
 }
 
 extern "C" void legion_pool_destroy(LegionMemoryPool* p_)

@@ -1,7 +1,7 @@
 """The sanitizer leg of the CPU suite: every piece of plain host C / C++ of the test infrastructure and the
 tools, built with AddressSanitizer + UndefinedBehaviorSanitizer (oracle/Makefile target `san`, -fno-sanitize-recover: any finding
 ends the program) and run -- the oracle under its own known-answer and property tests, rocThrust's host generator against the
-committed golden file, the runner-schedule simulation, and the protocol-only trainer end against a server end played by this test.
+committed golden file, the runner-schedule simulation, the plan headers' tables, and the protocol-only trainer end against a server end played by this test.
 CPU only: the GPU box has no sanitizer."""
 import ctypes
 import json
@@ -56,6 +56,14 @@ def test_runner_schedule_simulation_under_asan_ubsan(san):
 def test_batch_op_lists_under_asan_ubsan(san):
     """batch_ops.h fills fixed-size lists: its literal table once more, with every write checked."""
     res = subprocess.run([os.path.join(san, "batch_ops_test")], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
+    assert res.returncode == 0 and " 0 failed" in res.stdout and "runtime error" not in res.stdout, res.stdout[-3000:]
+
+
+@pytest.mark.parametrize("name", ["pool_plan_test", "runner_plan_test"])
+def test_memory_plans_under_asan_ubsan(san, name):
+    """pool_plan.h fills a fixed-size list of arrays and a vector per shape, runner_plan.h multiplies byte counts up to the HBM's size:
+    their literal tables once more, with every write and every signed operation checked."""
+    res = subprocess.run([os.path.join(san, name)], env=ENV, stdout=subprocess.PIPE, stderr=subprocess.STDOUT, text=True, timeout=600)
     assert res.returncode == 0 and " 0 failed" in res.stdout and "runtime error" not in res.stdout, res.stdout[-3000:]
 
 
