@@ -629,6 +629,47 @@ int32_t legion_negative_sample(legion_stream_t stream, LegionGraphStorage* graph
 int64_t legion_unique_ids_scratch_bytes(int32_t m);
 int32_t legion_unique_ids(legion_stream_t stream, const int32_t* ids_devptr /* int32[m] */, int32_t m, int32_t* unique_out /* int32[m] */,
                           int32_t* local_out /* int32[m] */, int32_t* count_out /* int32[1] */, void* scratch, int64_t scratch_bytes);
+/* A neighbourhood taken whole (DGL's g.in_edges(v, form='all'), the edges of MultiLayerFullNeighborSampler(1) and of dgl.in_subgraph
+ * followed by to_block), new in this build; no reference counterpart.  Two ops: the prefix sums of the degrees of a list of rows, and
+ * every entry of those rows as a (dst, src, eid) triple.  All buffers are device memory.  Each op is enqueued on `stream`, on the device
+ * current at the call; nothing synchronises with the host, and each call may be captured into a graph.  Both read the FULL CSR only (the
+ * arrays given to legion_graph_create).  A CSR row is the sampler's dst side and a column entry its src side, as above.  N = node_num;
+ * rows is int32[n], and its entries may repeat.
+ *
+ * legion_row_offsets (also DGL's g.in_degrees(v), by differences).  For i in [0, n), r = rows[i]:
+ *   1. deg(i) = indptr[r + 1] - indptr[r] for r in [0, N) (the pair is one 16-byte load); for r outside the graph deg(i) = 0 and no
+ *      memory is read for r.  Dead (negative) column entries count: a slot is a position in the row;
+ *   2. offsets_out[i] = the sum of deg(i') over i' < i, for i in [0, n], in int64: offsets_out[n] is the total M.
+ * offsets_out is int64[n + 1].  scratch: device memory, 8-byte aligned, of at least legion_row_offsets_scratch_bytes(n) bytes (one int64
+ * per tile of 256 rows; -1 for n < 0 or n > LEGION_IN_EDGES_MAX_ROWS, the reach of the one-workgroup scan over at most 4 096 tile sums);
+ * two calls in flight on different streams need scratch of their own.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, rows_devptr, offsets_out or scratch; n < 0;
+ * n > LEGION_IN_EDGES_MAX_ROWS; scratch_bytes below legion_row_offsets_scratch_bytes(n).  n == 0 returns 0 and writes offsets_out[0] = 0
+ * only.
+ *
+ * legion_in_edges takes rows, n, the offsets of the call above and m, the slots to write.  For slot p in [0, m):
+ *   1. i = #{ v in [0, n] : offsets[v] <= p } - 1, an upper-bound binary search over the n + 1 offsets: rows without entries are skipped
+ *      (a lower bound would name the first of a run of empty rows);
+ *   2. i >= n (that is, p >= offsets[n]): dst_out[p] = src_out[p] = -1 and eid_out[p] = -1;
+ *   3. else j = p - offsets[i], r = rows[i], e = indptr[r] + j in 64 bits: dst_out[p] = i (the position in rows: the block's dst index),
+ *      src_out[p] = col[e] (a dead entry stays -1, as everywhere else in the library), eid_out[p] = e;
+ *   4. memory safety does not rest on the caller's offsets: whatever they hold, nothing is read outside offsets[0 .. n], rows, indptr
+ *      and col.  A slot is -1 / -1 / -1 unless i lies in [0, n), r lies in [0, N) and 0 <= j < indptr[r + 1] - indptr[r] (the pair
+ *      loaded once).  For offsets that are not non-decreasing the search of 1. finds some i in [-1, n], which one is not specified;
+ *      the slot is then either -1 / -1 / -1 or the entry j = p - offsets[i] of row rows[i].
+ * m is a capacity: the whole of dst_out, src_out (int32[m]) and eid_out (int64[m], may be NULL) is defined.  m below M writes a prefix,
+ * m above M writes -1 from M on, so that a capturing caller picks a bound without a host read.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, rows_devptr, offsets_devptr, dst_out or src_out; n < 0;
+ * n > LEGION_IN_EDGES_MAX_ROWS; m < 0; m > 2^31 - 1.  m == 0 returns 0 and enqueues nothing.
+ * Not offered: out-edges (there is no reverse CSR); dropping dead entries; heterogeneous graphs; more than 2^20 rows a call (a caller
+ * batches); the server, the launcher and the wire. */
+#define LEGION_IN_EDGES_MAX_ROWS 1048576
+int64_t legion_row_offsets_scratch_bytes(int32_t n);
+int32_t legion_row_offsets(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                           int64_t* offsets_out /* int64[n + 1] */, void* scratch, int64_t scratch_bytes);
+int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                        const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t* dst_out /* int32[m] */,
+                        int32_t* src_out /* int32[m] */, int64_t* eid_out /* int64[m], or NULL */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -962,6 +962,25 @@ void launch_negative_sample(hipStream_t s, const NegativeParams& p);
 void launch_unique_ids(hipStream_t s, const int32_t* ids, int32_t m, int32_t* unique, int32_t* local, int32_t* count, void* scratch,
                        int64_t slots, int64_t n_tiles);
 
+// a neighbourhood taken whole (kernels_in_edges.hip; the rules: legion_row_offsets and legion_in_edges in legion_hip.h).  The arguments
+// are the caller's to check (in_edges_rule.h).
+// n_tiles: row_offsets_tiles(n); scratch: row_offsets_scratch_bytes(n) bytes, 8-byte aligned
+void launch_row_offsets(hipStream_t s, const int64_t* indptr, int32_t node_num, const int32_t* rows, int32_t n, int64_t* offsets,
+                        void* scratch, int64_t n_tiles);
+struct InEdgesParams {
+    const int64_t* indptr;          // the FULL CSR
+    const int32_t* col;
+    const int32_t* rows;            // int32[n]
+    const int64_t* offsets;         // int64[n + 1]: whatever they hold, nothing is read outside them, rows, indptr and col
+    int32_t* dst;                   // int32[m]
+    int32_t* src;                   // int32[m]
+    int64_t* eid;                   // int64[m], or null
+    int32_t node_num;
+    int32_t n;
+    int64_t m;                      // slots to write, <= 2^31 - 1
+};
+void launch_in_edges(hipStream_t s, const InEdgesParams& p);
+
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {
     WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the

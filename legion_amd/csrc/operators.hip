@@ -18,6 +18,7 @@
 #include "walk_rule.h"
 #include "node2vec_rule.h"
 #include "link_rule.h"
+#include "in_edges_rule.h"
 
 #include <iostream>
 
@@ -501,6 +502,38 @@ extern "C" int32_t legion_unique_ids(legion_stream_t stream, const int32_t* ids_
         return -1;
     lg::launch_unique_ids(static_cast<hipStream_t>(stream), ids_devptr, m, unique_out, local_out, count_out, scratch,
                           unique_ids_table_slots(m), unique_ids_tiles(m));
+    return 0;
+}
+
+// A neighbourhood taken whole (the rules: legion_hip.h; the refusals and the scratch size: in_edges_rule.h).  As above: every check
+// comes before the launch.
+extern "C" int64_t legion_row_offsets_scratch_bytes(int32_t n)
+{
+    return row_offsets_scratch_bytes(n);
+}
+
+extern "C" int32_t legion_row_offsets(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                      int64_t* offsets_out, void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_out || !scratch) return -1;
+    if (row_offsets_refusal(n, scratch_bytes) != InEdgesRefusal::Ok) return -1;
+    lg::launch_row_offsets(static_cast<hipStream_t>(stream), graph->GetCSRNodeIndexCPU(), graph->NodeNum(), rows_devptr, n, offsets_out,
+                           scratch, row_offsets_tiles(n));
+    return 0;
+}
+
+extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                   const int64_t* offsets_devptr, int64_t m, int32_t* dst_out, int32_t* src_out, int64_t* eid_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_devptr || !dst_out || !src_out) return -1;
+    if (in_edges_refusal(n, m) != InEdgesRefusal::Ok) return -1;
+    if (m == 0) return 0;
+    const lg::InEdgesParams p{.indptr = graph->GetCSRNodeIndexCPU(), .col = graph->GetCSRNodeMatrixCPU(), .rows = rows_devptr,
+                              .offsets = offsets_devptr, .dst = dst_out, .src = src_out, .eid = eid_out, .node_num = graph->NodeNum(),
+                              .n = n, .m = m};
+    lg::launch_in_edges(static_cast<hipStream_t>(stream), p);
     return 0;
 }
 

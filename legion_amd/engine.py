@@ -508,6 +508,105 @@ class GraphStorage:
         seeds, local, count = unique_ids(ids, stream=stream)
         return seeds, count, local[:B], local[B:2 * B], local[2 * B:].reshape(B, int(k))
 
+    IN_EDGES_MAX_ROWS = 2 ** 20                      # LEGION_IN_EDGES_MAX_ROWS
+
+    @staticmethod
+    def _check_rows(rows, name="rows"):
+        """The rows of row_offsets / in_edges by the rules of legion_row_offsets, before anything touches a device: ValueError with the
+        reason.  Returns (rows as a tensor, n)."""
+        rows = _as_1d(rows, torch.int32, name)
+        n = int(rows.numel())
+        if n > GraphStorage.IN_EDGES_MAX_ROWS:
+            raise ValueError(f"{n} {name} in one call, at most {GraphStorage.IN_EDGES_MAX_ROWS}")
+        return rows, n
+
+    def _row_offsets(self, rows, n, stream):
+        """rows: on the device, contiguous, checked."""
+        dev = self.col.device
+        if n == 0:                                   # (an empty tensor has no address to hand over)
+            return torch.zeros((1,), dtype=torch.int64, device=dev)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        nbytes = int(self._lib.legion_row_offsets_scratch_bytes(n))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+        _enqueue(self._lib, "legion_row_offsets", "row_offsets", dev, stream,
+                 (self.handle, _ptr(rows), n, _ptr(offsets), _ptr(scratch), nbytes), (rows, offsets, scratch))
+        return offsets
+
+    def row_offsets(self, rows, stream=None):
+        """The prefix sums of the degrees of rows (the rule: legion_row_offsets in legion_hip.h; DGL's g.in_degrees(rows) is
+        offsets[1:] - offsets[:-1]).  rows: int32 vertex ids, a CUDA tensor or anything torch.as_tensor takes; at most
+        IN_EDGES_MAX_ROWS of them; they may repeat, and a row outside the graph has no entries.  Returns int64 [n + 1]: offsets[i] is
+        where row i's entries start in what in_edges writes, offsets[n] their number M; dead (negative) column entries count.  No sync.
+        Enqueued on `stream` (default: the current one)."""
+        rows, n = self._check_rows(rows)
+        return self._row_offsets(rows.to(self.col.device).contiguous(), n, stream)
+
+    def _in_edges(self, rows, n, return_eids, stream, limit=None):
+        """(offsets, dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + M may be."""
+        dev = self.col.device
+        offsets = self._row_offsets(rows, n, stream)
+        if stream is None:
+            M = int(offsets[n].item())
+        else:
+            with torch.cuda.stream(stream):
+                M = int(offsets[n].item())
+        if M > 2 ** 31 - 1:
+            raise ValueError(f"the rows hold {M} entries, at most 2^31 - 1 a call")
+        if limit is not None and n + M > limit:
+            raise ValueError(f"{n} seeds and their {M} entries are {n + M} ids in one call, at most {limit}")
+        dst = torch.empty((M,), dtype=torch.int32, device=dev)
+        src = torch.empty((M,), dtype=torch.int32, device=dev)
+        eids = torch.empty((M,), dtype=torch.int64, device=dev) if return_eids else None
+        if M > 0:
+            _enqueue(self._lib, "legion_in_edges", "in_edges", dev, stream,
+                     (self.handle, _ptr(rows), n, _ptr(offsets), M, _ptr(dst), _ptr(src), _ptr(eids)), (rows, offsets, dst, src, eids))
+        return offsets, dst, src, eids
+
+    def in_edges(self, rows, *, return_eids=False, stream=None):
+        """Every entry of rows (DGL's g.in_edges(rows, form='all'); the rule: legion_in_edges in legion_hip.h).  rows as in row_offsets.
+        Returns (offsets, dst, src) and with return_eids also eids: offsets int64 [n + 1] as row_offsets returns them; dst, src int32
+        [M] and eids int64 [M] with M = offsets[n]: entry p of them is position p - offsets[i] of row rows[i], dst[p] = i (the index
+        into rows, not the vertex: rows[dst] is the vertex), src[p] = col[eids[p]], -1 for a dead entry, and eids[p] its position in
+        col.  The outputs are sized exactly, so offsets[n] is read back to the host once: the call synchronises `stream` (default: the
+        current one), on which everything is enqueued.  A capturing caller uses legion_in_edges with a capacity instead."""
+        _need_bool("return_eids", return_eids)
+        rows, n = self._check_rows(rows)
+        out = self._in_edges(rows.to(self.col.device).contiguous(), n, return_eids, stream)
+        return out if return_eids else out[:3]
+
+    def full_neighbor_block(self, seeds, *, return_eids=False, stream=None):
+        """The block of all in-edges of seeds (DGL's MultiLayerFullNeighborSampler(1), or dgl.in_subgraph followed by to_block): in_edges,
+        then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph, as rows in row_offsets.  Returns (input_nodes,
+        dst_local, src_local, offsets) and with return_eids also eids: input_nodes int32 [U], the distinct vertices, the seeds first
+        and in their order, then the other sources in order of first appearance; dst_local, src_local int32 [M], indices into
+        input_nodes (dst_local[p] is also the index into seeds; src_local[p] == -1 for a dead entry); offsets and eids as in_edges
+        returns them.  input_nodes is what FeatureStorage.set_ids takes, or what a feature table is indexed with.  ValueError if the
+        seeds and their entries are more than UNIQUE_MAX_IDS ids (before any device work beyond the offsets), and if a seed repeats or
+        lies outside the graph: a block's dst nodes are distinct.  Reads back offsets[n], the seeds' local indices and the number of
+        distinct vertices: it synchronises `stream` (default: the current one)."""
+        _need_bool("return_eids", return_eids)
+        seeds, n = self._check_rows(seeds, "seeds")
+        _check_unique(n)
+        seeds = seeds.to(self.col.device).contiguous()
+        offsets, dst, src, eids = self._in_edges(seeds, n, return_eids, stream, limit=UNIQUE_MAX_IDS)
+
+        def chain():
+            ids = torch.cat([seeds, src])
+            unique, local, count = unique_ids(ids, stream=stream)
+            ok = bool(torch.equal(local[:n], torch.arange(n, dtype=torch.int32, device=local.device)))      # distinct, none negative
+            ok = ok and bool((seeds < self.node_num).all())
+            return unique, local, int(count.item()), ok
+
+        if stream is None:
+            unique, local, U, ok = chain()
+        else:
+            with torch.cuda.stream(stream):
+                unique, local, U, ok = chain()
+        if not ok:
+            raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
+        out = (unique[:U], dst, local[n:], offsets)
+        return out + (eids,) if return_eids else out
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))
