@@ -670,6 +670,55 @@ int32_t legion_row_offsets(legion_stream_t stream, LegionGraphStorage* graph, co
 int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
                         const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t* dst_out /* int32[m] */,
                         int32_t* src_out /* int32[m] */, int64_t* eid_out /* int64[m], or NULL */);
+/* Layer-neighbour sampling (LABOR-0 of Balin and Catalyurek, NeurIPS 2023; DGL's dgl.sampling.sample_labors and
+ * dgl.dataloading.LaborSampler), new in this build; no reference counterpart.  Every SOURCE vertex t has one random number r_t for the
+ * whole call, and the entry t -> s is kept iff r_t < fanout / deg(s): a seed keeps fanout neighbours in expectation, and seeds with
+ * common neighbours keep the same ones, so a layer has fewer input nodes than per-seed sampling gives.  The ops are legion_in_edges with
+ * a predicate and a stable compaction.  Orientation, N, rows, the buffers, the stream and the FULL CSR are as for legion_in_edges: a
+ * CSR row is the dst side and a column entry the src side.  The result is a pure function of the arguments.
+ *
+ * The hash.  splitmix64(x): x += 0x9E3779B97F4A7C15; x = (x ^ x >> 30) * 0xBF58476D1CE4E5B9; x = (x ^ x >> 27) * 0x94D049BB133111EB;
+ * x ^ x >> 31, in uint64 (the function of the synthetic generators).  key = splitmix64((uint64)salt);
+ * labor_hash(v, salt) = (uint32)(splitmix64(key ^ (uint64)(uint32)v) >> 32).  The salt is hashed first so that two salts do not merely
+ * permute the same numbers among neighbouring ids.
+ * The predicate.  labor_keep(h, d, fanout) is true iff h * d < fanout * 2^32, evaluated exactly in integers (d is an int64 degree and
+ * may exceed 2^32: the product has up to 95 bits); there is no floating point anywhere in the rule.  Hence d <= fanout keeps every
+ * entry and h == 0 always keeps.
+ *
+ * For slot p in [0, m):
+ *   1. i, j, r, e and src = col[e] are found exactly as rules 1 - 4 of legion_in_edges find them, with the same guarantee: memory
+ *      safety does not rest on the caller's offsets;
+ *   2. d = indptr[r + 1] - indptr[r] from the pair loaded once, not from offsets: dead entries count in d, as they do in
+ *      legion_row_offsets, and so do the slots of the row at or past m;
+ *   3. the slot is kept iff it resolved to an entry (e >= 0), src >= 0, and labor_keep(labor_hash(src, salt), d, fanout);
+ *   4. kept slots are written in slot order: the kept slot p goes to position #{ kept p' < p }, its triple is (dst = i, src, eid = e).
+ *      dst is non-decreasing, so a caller gets CSR offsets by a search.
+ * legion_labor_count leaves in scratch the exclusive prefix sums of the kept counts per tile of 1 024 slots and their total K, and
+ * writes K to count_out[0] (int64[1]).  legion_labor_edges, given the same rows, n, offsets, m, fanout and salt and the scratch as
+ * _count left it, writes the kept triples to positions [0, min(K, cap)) and -1 / -1 / -1 to [K, cap).  cap is a capacity, as m is for
+ * legion_in_edges: dst_out, src_out (int32[cap]) and eid_out (int64[cap], may be NULL) are defined whole, and both calls may be captured
+ * into one graph with no host read between them.  Memory safety does not rest on the content of scratch: a triple whose position falls
+ * outside [0, cap) is dropped and the fill is clamped to [0, cap]; with a scratch that _count did not write the output values are
+ * unspecified, but nothing outside [0, cap) is written.
+ * scratch: device memory, 8-byte aligned, of at least legion_labor_scratch_bytes(m) bytes: one int64 per tile plus one, plus one int64
+ * per 256 tiles; -1 for m < 0 or m > LEGION_LABOR_MAX_SLOTS (2^20 tile counts make at most 4 096 second-level sums, the reach of the
+ * one-workgroup scan; a caller batches beyond it).  Two calls in flight on different streams need scratch of their own.
+ * Both return 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, rows_devptr, offsets_devptr, scratch, count_out,
+ * dst_out or src_out; n < 0; n > LEGION_IN_EDGES_MAX_ROWS; m < 0; m > LEGION_LABOR_MAX_SLOTS; fanout < 1; cap < 0; cap > 2^31 - 1;
+ * scratch_bytes below legion_labor_scratch_bytes(m).  m == 0: _count writes count_out[0] = 0 and a zero total only.  cap == 0 returns 0
+ * and enqueues nothing.
+ * Not offered: the importance-sampled variants (LABOR-1, LABOR-*); per-edge importance weights (with LABOR-0 the mean over the kept
+ * in-edges is the Hajek estimator); prob=; out-edges (there is no reverse CSR); heterogeneous graphs; the server, the launcher and the
+ * wire. */
+#define LEGION_LABOR_MAX_SLOTS 1073741824
+int64_t legion_labor_scratch_bytes(int64_t m);
+int32_t legion_labor_count(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                           const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t fanout, int64_t salt,
+                           int64_t* count_out /* int64[1] */, void* scratch, int64_t scratch_bytes);
+int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                           const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t fanout, int64_t salt,
+                           const void* scratch /* as legion_labor_count left it */, int64_t scratch_bytes, int64_t cap,
+                           int32_t* dst_out /* int32[cap] */, int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -18,6 +18,7 @@
 //     beside the offsets (12 KiB more LDS, seven workgroups a CU: 4 -- 20 % slower); neither is built.
 // Bound: in_edges by its stores and the col reads (12 -- 20 bytes a slot); no MFMA.
 #include "legion_core.h"
+#include "upper_counts.h"
 #include "walk_step.h"
 
 namespace lg {
@@ -125,35 +126,6 @@ void launch_row_offsets(hipStream_t s, const int64_t* indptr, int32_t node_num, 
 // ------------------------------------------------------------------------------------------
 // in_edges
 // ------------------------------------------------------------------------------------------
-// K upper bounds at once, their chains of dependent loads interleaved: c[j] = #{ v in [0, len) : a[v] <= q[j] } for a non-decreasing a
-// (for any other a: some value in [0, len]); len <= 0 or !live[j]: 0.  Reads a[0 .. len) only.
-template <int32_t K>
-__device__ __forceinline__ void upper_counts(const int64_t* a, int32_t len, const int64_t (&q)[K], const bool (&live)[K], int32_t (&c)[K])
-{
-    int32_t m[K];
-#pragma unroll
-    for (int32_t j = 0; j < K; j++) {
-        c[j] = 0;
-        m[j] = live[j] ? max(len, 0) : 0;
-    }
-    bool more = true;
-    while (more) {                                                    // each trip halves every m[j] > 0: at most 21 trips
-        more = false;
-        int64_t v[K];
-#pragma unroll
-        for (int32_t j = 0; j < K; j++) v[j] = m[j] > 0 ? a[c[j] + (m[j] >> 1)] : 0;      // (c + m / 2 < c + m <= len)
-#pragma unroll
-        for (int32_t j = 0; j < K; j++) {
-            if (m[j] > 0) {
-                const int32_t half = m[j] >> 1;
-                if (v[j] <= q[j]) { c[j] += half + 1; m[j] -= half + 1; }
-                else m[j] = half;
-                more |= m[j] > 0;
-            }
-        }
-    }
-}
-
 __global__ __launch_bounds__(LG_IN_EDGES_THREADS, 8) void in_edges_kernel(InEdgesParams p)
 {
     constexpr int32_t ILP = LG_IN_EDGES_ILP;

@@ -981,6 +981,30 @@ struct InEdgesParams {
 };
 void launch_in_edges(hipStream_t s, const InEdgesParams& p);
 
+// layer-neighbour sampling, LABOR-0 (kernels_labor.hip; the rule: legion_labor_count and legion_labor_edges in legion_hip.h, its text
+// labor_rule.h).  The arguments are the caller's to check (labor_rule.h).
+struct LaborParams {
+    const int64_t* indptr;          // the FULL CSR
+    const int32_t* col;
+    const int32_t* rows;            // int32[n]
+    const int64_t* offsets;         // int64[n + 1]: whatever they hold, nothing is read outside them, rows, indptr and col
+    int64_t* tiles;                 // the scratch: int64[n_tiles + 1 + n_groups]: the tiles' kept counts, then their exclusive prefix sums
+                                    // with the total K at [n_tiles]; behind it the sums per 256 tiles
+    int64_t* count;                 // int64[1] (launch_labor_count)
+    int32_t* dst;                   // int32[cap] (launch_labor_edges, as src and eid)
+    int32_t* src;                   // int32[cap]
+    int64_t* eid;                   // int64[cap], or null
+    int32_t node_num;
+    int32_t n;
+    int32_t fanout;                 // >= 1
+    int64_t m;                      // slots to look at, <= 2^30
+    int64_t n_tiles, n_groups;      // labor_tiles(m), labor_groups(m)
+    int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
+    uint64_t key;                   // labor_key(salt)
+};
+void launch_labor_count(hipStream_t s, const LaborParams& p);
+void launch_labor_edges(hipStream_t s, const LaborParams& p);
+
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {
     WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the

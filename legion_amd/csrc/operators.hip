@@ -19,6 +19,7 @@
 #include "node2vec_rule.h"
 #include "link_rule.h"
 #include "in_edges_rule.h"
+#include "labor_rule.h"
 
 #include <iostream>
 
@@ -534,6 +535,62 @@ extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* g
                               .offsets = offsets_devptr, .dst = dst_out, .src = src_out, .eid = eid_out, .node_num = graph->NodeNum(),
                               .n = n, .m = m};
     lg::launch_in_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// Layer-neighbour sampling (the rules: legion_hip.h; the hash, the predicate, the refusals and the scratch size: labor_rule.h).  As
+// above: every check comes before the launch.
+extern "C" int64_t legion_labor_scratch_bytes(int64_t m)
+{
+    return labor_scratch_bytes(m);
+}
+
+static lg::LaborParams labor_params(GraphStorage* graph, const int32_t* rows, int32_t n, const int64_t* offsets, int64_t m, int32_t fanout,
+                                    int64_t salt, void* scratch)
+{
+    lg::LaborParams p{};
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.rows = rows;
+    p.offsets = offsets;
+    p.tiles = static_cast<int64_t*>(scratch);
+    p.node_num = graph->NodeNum();
+    p.n = n;
+    p.fanout = fanout;
+    p.m = m;
+    p.n_tiles = labor_tiles(m);
+    p.n_groups = labor_groups(m);
+    p.key = labor_key(salt);
+    return p;
+}
+
+extern "C" int32_t legion_labor_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                      const int64_t* offsets_devptr, int64_t m, int32_t fanout, int64_t salt, int64_t* count_out,
+                                      void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_devptr || !count_out || !scratch) return -1;
+    if (labor_count_refusal(n, m, fanout, scratch_bytes) != LaborRefusal::Ok) return -1;
+    lg::LaborParams p = labor_params(graph, rows_devptr, n, offsets_devptr, m, fanout, salt, scratch);
+    p.count = count_out;
+    lg::launch_labor_count(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                      const int64_t* offsets_devptr, int64_t m, int32_t fanout, int64_t salt, const void* scratch,
+                                      int64_t scratch_bytes, int64_t cap, int32_t* dst_out, int32_t* src_out, int64_t* eid_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_devptr || !scratch || !dst_out || !src_out) return -1;
+    if (labor_edges_refusal(n, m, fanout, scratch_bytes, cap) != LaborRefusal::Ok) return -1;
+    if (cap == 0) return 0;
+    lg::LaborParams p = labor_params(graph, rows_devptr, n, offsets_devptr, m, fanout, salt, const_cast<void*>(scratch));
+    p.cap = cap;
+    p.dst = dst_out;
+    p.src = src_out;
+    p.eid = eid_out;
+    lg::launch_labor_edges(static_cast<hipStream_t>(stream), p);
     return 0;
 }
 

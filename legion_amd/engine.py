@@ -607,6 +607,106 @@ class GraphStorage:
         out = (unique[:U], dst, local[n:], offsets)
         return out + (eids,) if return_eids else out
 
+    LABOR_MAX_SLOTS = 2 ** 30                        # LEGION_LABOR_MAX_SLOTS
+
+    @staticmethod
+    def _check_labor(fanout, salt, return_eids):
+        """labor_edges' keywords by the rules of legion_labor_count, before anything touches a device: ValueError with the reason."""
+        _need_bool("return_eids", return_eids)
+        _need_int("fanout", fanout)
+        _need_int("salt", salt)
+        if not 1 <= fanout <= 2 ** 31 - 1:
+            raise ValueError(f"fanout must lie in [1, 2^31 - 1], not {fanout}")
+        if not -2 ** 63 <= salt <= 2 ** 63 - 1:
+            raise ValueError(f"salt must be an int64, not {salt}")
+
+    @staticmethod
+    def _check_labor_slots(M):
+        if M > GraphStorage.LABOR_MAX_SLOTS:
+            raise ValueError(f"the rows hold {M} entries, at most 2^30 a call")
+
+    def _labor_edges(self, rows, n, fanout, salt, return_eids, stream, limit=None):
+        """(dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + K may be."""
+        dev = self.col.device
+
+        def read(x):
+            if stream is None:
+                return int(x.item())
+            with torch.cuda.stream(stream):
+                return int(x.item())
+
+        offsets = self._row_offsets(rows, n, stream)
+        M = read(offsets[n])
+        self._check_labor_slots(M)
+        K = 0
+        if n > 0 and M > 0:
+            nbytes = int(self._lib.legion_labor_scratch_bytes(M))
+            scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+            count = torch.empty((1,), dtype=torch.int64, device=dev)
+            _enqueue(self._lib, "legion_labor_count", "labor_edges", dev, stream,
+                     (self.handle, _ptr(rows), n, _ptr(offsets), M, int(fanout), int(salt), _ptr(count), _ptr(scratch), nbytes),
+                     (rows, offsets, count, scratch))
+            K = read(count[0])
+        if limit is not None and n + K > limit:
+            raise ValueError(f"{n} seeds and their {K} kept entries are {n + K} ids in one call, at most {limit}")
+        dst = torch.empty((K,), dtype=torch.int32, device=dev)
+        src = torch.empty((K,), dtype=torch.int32, device=dev)
+        eids = torch.empty((K,), dtype=torch.int64, device=dev) if return_eids else None
+        if K > 0:
+            _enqueue(self._lib, "legion_labor_edges", "labor_edges", dev, stream,
+                     (self.handle, _ptr(rows), n, _ptr(offsets), M, int(fanout), int(salt), _ptr(scratch), nbytes, K, _ptr(dst),
+                      _ptr(src), _ptr(eids)), (rows, offsets, scratch, dst, src, eids))
+        return dst, src, eids
+
+    def labor_edges(self, rows, fanout, *, salt=0, return_eids=False, stream=None):
+        """Layer-neighbour sampling of the in-edges of rows (LABOR-0; DGL's dgl.sampling.sample_labors; the rule: legion_labor_count
+        and legion_labor_edges in legion_hip.h).  Every source vertex t has one random number, a hash of (t, salt); the entry t -> s is
+        kept iff that number lies below fanout / deg(s), so a row keeps fanout entries in expectation, every entry when its degree is
+        at most fanout, and rows with common neighbours keep the same ones.  rows as in row_offsets; fanout at least 1; salt any
+        int64.  Returns (dst, src) and with return_eids also eids: int32 [K], int32 [K] and int64 [K], the kept entries in the order
+        of in_edges (dst[p] is the index into rows, non-decreasing; src[p] = col[eids[p]]); dead entries are never kept.  The same
+        arguments give the same result.  The same salt for every layer of a batch is LABOR's layer dependency (the same r_t in all
+        layers); a new salt per batch is the caller's to choose.  The outputs are sized exactly: the number of entries M and the kept
+        number K are read back to the host, so the call synchronises `stream` (default: the current one) twice.  ValueError if the
+        rows hold more than 2^30 entries (a caller batches).  A capturing caller uses the C ABI with a capacity instead."""
+        self._check_labor(fanout, salt, return_eids)
+        rows, n = self._check_rows(rows)
+        out = self._labor_edges(rows.to(self.col.device).contiguous(), n, fanout, salt, return_eids, stream)
+        return out if return_eids else out[:2]
+
+    def labor_block(self, seeds, fanout, *, salt=0, return_eids=False, stream=None):
+        """The block of a LABOR-0 layer (DGL's LaborSampler with one fan-out): labor_edges, then unique_ids over [seeds | src].  seeds:
+        distinct int32 vertices of the graph.  Returns (input_nodes, dst_local, src_local) and with return_eids also eids: input_nodes
+        int32 [U], the seeds first and in their order, then the other kept sources in order of first appearance; dst_local, src_local
+        int32 [K], indices into input_nodes (dst_local[p] is also the index into seeds); eids as labor_edges returns them.
+        input_nodes is what FeatureStorage.set_ids takes, and the seeds of the next layer out.  The same salt for every layer of a
+        batch is LABOR's layer dependency (the same r_t in all layers: a vertex kept in one layer tends to be kept in the next, which
+        is what keeps the input nodes few); a new salt per batch is the caller's to choose.  ValueError if the seeds and their kept
+        entries are more than UNIQUE_MAX_IDS ids, and if a seed repeats or lies outside the graph, as full_neighbor_block.
+        Synchronises `stream` (default: the current one)."""
+        self._check_labor(fanout, salt, return_eids)
+        seeds, n = self._check_rows(seeds, "seeds")
+        _check_unique(n)
+        seeds = seeds.to(self.col.device).contiguous()
+        dst, src, eids = self._labor_edges(seeds, n, fanout, salt, return_eids, stream, limit=UNIQUE_MAX_IDS)
+
+        def chain():
+            ids = torch.cat([seeds, src])
+            unique, local, count = unique_ids(ids, stream=stream)
+            ok = bool(torch.equal(local[:n], torch.arange(n, dtype=torch.int32, device=local.device)))      # distinct, none negative
+            ok = ok and bool((seeds < self.node_num).all())
+            return unique, local, int(count.item()), ok
+
+        if stream is None:
+            unique, local, U, ok = chain()
+        else:
+            with torch.cuda.stream(stream):
+                unique, local, U, ok = chain()
+        if not ok:
+            raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
+        out = (unique[:U], dst, local[n:])
+        return out + (eids,) if return_eids else out
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))

@@ -153,6 +153,9 @@ SIGNATURES = {
     "legion_row_offsets_scratch_bytes": (c_i64, [c_i32]),
     "legion_row_offsets": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_p, c_i64]),
     "legion_in_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p]),
+    "legion_labor_scratch_bytes": (c_i64, [c_i64]),
+    "legion_labor_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_i64]),
+    "legion_labor_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
