@@ -16,7 +16,7 @@
 //                most `slots` probes: the table has at least 2 m slots, so a free one exists) and takes atomicMin of its index on the
 //                slot's first index -- whichever lane claims, the minimum is the first appearance.  The slot is remembered per id;
 //       count    first touches (first[slot[i]] == i) per tile of 256 ids;
-//       scan     ONE workgroup: the exclusive prefix sums of the tile counts in place, and the total to count_out;
+//       scan     ONE workgroup: the exclusive prefix sums of the tile counts in place, and the total to count_out (tile_scan.h);
 //       apply    a tile ranks its first touches (ballot prefix inside a wave, four wave totals through LDS), writes unique[rank]
 //                and remembers the rank at the first index;
 //       scatter  local[i] = the rank remembered at first[slot[i]]; unique[U .. m) = -1.
@@ -24,6 +24,7 @@
 // Bound: find_edges and the edge exclusion by the part's rate of dependent random requests; unique_ids by its atomics; no MFMA.
 #include "legion_core.h"
 #include "draw_rule.h"
+#include "tile_scan.h"
 #include "walk_step.h"
 
 namespace lg {
@@ -32,6 +33,7 @@ namespace lg {
 #define LG_FIND_EDGES_ILP 4      // edge ids per lane, searched for at once (1, 2 and 4 measured: DESIGN.md 4.14)
 
 static_assert(LG_LINK_THREADS == LG_WALK_THREADS, "the grids below are walk_grid's: a tile of 256 outputs, the walks' cap");
+static_assert(LG_LINK_THREADS == LG_SCAN_THREADS, "unique_scan_kernel is tile_scan.h's workgroup");
 
 // a tile is 256 x ILP edge ids; a lane's ILP ids lie 256 apart, so consecutive lanes read and write consecutive entries
 __global__ __launch_bounds__(LG_LINK_THREADS, 8) void find_edges_kernel(const int64_t* indptr, const int32_t* col, int32_t node_num,
@@ -202,27 +204,8 @@ __global__ __launch_bounds__(LG_LINK_THREADS) void unique_count_kernel(UniquePla
 // one workgroup: tiles[] becomes its exclusive prefix sums, count[0] the total
 __global__ __launch_bounds__(LG_LINK_THREADS) void unique_scan_kernel(UniquePlan p)
 {
-    __shared__ int32_t s_wave[LG_LINK_THREADS / 64];
-    const int32_t per = (p.n_tiles + LG_LINK_THREADS - 1) / LG_LINK_THREADS;      // a thread's run of consecutive tiles
-    const int32_t t0 = min((int32_t)threadIdx.x * per, p.n_tiles), t1 = min(t0 + per, p.n_tiles);
-    int32_t sum = 0;
-    for (int32_t t = t0; t < t1; t++) sum += p.tiles[t];
-    int32_t inc = sum;                                                // inclusive over the wave
-    const int32_t lane = threadIdx.x & 63;
-    for (int32_t off = 1; off < 64; off <<= 1) {
-        const int32_t y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += y;
-    }
-    if (lane == 63) s_wave[threadIdx.x >> 6] = inc;
-    __syncthreads();
-    int32_t before = inc - sum;
-    for (int32_t w = 0; w < (int32_t)(threadIdx.x >> 6); w++) before += s_wave[w];
-    for (int32_t t = t0; t < t1; t++) {
-        const int32_t c = p.tiles[t];
-        p.tiles[t] = before;
-        before += c;
-    }
-    if (threadIdx.x == LG_LINK_THREADS - 1) p.count[0] = before;      // (the last thread's run ends the array, or is empty behind it)
+    __shared__ int32_t s_wave[LG_SCAN_WAVES];
+    tile_scan_in_place<int32_t>(p.tiles, p.n_tiles, p.count, nullptr, s_wave);
 }
 
 __global__ __launch_bounds__(LG_LINK_THREADS) void unique_apply_kernel(UniquePlan p)

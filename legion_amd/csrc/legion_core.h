@@ -967,37 +967,39 @@ void launch_unique_ids(hipStream_t s, const int32_t* ids, int32_t m, int32_t* un
 // n_tiles: row_offsets_tiles(n); scratch: row_offsets_scratch_bytes(n) bytes, 8-byte aligned
 void launch_row_offsets(hipStream_t s, const int64_t* indptr, int32_t node_num, const int32_t* rows, int32_t n, int64_t* offsets,
                         void* scratch, int64_t n_tiles);
-struct InEdgesParams {
+// values[0 .. n) become their exclusive prefix sums, total[0] and (unless null) total2[0] their sum, in three launches: the sum per 256
+// values to sums[0 .. n_sums), n_sums = ceil(n / 256) <= 4 096 (summed: the caller's own launch has written them), ONE workgroup's
+// scan of the sums, the in-256 scan plus its base.  n == 0: the second launch alone, the totals 0
+void launch_scan_int64(hipStream_t s, int64_t* values, int32_t n, int64_t* sums, int32_t n_sums, bool summed, int64_t* total, int64_t* total2);
+// the rows whose entries are spread over slots, and the slots (row_slots.h)
+struct RowSlots {
     const int64_t* indptr;          // the FULL CSR
     const int32_t* col;
     const int32_t* rows;            // int32[n]
     const int64_t* offsets;         // int64[n + 1]: whatever they hold, nothing is read outside them, rows, indptr and col
+    int32_t node_num;
+    int32_t n;
+    int64_t m;                      // slots to look at
+};
+struct InEdgesParams {
+    RowSlots slots;                 // m: slots to write, <= 2^31 - 1
     int32_t* dst;                   // int32[m]
     int32_t* src;                   // int32[m]
     int64_t* eid;                   // int64[m], or null
-    int32_t node_num;
-    int32_t n;
-    int64_t m;                      // slots to write, <= 2^31 - 1
 };
 void launch_in_edges(hipStream_t s, const InEdgesParams& p);
 
 // layer-neighbour sampling, LABOR-0 (kernels_labor.hip; the rule: legion_labor_count and legion_labor_edges in legion_hip.h, its text
 // labor_rule.h).  The arguments are the caller's to check (labor_rule.h).
 struct LaborParams {
-    const int64_t* indptr;          // the FULL CSR
-    const int32_t* col;
-    const int32_t* rows;            // int32[n]
-    const int64_t* offsets;         // int64[n + 1]: whatever they hold, nothing is read outside them, rows, indptr and col
+    RowSlots slots;                 // m <= 2^30
     int64_t* tiles;                 // the scratch: int64[n_tiles + 1 + n_groups]: the tiles' kept counts, then their exclusive prefix sums
                                     // with the total K at [n_tiles]; behind it the sums per 256 tiles
     int64_t* count;                 // int64[1] (launch_labor_count)
     int32_t* dst;                   // int32[cap] (launch_labor_edges, as src and eid)
     int32_t* src;                   // int32[cap]
     int64_t* eid;                   // int64[cap], or null
-    int32_t node_num;
-    int32_t n;
     int32_t fanout;                 // >= 1
-    int64_t m;                      // slots to look at, <= 2^30
     int64_t n_tiles, n_groups;      // labor_tiles(m), labor_groups(m)
     int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
     uint64_t key;                   // labor_key(salt)

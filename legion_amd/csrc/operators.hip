@@ -524,6 +524,13 @@ extern "C" int32_t legion_row_offsets(legion_stream_t stream, LegionGraphStorage
     return 0;
 }
 
+// what legion_in_edges, legion_labor_count and legion_labor_edges hand the row expansion (row_slots.h)
+static lg::RowSlots row_slots(GraphStorage* graph, const int32_t* rows, int32_t n, const int64_t* offsets, int64_t m)
+{
+    return lg::RowSlots{.indptr = graph->GetCSRNodeIndexCPU(), .col = graph->GetCSRNodeMatrixCPU(), .rows = rows, .offsets = offsets,
+                        .node_num = graph->NodeNum(), .n = n, .m = m};
+}
+
 extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
                                    const int64_t* offsets_devptr, int64_t m, int32_t* dst_out, int32_t* src_out, int64_t* eid_out)
 {
@@ -531,9 +538,7 @@ extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* g
     if (!graph || !rows_devptr || !offsets_devptr || !dst_out || !src_out) return -1;
     if (in_edges_refusal(n, m) != InEdgesRefusal::Ok) return -1;
     if (m == 0) return 0;
-    const lg::InEdgesParams p{.indptr = graph->GetCSRNodeIndexCPU(), .col = graph->GetCSRNodeMatrixCPU(), .rows = rows_devptr,
-                              .offsets = offsets_devptr, .dst = dst_out, .src = src_out, .eid = eid_out, .node_num = graph->NodeNum(),
-                              .n = n, .m = m};
+    const lg::InEdgesParams p{.slots = row_slots(graph, rows_devptr, n, offsets_devptr, m), .dst = dst_out, .src = src_out, .eid = eid_out};
     lg::launch_in_edges(static_cast<hipStream_t>(stream), p);
     return 0;
 }
@@ -549,15 +554,9 @@ static lg::LaborParams labor_params(GraphStorage* graph, const int32_t* rows, in
                                     int64_t salt, void* scratch)
 {
     lg::LaborParams p{};
-    p.indptr = graph->GetCSRNodeIndexCPU();
-    p.col = graph->GetCSRNodeMatrixCPU();
-    p.rows = rows;
-    p.offsets = offsets;
+    p.slots = row_slots(graph, rows, n, offsets, m);
     p.tiles = static_cast<int64_t*>(scratch);
-    p.node_num = graph->NodeNum();
-    p.n = n;
     p.fanout = fanout;
-    p.m = m;
     p.n_tiles = labor_tiles(m);
     p.n_groups = labor_groups(m);
     p.key = labor_key(salt);

@@ -221,6 +221,14 @@ def _check_unique(m):
         raise ValueError(f"{m} ids in one call, at most {UNIQUE_MAX_IDS}")
 
 
+def _read_scalar(x, stream):
+    """The one-element device tensor x as an int, read under `stream` (None: the current one): it synchronises that stream."""
+    if stream is None:
+        return int(x.item())
+    with torch.cuda.stream(stream):
+        return int(x.item())
+
+
 def unique_ids(ids, stream=None):
     """The distinct ids in order of first appearance, and where each id sits among them (compact_graphs' relabelling; the rule:
     legion_unique_ids in legion_hip.h).  ids: int32, a CUDA tensor (its device is used) or anything torch.as_tensor takes (the current
@@ -545,11 +553,7 @@ class GraphStorage:
         """(offsets, dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + M may be."""
         dev = self.col.device
         offsets = self._row_offsets(rows, n, stream)
-        if stream is None:
-            M = int(offsets[n].item())
-        else:
-            with torch.cuda.stream(stream):
-                M = int(offsets[n].item())
+        M = _read_scalar(offsets[n], stream)
         if M > 2 ** 31 - 1:
             raise ValueError(f"the rows hold {M} entries, at most 2^31 - 1 a call")
         if limit is not None and n + M > limit:
@@ -574,6 +578,25 @@ class GraphStorage:
         out = self._in_edges(rows.to(self.col.device).contiguous(), n, return_eids, stream)
         return out if return_eids else out[:3]
 
+    def _block_tail(self, seeds, n, src, stream):
+        """The end of a block: unique_ids over [seeds | src] under `stream`.  Returns (input_nodes, src_local); ValueError unless the n
+        seeds are distinct vertices of the graph."""
+        def chain():
+            ids = torch.cat([seeds, src])
+            unique, local, count = unique_ids(ids, stream=stream)
+            ok = bool(torch.equal(local[:n], torch.arange(n, dtype=torch.int32, device=local.device)))      # distinct, none negative
+            ok = ok and bool((seeds < self.node_num).all())
+            return unique, local, int(count.item()), ok
+
+        if stream is None:
+            unique, local, U, ok = chain()
+        else:
+            with torch.cuda.stream(stream):
+                unique, local, U, ok = chain()
+        if not ok:
+            raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
+        return unique[:U], local[n:]
+
     def full_neighbor_block(self, seeds, *, return_eids=False, stream=None):
         """The block of all in-edges of seeds (DGL's MultiLayerFullNeighborSampler(1), or dgl.in_subgraph followed by to_block): in_edges,
         then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph, as rows in row_offsets.  Returns (input_nodes,
@@ -589,22 +612,8 @@ class GraphStorage:
         _check_unique(n)
         seeds = seeds.to(self.col.device).contiguous()
         offsets, dst, src, eids = self._in_edges(seeds, n, return_eids, stream, limit=UNIQUE_MAX_IDS)
-
-        def chain():
-            ids = torch.cat([seeds, src])
-            unique, local, count = unique_ids(ids, stream=stream)
-            ok = bool(torch.equal(local[:n], torch.arange(n, dtype=torch.int32, device=local.device)))      # distinct, none negative
-            ok = ok and bool((seeds < self.node_num).all())
-            return unique, local, int(count.item()), ok
-
-        if stream is None:
-            unique, local, U, ok = chain()
-        else:
-            with torch.cuda.stream(stream):
-                unique, local, U, ok = chain()
-        if not ok:
-            raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
-        out = (unique[:U], dst, local[n:], offsets)
+        input_nodes, src_local = self._block_tail(seeds, n, src, stream)
+        out = (input_nodes, dst, src_local, offsets)
         return out + (eids,) if return_eids else out
 
     LABOR_MAX_SLOTS = 2 ** 30                        # LEGION_LABOR_MAX_SLOTS
@@ -628,15 +637,8 @@ class GraphStorage:
     def _labor_edges(self, rows, n, fanout, salt, return_eids, stream, limit=None):
         """(dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + K may be."""
         dev = self.col.device
-
-        def read(x):
-            if stream is None:
-                return int(x.item())
-            with torch.cuda.stream(stream):
-                return int(x.item())
-
         offsets = self._row_offsets(rows, n, stream)
-        M = read(offsets[n])
+        M = _read_scalar(offsets[n], stream)
         self._check_labor_slots(M)
         K = 0
         if n > 0 and M > 0:
@@ -646,7 +648,7 @@ class GraphStorage:
             _enqueue(self._lib, "legion_labor_count", "labor_edges", dev, stream,
                      (self.handle, _ptr(rows), n, _ptr(offsets), M, int(fanout), int(salt), _ptr(count), _ptr(scratch), nbytes),
                      (rows, offsets, count, scratch))
-            K = read(count[0])
+            K = _read_scalar(count[0], stream)
         if limit is not None and n + K > limit:
             raise ValueError(f"{n} seeds and their {K} kept entries are {n + K} ids in one call, at most {limit}")
         dst = torch.empty((K,), dtype=torch.int32, device=dev)
@@ -689,22 +691,8 @@ class GraphStorage:
         _check_unique(n)
         seeds = seeds.to(self.col.device).contiguous()
         dst, src, eids = self._labor_edges(seeds, n, fanout, salt, return_eids, stream, limit=UNIQUE_MAX_IDS)
-
-        def chain():
-            ids = torch.cat([seeds, src])
-            unique, local, count = unique_ids(ids, stream=stream)
-            ok = bool(torch.equal(local[:n], torch.arange(n, dtype=torch.int32, device=local.device)))      # distinct, none negative
-            ok = ok and bool((seeds < self.node_num).all())
-            return unique, local, int(count.item()), ok
-
-        if stream is None:
-            unique, local, U, ok = chain()
-        else:
-            with torch.cuda.stream(stream):
-                unique, local, U, ok = chain()
-        if not ok:
-            raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
-        out = (unique[:U], dst, local[n:])
+        input_nodes, src_local = self._block_tail(seeds, n, src, stream)
+        out = (input_nodes, dst, src_local)
         return out + (eids,) if return_eids else out
 
     def column_slots(self, dev_id=0):

@@ -209,6 +209,8 @@ def test_all_seeds_empty(world):
     assert k == 0 and np.all(dst == -1) and np.all(src == -1) and np.all(eid == -1)
     k, dst, src, eid = abi(world["L"], world["graph"], rows, off, 1500, 5, 0, 700)        # slots that resolve to no row
     assert k == 0 and np.all(dst == -1) and np.all(src == -1) and np.all(eid == -1)
+    k, dst, src, eid = abi(world["L"], world["graph"], np.zeros(0, np.int32), np.zeros(1, np.int64), 0, 5, 0, 8)      # n == 0: the same
+    assert k == 0 and np.all(dst == -1) and np.all(src == -1) and np.all(eid == -1)
     none = world["graph"].labor_edges(np.zeros(0, np.int32), 3, return_eids=True)
     assert all(x.shape == (0,) for x in none)
 
