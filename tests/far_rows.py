@@ -1,5 +1,5 @@
 """A graph whose live rows sit at a chosen edge offset: the layout of the far-row tests (tests/test_far_rows_cpu.py,
-tests/test_gpu_far_rows.py), host-only numpy.  A helper of the tests, not a test file.
+tests/test_gpu_*far_rows.py), host-only numpy but for device_world, which puts it on a device.  A helper of the tests, not a test file.
 
   * ballast: vertices 0 .. B - 1 own B rows of L entries each, the last one shortened, `offset` = boundary - k entries in all.  Nothing
     ever reads them: no seed is a ballast vertex and no live column entry names one.  Their column entries are 0 (non-decreasing: the
@@ -17,17 +17,23 @@ tests/test_gpu_far_rows.py), host-only numpy.  A helper of the tests, not a test
 Every `want_*` below computes one operation's reference ON THE VIEW, turns its edge ids into true ones, and asserts what makes the case
 worth running at this boundary (edge ids on both sides of it, the straddling row left to both sides, ...).  An input that fails a
 condition is replaced, never the condition."""
+import contextlib
 import functools
+import time
 
 import numpy as np
 
-from tests import distinct_ref, edge_ids_ref, node2vec_ref, pinsage_ref, walk_ref, weighted_ref
+from tests import distinct_ref, edge_ids_ref, in_edges_ref, node2vec_ref, pinsage_ref, walk_ref, weighted_ref
 
 LIVE_NODES = 1000
 LIVE_HUBS = {0: 63, 1: 64, 2: 65, 3: 255, 4: 256, 5: 257, 6: 513}    # as node2vec_ref.HUBS, the longest row shorter
 LIVE_EMPTY = (7, 40, 41, 234, 500, 998)
 STRADDLER = 6                                                      # sym_graph's name of the row that straddles the boundary
 BOUNDARIES = {"5000": (5000, 64), "2^31": (2 ** 31, 2 ** 20), "2^32": (2 ** 32, 2 ** 20)}      # name -> (boundary, L)
+# how a failure at a boundary reads: the end of every assertion message of the GPU tests (world["why"])
+WHY = {"5000": "fails at boundary 5000: the harness, or the kernel at any size",
+       "2^31": "if only from boundary 2^31 on: a signed 32-bit truncation of an edge offset",
+       "2^32": "if at boundary 2^32 only: an unsigned 32-bit truncation of an edge offset"}
 
 
 def rotate(indptr, col, w, shift):
@@ -232,6 +238,64 @@ class FarRows:
 @functools.lru_cache(maxsize=None)
 def layout(name):
     return FarRows(*BOUNDARIES[name])
+
+
+def expand_rows(g, ballast_row, m=None):
+    """(rows, offsets, i, r, eid, is_live, src) of the row expansion in_edges and labor_edges share: the live seeds of the layout with the
+    straddler every fifth, one whole ballast row in the middle and every live row once behind it.  Over the first m slots (None: every
+    slot): i the seed a slot belongs to, r its row, eid its TRUE edge id, src its entry -- the reference view's in a live row, 0 in the
+    ballast row."""
+    live = np.arange(g.B, g.node_num, dtype=np.int32)
+    rows = np.concatenate([g.seeds(300), [ballast_row], live, [g.hub, -1, g.node_num]]).astype(np.int32)
+    offsets = in_edges_ref.row_offsets(g.indptr, rows)
+    p = np.arange(int(offsets[-1]) if m is None else m, dtype=np.int64)
+    i = np.searchsorted(offsets, p, side="right") - 1
+    r = rows[i].astype(np.int64)
+    eid = g.indptr[r] + (p - offsets[i])
+    is_live = r >= g.B
+    src = np.zeros(p.size, dtype=np.int32)
+    src[is_live] = g.col_ref[eid[is_live] - g.offset]
+    return rows, offsets, i, r, eid, is_live, src
+
+
+@contextlib.contextmanager
+def device_world(lib, boundary, weights=False):
+    """The whole graph of layout(boundary) on the device, the only place one is put there: col zeros of E entries (weights: and w ones)
+    with the live tail written from the host, the row pointers, and the graph (weights: with its table).  Yields what the GPU tests read:
+    g, graph, indptr, col, (w,) L = lib, why, name.  Closed and freed on the way out, in the order that lets the next boundary's 16 GiB
+    fit: synchronise, close the graph, clear the dict, drop the tensors, empty the cache."""
+    import torch
+    from legion_amd import engine
+    dev = "cuda:0"
+    g = layout(boundary)
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    col = torch.zeros(g.E, dtype=torch.int32, device=dev)
+    col[g.offset:] = torch.from_numpy(g.col_ref.copy()).to(dev)
+    w = None
+    if weights:
+        w = torch.ones(g.E, dtype=torch.float32, device=dev)
+        w[g.offset:] = torch.from_numpy(g.w_ref.copy()).to(dev)
+    indptr = torch.from_numpy(g.indptr.copy()).to(dev)
+    torch.cuda.synchronize()
+    t1 = time.perf_counter()
+    graph = engine.GraphStorage(1, indptr, col)
+    if weights:
+        graph.set_edge_weights(w)
+    torch.cuda.synchronize()
+    t2 = time.perf_counter()
+    print(f"\nfar rows at {boundary}: E = {g.E}, B = {g.B}; arrays {t1 - t0:.3f} s, graph{' and table build' * weights} {t2 - t1:.3f} s")
+    out = dict(g=g, graph=graph, indptr=indptr, col=col, L=lib, why=" -- " + WHY[boundary], name=boundary)
+    if weights:
+        out["w"] = w
+    try:
+        yield out
+    finally:
+        torch.cuda.synchronize()
+        graph.close()
+        out.clear()
+        del graph, col, w, indptr
+        torch.cuda.empty_cache()
 
 
 # ---- the cases both test files run -------------------------------------------------------------------------------------------------

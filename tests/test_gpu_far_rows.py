@@ -18,54 +18,19 @@ import torch
 from legion_amd import synth
 from tests import far_rows
 from tests import node2vec_ref
+from tests.compare import same_arrays
 from tests.helpers import KEYS_EXACT
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 DIM = 16
-WHY = {"5000": "fails at boundary 5000: the harness, or the kernel at any size",
-       "2^31": "if only from boundary 2^31 on: a signed 32-bit truncation of an edge offset",
-       "2^32": "if at boundary 2^32 only: an unsigned 32-bit truncation of an edge offset"}
-
 
 @pytest.fixture(scope="module", params=list(far_rows.BOUNDARIES))
 def world(hip, request):
-    """The whole graph on the device at one boundary: col zeros and w ones of E entries with the live tail written from the host, the
-    graph with its table, and the layout.  Closed and freed before the next boundary opens."""
-    from legion_amd import engine
-    g = far_rows.layout(request.param)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    col = torch.zeros(g.E, dtype=torch.int32, device=DEV)
-    col[g.offset:] = torch.from_numpy(g.col_ref.copy()).to(DEV)
-    w = torch.ones(g.E, dtype=torch.float32, device=DEV)
-    w[g.offset:] = torch.from_numpy(g.w_ref.copy()).to(DEV)
-    indptr = torch.from_numpy(g.indptr.copy()).to(DEV)
-    torch.cuda.synchronize()
-    t1 = time.perf_counter()
-    graph = engine.GraphStorage(1, indptr, col)
-    graph.set_edge_weights(w)
-    torch.cuda.synchronize()
-    t2 = time.perf_counter()
-    print(f"\nfar rows at {request.param}: E = {g.E}, B = {g.B}; arrays {t1 - t0:.3f} s, graph and table build {t2 - t1:.3f} s")
-    out = dict(g=g, graph=graph, indptr=indptr, col=col, w=w, L=hip, why=" -- " + WHY[request.param], name=request.param)
-    yield out
-    torch.cuda.synchronize()
-    graph.close()
-    out.clear()
-    del graph, col, w, indptr
-    torch.cuda.empty_cache()
-
-
-def _same(got, want, ctx):
-    """Two arrays of a walk (traces and true edge ids) or of PinSAGE (neighbours and counts)."""
-    for name, a, b in zip(("first", "second"), got, want):
-        a = a.cpu().numpy()
-        assert a.dtype == b.dtype and a.shape == b.shape, ctx
-        bad = np.argwhere(a != b)
-        assert bad.size == 0, f"{ctx}: {len(bad)} entries of the {name} array differ, first at {bad[0]}: got {a[tuple(bad[0])]} " \
-                              f"want {b[tuple(bad[0])]}"
+    """The whole graph on the device at one boundary, with its weights and table (far_rows.device_world)."""
+    with far_rows.device_world(hip, request.param, weights=True) as w:
+        yield w
 
 
 # ---- the table ----------------------------------------------------------------------------------------------------------------------
@@ -147,7 +112,7 @@ def test_random_walk(world, case):
     got = world["graph"].random_walk(seeds, length, weighted=weighted, restart_prob=restart, return_eids=True)
     only = world["graph"].random_walk(seeds, length, weighted=weighted, restart_prob=restart)
     torch.cuda.synchronize()
-    _same(got, want, f"random_walk {case}" + world["why"])
+    same_arrays(got, want, f"random_walk {case}" + world["why"])
     assert torch.equal(only, got[0]), f"random_walk {case}: traces without edge ids" + world["why"]
 
 
@@ -161,7 +126,7 @@ def test_node2vec(world, case):
     seeds = torch.from_numpy(g.seeds(count)).to(DEV)
     got = world["graph"].node2vec_random_walk(seeds, p, q, length, weighted=weighted, return_eids=True, max_tries=tries)
     torch.cuda.synchronize()
-    _same(got, want, f"node2vec {case}" + world["why"])
+    same_arrays(got, want, f"node2vec {case}" + world["why"])
 
 
 @pytest.mark.parametrize("case", far_rows.PINSAGE_CASES, ids=lambda c: "-".join(map(str, c)))
@@ -173,7 +138,7 @@ def test_pinsage(world, case):
     g.assert_no_ballast_read(reads, view=True)
     got = world["graph"].pinsage_neighbors(torch.from_numpy(g.seeds(count)).to(DEV), R, T, k, termination_prob=termination, weighted=weighted)
     torch.cuda.synchronize()
-    _same(got, want, f"pinsage {case}" + world["why"])
+    same_arrays(got, want, f"pinsage {case}" + world["why"])
 
 
 # ---- the neighbour sampler ----------------------------------------------------------------------------------------------------------

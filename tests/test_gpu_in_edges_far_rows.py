@@ -1,61 +1,34 @@
 """row_offsets and in_edges at edge offsets beyond 2^31 and 2^32: the layout of tests/far_rows.py, whose live rows straddle the boundary
-behind ballast rows of L zeros, built as tests/test_gpu_link_far_rows.py builds it.  The seeds are live rows on both sides of the
+behind ballast rows of L zeros, put on the device by far_rows.device_world.  The seeds are live rows on both sides of the
 boundary, the straddling hub and one ballast row (its expected entries are all 0), so the edge ids lie on both sides of the boundary and
 col is read beyond it; every row of the graph at once takes the offsets themselves past the boundary.  The whole column array exists on
 the device only.  A failure at 5000 is a fault at any size; at 2^31 but not at 5000 an offset that went through a signed 32-bit value; at
 2^32 only, through an unsigned one."""
-import time
-
 import numpy as np
 import pytest
 import torch
 
 from tests import far_rows
 from tests import in_edges_ref as ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-WHY = {"5000": "fails at boundary 5000: the harness, or the kernel at any size",
-       "2^31": "if only from boundary 2^31 on: a signed 32-bit truncation of an edge offset",
-       "2^32": "if at boundary 2^32 only: an unsigned 32-bit truncation of an edge offset"}
 
 
 @pytest.fixture(scope="module", params=list(far_rows.BOUNDARIES))
 def world(hip, request):
-    """The whole graph on the device at one boundary; closed and freed before the next boundary opens."""
-    from legion_amd import engine
-    g = far_rows.layout(request.param)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    col = torch.zeros(g.E, dtype=torch.int32, device=DEV)
-    col[g.offset:] = torch.from_numpy(g.col_ref.copy()).to(DEV)
-    indptr = torch.from_numpy(g.indptr.copy()).to(DEV)
-    graph = engine.GraphStorage(1, indptr, col)
-    torch.cuda.synchronize()
-    print(f"\nfar rows at {request.param}: E = {g.E}, B = {g.B}; arrays and graph {time.perf_counter() - t0:.3f} s")
-    out = dict(g=g, graph=graph, indptr=indptr, col=col, why=" -- " + WHY[request.param], name=request.param)
-    yield out
-    torch.cuda.synchronize()
-    graph.close()
-    out.clear()
-    del graph, col, indptr
-    torch.cuda.empty_cache()
+    """The whole graph on the device at one boundary (far_rows.device_world)."""
+    with far_rows.device_world(hip, request.param) as w:
+        yield w
 
 
 def want_in_edges(g, ballast_row):
     """(rows, offsets, dst, src, true eids): the live seeds of the layout with the straddler every fifth, one whole ballast row in the
     middle and every live row once behind it.  The live entries come from the reference view, the ballast row's are 0."""
-    live = np.arange(g.B, g.node_num, dtype=np.int32)
-    rows = np.concatenate([g.seeds(300), [ballast_row], live, [g.hub, -1, g.node_num]]).astype(np.int32)
-    offsets = ref.row_offsets(g.indptr, rows)
+    rows, offsets, i, r, eid, is_live, src = far_rows.expand_rows(g, ballast_row)
     M = int(offsets[-1])
-    i = np.searchsorted(offsets, np.arange(M, dtype=np.int64), side="right") - 1
-    r = rows[i].astype(np.int64)
-    eid = g.indptr[r] + (np.arange(M, dtype=np.int64) - offsets[i])
-    is_live = r >= g.B
-    src = np.zeros(M, dtype=np.int32)
-    src[is_live] = g.col_ref[eid[is_live] - g.offset]
     # what makes the case worth running at this boundary
     assert (~is_live).sum() == g.deg[ballast_row] >= 64 and np.all(r[~is_live] == ballast_row), "one ballast row, whole"
     low, high = is_live & (eid < g.boundary), is_live & (eid >= g.boundary)
@@ -70,14 +43,10 @@ def want_in_edges(g, ballast_row):
 def test_in_edges(world):
     g = world["g"]
     for ballast_row in (g.B - 2, 0):                                   # a row close under the boundary, and the very first
-        rows, off, dst, src, eid = want_in_edges(g, ballast_row)
+        rows, *want = want_in_edges(g, ballast_row)
         got = world["graph"].in_edges(torch.from_numpy(rows).to(DEV), return_eids=True)
         torch.cuda.synchronize()
-        for name, x, w in zip(("offsets", "dst", "src", "eid"), got, (off, dst, src, eid)):
-            x = x.cpu().numpy()
-            bad = np.nonzero(x != w)[0] if x.shape == w.shape else np.array([0])
-            assert x.shape == w.shape and bad.size == 0, \
-                f"{bad.size} entries of {name} differ, first at {bad[0]}: got {x[bad[0]]} want {w[bad[0]]}" + world["why"]
+        same_arrays(got, want, f"ballast row {ballast_row}" + world["why"], names=("offsets", "dst", "src", "eid"))
 
 
 def test_offsets_past_the_boundary(world):

@@ -11,6 +11,7 @@ import torch
 
 from tests import in_edges_ref as ref
 from tests import link_ref, walk_ref
+from tests.compare import same_arrays
 from tests.test_gpu_in_edges import abi
 from tests.test_gpu_node2vec_fuzz import fuzz_shape
 
@@ -81,13 +82,6 @@ def cases(hip):
         c["graph"].close()
 
 
-def _same(got, want, ctx):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
-    assert got.dtype == want.dtype and got.shape == want.shape, f"{ctx}: {got.dtype} {got.shape}"
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, f"{ctx}: {bad.size} entries differ, first at {bad[0]}: got {got[bad[0]]} want {want[bad[0]]}"
-
-
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_rows_match_the_reference(cases, hip, seed):
     c = cases(seed)
@@ -96,21 +90,21 @@ def test_random_rows_match_the_reference(cases, hip, seed):
     off = g.row_offsets(c["rows"])
     got = g.in_edges(c["rows"], return_eids=c["eids"])
     torch.cuda.synchronize()
-    _same(off, c["offsets"], ctx + "row_offsets")
-    _same(got[0], c["offsets"], ctx + "offsets")
+    same_arrays(off, c["offsets"], ctx + "row_offsets")
+    same_arrays(got[0], c["offsets"], ctx + "offsets")
     for name, x, w in zip(("dst", "src", "eid"), got[1:], want):
-        _same(x, w, ctx + name)
+        same_arrays(x, w, ctx + name)
     for m in c["caps"]:
         capped = ref.in_edges(c["indptr"], c["col"], c["rows"], c["offsets"], m)
         out = abi(hip, g, c["rows"], None, m, c["eids"])
         for name, x, w in zip(("dst", "src", "eid"), out[:3], capped):
             if x is not None:
-                _same(x, w, ctx + f"m {m} {name}")
+                same_arrays(x, w, ctx + f"m {m} {name}")
     b = c["block"]
     blk = g.full_neighbor_block(c["seeds"], return_eids=True)
     torch.cuda.synchronize()
     for name, x in zip(("input_nodes", "dst_local", "src_local", "offsets", "eids"), blk):
-        _same(x, b[name], ctx + "block " + name)
+        same_arrays(x, b[name], ctx + "block " + name)
 
 
 def test_the_seed_set_holds_its_conditions(cases):

@@ -3,12 +3,15 @@ symmetric graph of tests/node2vec_ref.py.  seeds_for(5000) gives 4 126 670 slots
 of the hub: a second trip that repeats the tile one stride earlier differs in most of its slots.  524 289, 524 545 and 2^20 rows of low
 degree, every other one without entries, cross the offsets kernels' stride of 2 048 x 256 rows (the second trip holds a hub, empty and
 out-of-graph seeds) and take the scan's runs of tiles from 1 through 2 and 9 to 16."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from tests import in_edges_ref as ref
 from tests import node2vec_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -79,22 +82,17 @@ def test_the_cases_hold_their_conditions_before_any_launch(world):
         row_case(world["indptr"], n)
 
 
-def _same(got, want, what):
-    for name, g, w in zip(("offsets", "dst", "src", "eid"), got, want):
-        g = g.cpu().numpy()
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name)
-        bad = np.nonzero(g != w)[0]
-        assert bad.size == 0, f"{what}: {bad.size} entries of {name} differ, first at {bad[0]}: got {g[bad[0]]} want {w[bad[0]]}"
+same_in_edges = functools.partial(same_arrays, names=("offsets", "dst", "src", "eid"))
 
 
 def test_more_slots_than_one_stride(world):
     rows, want = slot_case(world["indptr"], world["col"])
     got = world["graph"].in_edges(torch.from_numpy(rows).to(DEV), return_eids=True)
     torch.cuda.synchronize()
-    _same(got, want, "5 000 seeds")
+    same_in_edges(got, want, "5 000 seeds")
     got = world["graph"].in_edges(torch.from_numpy(rows).to(DEV))
     torch.cuda.synchronize()
-    _same(got, want[:3], "5 000 seeds, no edge ids")
+    same_in_edges(got, want[:3], "5 000 seeds, no edge ids")
 
 
 @pytest.mark.parametrize("n", ROW_COUNTS)
@@ -109,5 +107,5 @@ def test_more_rows_than_one_stride(world, n):
     want = (off,) + ref.in_edges(indptr, col, rows, off, int(off[-1]))
     got = world["graph"].in_edges(torch.from_numpy(rows).to(DEV), return_eids=True)
     torch.cuda.synchronize()
-    _same(got, want, f"{n} rows")
+    same_in_edges(got, want, f"{n} rows")
     assert np.array_equal(np.unique(want[1]), np.nonzero(np.diff(off) > 0)[0]), "no row with entries is skipped"

@@ -1,5 +1,5 @@
 """Layer-neighbour sampling at edge offsets beyond 2^31 and 2^32: the layout of tests/far_rows.py, whose live rows straddle the boundary
-behind ballast rows of L zeros, built as tests/test_gpu_in_edges_far_rows.py builds it.  The seeds are live rows on both sides of the
+behind ballast rows of L zeros, put on the device by far_rows.device_world.  The seeds are live rows on both sides of the
 boundary, the straddling hub and one ballast row in the middle, so the kept edge ids lie on both sides of the boundary and col is read
 beyond it.  Every entry of the ballast row is vertex 0, which has one number: at fan-out 5 the row keeps nothing (whole tiles of it), at
 a fan-out of its degree everything (whole tiles again).  Through m a prefix that ends inside the ballast row is looked at; its degree
@@ -7,46 +7,27 @@ stays L.  The whole column array exists on the device only.  A failure at 5000 i
 that went through a signed 32-bit value; at 2^32 only, through an unsigned one.  No row of these layouts has 2^32 entries (L is 2^20 at
 most), so a product h * d truncated to 64 bits cannot differ here: labor_rule.h's table (tests/cpu/labor_rule_test.cpp) is where degrees
 from 2^32 on are pinned, over the text the device runs."""
-import time
-
 import numpy as np
 import pytest
 import torch
 
 from tests import far_rows
-from tests import in_edges_ref
 from tests import labor_ref as ref
+from tests.compare import same_arrays
 from tests.test_gpu_labor import abi
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
 SALT = 0                                                           # labor_hash(0, 0) = 0xa706dd2f: 0.65 of 2^32
-WHY = {"5000": "fails at boundary 5000: the harness, or the kernel at any size",
-       "2^31": "if only from boundary 2^31 on: a signed 32-bit truncation of an edge offset",
-       "2^32": "if at boundary 2^32 only: an unsigned 32-bit truncation of an edge offset"}
+NAMES = ("dst", "src", "eid")
 
 
 @pytest.fixture(scope="module", params=list(far_rows.BOUNDARIES))
 def world(hip, request):
-    """The whole graph on the device at one boundary; closed and freed before the next boundary opens."""
-    from legion_amd import engine
-    g = far_rows.layout(request.param)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    col = torch.zeros(g.E, dtype=torch.int32, device=DEV)
-    col[g.offset:] = torch.from_numpy(g.col_ref.copy()).to(DEV)
-    indptr = torch.from_numpy(g.indptr.copy()).to(DEV)
-    graph = engine.GraphStorage(1, indptr, col)
-    torch.cuda.synchronize()
-    print(f"\nfar rows at {request.param}: E = {g.E}, B = {g.B}; arrays and graph {time.perf_counter() - t0:.3f} s")
-    out = dict(g=g, graph=graph, indptr=indptr, col=col, why=" -- " + WHY[request.param], name=request.param, L=hip)
-    yield out
-    torch.cuda.synchronize()
-    graph.close()
-    out.clear()
-    del graph, col, indptr
-    torch.cuda.empty_cache()
+    """The whole graph on the device at one boundary (far_rows.device_world)."""
+    with far_rows.device_world(hip, request.param) as w:
+        yield w
 
 
 def want_labor(g, fanout, m=None):
@@ -54,18 +35,9 @@ def want_labor(g, fanout, m=None):
     the middle and every live row once behind it; m None: every slot, else the first m.  The live entries come from the reference view,
     the ballast row's are vertex 0."""
     ballast_row = g.B - 2
-    live = np.arange(g.B, g.node_num, dtype=np.int32)
-    rows = np.concatenate([g.seeds(300), [ballast_row], live, [g.hub, -1, g.node_num]]).astype(np.int32)
-    offsets = in_edges_ref.row_offsets(g.indptr, rows)
+    rows, offsets, i, r, eid, is_live, src = far_rows.expand_rows(g, ballast_row, m)
     M = int(offsets[-1])
     m = M if m is None else m
-    p = np.arange(m, dtype=np.int64)
-    i = np.searchsorted(offsets, p, side="right") - 1
-    r = rows[i].astype(np.int64)
-    eid = g.indptr[r] + (p - offsets[i])
-    is_live = r >= g.B
-    src = np.zeros(m, dtype=np.int32)
-    src[is_live] = g.col_ref[eid[is_live] - g.offset]
     ok = src >= 0
     kept = np.zeros(m, dtype=bool)
     kept[ok] = ref.keeps(ref.hashes(src[ok], SALT), g.deg[r[ok]], fanout)
@@ -83,14 +55,6 @@ def want_labor(g, fanout, m=None):
     return rows, offsets, m, int(kept.sum()), i.astype(np.int32)[kept], src[kept], eid[kept]
 
 
-def _same(got, want, what):
-    for name, x, w in zip(("dst", "src", "eid"), got, want):
-        x = x.cpu().numpy() if isinstance(x, torch.Tensor) else x
-        bad = np.nonzero(x != w)[0] if x.shape == w.shape else np.array([0])
-        assert x.shape == w.shape and bad.size == 0, f"{what}: {bad.size} entries of {name} differ, first at {bad[0]}" + \
-            (f": got {x[bad[0]]} want {w[bad[0]]}" if x.shape == w.shape else f": shapes {x.shape} {w.shape}")
-
-
 def test_labor_edges(world):
     g = world["g"]
     for fanout in (5, g.L):                                            # the ballast row keeps nothing, then everything
@@ -98,7 +62,7 @@ def test_labor_edges(world):
         got = world["graph"].labor_edges(torch.from_numpy(rows).to(DEV), fanout, salt=SALT, return_eids=True)
         torch.cuda.synchronize()
         assert got[0].shape == (K,), f"fanout {fanout}: K {got[0].shape[0]} want {K}" + world["why"]
-        _same(got, (dst, src, eid), f"fanout {fanout}" + world["why"])
+        same_arrays(got, (dst, src, eid), f"fanout {fanout}" + world["why"], names=NAMES)
 
 
 def test_a_prefix_that_ends_inside_the_ballast_row(world):
@@ -113,5 +77,5 @@ def test_a_prefix_that_ends_inside_the_ballast_row(world):
     assert np.all(rows[dst] >= g.B) and K >= 100, "live entries only"
     k, *out = abi(world["L"], world["graph"], rows, off, m, below, SALT, K + 5)
     assert k == K, f"K {k} want {K} ({K + below} if the degree were the slots below m)" + world["why"]
-    _same([x[:k] for x in out], (dst, src, eid), "prefix" + world["why"])
+    same_arrays([x[:k] for x in out], (dst, src, eid), "prefix" + world["why"], names=NAMES)
     assert all(np.all(x[k:] == -1) for x in out)

@@ -13,6 +13,7 @@ import torch
 from tests import in_edges_ref
 from tests import labor_ref as ref
 from tests import link_ref, walk_ref
+from tests.compare import same_arrays
 from tests.test_gpu_labor import abi
 from tests.test_gpu_node2vec_fuzz import fuzz_shape
 
@@ -91,13 +92,6 @@ def cases(hip):
         c["graph"].close()
 
 
-def _same(got, want, ctx):
-    got = got.cpu().numpy() if isinstance(got, torch.Tensor) else got
-    assert got.dtype == want.dtype and got.shape == want.shape, f"{ctx}: {got.dtype} {got.shape}"
-    bad = np.nonzero(got != want)[0]
-    assert bad.size == 0, f"{ctx}: {bad.size} entries differ, first at {bad[0]}: got {got[bad[0]]} want {want[bad[0]]}"
-
-
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_rows_match_the_reference(cases, hip, seed):
     c = cases(seed)
@@ -107,19 +101,19 @@ def test_random_rows_match_the_reference(cases, hip, seed):
     got = g.labor_edges(c["rows"], c["fanout"], salt=c["salt"], return_eids=c["eids"])
     torch.cuda.synchronize()
     for name, x, w in zip(("dst", "src", "eid"), got, c["full"]):
-        _same(x, w, ctx + name)
+        same_arrays(x, w, ctx + name)
     for cap in c["caps"]:
         want = ref.edges(c["indptr"], c["col"], c["rows"], c["offsets"], c["m"], c["fanout"], c["salt"], cap=cap)
         k, *out = abi(hip, g, c["rows"], c["offsets"], c["m"], c["fanout"], c["salt"], cap, c["eids"])
         assert k == c["K"] == want[0], ctx + f"count {k}"
         for name, x, w in zip(("dst", "src", "eid"), out, want[1:]):
             if x is not None:
-                _same(x, w, ctx + f"cap {cap} {name}")
+                same_arrays(x, w, ctx + f"cap {cap} {name}")
     b = c["block"]
     blk = g.labor_block(c["seeds"], c["fanout"], salt=c["salt"], return_eids=True)
     torch.cuda.synchronize()
     for name, x in zip(("input_nodes", "dst_local", "src_local", "eids"), blk):
-        _same(x, b[name], ctx + "block " + name)
+        same_arrays(x, b[name], ctx + "block " + name)
 
 
 def test_the_seed_set_holds_its_conditions(cases):

@@ -5,6 +5,8 @@ tests/labor_ref.py.  Two inputs:
   * 2^17 + 1 copies of one row of 1 030 entries: 135 005 190 slots, 131 842 tiles and 516 second-level sums, so a scan thread's run
     holds three of them, and since 1 030 is no divisor of 1 024 the tile boundaries drift through the rows.  The reference tiles one
     row's mask: numpy never expands the slots."""
+import functools
+
 import numpy as np
 import pytest
 import torch
@@ -12,6 +14,7 @@ import torch
 from tests import in_edges_ref
 from tests import labor_ref as ref
 from tests import node2vec_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -72,12 +75,7 @@ def test_the_cases_hold_their_conditions_before_any_launch():
     assert np.array_equal(small[0], dst[:7 * k]) and np.array_equal(small[1], src[:7 * k]) and np.array_equal(small[2], eid[:7 * k])
 
 
-def _same(got, want, what):
-    for name, g, w in zip(("dst", "src", "eid"), got, want):
-        g = g.cpu().numpy()
-        assert g.dtype == w.dtype and g.shape == w.shape, (what, name, g.shape, w.shape)
-        bad = np.nonzero(g != w)[0]
-        assert bad.size == 0, f"{what}: {bad.size} entries of {name} differ, first at {bad[0]}: got {g[bad[0]]} want {w[bad[0]]}"
+same_labor = functools.partial(same_arrays, names=("dst", "src", "eid"))
 
 
 def test_more_slots_than_one_stride(hip):
@@ -88,10 +86,10 @@ def test_more_slots_than_one_stride(hip):
     try:
         got = g.labor_edges(torch.from_numpy(rows).to(DEV), 25, return_eids=True)
         torch.cuda.synchronize()
-        _same(got, (dst, src, eid), "5 000 seeds")
+        same_labor(got, (dst, src, eid), "5 000 seeds")
         got = g.labor_edges(torch.from_numpy(rows).to(DEV), 25)
         torch.cuda.synchronize()
-        _same(got, (dst, src), "5 000 seeds, no edge ids")
+        same_labor(got, (dst, src), "5 000 seeds, no edge ids")
     finally:
         torch.cuda.synchronize()
         g.close()
@@ -105,7 +103,7 @@ def test_more_tiles_than_one_run_of_the_scan(hip):
         got = g.labor_edges(torch.from_numpy(rows).to(DEV), 10, salt=5, return_eids=True)
         torch.cuda.synchronize()
         assert got[0].shape == (K,)
-        _same(got, (dst, src, eid), f"{COPIES} copies of a row of {WIDE}")
+        same_labor(got, (dst, src, eid), f"{COPIES} copies of a row of {WIDE}")
     finally:
         torch.cuda.synchronize()
         g.close()

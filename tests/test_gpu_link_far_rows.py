@@ -1,45 +1,25 @@
 """find_edges and negative_sample at edge offsets beyond 2^31 and 2^32: the layout of tests/far_rows.py, whose live rows straddle the
-boundary behind ballast rows of L zeros, with the world of tests/test_gpu_far_rows.py (without the weights: neither op reads them).  The
+boundary behind ballast rows of L zeros, put on the device by far_rows.device_world (without the weights: neither op reads them).  The
 references run on the reference view; the whole column array exists on the device only.  A failure at 5000 is a fault at any size; at
 2^31 but not at 5000 an offset that went through a signed 32-bit value; at 2^32 only, through an unsigned one."""
-import time
-
 import numpy as np
 import pytest
 import torch
 
 from tests import far_rows
 from tests import link_ref as ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
 DEV = "cuda:0"
-WHY = {"5000": "fails at boundary 5000: the harness, or the kernel at any size",
-       "2^31": "if only from boundary 2^31 on: a signed 32-bit truncation of an edge offset",
-       "2^32": "if at boundary 2^32 only: an unsigned 32-bit truncation of an edge offset"}
 
 
 @pytest.fixture(scope="module", params=list(far_rows.BOUNDARIES))
 def world(hip, request):
-    """The whole graph on the device at one boundary: col zeros of E entries with the live tail written from the host, the graph, and
-    the layout.  Closed and freed before the next boundary opens."""
-    from legion_amd import engine
-    g = far_rows.layout(request.param)
-    torch.cuda.synchronize()
-    t0 = time.perf_counter()
-    col = torch.zeros(g.E, dtype=torch.int32, device=DEV)
-    col[g.offset:] = torch.from_numpy(g.col_ref.copy()).to(DEV)
-    indptr = torch.from_numpy(g.indptr.copy()).to(DEV)
-    graph = engine.GraphStorage(1, indptr, col)
-    torch.cuda.synchronize()
-    print(f"\nfar rows at {request.param}: E = {g.E}, B = {g.B}; arrays and graph {time.perf_counter() - t0:.3f} s")
-    out = dict(g=g, graph=graph, indptr=indptr, col=col, why=" -- " + WHY[request.param], name=request.param)
-    yield out
-    torch.cuda.synchronize()
-    graph.close()
-    out.clear()
-    del graph, col, indptr
-    torch.cuda.empty_cache()
+    """The whole graph on the device at one boundary (far_rows.device_world)."""
+    with far_rows.device_world(hip, request.param) as w:
+        yield w
 
 
 def far_eids(g):
@@ -99,6 +79,4 @@ def test_negative_sample(world, count, k, tries, base):
     rows, want = want_negatives(g, count, k, tries, base)
     got = world["graph"].negative_sample(torch.from_numpy(rows).to(DEV), k, max_tries=tries, base=base)
     torch.cuda.synchronize()
-    got = got.cpu().numpy()
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{len(bad)} negatives differ, first at {bad[0]}: got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}" + world["why"]
+    same_arrays(got, want, f"negative_sample {count} x {k} tries {tries} base {base}" + world["why"], names=["negatives (row, slot)"])

@@ -12,6 +12,7 @@ import torch
 
 from tests import link_ref as ref
 from tests import walk_ref
+from tests.compare import same_arrays
 from tests.test_gpu_node2vec_fuzz import fuzz_shape
 
 pytestmark = pytest.mark.gpu
@@ -79,13 +80,6 @@ def cases(hip):
         c["graph"].close()
 
 
-def _same(got, want, ctx):
-    got = got.cpu().numpy()
-    assert got.dtype == want.dtype and got.shape == want.shape, f"{ctx}: {got.dtype} {got.shape}"
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{ctx}: {len(bad)} entries differ, first at {bad[0]}: got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}"
-
-
 @pytest.mark.parametrize("seed", SEEDS)
 def test_random_link_seeds_match_the_reference(cases, seed):
     from legion_amd import engine
@@ -99,15 +93,15 @@ def test_random_link_seeds_match_the_reference(cases, seed):
     seeds, num, pos_row, pos_col, neg_col = g.edge_prediction_seeds(c["eids"], k, **kw)
     torch.cuda.synchronize()
     B = c["B"]
-    _same(row, want["row"], ctx + "row")
-    _same(col, want["col"], ctx + "col")
-    _same(neg, want["neg"], ctx + "neg")
-    _same(unique, want["seeds"], ctx + "unique")
-    _same(local, np.concatenate([want["pos_row"], want["pos_col"], want["neg_col"].reshape(-1)]), ctx + "local")
-    _same(seeds, want["seeds"], ctx + "seeds")
-    _same(pos_row, want["pos_row"], ctx + "pos_row")
-    _same(pos_col, want["pos_col"], ctx + "pos_col")
-    _same(neg_col, want["neg_col"], ctx + "neg_col")
+    same_arrays(row, want["row"], ctx + "row")
+    same_arrays(col, want["col"], ctx + "col")
+    same_arrays(neg, want["neg"], ctx + "neg")
+    same_arrays(unique, want["seeds"], ctx + "unique")
+    same_arrays(local, np.concatenate([want["pos_row"], want["pos_col"], want["neg_col"].reshape(-1)]), ctx + "local")
+    same_arrays(seeds, want["seeds"], ctx + "seeds")
+    same_arrays(pos_row, want["pos_row"], ctx + "pos_row")
+    same_arrays(pos_col, want["pos_col"], ctx + "pos_col")
+    same_arrays(neg_col, want["neg_col"], ctx + "neg_col")
     assert int(count.item()) == int(num.item()) == want["num_seeds"], ctx + "count"
     assert seeds.shape == (B * (2 + k),) and neg_col.shape == (B, k)
 

@@ -7,12 +7,15 @@ not what a float32 product gives.
 The grid is the product thinned: case number c of the 18 (rows, k) pairs takes exclude c mod 4, max_tries number (c + c div 4) mod 4
 and base number (c div 2) mod 3, so every exclusion meets every max_tries.  The references are computed once, with the counters that
 show, before any launch, what the cases exercise."""
+import functools
+
 import numpy as np
 import pytest
 import torch
 
 from tests import link_ref as ref
 from tests import node2vec_ref, walk_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -59,11 +62,7 @@ def world(hip):
         g.close()
 
 
-def _same(got, want, ctx):
-    got = got.cpu().numpy()
-    assert got.dtype == np.int32 and got.shape == want.shape, ctx
-    bad = np.argwhere(got != want)
-    assert bad.size == 0, f"{ctx}: {len(bad)} negatives differ, first at row, slot {bad[0]}: got {got[tuple(bad[0])]} want {want[tuple(bad[0])]}"
+same_negatives = functools.partial(same_arrays, names=("negatives (row, slot)",))
 
 
 def test_the_cases_show_every_rejection_before_any_launch(world):
@@ -104,7 +103,7 @@ def test_negatives_are_the_reference_bit_for_bit(world, n, k):
     got = world["graph"].negative_sample(rows, k, exclude_self=bool(c["exclude"] & 1), exclude_edges=bool(c["exclude"] & 2),
                                          max_tries=c["tries"], base=c["base"])
     torch.cuda.synchronize()
-    _same(got, want, str(c))
+    same_negatives(got, want, str(c))
 
 
 @pytest.mark.parametrize("tries", [1, 3, 256])
@@ -119,8 +118,8 @@ def test_a_complete_graph_has_no_negatives(world, tries):
     got = g.negative_sample(rows, 5, max_tries=tries, base=11)
     got_own = g.negative_sample(rows, 5, exclude_self=False, max_tries=tries, base=11)
     torch.cuda.synchronize()
-    _same(got, want, f"K_8 exclude 3 tries {tries}")
-    _same(got_own, own, f"K_8 exclude 2 tries {tries}")
+    same_negatives(got, want, f"K_8 exclude 3 tries {tries}")
+    same_negatives(got_own, own, f"K_8 exclude 2 tries {tries}")
 
 
 @pytest.mark.parametrize("tries", [1, 2, 256])
@@ -133,8 +132,8 @@ def test_a_ring_rejects_the_row_itself(world, tries):
     got = g.negative_sample(rows, 5, exclude_edges=False, max_tries=tries)
     both = g.negative_sample(rows, 5, max_tries=tries)
     torch.cuda.synchronize()
-    _same(got, want, f"ring exclude 1 tries {tries}")
-    _same(both, ref.negative_sample(ip, c, rows, 5, 3, tries, 0), f"ring exclude 3 tries {tries}")
+    same_negatives(got, want, f"ring exclude 1 tries {tries}")
+    same_negatives(both, ref.negative_sample(ip, c, rows, 5, 3, tries, 0), f"ring exclude 3 tries {tries}")
 
 
 def test_one_vertex(hip):
@@ -149,7 +148,7 @@ def test_one_vertex(hip):
         for e in range(4):
             got = g.negative_sample(rows, 5, exclude_self=bool(e & 1), exclude_edges=bool(e & 2), max_tries=3, base=9)
             torch.cuda.synchronize()
-            _same(got, want[e], f"one vertex, exclude {e}")
+            same_negatives(got, want[e], f"one vertex, exclude {e}")
     finally:
         torch.cuda.synchronize()
         g.close()
@@ -212,7 +211,7 @@ def test_the_draw_over_more_than_2_24_vertices(hip, node_num):
         for exclude in (0, 3):
             got = g.negative_sample(rows, BIG_K, exclude_self=bool(exclude & 1), exclude_edges=bool(exclude & 2), base=BIG_BASE)
             torch.cuda.synchronize()
-            _same(got, want[exclude], f"N {node_num}, exclude {exclude}")
+            same_negatives(got, want[exclude], f"N {node_num}, exclude {exclude}")
     finally:
         torch.cuda.synchronize()
         g.close()

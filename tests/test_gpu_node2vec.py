@@ -7,6 +7,7 @@ The grid is the product thinned: case number c of the 36 (walks, steps) pairs ta
 the weights c mod 3 and the base (c div 3) mod 3 -- 5, 4 and 3 are coprime, so every value meets every other somewhere -- and runs with
 and without edge ids.  The references are computed once, with the counters that show, before any launch, what the cases exercise."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -15,6 +16,7 @@ import torch
 from tests import node2vec_ref as ref
 from tests import walk_ref
 from tests import weighted_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -68,15 +70,7 @@ def world(hip):
         graphs[k].close()
 
 
-def _same(got, want, ctx):
-    traces, eids = (x.cpu().numpy() for x in got)
-    assert traces.dtype == np.int32 and eids.dtype == np.int64
-    assert traces.shape == want[0].shape and eids.shape == want[1].shape, ctx
-    bad = np.argwhere(traces != want[0])
-    assert bad.size == 0, f"{ctx}: {len(bad)} trace entries differ, first at walk, position {bad[0]}: " \
-                          f"got {traces[tuple(bad[0])]} want {want[0][tuple(bad[0])]}"
-    bad = np.argwhere(eids != want[1])
-    assert bad.size == 0, f"{ctx}: {len(bad)} edge ids differ, first at walk, step {bad[0]}"
+same_walk = functools.partial(same_arrays, names=("trace entries (walk, position)", "edge ids (walk, step)"))
 
 
 def test_the_cases_show_every_class_before_any_launch(world):
@@ -114,7 +108,7 @@ def test_walks_are_the_reference_bit_for_bit(world, num_walks, length):
     got = g.node2vec_random_walk(seeds, *c["pq"], length, return_eids=True, **kw)
     only = g.node2vec_random_walk(seeds, *c["pq"], length, **kw)
     torch.cuda.synchronize()
-    _same(got, want, str(c))
+    same_walk(got, want, str(c))
     walk_ref.check(world["indptr"], world["col"], seeds.cpu().numpy(), got[0].cpu().numpy(), got[1].cpu().numpy())
     assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), str(c) + ": traces without edge ids"
 
@@ -140,7 +134,7 @@ def test_chunk_edges_of_the_staging_tile(world, num_walks, length):
     only = world["graph"].node2vec_random_walk(d_seeds, *pq, length, weighted=weighted, base=77)
     torch.cuda.synchronize()
     ctx = f"{num_walks} x {length}, (p, q) = {pq}, {'weighted' if weighted else 'uniform'}"
-    _same(got, want, ctx)
+    same_walk(got, want, ctx)
     assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), ctx + ": traces without edge ids"
 
 
@@ -174,7 +168,7 @@ def test_a_walk_on_another_stream_is_the_default_streams(world):
     host = g.node2vec_random_walk(ref.seeds_for(5000), 4.0, 0.25, 17, base=5, stream=s)      # seeds from the host: copied, then walked on s
     s.synchronize()
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(only, plain) and torch.equal(host, plain)
-    _same(got, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), 17, 0.5, 2.0, table=world["table"], base=5), "stream=")
+    same_walk(got, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), 17, 0.5, 2.0, table=world["table"], base=5), "stream=")
 
 
 def test_empty_call_returns_empty_arrays(world):
@@ -260,7 +254,7 @@ def test_a_captured_walk_replays_the_eager_result(world):
     traces = torch.zeros((n, length + 1), dtype=torch.int32, device=DEV)
     eids = torch.zeros((n, length), dtype=torch.int64, device=DEV)
     torch.cuda.synchronize()
-    _same(eager, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), length, 4.0, 0.25, table=world["table"], base=5), "eager")
+    same_walk(eager, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), length, 4.0, 0.25, table=world["table"], base=5), "eager")
     graph = torch.cuda.CUDAGraph()
     with torch.cuda.graph(graph):
         rc = L.legion_node2vec_walk(ctypes.c_void_p(torch.cuda.current_stream().cuda_stream), world["graph"].handle,

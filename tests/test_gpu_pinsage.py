@@ -4,6 +4,7 @@ visits per seed and both sides of each class edge, tile edges in seeds, uniform 
 range of the draw index -- its composition with this build's own random_walk, the C ABI's refusals, the fixed table, and a captured
 launch."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -12,6 +13,7 @@ import torch
 from tests import pinsage_ref as ref
 from tests import walk_ref
 from tests import weighted_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -47,13 +49,7 @@ def world(hip):
         graphs[k].close()
 
 
-def _same(got, want, ctx):
-    nb, ct = (x.cpu().numpy() for x in got)
-    assert nb.dtype == np.int32 and ct.dtype == np.int32
-    assert nb.shape == want[0].shape and ct.shape == want[1].shape, ctx
-    bad = np.argwhere((nb != want[0]) | (ct != want[1]))
-    assert bad.size == 0, f"{ctx}: {len(bad)} slots differ, first at seed, slot {bad[0]}: got {nb[tuple(bad[0])]} x {ct[tuple(bad[0])]} " \
-                          f"want {want[0][tuple(bad[0])]} x {want[1][tuple(bad[0])]}"
+same_slots = functools.partial(same_arrays, names=("neighbours (seed, slot)", "counts (seed, slot)"))
 
 
 def test_every_index_the_walks_form_is_inside_its_array(world):
@@ -82,7 +78,7 @@ def test_neighbours_are_the_reference_bit_for_bit(world, n, shape, weighted):
                              termination_prob=p, base=BASE)
         got = world["graph"].pinsage_neighbors(d_seeds, R, T, k, termination_prob=p, weighted=weighted, base=BASE)
         torch.cuda.synchronize()
-        _same(got, want, f"{n} seeds, {shape}, {'weighted' if weighted else 'uniform'}, termination {p}")
+        same_slots(got, want, f"{n} seeds, {shape}, {'weighted' if weighted else 'uniform'}, termination {p}")
 
 
 @pytest.mark.parametrize("shape", [(10, 2, 3), (5, 13, 4), (65, 3, 200), (64, 16, 10)], ids=lambda s: "x".join(map(str, s)))
@@ -96,7 +92,7 @@ def test_composition_with_this_builds_random_walk(world, shape):
         got = world["graph"].pinsage_neighbors(seeds, R, T, k, termination_prob=0.0, weighted=weighted, base=base)
         torch.cuda.synchronize()
         want = ref.topk(traces.cpu().numpy()[:, 1:].reshape(257, R * T), k)
-        _same(got, want, f"{shape} weighted {weighted}")
+        same_slots(got, want, f"{shape} weighted {weighted}")
 
 
 def test_termination_one_leaves_the_first_steps(world):
@@ -106,7 +102,7 @@ def test_termination_one_leaves_the_first_steps(world):
                              termination_prob=1.0, base=BASE)
         got = world["graph"].pinsage_neighbors(seeds, 10, 2, 3, termination_prob=1.0, weighted=weighted, base=BASE)
         torch.cuda.synchronize()
-        _same(got, want, f"termination 1.0 weighted {weighted}")
+        same_slots(got, want, f"termination 1.0 weighted {weighted}")
         assert np.all(want[1].sum(axis=1) <= 10) and (want[1] > 0).any()      # one visit per walk at the most, and some
 
 
@@ -117,7 +113,7 @@ def test_unit_weights_are_the_unweighted_sampler(world):
         b = world["unit"].pinsage_neighbors(seeds, *shape, weighted=False, termination_prob=0.3, base=9)
         torch.cuda.synchronize()
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-        _same(a, ref.neighbors(world["indptr"], world["col"], seeds, *shape, termination_prob=0.3, base=9), "unit weights")
+        same_slots(a, ref.neighbors(world["indptr"], world["col"], seeds, *shape, termination_prob=0.3, base=9), "unit weights")
 
 
 @pytest.mark.parametrize("base", [0, 1234567890, M31 - 65 * 5 * 13], ids=["zero", "mid", "largest"])
@@ -129,7 +125,7 @@ def test_base(world, base):
                              termination_prob=p, base=base)
         got = world["graph"].pinsage_neighbors(seeds, 5, 13, 4, termination_prob=p, weighted=weighted, base=base)
         torch.cuda.synchronize()
-        _same(got, want, f"base {base} weighted {weighted} termination {p}")
+        same_slots(got, want, f"base {base} weighted {weighted} termination {p}")
 
 
 def test_a_call_on_another_stream_is_the_default_streams(world):
@@ -145,8 +141,8 @@ def test_a_call_on_another_stream_is_the_default_streams(world):
     s.synchronize()
     for a, b in zip(got + [host], want + [want[0]]):
         assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    _same(got[0], ref.neighbors(world["indptr"], world["col"], seeds.cpu().numpy(), *shapes[0], table=world["table"], termination_prob=0.3,
-                                base=5), "stream=")
+    same_slots(got[0], ref.neighbors(world["indptr"], world["col"], seeds.cpu().numpy(), *shapes[0], table=world["table"], termination_prob=0.3,
+                                     base=5), "stream=")
 
 
 def test_empty_call_returns_empty_arrays(world):
@@ -184,7 +180,7 @@ def test_c_abi_refusals_leave_the_outputs_untouched(world):
     torch.cuda.synchronize()
     assert not bool((nb == 0x5A5A5A5A).any()) and not bool((ct == 0x5A5A5A5A).any())
     want = ref.neighbors(world["indptr"], world["col"], seeds.cpu().numpy(), R, T, k, termination_prob=0.5, base=M31 - n * R * T)
-    _same((nb, ct), want, "the largest base through the C ABI")
+    same_slots((nb, ct), want, "the largest base through the C ABI")
     with pytest.raises(ValueError, match="set_edge_weights"):
         world["bare"].pinsage_neighbors(seeds, R, T, k, weighted=True)
 

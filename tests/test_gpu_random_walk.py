@@ -2,6 +2,7 @@
 in tests/walk_ref.py on a hand-built graph -- every workgroup / chunk boundary in walks and steps, uniform and weighted picks, the
 restart draw, the whole range of the draw index -- and the C ABI's refusals, the fixed table, and a captured launch."""
 import ctypes
+import functools
 
 import numpy as np
 import pytest
@@ -9,6 +10,7 @@ import torch
 
 from tests import walk_ref as ref
 from tests import weighted_ref
+from tests.compare import same_arrays
 
 pytestmark = pytest.mark.gpu
 
@@ -36,15 +38,7 @@ def world(hip):
         graphs[k].close()
 
 
-def _same(got, want, ctx):
-    traces, eids = (x.cpu().numpy() for x in got)
-    assert traces.dtype == np.int32 and eids.dtype == np.int64
-    assert traces.shape == want[0].shape and eids.shape == want[1].shape, ctx
-    bad = np.argwhere(traces != want[0])
-    assert bad.size == 0, f"{ctx}: {len(bad)} trace entries differ, first at walk, position {bad[0]}: " \
-                          f"got {traces[tuple(bad[0])]} want {want[0][tuple(bad[0])]}"
-    bad = np.argwhere(eids != want[1])
-    assert bad.size == 0, f"{ctx}: {len(bad)} edge ids differ, first at walk, step {bad[0]}"
+same_walk = functools.partial(same_arrays, names=("trace entries (walk, position)", "edge ids (walk, step)"))
 
 
 def test_every_index_the_walks_form_is_inside_its_array(world):
@@ -71,7 +65,7 @@ def test_walks_are_the_reference_bit_for_bit(world, num_walks, length):
         got = world["graph"].random_walk(d_seeds, length, weighted=weighted, return_eids=True)
         only = world["graph"].random_walk(d_seeds, length, weighted=weighted)
         torch.cuda.synchronize()
-        _same(got, want, ctx)
+        same_walk(got, want, ctx)
         ref.check(world["indptr"], world["col"], seeds, got[0].cpu().numpy(), got[1].cpu().numpy())
         assert isinstance(only, torch.Tensor) and torch.equal(only, got[0]), ctx + ": traces without edge ids"
 
@@ -98,7 +92,7 @@ def test_restart(world, weighted, restart, eids):
     got = world["graph"].random_walk(seeds, 17, weighted=weighted, restart_prob=restart, return_eids=eids, base=40)
     torch.cuda.synchronize()
     if eids:
-        _same(got, want, f"restart {restart}")
+        same_walk(got, want, f"restart {restart}")
     else:
         assert np.array_equal(got.cpu().numpy(), want[0])
     if restart == 1.0:
@@ -113,7 +107,7 @@ def test_unit_weights_are_the_unweighted_walk(world):
     b = world["unit"].random_walk(seeds, 16, weighted=False, return_eids=True, base=9)
     torch.cuda.synchronize()
     assert torch.equal(a[0], b[0]) and torch.equal(a[1], b[1])
-    _same(a, ref.walk(world["indptr"], world["col"], seeds, 16, base=9), "unit weights")
+    same_walk(a, ref.walk(world["indptr"], world["col"], seeds, 16, base=9), "unit weights")
 
 
 @pytest.mark.parametrize("base", [0, 1234567890, M31 - 65 * 17], ids=["zero", "mid", "largest"])
@@ -125,7 +119,7 @@ def test_base(world, base):
                         base=base)
         got = world["graph"].random_walk(seeds, 17, weighted=weighted, restart_prob=restart, return_eids=True, base=base)
         torch.cuda.synchronize()
-        _same(got, want, f"base {base} weighted {weighted} restart {restart}")
+        same_walk(got, want, f"base {base} weighted {weighted} restart {restart}")
 
 
 def test_a_walk_on_another_stream_is_the_default_streams(world):
@@ -141,7 +135,7 @@ def test_a_walk_on_another_stream_is_the_default_streams(world):
     host = world["graph"].random_walk(ref.seeds_for(5000), 17, base=5, stream=s)      # seeds from the host: copied, then walked on s
     s.synchronize()
     assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and torch.equal(only, plain) and torch.equal(host, plain)
-    _same(got, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), 17, table=world["table"], restart_prob=0.3, base=5), "stream=")
+    same_walk(got, ref.walk(world["indptr"], world["col"], seeds.cpu().numpy(), 17, table=world["table"], restart_prob=0.3, base=5), "stream=")
 
 
 def test_empty_call_returns_empty_arrays(world):
