@@ -34,8 +34,9 @@ def _newer(target, deps):
 def build_lib(force=False, verbose=True):
     objdir = os.path.join(HERE, "_obj")
     os.makedirs(objdir, exist_ok=True)
-    # every header a source may include: a changed plan header (gather_plan.h, sample_plan.h) rebuilds its kernels too
-    headers = glob.glob(os.path.join(CSRC, "*.h")) + [os.path.join(HERE, "..", "include", "legion_hip.h")]
+    # every header a source may include: a changed plan header (gather_plan.h, sample_plan.h) rebuilds its kernels too, a changed
+    # trainer/vmm_*.h the library's receiving end of a chunked arena (storage.hip)
+    headers = glob.glob(os.path.join(CSRC, "*.h")) + glob.glob(os.path.join(HERE, "trainer", "*.h")) + [os.path.join(HERE, "..", "include", "legion_hip.h")]
     objs, procs = [], []
     for src in SOURCES:
         s = os.path.join(CSRC, src)
@@ -77,7 +78,8 @@ def build_lib(force=False, verbose=True):
 def build_trainer(verbose=True, force=False):
     tdir = os.path.join(HERE, "trainer")
     built = glob.glob(os.path.join(tdir, "ipc_service*.so"))
-    srcs = [os.path.join(tdir, "ipc_service.cpp"), os.path.join(tdir, "vmm_probe.h"), os.path.join(tdir, "setup.py")]
+    srcs = [os.path.join(tdir, "ipc_service.cpp"), os.path.join(tdir, "vmm_probe.h"), os.path.join(tdir, "vmm_map.h"), os.path.join(CSRC, "ipc_wire.h"),
+            os.path.join(HERE, "..", "include", "legion_hip.h"), os.path.join(tdir, "setup.py")]
     if built and not force and not _newer(built[0], srcs):
         return built[0]
     env = dict(os.environ, PYTORCH_ROCM_ARCH=ARCH)

@@ -1,19 +1,12 @@
 // ipc_env.hip -- server end of the server <-> trainer wire protocol.
 //
 // Reference: SS/engine/ipc_service.cu (CUDAIPCEnv :33-349), SS/engine/helper_multiprocess.cu
-// (only sharedMemoryCreate/Open/Close are used).  The protocol is kept bit-for-bit:
-//   * POSIX shm "simpleIPCshm" = struct { int32 steps[3]; IpcMemHandle(64 B) memHandle[8][2][7]; }, exactly that size
-//     slot order: 0 ids, 1 features, 2 labels, 3 agg_src, 4 agg_dst, 5 node_counter, 6 edge_counter
-//   * named semaphores sem_r_<dev>_<pipe> (trainer -> server, buffer free) and
-//     sem_w_<dev>_<pipe> (server -> trainer, batch ready), created with value 0
-//   * step schedule (train+valid)*epoch + test, valid/test batch = ceil(n_p / ceil(max n / 512))
-// hipIpcMemHandle_t is 64 bytes like cudaIpcMemHandle_t.  LEGION_IPC_NAMESPACE (optional env)
-// suffixes the shm/semaphore names so that independent servers (tests) can share a host.
+// (only sharedMemoryCreate/Open/Close are used).  The protocol is kept bit-for-bit; its layouts, names and versions are
+// ipc_wire.h's (the slab, the mirror object, the semaphores of every (device, pipe slot), created here with value 0), the
+// step schedule is (train+valid)*epoch + test, valid/test batch = ceil(n_p / ceil(max n / 512)).
+// LEGION_IPC_NAMESPACE (optional env) suffixes the shm/semaphore names so that independent servers (tests) can share a host.
+#include "ipc_wire.h"
 #include "legion_core.h"
-#include <sys/socket.h>
-#include <sys/un.h>
-#include <cerrno>
-#include <cstddef>
 #include <thread>
 
 #include <fcntl.h>
@@ -27,52 +20,7 @@
 #include <cstring>
 #include <iostream>
 
-static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size is part of the wire format");
-
-// The slab is the reference's, byte for byte and no larger (SS/engine/ipc_service.cu:28-31): a trainer built from the
-// reference opens it with shm_open + ftruncate(sizeof(its struct)) (TB/helper_multiprocess.cpp:30-37), which must not
-// change its size.  This build's extra -- per (device, pipe slot) the 16 + 16 counters of the batch in that slot in
-// HOST memory, so the trainer end needs no device-to-host copy per batch (the reference does two blocking 64-byte
-// cudaMemcpy per get_next, TB/ipc_cuda_kernel.cu:186-187) -- lives in a shm object of its own, "legionIPCext<suffix>":
-// registered with HIP, written by the GPU, opened by this build's ipc_service when it exists.
-#define LEGION_SHM_EXT_MAGIC 0x4C47494F   /* "LGIO" */
-typedef struct shmStruct_st {
-    int32_t steps[3];
-    hipIpcMemHandle_t memHandle[MAX_DEVICE][INTERBATCH_CON][MEMORY_USAGE];
-} shmStruct;
-static_assert(offsetof(shmStruct, memHandle) == 12 && sizeof(shmStruct) == 12 + MAX_DEVICE * INTERBATCH_CON * MEMORY_USAGE * 64,
-              "the reference's slab layout is the wire format");
-// Version 2 of the object (round 4) adds the "direct view" hand-over.  The server produces mini-batches in launch groups
-// into per-lane buffers (server.hip) that all live in ONE device allocation per GPU, the lane arena; its IPC handle is
-// published here.  A trainer end that can open it (this build's ipc_service) says so in trainer_direct[dev] BEFORE its first
-// sem_post; from then on a hand-over is no GPU work at all: the server writes, per (device, pipe slot), where the five
-// trainer-visible arrays of the batch start inside the arena and posts sem_w -- same semaphores, same two-slot order, and
-// the reference-sized slab above stays valid for a trainer that knows nothing of this (it gets copies in the slot buffers).
-typedef struct shmExt_st {
-    int32_t ext_magic;                                         // LEGION_SHM_EXT_MAGIC once the mirror below is live
-    int32_t ext_version;                                       // >= 2: the fields behind `counters` exist; 3: those behind `view` too
-    int32_t server_state;                                      // 0 serving, 1 the server stopped on an error (trainers must not wait)
-    int32_t ext_reserved;
-    int32_t counters[MAX_DEVICE][INTERBATCH_CON][32];          // [0..15] node_counter, [16..31] edge_counter
-    hipIpcMemHandle_t arena[MAX_DEVICE];                       // lane arena of each server GPU, valid when arena_bytes > 0
-    int64_t arena_bytes[MAX_DEVICE];
-    int32_t trainer_direct[MAX_DEVICE];                        // written by the trainer end: 1 = it opened the arena and takes views
-    int32_t view_on[MAX_DEVICE][INTERBATCH_CON];               // 1: the batch in this slot is the view below, 0: it is in the slot's buffers
-    int64_t view[MAX_DEVICE][INTERBATCH_CON][5];               // byte offsets into the arena: ids, features, labels, agg_src, agg_dst
-    // version 3: the arena may be built from physical chunks mapped in shuffled order (storage.hip d_alloc_scattered: the gathers then
-    // write a group's rows all over the HBM, +7 %), which hipIpcGetMemHandle cannot export.  arena_kind 1: `arena` is unused; the trainer
-    // connects to the abstract unix socket "legion_arena_<arena_sock_pid>_<dev>", receives arena_chunks file descriptors (SCM_RIGHTS, in
-    // mapping order), imports each (hipMemImportFromShareableHandle) and maps them back to back: arena_chunks x arena_chunk_bytes >= arena_bytes
-    int32_t arena_kind[MAX_DEVICE];
-    int32_t arena_chunks[MAX_DEVICE];
-    int64_t arena_chunk_bytes[MAX_DEVICE];
-    int32_t arena_sock_pid;
-    int32_t ext_reserved2;
-    // version 4: dtype of the feature rows of each server GPU's batches (LEGION_FEATURE_*; 1 = bf16[n x D]), in the pipe slots and
-    // in the views alike.  A trainer end that reads an older version takes float32 rows.
-    int32_t feature_out_dtype[MAX_DEVICE];
-} shmExt;
-#define LEGION_SHM_EXT_VERSION 4
+static_assert(sizeof(hipIpcMemHandle_t) == sizeof(wireIpcHandle), "IPC handle size is part of the wire format");
 
 typedef struct sharedMemoryInfo_st {
     void* addr;
@@ -85,6 +33,9 @@ static std::string ipc_suffix()
     const char* ns = getenv("LEGION_IPC_NAMESPACE");
     return ns ? std::string(ns) : std::string();
 }
+
+// a name of ipc_wire.h as a string: wire_name(wire_sem_r_name, dev, pipe, suffix)
+template <class Build, class... A> static std::string wire_name(Build build, A... a) { char name[WIRE_NAME_MAX]; build(name, sizeof(name), a...); return name; }
 
 static int sharedMemoryCreate(const char* name, size_t sz, sharedMemoryInfo* info)
 {
@@ -113,7 +64,7 @@ public:
         info_.addr = nullptr;
         info_.shmFd = -1;
         if (create_shm) {
-            shm_name_ = std::string("simpleIPCshm") + ipc_suffix();
+            shm_name_ = wire_name(wire_slab_name, ipc_suffix().c_str());
             if (sharedMemoryCreate(shm_name_.c_str(), sizeof(*shm_), &info_) != 0) {
                 printf("Failed to create shared memory slab\n");
                 exit(EXIT_FAILURE);
@@ -123,7 +74,7 @@ public:
             // the counter mirror: a shm object of its own that the GPUs write straight into
             ext_info_.addr = nullptr;
             ext_info_.shmFd = -1;
-            ext_name_ = std::string("legionIPCext") + ipc_suffix();
+            ext_name_ = wire_name(wire_mirror_name, ipc_suffix().c_str());
             if (lg::tuning().shm_mirror && sharedMemoryCreate(ext_name_.c_str(), sizeof(shmExt), &ext_info_) == 0) {
                 ext_ = (volatile shmExt*)ext_info_.addr;
                 memset((void*)ext_, 0, sizeof(shmExt));
@@ -204,12 +155,12 @@ public:
         semw_[device_id].resize(pipeline_depth);
         for (int32_t i = 0; i < pipeline_depth; i++) {
             auto slot = [&](int k) { return (void*)&shm_->memHandle[device_id][i][k]; };
-            void* new_ids = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(0), __FILE__, __LINE__);
-            void* new_labels = lg_alloc_exported((int64_t)batch_size * sizeof(int32_t), slot(2), __FILE__, __LINE__);
-            void* new_agg_src = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(3), __FILE__, __LINE__);
-            void* new_agg_dst = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(4), __FILE__, __LINE__);
-            void* new_node_counter = lg_alloc_exported(16 * sizeof(int32_t), slot(5), __FILE__, __LINE__);
-            void* new_edge_counter = lg_alloc_exported(16 * sizeof(int32_t), slot(6), __FILE__, __LINE__);
+            void* new_ids = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(WIRE_SLOT_IDS), __FILE__, __LINE__);
+            void* new_labels = lg_alloc_exported((int64_t)batch_size * sizeof(int32_t), slot(WIRE_SLOT_LABELS), __FILE__, __LINE__);
+            void* new_agg_src = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(WIRE_SLOT_AGG_SRC), __FILE__, __LINE__);
+            void* new_agg_dst = lg_alloc_exported((int64_t)num_ids * sizeof(int32_t), slot(WIRE_SLOT_AGG_DST), __FILE__, __LINE__);
+            void* new_node_counter = lg_alloc_exported(16 * sizeof(int32_t), slot(WIRE_SLOT_NODE_COUNTER), __FILE__, __LINE__);
+            void* new_edge_counter = lg_alloc_exported(16 * sizeof(int32_t), slot(WIRE_SLOT_EDGE_COUNTER), __FILE__, __LINE__);
             HIP_CALL(hipMemset(new_node_counter, 0, 64));
             HIP_CALL(hipMemset(new_edge_counter, 0, 64));
             ids_[device_id].push_back(new_ids);
@@ -219,8 +170,8 @@ public:
             node_counter_[device_id].push_back(new_node_counter);
             edge_counter_[device_id].push_back(new_edge_counter);
 
-            const std::string ssri = "sem_r_" + std::to_string(device_id) + "_" + std::to_string(i) + sfx;
-            const std::string sswi = "sem_w_" + std::to_string(device_id) + "_" + std::to_string(i) + sfx;
+            const std::string ssri = wire_name(wire_sem_r_name, device_id, i, sfx.c_str());
+            const std::string sswi = wire_name(wire_sem_w_name, device_id, i, sfx.c_str());
             // a crashed run (every HIP error path exits without Finalize) leaves semaphores with counts behind; a stale
             // sem_r count would let this server overwrite a buffer the trainer still reads, a stale sem_w count would
             // hand the trainer a batch that was never produced.  The server owns the names and starts first.
@@ -248,7 +199,7 @@ public:
         SetGPUDevice(device_id);
         for (int32_t i = 0; i < pipeline_depth; i++) {
             void* new_features = lg_alloc_exported((int64_t)num_ids * feature_dim * lg_feature_out_bytes(feature_out_dtype),
-                                                   (void*)&shm_->memHandle[device_id][i][1], __FILE__, __LINE__);
+                                                   (void*)&shm_->memHandle[device_id][i][WIRE_SLOT_FEATURES], __FILE__, __LINE__);
             float_features_[device_id].push_back(new_features);
         }
     }
@@ -319,9 +270,8 @@ public:
         int32_t n_chunks = 0;
         const int64_t chunk_bytes = lg_scattered_info(base, &n_chunks);
         if (chunk_bytes > 0) {          // an arena of shuffled chunks: handed over as file descriptors (shmExt, version 3)
-            char name[64];
-            snprintf(name, sizeof(name), "legion_arena_%d_%d", (int)getpid(), dev_id);
-            if (!lg_scattered_serve(base, name)) return false;      // (storage.hip: a thread hands the chunks' descriptors to a same-user peer)
+            const std::string name = wire_name(wire_arena_socket_name, (int)getpid(), dev_id);
+            if (!lg_scattered_serve(base, name.c_str())) return false;      // (storage.hip: a thread hands the chunks' descriptors to a same-user peer)
             ext_->arena_kind[dev_id] = 1;
             ext_->arena_chunks[dev_id] = n_chunks;
             ext_->arena_chunk_bytes[dev_id] = chunk_bytes;
@@ -355,8 +305,8 @@ public:
         for (int32_t i = 0; i < device_count_; i++)
             for (size_t j = 0; j < semw_[i].size(); j++) {
                 if (semw_[i][j] != nullptr && semw_[i][j] != SEM_FAILED) { sem_post(semw_[i][j]); sem_post(semw_[i][j]); }
-                sem_unlink(("sem_r_" + std::to_string(i) + "_" + std::to_string(j) + sfx).c_str());
-                sem_unlink(("sem_w_" + std::to_string(i) + "_" + std::to_string(j) + sfx).c_str());
+                sem_unlink(wire_name(wire_sem_r_name, i, (int)j, sfx.c_str()).c_str());
+                sem_unlink(wire_name(wire_sem_w_name, i, (int)j, sfx.c_str()).c_str());
             }
         if (!shm_name_.empty()) shm_unlink(shm_name_.c_str());
         if (!ext_name_.empty()) shm_unlink(ext_name_.c_str());
@@ -383,10 +333,8 @@ public:
                 d_free_space(edge_counter_[i][j]);
                 if (sem_close(semw_[i][j]) == -1) std::cout << "close sem " << i << " " << j << " failed\n";
                 sem_close(semr_[i][j]);
-                const std::string ssri = "sem_r_" + std::to_string(i) + "_" + std::to_string(j) + sfx;
-                const std::string sswi = "sem_w_" + std::to_string(i) + "_" + std::to_string(j) + sfx;
-                sem_unlink(ssri.c_str());
-                sem_unlink(sswi.c_str());
+                sem_unlink(wire_name(wire_sem_r_name, i, j, sfx.c_str()).c_str());
+                sem_unlink(wire_name(wire_sem_w_name, i, j, sfx.c_str()).c_str());
             }
             ids_[i].clear();
         }

@@ -17,6 +17,7 @@
 //     HEAD (seeds + every hop but the last) of group k+1 runs on a low-priority stream under the heavy kernels of group k
 //     (see phases_of).  The plain two-stream split (every sampler on one stream, every gather on another, with CU masks and
 //     priorities) was measured against it in rounds 2-4 and removed in round 5: DESIGN_HISTORY.md 4.5.
+#include "ipc_wire.h"
 #include "legion_core.h"
 
 #include <unistd.h>
@@ -57,7 +58,7 @@ struct BulkState {
     std::vector<lg::BulkLists> mine;             // [slot]
     std::vector<BulkPeer> peers;                 // [Kg]
     std::vector<hipStream_t> owner_streams;      // [Kg] in-process pull: a stream on each owner's device for THIS requester's pushes
-    int32_t served_tag = -1;                     // >= 0: this arena's chunks are served on "legion_bulk_<pid>_<tag>"
+    int32_t served_tag = -1;                     // >= 0: this arena's chunks are served on wire_bulk_socket_name(pid, tag)
 };
 
 struct LegionPipeline {
@@ -536,7 +537,7 @@ struct LegionBulkHandles {
     int64_t cap;
     int32_t slots, member;
     // arena_kind 1: the arena consists of arena_chunks chunks of arena_chunk_bytes, served as file descriptors on the abstract unix
-    // socket "legion_bulk_<arena_pid>_<arena_tag>"
+    // socket wire_bulk_socket_name(arena_pid, arena_tag)
     int32_t arena_kind, arena_chunks, arena_pid, arena_tag;
     int64_t arena_chunk_bytes;
 };
@@ -630,8 +631,8 @@ extern "C" int32_t legion_pipeline_bulk_export(LegionPipeline* p, void* out_hand
         static std::atomic<int32_t> next_tag{0};
         if (p->bulk->served_tag < 0) {
             p->bulk->served_tag = next_tag.fetch_add(1);
-            char name[64];
-            snprintf(name, sizeof(name), "legion_bulk_%d_%d", (int)getpid(), p->bulk->served_tag);
+            char name[WIRE_NAME_MAX];
+            wire_bulk_socket_name(name, sizeof(name), (int)getpid(), p->bulk->served_tag);
             if (!lg_scattered_serve(p->arena.base, name)) { printf("legion_hip: could not serve the lane arena's chunks on %s\n", name); return 0; }
         }
         h.arena_kind = 1;
@@ -666,8 +667,8 @@ extern "C" int32_t legion_pipeline_bulk_import(LegionPipeline* p, const void* ha
     BulkPeer& peer = p->bulk->peers[h.member];
     void* a = nullptr;
     if (h.arena_kind == 1) {
-        char name[64];
-        snprintf(name, sizeof(name), "legion_bulk_%d_%d", h.arena_pid, h.arena_tag);
+        char name[WIRE_NAME_MAX];
+        wire_bulk_socket_name(name, sizeof(name), h.arena_pid, h.arena_tag);
         a = lg_scattered_map_remote(name, h.arena_chunks, h.arena_chunk_bytes);
         if (a == nullptr) return 0;
         peer.mapped_chunks = true;

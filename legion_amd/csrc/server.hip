@@ -12,6 +12,7 @@
 // device), and the batch is posted only after the LAST op has completed (the reference records
 // only stream 0's last event).  Full CSR / feature table go to HBM when they fit
 // (288 GB per MI355X), to mapped pinned host memory otherwise.
+#include "ipc_wire.h"
 #include "legion_core.h"
 
 #include <pthread.h>
@@ -587,7 +588,7 @@ public:
             // validation / test seeds with heavier neighbourhoods exceed it) is not a reason to stop serving: its rows are
             // gathered once more, ALL of them, into the pipe slot's overflow buffer -- num_ids rows, inside the arena -- and the view of
             // its rows points there.  The slot's previous batch has been released (the token this call consumed), so the buffer is free.
-            const int32_t batch_rows = lp->counter_mirror_host != nullptr ? lp->counter_mirror_host[INTRABATCH_CON * 3 + hop_num_] : 0;
+            const int32_t batch_rows = lp->counter_mirror_host != nullptr ? lp->counter_mirror_host[wire_rows_index(hop_num_)] : 0;
             bool overflowed = false;
             if (float_feature_len_ > 0 && batch_rows > lane_feature_rows_ && overflow_[p] != nullptr) {
                 UnifiedCache* cache = (UnifiedCache*)(params->cache);

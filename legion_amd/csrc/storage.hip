@@ -17,14 +17,11 @@
 
 #include <cstring>
 #include <cerrno>
-#include <cstddef>
 #include <string>
 #include <thread>
-#include <sys/socket.h>
 #include <sys/time.h>
-#include <sys/un.h>
 
-#include "../trainer/vmm_probe.h"      // vmm_import_fd(): imports a received descriptor whichever way THIS process's HIP runtime takes one
+#include "../trainer/vmm_map.h"        // vmm_map_chunks(): a range of this process built from another process's chunks (+ ipc_wire.h: the messages)
 
 // ---- device helpers: logical device ids beyond the physical count map round-robin onto the
 //      physical GPUs, so that clique striping (Kg > 1) can be exercised on a 1-GPU box ----------
@@ -200,10 +197,8 @@ extern "C" int32_t lg_scattered_serve(void* ptr, const char* name)
     const int ls = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
     if (ls < 0) return 0;
     sockaddr_un addr;
-    memset(&addr, 0, sizeof(addr));
-    addr.sun_family = AF_UNIX;
-    const int len = snprintf(addr.sun_path + 1, sizeof(addr.sun_path) - 1, "%s", name);
-    if (bind(ls, (sockaddr*)&addr, (socklen_t)(offsetof(sockaddr_un, sun_path) + 1 + len)) != 0 || listen(ls, 16) != 0) { close(ls); return 0; }
+    const socklen_t len = wire_abstract_address(&addr, name);
+    if (bind(ls, (sockaddr*)&addr, len) != 0 || listen(ls, 16) != 0) { close(ls); return 0; }
     {
         std::lock_guard<std::mutex> lk(g_scatter_mu);
         auto it = g_scatter_live.find(ptr);
@@ -244,23 +239,11 @@ extern "C" int32_t lg_scattered_serve(void* ptr, const char* name)
                 }
             }
             bool ok = true;
-            for (int32_t i0 = 0; i0 < n_chunks && ok; i0 += 64) {
-                const int32_t n = std::min(64, n_chunks - i0);
-                int fds[64];
+            for (int32_t i0 = 0; i0 < n_chunks && ok; i0 += WIRE_FD_BATCH) {
+                const int32_t n = std::min(WIRE_FD_BATCH, n_chunks - i0);
+                int fds[WIRE_FD_BATCH];
                 for (int32_t i = 0; i < n; i++) { fds[i] = lg_scattered_export_fd(ptr, i0 + i); ok = ok && fds[i] >= 0; }
-                if (ok) {
-                    char payload = 'f';
-                    iovec io = {&payload, 1};
-                    alignas(cmsghdr) char ctl[CMSG_SPACE(sizeof(int) * 64)];
-                    memset(ctl, 0, sizeof(ctl));
-                    msghdr msg;
-                    memset(&msg, 0, sizeof(msg));
-                    msg.msg_iov = &io; msg.msg_iovlen = 1; msg.msg_control = ctl; msg.msg_controllen = CMSG_SPACE(sizeof(int) * n);
-                    cmsghdr* cm = CMSG_FIRSTHDR(&msg);
-                    cm->cmsg_level = SOL_SOCKET; cm->cmsg_type = SCM_RIGHTS; cm->cmsg_len = CMSG_LEN(sizeof(int) * n);
-                    memcpy(CMSG_DATA(cm), fds, sizeof(int) * n);
-                    ok = sendmsg(c, &msg, MSG_NOSIGNAL) == 1;
-                }
+                if (ok) ok = wire_send_fd_batch(c, fds, n) == 0;
                 for (int32_t i = 0; i < n; i++) if (fds[i] >= 0) close(fds[i]);
             }
             close(c);
@@ -276,65 +259,12 @@ static std::map<void*, RemoteMap> g_remote_maps;
 extern "C" void* lg_scattered_map_remote(const char* name, int32_t n_chunks, int64_t chunk_bytes)
 {
     if (n_chunks <= 0 || chunk_bytes <= 0) return nullptr;
-    const int c = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
-    if (c < 0) return nullptr;
-    sockaddr_un addr;
-    memset(&addr, 0, sizeof(addr));
-    addr.sun_family = AF_UNIX;
-    const int len = snprintf(addr.sun_path + 1, sizeof(addr.sun_path) - 1, "%s", name);
-    if (connect(c, (sockaddr*)&addr, (socklen_t)(offsetof(sockaddr_un, sun_path) + 1 + len)) != 0) { close(c); printf("legion_hip: connect(%s) failed\n", name); return nullptr; }
-    {
-        ucred cr;
-        socklen_t cl = sizeof(cr);
-        if (getsockopt(c, SOL_SOCKET, SO_PEERCRED, &cr, &cl) != 0 || cr.uid != geteuid()) { close(c); printf("legion_hip: %s belongs to another user\n", name); return nullptr; }
-    }
     int dev = 0;
     HIP_CALL(hipGetDevice(&dev));
-    void* base = nullptr;
-    HIP_CALL(hipMemAddressReserve(&base, (size_t)n_chunks * (size_t)chunk_bytes, 0, nullptr, 0));
-    int got = 0;
-    bool ok = true;
-    while (got < n_chunks && ok) {
-        char payload = 0;
-        iovec io = {&payload, 1};
-        alignas(cmsghdr) char ctl[CMSG_SPACE(sizeof(int) * 64)];
-        msghdr msg;
-        memset(&msg, 0, sizeof(msg));
-        msg.msg_iov = &io; msg.msg_iovlen = 1; msg.msg_control = ctl; msg.msg_controllen = sizeof(ctl);
-        if (recvmsg(c, &msg, MSG_CMSG_CLOEXEC) != 1) { ok = false; break; }
-        cmsghdr* cm = CMSG_FIRSTHDR(&msg);
-        if (cm == nullptr || cm->cmsg_level != SOL_SOCKET || cm->cmsg_type != SCM_RIGHTS) { ok = false; break; }
-        const int n = (int)((cm->cmsg_len - CMSG_LEN(0)) / sizeof(int));
-        int fds[64];
-        memcpy(fds, CMSG_DATA(cm), sizeof(int) * (size_t)n);
-        for (int i = 0; i < n; i++) {
-            if (ok && got < n_chunks) {
-                hipMemGenericAllocationHandle_t h;
-                if (vmm_import_fd(&h, fds[i]) != hipSuccess) {
-                    (void)hipGetLastError();
-                    ok = false;
-                } else {
-                    if (hipMemMap((char*)base + (size_t)got * (size_t)chunk_bytes, (size_t)chunk_bytes, 0, h, 0) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-                    else got++;
-                    if (hipMemRelease(h) != hipSuccess) (void)hipGetLastError();
-                }
-            }
-            close(fds[i]);
-        }
-    }
-    close(c);
-    if (ok) {
-        hipMemAccessDesc acc = {};
-        acc.location.type = hipMemLocationTypeDevice;
-        acc.location.id = dev;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        if (hipMemSetAccess(base, (size_t)n_chunks * (size_t)chunk_bytes, &acc, 1) != hipSuccess) { (void)hipGetLastError(); ok = false; }
-    }
-    if (!ok) {
-        for (int i = 0; i < got; i++) (void)hipMemUnmap((char*)base + (size_t)i * (size_t)chunk_bytes, (size_t)chunk_bytes);
-        (void)hipMemAddressFree(base, (size_t)n_chunks * (size_t)chunk_bytes);
-        (void)hipGetLastError();
-        printf("legion_hip: mapping %d chunks of %s failed\n", n_chunks, name);
+    const char* why = "";
+    void* base = vmm_map_chunks(name, n_chunks, chunk_bytes, dev, &why);
+    if (base == nullptr) {
+        printf("legion_hip: mapping %d chunks of %s failed (%s)\n", n_chunks, name, why);
         return nullptr;
     }
     std::lock_guard<std::mutex> lk(g_scatter_mu);
@@ -351,9 +281,7 @@ extern "C" void lg_scattered_unmap_remote(void* base)
         m = it->second;
         g_remote_maps.erase(it);
     }
-    for (int32_t i = 0; i < m.n_chunks; i++)
-        if (hipMemUnmap((char*)base + (size_t)i * m.chunk_bytes, m.chunk_bytes) != hipSuccess) (void)hipGetLastError();
-    if (hipMemAddressFree(base, (size_t)m.n_chunks * m.chunk_bytes) != hipSuccess) (void)hipGetLastError();
+    vmm_unmap_chunks(base, m.n_chunks, m.n_chunks, (long long)m.chunk_bytes);
 }
 
 static bool d_free_scattered(void* ptr)

@@ -5,18 +5,16 @@
 // training_backend/ipc_cuda_kernel.cu:35-235 (GPUIPCEnv, cuda_get_next),
 // training_backend/helper_multiprocess.cpp (sharedMemoryCreate).  Same module name, same six
 // functions, same return shapes/dtypes, same shm slab / semaphore names / IPC-handle slot order
-// (0 ids, 1 features, 2 labels, 3 agg_src, 4 agg_dst, 5 node_counter, 6 edge_counter).
+// (all of them ../csrc/ipc_wire.h's, the one definition both ends include).
 // HIP runtime calls replace the CUDA ones (hipIpcOpenMemHandle, hipMemcpy); there is no device
 // code in this module.  LEGION_IPC_NAMESPACE (optional) must match the server's.
-#include <sys/socket.h>
-#include <sys/un.h>
-#include <cstddef>
 #include <fcntl.h>
 #include <semaphore.h>
 #include <sys/mman.h>
 #include <unistd.h>
 
 #include <algorithm>
+#include <array>
 #include <cerrno>
 #include <cstdint>
 #include <cstdio>
@@ -28,10 +26,7 @@
 #include <hip/hip_runtime_api.h>
 #include <torch/extension.h>
 
-#define INTRABATCH_CON 3
-#define INTERBATCH_CON 2
-#define MAX_DEVICE 8
-#define MEMORY_USAGE 7
+#include "vmm_map.h"       // vmm_map_chunks(): the server's lane arena from its chunks; ../csrc/ipc_wire.h: the wire format
 
 #define hipCheckError()                                                                       \
     {                                                                                         \
@@ -42,43 +37,22 @@
         }                                                                                     \
     }
 
-// The slab is the reference's (TB/ipc_cuda_kernel.cu:30-33), same size.  This build's server also publishes, in a shm
-// object of its own ("legionIPCext<suffix>"), the counters of the batch in every (device, pipe slot) in host memory,
-// written by the GPU before the batch is posted: when that object exists and its magic says so, get_next reads them
-// there instead of making the reference's two blocking 64-byte device-to-host copies per batch.
-#define LEGION_SHM_EXT_MAGIC 0x4C47494F
-typedef struct shmStruct_st {
-    int32_t steps[3];
-    hipIpcMemHandle_t memHandle[MAX_DEVICE][INTERBATCH_CON][MEMORY_USAGE];
-} shmStruct;
-// Version 2 of that object adds the direct-view hand-over (server: ipc_env.hip): the server's mini-batches are produced into
-// per-lane buffers that all live in one device allocation per GPU, the lane arena, whose IPC handle is published here.  This
-// module opens it, says so in trainer_direct[dev] before its first sem_post, and from then on get_next returns VIEWS of the
-// batch's lane (view[dev][pipe] = byte offsets into the arena) instead of views of the two pipe slots' buffers: the server
-// then does no per-batch GPU work at all.  Same semaphores, same two-slot order, same tensors as far as a training script
-// can tell.  LEGION_NO_DIRECT_VIEWS=1 keeps this module on the slot buffers.
-typedef struct shmExt_st {
-    int32_t ext_magic;
-    int32_t ext_version;
-    int32_t server_state;          // 1: the server stopped on an error
-    int32_t ext_reserved;
-    int32_t counters[MAX_DEVICE][INTERBATCH_CON][32];
-    hipIpcMemHandle_t arena[MAX_DEVICE];
-    int64_t arena_bytes[MAX_DEVICE];
-    int32_t trainer_direct[MAX_DEVICE];
-    int32_t view_on[MAX_DEVICE][INTERBATCH_CON];
-    int64_t view[MAX_DEVICE][INTERBATCH_CON][5];
-    // version 3 (ipc_env.hip): arena_kind 1 = the arena consists of arena_chunks physical chunks of arena_chunk_bytes, received as file
-    // descriptors from the abstract unix socket "legion_arena_<arena_sock_pid>_<dev>" and mapped back to back
-    int32_t arena_kind[MAX_DEVICE];
-    int32_t arena_chunks[MAX_DEVICE];
-    int64_t arena_chunk_bytes[MAX_DEVICE];
-    int32_t arena_sock_pid;
-    int32_t ext_reserved2;
-    // version 4: dtype of the feature rows (0 float32, 1 bfloat16), pipe slots and views alike
-    int32_t feature_out_dtype[MAX_DEVICE];
-} shmExt;
-static_assert(sizeof(hipIpcMemHandle_t) == 64, "IPC handle size is part of the wire format");
+static_assert(sizeof(hipIpcMemHandle_t) == sizeof(wireIpcHandle), "IPC handle size is part of the wire format");
+
+// Opens an IPC handle of the server's.  Observed on ROCm 7.2 (dmabuf IPC): while the exporting server process is busy allocating (its
+// runners start right after "ready") and another trainer attaches at the same moment, an open can fail transiently with 'invalid
+// device pointer'; the handle itself is fine.  Retries briefly before giving up; *retries = how many it took.
+static hipError_t open_ipc_handle(void** ptr, const volatile wireIpcHandle* wire, int* retries)
+{
+    const hipIpcMemHandle_t h = *(const hipIpcMemHandle_t*)wire;
+    hipError_t e = hipIpcOpenMemHandle(ptr, h, hipIpcMemLazyEnablePeerAccess);
+    for (*retries = 0; e != hipSuccess && *retries < 10; ++*retries) {
+        (void)hipGetLastError();
+        usleep(25000);
+        e = hipIpcOpenMemHandle(ptr, h, hipIpcMemLazyEnablePeerAccess);
+    }
+    return e;
+}
 
 // What this module reads from the environment, once, in initialize() (it is an extension of its own: LegionTuning lives in the
 // server's library).  Deployment: LEGION_IPC_NAMESPACE (suffix of every shm / semaphore name; must match the server's),
@@ -100,86 +74,6 @@ struct TrainerOptions {
     }
 };
 
-#include "vmm_probe.h"      // vmm_import_fd(): imports a received descriptor whichever way THIS process's HIP runtime takes one
-
-// The server's lane arena as chunks: connect, receive the descriptors (64 per message), import and map them in order.  An import
-// handle is released as soon as its chunk is mapped (the mapping keeps the memory alive, nothing else has to); on any failure
-// what was mapped is unmapped again and the range given back, and the caller falls back to the pipe slots.
-static void unmap_arena_chunks(void* base, int n_mapped, int n_chunks, long long chunk_bytes)
-{
-    if (base == nullptr) return;
-    for (int i = 0; i < n_mapped; i++)
-        if (hipMemUnmap((char*)base + (size_t)i * (size_t)chunk_bytes, (size_t)chunk_bytes) != hipSuccess) (void)hipGetLastError();
-    if (hipMemAddressFree(base, (size_t)n_chunks * (size_t)chunk_bytes) != hipSuccess) (void)hipGetLastError();
-}
-static void* map_arena_chunks(const std::string& suffix, int pid, int dev, int n_chunks, long long chunk_bytes, int hip_dev, std::string* why)
-{
-    const int c = socket(AF_UNIX, SOCK_STREAM | SOCK_CLOEXEC, 0);
-    if (c < 0) { *why = "socket()"; return nullptr; }
-    sockaddr_un addr;
-    memset(&addr, 0, sizeof(addr));
-    addr.sun_family = AF_UNIX;
-    const int len = snprintf(addr.sun_path + 1, sizeof(addr.sun_path) - 1, "legion_arena_%d_%d", pid, dev);
-    if (connect(c, (sockaddr*)&addr, (socklen_t)(offsetof(sockaddr_un, sun_path) + 1 + len)) != 0) { close(c); *why = "connect()"; return nullptr; }
-    {   // whoever answers under that name hands out descriptors this process will map: it must be the same user's process
-        ucred cr;
-        socklen_t cl = sizeof(cr);
-        if (getsockopt(c, SOL_SOCKET, SO_PEERCRED, &cr, &cl) != 0 || cr.uid != geteuid()) { close(c); *why = "the arena socket belongs to another user"; return nullptr; }
-    }
-    (void)suffix;
-    void* base = nullptr;
-    if (hipMemAddressReserve(&base, (size_t)n_chunks * (size_t)chunk_bytes, 0, nullptr, 0) != hipSuccess) { (void)hipGetLastError(); close(c); *why = "hipMemAddressReserve"; return nullptr; }
-    int got = 0;
-    bool ok = true;
-    while (got < n_chunks && ok) {
-        char payload = 0;
-        iovec io = {&payload, 1};
-        alignas(cmsghdr) char ctl[CMSG_SPACE(sizeof(int) * 64)];
-        msghdr msg;
-        memset(&msg, 0, sizeof(msg));
-        msg.msg_iov = &io; msg.msg_iovlen = 1; msg.msg_control = ctl; msg.msg_controllen = sizeof(ctl);
-        if (recvmsg(c, &msg, MSG_CMSG_CLOEXEC) != 1) { *why = "recvmsg()"; ok = false; break; }
-        cmsghdr* cm = CMSG_FIRSTHDR(&msg);
-        if (cm == nullptr || cm->cmsg_level != SOL_SOCKET || cm->cmsg_type != SCM_RIGHTS) { *why = "no descriptors in the message"; ok = false; break; }
-        const int n = (int)((cm->cmsg_len - CMSG_LEN(0)) / sizeof(int));
-        int fds[64];
-        memcpy(fds, CMSG_DATA(cm), sizeof(int) * (size_t)n);
-        for (int i = 0; i < n; i++) {
-            if (ok && got < n_chunks) {
-                hipMemGenericAllocationHandle_t h;
-                if (vmm_import_fd(&h, fds[i]) != hipSuccess) {
-                    (void)hipGetLastError();
-                    *why = "hipMemImportFromShareableHandle";
-                    ok = false;
-                } else {
-                    if (hipMemMap((char*)base + (size_t)got * (size_t)chunk_bytes, (size_t)chunk_bytes, 0, h, 0) != hipSuccess) {
-                        (void)hipGetLastError();
-                        *why = "hipMemMap";
-                        ok = false;
-                    } else {
-                        got++;
-                    }
-                    if (hipMemRelease(h) != hipSuccess) (void)hipGetLastError();      // (mapped or not: the handle is not needed again)
-                }
-            }
-            close(fds[i]);
-        }
-    }
-    close(c);
-    if (ok) {
-        hipMemAccessDesc acc = {};
-        acc.location.type = hipMemLocationTypeDevice;
-        acc.location.id = hip_dev;
-        acc.flags = hipMemAccessFlagsProtReadWrite;
-        if (hipMemSetAccess(base, (size_t)n_chunks * (size_t)chunk_bytes, &acc, 1) != hipSuccess) { (void)hipGetLastError(); *why = "hipMemSetAccess"; ok = false; }
-    }
-    if (!ok) {
-        unmap_arena_chunks(base, got, n_chunks, chunk_bytes);
-        return nullptr;
-    }
-    return base;
-}
-
 class GPUIPCEnv {
 public:
     int Initialize()
@@ -192,8 +86,9 @@ public:
         // LEGION_IPC_DEVICE (testing): attach to the buffers / semaphores of this LOGICAL server GPU while staying on the
         // current physical device (a server with more logical GPUs than the box has, see storage.hip SetGPUDevice)
         if (opt_.ipc_device >= 0) central_device = opt_.ipc_device;
-        const std::string shm_name = std::string("simpleIPCshm") + opt_.suffix;
-        int fd = shm_open(shm_name.c_str(), O_RDWR | O_CREAT, 0777);
+        char name[WIRE_NAME_MAX];
+        wire_slab_name(name, sizeof(name), opt_.suffix.c_str());
+        int fd = shm_open(name, O_RDWR | O_CREAT, 0777);
         if (fd < 0 || ftruncate(fd, sizeof(shmStruct)) != 0) {     // the reference's call; the slab has exactly this size
             printf("Failed to create shared memory slab\n");
             exit(EXIT_FAILURE);
@@ -207,32 +102,23 @@ public:
         train_step_ = shm->steps[0];
         valid_step_ = shm->steps[1];
         test_step_ = shm->steps[2];
-        std::vector<void*>* slots[MEMORY_USAGE] = {&ids_, &float_features_, &labels_, &agg_src_, &agg_dst_,
-                                                   &node_counter_, &edge_counter_};
+        const auto slots = Slots();
         for (auto* s : slots) s->assign(INTERBATCH_CON, nullptr);
         for (int i = 0; i < INTERBATCH_CON; i++) {
             for (int k = 0; k < MEMORY_USAGE; k++) {
-                hipIpcMemHandle_t h = *(hipIpcMemHandle_t*)&shm->memHandle[central_device][i][k];
-                hipError_t e = hipIpcOpenMemHandle(&(*slots[k])[i], h, hipIpcMemLazyEnablePeerAccess);
-                // Observed on ROCm 7.2 (dmabuf IPC): while the exporting server process is busy allocating (its runners
-                // start right after "ready") and another trainer attaches at the same moment, an open can fail transiently
-                // with 'invalid device pointer'; the handle itself is fine.  Retry briefly before giving up.
-                for (int attempt = 0; e != hipSuccess && attempt < 10; attempt++) {
-                    (void)hipGetLastError();
-                    usleep(25000);
-                    e = hipIpcOpenMemHandle(&(*slots[k])[i], h, hipIpcMemLazyEnablePeerAccess);
-                    if (e == hipSuccess) printf("ipc_service: IPC handle (slot %d pipe %d) opened after %d retries\n", k, i, attempt + 1);
-                }
+                int retries = 0;
+                const hipError_t e = open_ipc_handle(&(*slots[k])[i], &shm->memHandle[central_device][i][k], &retries);
                 if (e != hipSuccess) {
                     printf("HIP failure %s:%d: '%s' (slot %d pipe %d)\n", __FILE__, __LINE__, hipGetErrorString(e), k, i);
                     exit(EXIT_FAILURE);
                 }
+                if (retries > 0) printf("ipc_service: IPC handle (slot %d pipe %d) opened after %d retries\n", k, i, retries);
             }
         }
         std::cout << "HIP: " << central_device << " IPC shared memory opened\n";
         if (opt_.shm_mirror) {                                  // this build's server: counters in host memory (never created here)
-            const std::string ext_name = std::string("legionIPCext") + opt_.suffix;
-            const int efd = shm_open(ext_name.c_str(), O_RDWR, 0);
+            wire_mirror_name(name, sizeof(name), opt_.suffix.c_str());
+            const int efd = shm_open(name, O_RDWR, 0);
             if (efd >= 0) {
                 void* ea = mmap(0, sizeof(shmExt), PROT_READ | PROT_WRITE, MAP_SHARED, efd, 0);
                 if (ea != MAP_FAILED && ((volatile shmExt*)ea)->ext_magic == LEGION_SHM_EXT_MAGIC) mirror_ = (volatile shmExt*)ea;
@@ -242,13 +128,13 @@ public:
         }
         // direct views: open the server's lane arena and say so BEFORE the first sem_post below (the server reads the flag
         // when its first wait returns)
-        if (mirror_ != nullptr && mirror_->ext_version >= 3 && mirror_->arena_bytes[central_device] > 0 && mirror_->arena_kind[central_device] == 1 &&
+        if (mirror_ != nullptr && mirror_->ext_version >= LEGION_SHM_EXT_HAS_CHUNKED_ARENA && mirror_->arena_bytes[central_device] > 0 && mirror_->arena_kind[central_device] == 1 &&
             opt_.direct_views) {
             int hip_dev = 0;
             (void)hipGetDevice(&hip_dev);
-            std::string why;
-            arena_ = map_arena_chunks(opt_.suffix, mirror_->arena_sock_pid, central_device, mirror_->arena_chunks[central_device],
-                                      mirror_->arena_chunk_bytes[central_device], hip_dev, &why);
+            const char* why = "";
+            wire_arena_socket_name(name, sizeof(name), mirror_->arena_sock_pid, central_device);
+            arena_ = vmm_map_chunks(name, mirror_->arena_chunks[central_device], mirror_->arena_chunk_bytes[central_device], hip_dev, &why);
             if (arena_ != nullptr) {
                 arena_bytes_ = mirror_->arena_bytes[central_device];
                 arena_chunks_ = mirror_->arena_chunks[central_device];
@@ -258,16 +144,11 @@ public:
                 std::cout << "HIP: " << central_device << " lane arena mapped (" << (arena_bytes_ >> 20) << " MiB in " << mirror_->arena_chunks[central_device]
                           << " chunks): batches arrive as views" << std::endl;
             } else {
-                printf("ipc_service: could not map the server's lane arena (%s); batches arrive in the pipe slots\n", why.c_str());
+                printf("ipc_service: could not map the server's lane arena (%s); batches arrive in the pipe slots\n", why);
             }
-        } else if (mirror_ != nullptr && mirror_->ext_version >= 2 && mirror_->arena_bytes[central_device] > 0 && opt_.direct_views) {
-            hipIpcMemHandle_t h = *(hipIpcMemHandle_t*)&mirror_->arena[central_device];
-            hipError_t e = hipIpcOpenMemHandle(&arena_, h, hipIpcMemLazyEnablePeerAccess);
-            for (int attempt = 0; e != hipSuccess && attempt < 10; attempt++) {
-                (void)hipGetLastError();
-                usleep(25000);
-                e = hipIpcOpenMemHandle(&arena_, h, hipIpcMemLazyEnablePeerAccess);
-            }
+        } else if (mirror_ != nullptr && mirror_->ext_version >= LEGION_SHM_EXT_HAS_VIEWS && mirror_->arena_bytes[central_device] > 0 && opt_.direct_views) {
+            int retries = 0;
+            const hipError_t e = open_ipc_handle(&arena_, &mirror_->arena[central_device], &retries);
             if (e == hipSuccess) {
                 arena_bytes_ = mirror_->arena_bytes[central_device];
                 mirror_->trainer_direct[central_device] = 1;
@@ -281,16 +162,15 @@ public:
         }
         semr_.resize(INTERBATCH_CON);
         semw_.resize(INTERBATCH_CON);
-        const std::string sfx = opt_.suffix;
         for (int i = 0; i < INTERBATCH_CON; i++) {
-            const std::string ssri = "sem_r_" + std::to_string(central_device) + "_" + std::to_string(i) + sfx;
-            const std::string sswi = "sem_w_" + std::to_string(central_device) + "_" + std::to_string(i) + sfx;
-            semr_[i] = sem_open(ssri.c_str(), O_CREAT | O_RDWR, 0666, 0);
+            wire_sem_r_name(name, sizeof(name), central_device, i, opt_.suffix.c_str());
+            semr_[i] = sem_open(name, O_CREAT | O_RDWR, 0666, 0);
             if (semr_[i] == SEM_FAILED) {
                 printf("errno = %d\n", errno);
                 return -1;
             }
-            semw_[i] = sem_open(sswi.c_str(), O_CREAT | O_RDWR, 0666, 0);
+            wire_sem_w_name(name, sizeof(name), central_device, i, opt_.suffix.c_str());
+            semw_[i] = sem_open(name, O_CREAT | O_RDWR, 0666, 0);
             if (semw_[i] == SEM_FAILED) {
                 printf("errno = %d\n", errno);
                 return -1;
@@ -322,7 +202,7 @@ public:
     }
     void* Arena() const { return arena_; }
     // feature rows of the server's batches are bfloat16 (shmExt version 4), else float32
-    bool Bf16Rows() const { return mirror_ != nullptr && mirror_->ext_version >= 4 && mirror_->feature_out_dtype[slab_device_] == 1; }
+    bool Bf16Rows() const { return mirror_ != nullptr && mirror_->ext_version >= LEGION_SHM_EXT_HAS_FEATURE_DTYPE && mirror_->feature_out_dtype[slab_device_] == 1; }
     long long ArenaBytes() const { return arena_bytes_; }
     void Post()
     {
@@ -350,8 +230,7 @@ public:
     // ends": a trainer that outlived its server kept the server's whole arena alive in HBM.)
     void Finalize()
     {
-        std::vector<void*>* slots[MEMORY_USAGE] = {&ids_, &float_features_, &labels_, &agg_src_, &agg_dst_,
-                                                   &node_counter_, &edge_counter_};
+        const auto slots = Slots();
         (void)hipDeviceSynchronize();                      // nothing of this process still reads a view or a slot buffer
         for (int i = 0; i < (int)semw_.size(); i++) {
             for (auto* s : slots)
@@ -363,7 +242,7 @@ public:
         semw_.clear();
         semr_.clear();
         if (arena_ != nullptr) {
-            if (arena_chunks_ > 0) unmap_arena_chunks(arena_, arena_chunks_, arena_chunks_, arena_chunk_bytes_);
+            if (arena_chunks_ > 0) vmm_unmap_chunks(arena_, arena_chunks_, arena_chunks_, arena_chunk_bytes_);
             else if (hipIpcCloseMemHandle(arena_) != hipSuccess) (void)hipGetLastError();
         }
         arena_ = nullptr;
@@ -376,6 +255,16 @@ public:
     }
 
 private:
+    // the seven buffers of a pipe slot in the order of the slab's handles
+    std::array<std::vector<void*>*, MEMORY_USAGE> Slots()
+    {
+        std::array<std::vector<void*>*, MEMORY_USAGE> s{};
+        s[WIRE_SLOT_IDS] = &ids_; s[WIRE_SLOT_FEATURES] = &float_features_; s[WIRE_SLOT_LABELS] = &labels_;
+        s[WIRE_SLOT_AGG_SRC] = &agg_src_; s[WIRE_SLOT_AGG_DST] = &agg_dst_;
+        s[WIRE_SLOT_NODE_COUNTER] = &node_counter_; s[WIRE_SLOT_EDGE_COUNTER] = &edge_counter_;
+        return s;
+    }
+
     std::vector<void*> ids_, float_features_, labels_, agg_src_, agg_dst_, node_counter_, edge_counter_;
     std::vector<sem_t*> semw_, semr_;
     int32_t train_step_ = 0, valid_step_ = 0, test_step_ = 0;

@@ -69,10 +69,10 @@ def test_memory_plans_under_asan_ubsan(san, name):
 
 # ---- the wire protocol's server end, played in Python for tools/boundary_consumer.c ------------------------------------------------
 MAX_DEVICE, INTERBATCH_CON, MEMORY_USAGE = 8, 2, 7
-SHM_BYTES = 12 + MAX_DEVICE * INTERBATCH_CON * MEMORY_USAGE * 64                       # simpleIPCshm (SS/engine/ipc_service.cu:28-31)
+# (the sizes and the offset that tests/cpu/ipc_wire_test.cpp pins for legion_amd/csrc/ipc_wire.h; tests/test_ipc_wire_cpu.py holds them equal)
+SHM_BYTES = 7180                                                                       # simpleIPCshm (SS/engine/ipc_service.cu:28-31)
 EXT_COUNTERS = 16                                                                      # legionIPCext: 4 ints, then counters[8][2][32]
-EXT_BYTES = 16 + MAX_DEVICE * INTERBATCH_CON * 32 * 4 + MAX_DEVICE * 64 + MAX_DEVICE * 8 + MAX_DEVICE * 4 + \
-    MAX_DEVICE * INTERBATCH_CON * 4 + MAX_DEVICE * INTERBATCH_CON * 5 * 8
+EXT_BYTES = 3544                                                                       # ... the whole object, as the consumer maps it
 
 
 class Sem:

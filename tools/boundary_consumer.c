@@ -1,5 +1,5 @@
 /* boundary_consumer.c -- the trainer end of the wire protocol with nothing else in it: waits for a batch
- * (sem_w_<dev>_<pipe>), reads its counters from the server's host-visible mirror, releases the slot (sem_r_...).
+ * (the "ready" semaphore of its pipe slot), reads its counters from the server's host-visible mirror, releases the slot (the "free" one).
  * Used by tools/server_throughput.py --consumer native to measure what the SERVER can hand over per second when
  * the consumer costs nothing (the Python consumer adds ~15 us of tensor wrapping per batch).
  *   gcc -O2 boundary_consumer.c -o boundary_consumer -lrt -lpthread
@@ -7,36 +7,13 @@
  * `views` = 1: announce a trainer end that takes batches as views of the server's lane arena (this consumer touches no
  * device memory, so it never opens the arena: it measures the hand-over protocol of that mode).
  * Protocol: SS/engine/ipc_service.cu:28-31,181-192,283-291; TB/ipc_cuda_kernel.cu:75-106. */
+#include "../legion_amd/csrc/ipc_wire.h"        /* the layouts, names and counter indices; first: it asks for _GNU_SOURCE */
+
 #include <fcntl.h>
 #include <semaphore.h>
-#include <stdint.h>
-#include <stdio.h>
 #include <stdlib.h>
-#include <string.h>
 #include <sys/mman.h>
 #include <time.h>
-#include <unistd.h>
-
-#define MAX_DEVICE 8
-#define INTERBATCH_CON 2
-#define MEMORY_USAGE 7
-#define MAGIC 0x4C47494F
-typedef struct {
-    int32_t steps[3];
-    char memHandle[MAX_DEVICE][INTERBATCH_CON][MEMORY_USAGE][64];
-} shmStruct;
-typedef struct {            /* "legionIPCext<suffix>": the server's host-visible counter mirror + direct-view hand-over (ipc_env.hip) */
-    int32_t ext_magic;
-    int32_t ext_version;
-    int32_t server_state;
-    int32_t ext_reserved;
-    int32_t counters[MAX_DEVICE][INTERBATCH_CON][32];
-    char arena[MAX_DEVICE][64];
-    int64_t arena_bytes[MAX_DEVICE];
-    int32_t trainer_direct[MAX_DEVICE];
-    int32_t view_on[MAX_DEVICE][INTERBATCH_CON];
-    int64_t view[MAX_DEVICE][INTERBATCH_CON][5];
-} shmExt;
 
 static double now(void) { struct timespec t; clock_gettime(CLOCK_MONOTONIC, &t); return t.tv_sec + 1e-9 * t.tv_nsec; }
 
@@ -46,24 +23,24 @@ int main(int argc, char** argv)
     const char* sfx = argv[1];
     const int dev = atoi(argv[2]), hops = atoi(argv[3]), skip = atoi(argv[4]), epochs = argc >= 6 ? atoi(argv[5]) : 1;
     const int views = argc >= 7 ? atoi(argv[6]) : 0;
-    char name[128];
-    snprintf(name, sizeof name, "simpleIPCshm%s", sfx);
+    char name[WIRE_NAME_MAX];
+    wire_slab_name(name, sizeof name, sfx);
     int fd = shm_open(name, O_RDWR, 0777);
     if (fd < 0) { perror("shm_open"); return 1; }
     volatile shmStruct* shm = (volatile shmStruct*)mmap(0, sizeof(shmStruct), PROT_READ | PROT_WRITE, MAP_SHARED, fd, 0);
     if (shm == MAP_FAILED) { perror("mmap"); return 1; }
-    snprintf(name, sizeof name, "legionIPCext%s", sfx);
+    wire_mirror_name(name, sizeof name, sfx);
     int efd = shm_open(name, O_RDWR, 0);
     if (efd < 0) { fprintf(stderr, "server does not publish the counter mirror\n"); return 1; }
     volatile shmExt* ext = (volatile shmExt*)mmap(0, sizeof(shmExt), PROT_READ | PROT_WRITE, MAP_SHARED, efd, 0);
-    if (ext == MAP_FAILED || ext->ext_magic != MAGIC) { fprintf(stderr, "server does not publish the counter mirror\n"); return 1; }
+    if (ext == MAP_FAILED || ext->ext_magic != LEGION_SHM_EXT_MAGIC) { fprintf(stderr, "server does not publish the counter mirror\n"); return 1; }
     int took_views = 0;
-    if (views && ext->ext_version >= 2 && ext->arena_bytes[dev] > 0) { ext->trainer_direct[dev] = 1; __sync_synchronize(); took_views = 1; }
+    if (views && ext->ext_version >= LEGION_SHM_EXT_HAS_VIEWS && ext->arena_bytes[dev] > 0) { ext->trainer_direct[dev] = 1; __sync_synchronize(); took_views = 1; }
     sem_t *sr[2], *sw[2];
     for (int i = 0; i < 2; i++) {
-        snprintf(name, sizeof name, "sem_r_%d_%d%s", dev, i, sfx);
+        wire_sem_r_name(name, sizeof name, dev, i, sfx);
         sr[i] = sem_open(name, O_CREAT | O_RDWR, 0666, 0);
-        snprintf(name, sizeof name, "sem_w_%d_%d%s", dev, i, sfx);
+        wire_sem_w_name(name, sizeof name, dev, i, sfx);
         sw[i] = sem_open(name, O_CREAT | O_RDWR, 0666, 0);
         if (sr[i] == SEM_FAILED || sw[i] == SEM_FAILED) { perror("sem_open"); return 1; }
         sem_post(sr[i]);                                   /* both pipe slots start free */
@@ -78,8 +55,8 @@ int main(int argc, char** argv)
         sem_wait(sw[pipe]);
         if (i == skip) { t0 = now(); edges = nodes = 0; timed = 0; }
         if (i < train) {
-            edges += ext->counters[dev][pipe][16 + 9 + hops];
-            nodes += ext->counters[dev][pipe][9 + hops];
+            edges += ext->counters[dev][pipe][wire_edges_index(hops)];
+            nodes += ext->counters[dev][pipe][wire_rows_index(hops)];
             timed++;
         }
         sem_post(sr[pipe]);
