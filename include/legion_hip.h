@@ -719,6 +719,76 @@ int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage* graph, co
                            const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t fanout, int64_t salt,
                            const void* scratch /* as legion_labor_count left it */, int64_t scratch_bytes, int64_t cap,
                            int32_t* dst_out /* int32[cap] */, int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */);
+/* Induced subgraphs (DGL's g.subgraph / dgl.node_subgraph: the op behind ClusterGCN's partitions, GraphSAINT's walk-visited vertices and
+ * ShaDow-GNN's k-hop neighbourhoods), new in this build; no reference counterpart.  Three pieces: a vertex set as an object of its own,
+ * the in-edges of a list of rows whose SOURCE is a member of the set, written with the member's position in the set, and the row
+ * pointers of that result.  Orientation, N, rows, the buffers, the stream, capture and the FULL CSR are as for legion_in_edges: a CSR row
+ * is the dst side and a column entry the src side.  All buffers are device memory; nothing synchronises with the host.
+ *
+ * The vertex set.  nodes is int32[k], 0 <= k <= LEGION_NODE_SET_MAX_IDS.  pos(v) = min{ j : nodes[j] == v } for v >= 0; pos(v) = -1 for
+ * v < 0 and for a v that does not occur.  Negative entries of nodes are members of nothing.  Ids at or above N are legal: no graph is
+ * involved in building the set, and such ids simply never match a column entry.  The set lives in caller-held device memory, 4-byte
+ * aligned (at a 16-byte boundary the probes load four keys at once; the results are the same), of at least legion_node_set_bytes(k) bytes: int32 keys[S] then uint32 first[S], 8 S bytes, S the smallest power of two that is
+ * at least 256 and at least 2 k (legion_unique_ids' sizing); -1 for k outside [0, LEGION_NODE_SET_MAX_IDS].  It is an open-addressing
+ * table: the home slot of v is ((uint32)v * 2654435769u) >> (32 - log2 S), probing is linear and wraps, at most S probes, an empty key is
+ * all-ones.
+ * legion_node_set_build clears the table on `stream` itself, inserts every non-negative entry (atomicCAS on the key, then atomicMin of the
+ * entry's index on first) and writes the number of distinct non-negative values to distinct_out[0] (int32[1]).  Which slot a key lands in
+ * depends on the order in which the device takes the entries; pos and the count do not, and nothing else of the table is specified.
+ * k == 0 clears, writes 0 and nothing else.  Two sets in flight on different streams need memory of their own.
+ * legion_node_set_lookup: local_out[i] = pos(ids[i]) for i in [0, m), ids and local_out int32[m].  v >= 0 is tested before any probe: a
+ * dead column entry is -1, the bit pattern of the empty key, and never matches it.  A probe stops at the key, at an empty key, or after
+ * S probes; the value read from first is accepted only if it lies in [0, k).  Memory safety does not rest on what the set holds: with a
+ * set that _build did not write the values are unspecified but lie in {-1} u [0, k), and nothing outside keys[0 .. S) and first[0 .. S)
+ * is read.  k and set_bytes are those of the build.
+ * _build returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null nodes_devptr, set or distinct_out; k outside
+ * [0, LEGION_NODE_SET_MAX_IDS]; set_bytes below legion_node_set_bytes(k).  _lookup likewise for: a null set, ids_devptr or local_out; k
+ * and set_bytes as above; m outside [0, 2^31 - 1].  m == 0 returns 0 and enqueues nothing.
+ *
+ * The edges.  legion_induced_count / legion_induced_edges take what legion_labor_count / legion_labor_edges take, with set, set_bytes
+ * and k in place of fanout and salt.  For slot p in [0, m), rules 1, 2 and 4 of the LABOR contract stand unchanged (the resolution of p
+ * to i, j, r, e and src = col[e]; memory safety independent of offsets; kept slots written in slot order, so dst is non-decreasing), and
+ *   3. the slot is kept iff it resolved to an entry (e >= 0), src >= 0 and pos(src) lies in [0, k);
+ * a kept slot writes (dst = i, src_local = pos(src), eid = e).  rows and the set are independent arguments: the row side need not equal
+ * the set (edges from a set into a frontier: ShaDow's and a bipartite block's case).  Parallel entries and self-loops are kept like any
+ * other entry; dead entries never are.  _count leaves in scratch the exclusive prefix sums of the kept counts per tile of 1 024 slots
+ * and their total K, and writes K to count_out[0] (int64[1]); _edges, given the same rows, n, offsets, m and set and the scratch as
+ * _count left it, writes the kept triples to [0, min(K, cap)) and -1 / -1 / -1 to [K, cap).  cap is a capacity as in
+ * legion_labor_edges: a triple whose position falls outside [0, cap) is dropped whatever the scratch holds, and the fill is clamped to
+ * [0, cap].  scratch: device memory, 8-byte aligned, of at least legion_induced_scratch_bytes(m) bytes, LABOR's formula: one int64 per
+ * tile plus one, plus one per 256 tiles; -1 for m outside [0, LEGION_INDUCED_MAX_SLOTS].
+ * Both return 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: a null graph, rows_devptr, offsets_devptr, set,
+ * scratch, count_out, dst_out or src_local_out (eid_out may be null); n outside [0, LEGION_IN_EDGES_MAX_ROWS]; m outside
+ * [0, LEGION_INDUCED_MAX_SLOTS]; k outside [0, LEGION_NODE_SET_MAX_IDS]; set_bytes below legion_node_set_bytes(k); cap outside
+ * [0, 2^31 - 1]; scratch_bytes below legion_induced_scratch_bytes(m).  m == 0: _count writes count_out[0] = 0 and a zero total only.
+ * cap == 0 returns 0 and enqueues nothing.
+ *
+ * The row pointers.  legion_dst_offsets: L = count[0] clamped to [0, cap], read on the device (count: int64[1], device memory);
+ * indptr_out[i] = #{ p in [0, L) : dst[p] < i } for i in [0, n], int64[n + 1].  It is a lower-bound search over dst[0 .. L) and nothing
+ * else: exact for a non-decreasing dst, which _edges guarantees, and some value in [0, L] otherwise.  No host read: count, edges and
+ * offsets can be captured in one graph.  Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null dst_devptr, count_devptr
+ * or indptr_out; cap outside [0, 2^31 - 1]; n outside [0, LEGION_IN_EDGES_MAX_ROWS].
+ * Not offered: edge_subgraph; out-edges (there is no reverse CSR); khop_in_subgraph as one call; heterogeneous graphs; more than 2^20
+ * set members or rows a call (a caller batches); keeping the original ids (nodes[src_local], one gather); the server, the launcher and
+ * the wire. */
+#define LEGION_NODE_SET_MAX_IDS 1048576
+#define LEGION_INDUCED_MAX_SLOTS 1073741824
+int64_t legion_node_set_bytes(int32_t k);
+int32_t legion_node_set_build(legion_stream_t stream, const int32_t* nodes_devptr /* int32[k] */, int32_t k, void* set, int64_t set_bytes,
+                              int32_t* distinct_out /* int32[1] */);
+int32_t legion_node_set_lookup(legion_stream_t stream, const void* set /* as legion_node_set_build left it */, int64_t set_bytes, int32_t k,
+                               const int32_t* ids_devptr /* int32[m] */, int64_t m, int32_t* local_out /* int32[m] */);
+int64_t legion_induced_scratch_bytes(int64_t m);
+int32_t legion_induced_count(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                             const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                             int64_t* count_out /* int64[1] */, void* scratch, int64_t scratch_bytes);
+int32_t legion_induced_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                             const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                             const void* scratch /* as legion_induced_count left it */, int64_t scratch_bytes, int64_t cap,
+                             int32_t* dst_out /* int32[cap] */, int32_t* src_local_out /* int32[cap] */,
+                             int64_t* eid_out /* int64[cap], or NULL */);
+int32_t legion_dst_offsets(legion_stream_t stream, const int32_t* dst_devptr /* int32[cap] */, int64_t cap,
+                           const int64_t* count_devptr /* int64[1] */, int32_t n, int64_t* indptr_out /* int64[n + 1] */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

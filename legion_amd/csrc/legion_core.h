@@ -1007,6 +1007,35 @@ struct LaborParams {
 void launch_labor_count(hipStream_t s, const LaborParams& p);
 void launch_labor_edges(hipStream_t s, const LaborParams& p);
 
+// a vertex set and induced subgraphs (kernels_induced.hip; the rules: legion_node_set_build .. legion_dst_offsets in legion_hip.h, their
+// text induced_rule.h).  The arguments are the caller's to check (induced_rule.h).
+struct NodeSetView {
+    const int32_t* keys;            // int32[S]: an empty key is all-ones
+    const uint32_t* first;          // uint32[S]: the first position of the slot's key in the nodes
+    uint32_t mask;                  // S - 1
+    int32_t shift;                  // 32 - log2 S
+    int32_t k;                      // the nodes the set was built from: a position is accepted inside [0, k)
+    int32_t wide;                   // keys starts at a 16-byte boundary: a probe step loads four keys at once (node_set.h)
+};
+// set: node_set_bytes(k) bytes, cleared here on s; distinct: int32[1]
+void launch_node_set_build(hipStream_t s, const int32_t* nodes, int32_t k, void* set, int32_t* distinct);
+void launch_node_set_lookup(hipStream_t s, const NodeSetView& set, const int32_t* ids, int64_t m, int32_t* local);
+struct InducedParams {
+    RowSlots slots;                 // m <= 2^30
+    NodeSetView set;
+    int64_t* tiles;                 // the scratch, as LaborParams::tiles
+    int64_t* count;                 // int64[1] (launch_induced_count)
+    int32_t* dst;                   // int32[cap] (launch_induced_edges, as src and eid)
+    int32_t* src;                   // int32[cap]: positions in the set
+    int64_t* eid;                   // int64[cap], or null
+    int64_t n_tiles, n_groups;      // induced_tiles(m), induced_groups(m)
+    int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
+};
+void launch_induced_count(hipStream_t s, const InducedParams& p);
+void launch_induced_edges(hipStream_t s, const InducedParams& p);
+// indptr[i] = #{ p in [0, L) : dst[p] < i } for i in [0, n], L = count[0] clamped to [0, cap]
+void launch_dst_offsets(hipStream_t s, const int32_t* dst, int64_t cap, const int64_t* count, int32_t n, int64_t* indptr);
+
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {
     WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the

@@ -20,6 +20,7 @@
 #include "link_rule.h"
 #include "in_edges_rule.h"
 #include "labor_rule.h"
+#include "induced_rule.h"
 
 #include <iostream>
 
@@ -590,6 +591,99 @@ extern "C" int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage
     p.src = src_out;
     p.eid = eid_out;
     lg::launch_labor_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// A vertex set and the subgraph it induces (the rules: legion_hip.h; the table's size, the refusals and the scratch size:
+// induced_rule.h).  As above: every check comes before the launch.
+extern "C" int64_t legion_node_set_bytes(int32_t k)
+{
+    return node_set_bytes(k);
+}
+
+// the table in the caller's memory (k, set_bytes legal)
+static lg::NodeSetView node_set_view(const void* set, int32_t k)
+{
+    const int64_t slots = node_set_slots(k);
+    const int32_t* keys = static_cast<const int32_t*>(set);
+    return lg::NodeSetView{.keys = keys, .first = reinterpret_cast<const uint32_t*>(keys + slots), .mask = (uint32_t)(slots - 1),
+                           .shift = node_set_shift(slots), .k = k,
+                           .wide = ((uintptr_t)set & 15u) == 0 ? 1 : 0};
+}
+
+extern "C" int32_t legion_node_set_build(legion_stream_t stream, const int32_t* nodes_devptr, int32_t k, void* set, int64_t set_bytes,
+                                         int32_t* distinct_out)
+{
+    if (!nodes_devptr || !set || !distinct_out) return -1;
+    if (node_set_build_refusal(k, set_bytes) != InducedRefusal::Ok) return -1;
+    lg::launch_node_set_build(static_cast<hipStream_t>(stream), nodes_devptr, k, set, distinct_out);
+    return 0;
+}
+
+extern "C" int32_t legion_node_set_lookup(legion_stream_t stream, const void* set, int64_t set_bytes, int32_t k, const int32_t* ids_devptr,
+                                          int64_t m, int32_t* local_out)
+{
+    if (!set || !ids_devptr || !local_out) return -1;
+    if (node_set_lookup_refusal(k, set_bytes, m) != InducedRefusal::Ok) return -1;
+    if (m == 0) return 0;
+    lg::launch_node_set_lookup(static_cast<hipStream_t>(stream), node_set_view(set, k), ids_devptr, m, local_out);
+    return 0;
+}
+
+extern "C" int64_t legion_induced_scratch_bytes(int64_t m)
+{
+    return induced_scratch_bytes(m);
+}
+
+static lg::InducedParams induced_params(GraphStorage* graph, const int32_t* rows, int32_t n, const int64_t* offsets, int64_t m, const void* set,
+                                        int32_t k, void* scratch)
+{
+    lg::InducedParams p{};
+    p.slots = row_slots(graph, rows, n, offsets, m);
+    p.set = node_set_view(set, k);
+    p.tiles = static_cast<int64_t*>(scratch);
+    p.n_tiles = induced_tiles(m);
+    p.n_groups = induced_groups(m);
+    return p;
+}
+
+extern "C" int32_t legion_induced_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                        const int64_t* offsets_devptr, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                                        int64_t* count_out, void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_devptr || !set || !count_out || !scratch) return -1;
+    if (induced_count_refusal(n, m, k, set_bytes, scratch_bytes) != InducedRefusal::Ok) return -1;
+    lg::InducedParams p = induced_params(graph, rows_devptr, n, offsets_devptr, m, set, k, scratch);
+    p.count = count_out;
+    lg::launch_induced_count(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int32_t legion_induced_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                        const int64_t* offsets_devptr, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                                        const void* scratch, int64_t scratch_bytes, int64_t cap, int32_t* dst_out, int32_t* src_local_out,
+                                        int64_t* eid_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !rows_devptr || !offsets_devptr || !set || !scratch || !dst_out || !src_local_out) return -1;
+    if (induced_edges_refusal(n, m, k, set_bytes, scratch_bytes, cap) != InducedRefusal::Ok) return -1;
+    if (cap == 0) return 0;
+    lg::InducedParams p = induced_params(graph, rows_devptr, n, offsets_devptr, m, set, k, const_cast<void*>(scratch));
+    p.cap = cap;
+    p.dst = dst_out;
+    p.src = src_local_out;
+    p.eid = eid_out;
+    lg::launch_induced_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int32_t legion_dst_offsets(legion_stream_t stream, const int32_t* dst_devptr, int64_t cap, const int64_t* count_devptr, int32_t n,
+                                      int64_t* indptr_out)
+{
+    if (!dst_devptr || !count_devptr || !indptr_out) return -1;
+    if (dst_offsets_refusal(cap, n) != InducedRefusal::Ok) return -1;
+    lg::launch_dst_offsets(static_cast<hipStream_t>(stream), dst_devptr, cap, count_devptr, n, indptr_out);
     return 0;
 }
 

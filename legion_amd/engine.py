@@ -253,6 +253,52 @@ def unique_ids(ids, stream=None):
     return unique, local, count
 
 
+NODE_SET_MAX_IDS = 2 ** 20                           # LEGION_NODE_SET_MAX_IDS
+
+
+class NodeSet:
+    """A vertex set on the device (the rule: legion_node_set_build / legion_node_set_lookup in legion_hip.h): an open-addressing table
+    that answers pos(v) = the first position of v in nodes, -1 for a negative v and for one that does not occur.  nodes: int32, a CUDA
+    tensor (its device is used) or anything torch.as_tensor takes (`device`, default: the current one); at most NODE_SET_MAX_IDS of
+    them (ValueError before anything touches a device); they may repeat, negative entries are members of nothing, and ids past any
+    graph are legal.  .nodes: the nodes on the device; .k: their number; .distinct: the number of distinct non-negative values, a
+    one-element int32 device tensor (no sync).  The table is built on `stream` (default: the current one); a set is what
+    GraphStorage.induced_edges and node_subgraph take, and may be used any number of times."""
+
+    def __init__(self, nodes, device=None, stream=None):
+        nodes = _as_1d(nodes, torch.int32, "nodes")
+        k = int(nodes.numel())
+        if k > NODE_SET_MAX_IDS:
+            raise ValueError(f"{k} nodes in one set, at most {NODE_SET_MAX_IDS}")
+        self._lib = _libmod.load()
+        if nodes.is_cuda:
+            dev = nodes.device
+        else:
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.nodes = nodes.to(dev).contiguous()
+        self.k = k
+        self.set_bytes = int(self._lib.legion_node_set_bytes(k))
+        self.table = torch.empty((self.set_bytes // 4,), dtype=torch.int32, device=dev)
+        self.distinct = torch.empty((1,), dtype=torch.int32, device=dev)
+        src = self.nodes if k > 0 else self.distinct          # (an empty tensor has no address to hand over; k == 0 reads nothing)
+        _enqueue(self._lib, "legion_node_set_build", "NodeSet", dev, stream,
+                 (_ptr(src), k, _ptr(self.table), self.set_bytes, _ptr(self.distinct)), (self.nodes, self.table, self.distinct))
+
+    def lookup(self, ids, stream=None):
+        """pos(ids[i]) for every i: int32 [m], -1 for a negative id and for a non-member.  ids: int32, a CUDA tensor or anything
+        torch.as_tensor takes.  No sync.  Enqueued on `stream` (default: the current one)."""
+        ids = _as_1d(ids, torch.int32, "ids")
+        m = int(ids.numel())
+        ids = ids.to(self.device).contiguous()
+        local = torch.empty((m,), dtype=torch.int32, device=self.device)
+        if m == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return local
+        _enqueue(self._lib, "legion_node_set_lookup", "NodeSet.lookup", self.device, stream,
+                 (_ptr(self.table), self.set_bytes, self.k, _ptr(ids), m, _ptr(local)), (self.table, ids, local))
+        return local
+
+
 class GraphStorage:
     """Full CSR (slot P of the pointer tables) from device tensors: indptr int64[N+1], col int32[E]."""
 
@@ -694,6 +740,106 @@ class GraphStorage:
         input_nodes, src_local = self._block_tail(seeds, n, src, stream)
         out = (input_nodes, dst, src_local)
         return out + (eids,) if return_eids else out
+
+    @staticmethod
+    def _check_nodes(nodes, limit=NODE_SET_MAX_IDS):
+        """The nodes of induced_edges / node_subgraph by the rules of legion_node_set_build, before anything touches a device:
+        ValueError with the reason.  Returns a NodeSet as it is, anything else as a tensor."""
+        if not isinstance(nodes, NodeSet):
+            nodes = _as_1d(nodes, torch.int32, "nodes")
+        k = nodes.k if isinstance(nodes, NodeSet) else int(nodes.numel())
+        if k > limit:
+            raise ValueError(f"{k} nodes in one call, at most {limit}")
+        return nodes
+
+    def _node_set(self, nodes, stream):
+        """nodes (checked) as a NodeSet on the graph's device: one as it is, anything else built here on `stream`."""
+        if isinstance(nodes, NodeSet):
+            if nodes.device != self.col.device:
+                raise ValueError(f"the NodeSet lives on {nodes.device}, the graph on {self.col.device}")
+            return nodes
+        return NodeSet(nodes, device=self.col.device, stream=stream)
+
+    def _induced_edges(self, rows, n, ns, return_eids, stream):
+        """(dst, src_local, eids or None, K's device tensor or None) of rows (on the device, contiguous, checked) against the set ns."""
+        dev = self.col.device
+        offsets = self._row_offsets(rows, n, stream)
+        M = _read_scalar(offsets[n], stream)
+        self._check_labor_slots(M)
+        K, count = 0, None
+        if n > 0 and M > 0:
+            nbytes = int(self._lib.legion_induced_scratch_bytes(M))
+            scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+            count = torch.empty((1,), dtype=torch.int64, device=dev)
+            _enqueue(self._lib, "legion_induced_count", "induced_edges", dev, stream,
+                     (self.handle, _ptr(rows), n, _ptr(offsets), M, _ptr(ns.table), ns.set_bytes, ns.k, _ptr(count), _ptr(scratch), nbytes),
+                     (rows, offsets, ns.table, count, scratch))
+            K = _read_scalar(count[0], stream)
+        dst = torch.empty((K,), dtype=torch.int32, device=dev)
+        src = torch.empty((K,), dtype=torch.int32, device=dev)
+        eids = torch.empty((K,), dtype=torch.int64, device=dev) if return_eids else None
+        if K > 0:
+            _enqueue(self._lib, "legion_induced_edges", "induced_edges", dev, stream,
+                     (self.handle, _ptr(rows), n, _ptr(offsets), M, _ptr(ns.table), ns.set_bytes, ns.k, _ptr(scratch), nbytes, K, _ptr(dst),
+                      _ptr(src), _ptr(eids)), (rows, offsets, ns.table, scratch, dst, src, eids))
+        return dst, src, eids, count
+
+    def induced_edges(self, rows, nodes, *, return_eids=False, stream=None):
+        """The in-edges of rows whose source is a member of a vertex set (the rule: legion_induced_count and legion_induced_edges in
+        legion_hip.h).  rows as in row_offsets; nodes: a NodeSet, or anything NodeSet takes (the set is then built here).  rows and
+        nodes are independent: the edges from a set into a frontier are a bipartite block's and ShaDow-GNN's case.  Returns (dst,
+        src_local) and with return_eids also eids: int32 [K], int32 [K] and int64 [K], the kept entries in the order of in_edges:
+        dst[p] is the index into rows, non-decreasing; src_local[p] the first position of the source in nodes (nodes[src_local] is the
+        vertex); eids[p] the entry's position in col.  Parallel entries and self-loops are kept like any other entry, dead entries
+        never.  The outputs are sized exactly: the number of entries M and the kept number K are read back to the host, so the call
+        synchronises `stream` (default: the current one) twice.  ValueError if the rows hold more than 2^30 entries (a caller
+        batches).  A capturing caller uses the C ABI with a capacity instead."""
+        _need_bool("return_eids", return_eids)
+        rows, n = self._check_rows(rows)
+        ns = self._node_set(self._check_nodes(nodes), stream)
+        out = self._induced_edges(rows.to(self.col.device).contiguous(), n, ns, return_eids, stream)[:3]
+        return out if return_eids else out[:2]
+
+    def node_subgraph(self, nodes, *, return_eids=False, stream=None):
+        """The subgraph a vertex set induces, in this library's CSR (DGL's g.subgraph(nodes) / dgl.node_subgraph; what ClusterGCN takes
+        of a partition, GraphSAINT of the vertices its walks visited, ShaDow-GNN of a sampled k-hop neighbourhood): induced_edges with
+        rows = nodes, then legion_dst_offsets.  nodes: k distinct int32 vertices of the graph, a NodeSet or anything NodeSet takes.
+        Returns (indptr_sub, col_sub) and with return_eids also eids: indptr_sub int64 [k + 1], col_sub int32 [K], eids int64 [K].
+        Vertex j of the subgraph is nodes[j]; row j holds the positions in nodes of the live in-neighbours of nodes[j] that are
+        members, in the order of the graph's row.  GraphStorage(1, indptr_sub, col_sub) is a graph this library samples and walks;
+        eids are DGL's subgraph.edata[dgl.EID], the entries' positions in this graph's col.  For ascending nodes sorted rows stay
+        sorted (the map is monotone), and dead entries are gone.  ValueError if a node repeats, is negative or lies at or past
+        node_num: a subgraph's vertices are distinct vertices of the graph (read back after the set's build, before the expansion).
+        Synchronises `stream` (default: the current one)."""
+        _need_bool("return_eids", return_eids)
+        ns = self._node_set(self._check_nodes(nodes, GraphStorage.IN_EDGES_MAX_ROWS), stream)
+        dev, k = self.col.device, ns.k
+
+        def legal():
+            if k == 0:
+                return True
+            inside = (ns.nodes >= 0).all() & (ns.nodes < self.node_num).all() & (ns.distinct[0] == k)
+            return bool(inside.item())
+
+        if stream is None:
+            ok = legal()
+        else:
+            with torch.cuda.stream(stream):
+                ok = legal()
+        if not ok:
+            raise ValueError("the nodes of a subgraph must be distinct vertices of the graph: one repeats or lies outside it")
+        dst, src, eids, count = self._induced_edges(ns.nodes, k, ns, return_eids, stream)
+        K = int(dst.numel())
+        if K > 0:
+            indptr = torch.empty((k + 1,), dtype=torch.int64, device=dev)
+            _enqueue(self._lib, "legion_dst_offsets", "node_subgraph", dev, stream, (_ptr(dst), K, _ptr(count), k, _ptr(indptr)),
+                     (dst, count, indptr))
+        elif stream is None:
+            indptr = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
+        else:
+            with torch.cuda.stream(stream):
+                indptr = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
+        return (indptr, src, eids) if return_eids else (indptr, src)
 
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
