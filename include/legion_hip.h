@@ -789,6 +789,60 @@ int32_t legion_induced_edges(legion_stream_t stream, LegionGraphStorage* graph, 
                              int64_t* eid_out /* int64[cap], or NULL */);
 int32_t legion_dst_offsets(legion_stream_t stream, const int32_t* dst_devptr /* int32[cap] */, int64_t cap,
                            const int64_t* count_devptr /* int64[1] */, int32_t n, int64_t* indptr_out /* int64[n + 1] */);
+/* The k best entries of each row (DGL's dgl.sampling.select_topk, and sample_neighbors(prob=w, replace=False): weighted sampling
+ * WITHOUT replacement), new in this build; no reference counterpart.  One selection kernel, the k smallest keys of a row; only the key
+ * differs between the modes.  Orientation, N, rows, the buffers, the stream, capture and the FULL CSR are as for legion_in_edges: a CSR
+ * row is the dst side and a column entry the src side.  w is float32[E], device memory, aligned with col (the caller's array: the
+ * graph's prefix-sum table is not involved); in LEGION_TOPK_SAMPLE it may be NULL, which means every weight is 1.
+ *
+ * Eligibility and key of an entry e (a position in col, in row v).  A smaller key is better.
+ *   LARGEST   eligible iff col[e] >= 0 and w[e] is not NaN;                     K(e) = 0xFFFFFFFF - o
+ *   SMALLEST  eligible iff col[e] >= 0 and w[e] is not NaN;                     K(e) = o
+ *   SAMPLE    eligible iff col[e] >= 0 and w[e] is finite and > 0 (the rule of  K(e) = the uint64 bit pattern of
+ *             legion_graph_set_edge_weights; every live entry when w == NULL);         E(e, salt) / (double) w[e]
+ * o is a monotone uint32 of the weight: b = the bits of w[e], -0 taken as +0; o = (b & 0x80000000) ? ~b : (b | 0x80000000).  +-inf are
+ * eligible and order as IEEE does.  In SAMPLE the key is a positive finite double, so its bits order as its value.
+ * E(e, salt) is an Exp(1) variate (the Efraimidis-Spirakis / exponential-clock key: the k smallest E / w are a weighted sample without
+ * replacement), the same to the last bit on the device, in numpy and under g++.  x = splitmix64(key ^ (uint64) e), key =
+ * splitmix64((uint64) salt) as LABOR's, then
+ *   j = x >> 12;  u = (double)(2 j + 1) * 2^-53                         exact, in (0, 1)
+ *   (m, ex) = frexp(u), m in [0.5, 1);  if (m < SQ) { m = 2 m; ex -= 1; }      SQ = 0.7071067811865476
+ *   s = (m - 1) / (m + 1);  z = s * s
+ *   p = C[10];  for t = 9 .. 0:  p = p * z + C[t]                       C[t] = 1.0 / (2 t + 1), a rounded division of literals
+ *   E = -((double) ex * LN2 + (2 s) * p)                                LN2 = 0.6931471805599453
+ * with every *, +, / one IEEE double operation rounded on its own (p * z + C[t] is never fused).  0 < E < 37, and E / w is finite for
+ * every positive float32, denormals included.
+ *
+ * legion_row_topk.  For i in [0, n), r = rows[i]: the eligible entries of row r ordered by (K(e), e) ascending -- a tie goes to the
+ * smaller position -- are e_0, e_1, ...; c_i = min(k, their number); src_out[i k + j] = col[e_j] and eid_out[i k + j] = e_j for
+ * j < c_i, both -1 for j in [c_i, k); count_out[i] = c_i.  src_out is int32[n x k]; eid_out (int64[n x k]) and count_out (int32[n]) may
+ * be NULL.  A row id outside [0, N) has no entries, and no memory is read for it.  A row's result depends only on (graph, w, row, k,
+ * mode, salt): the same row listed twice gets the same picks, and a fresh salt per batch is the caller's to choose.  Whatever rows holds,
+ * nothing outside rows, indptr, col and w is read.
+ * scratch: device memory, 4-byte aligned, of at least legion_row_topk_scratch_bytes(n) = 4 (n + 1) bytes (a counter and the list of
+ * rows of more than 4 096 entries; -1 for n outside [0, LEGION_IN_EDGES_MAX_ROWS]); the call clears the counter on `stream` itself, and
+ * two calls in flight on different streams need scratch of their own.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: n < 0; n > LEGION_IN_EDGES_MAX_ROWS; k < 1;
+ * k > LEGION_TOPK_MAX_K; a mode outside 0 .. 2; w == NULL outside SAMPLE; a null graph, rows_devptr, src_out or scratch; scratch_bytes
+ * below legion_row_topk_scratch_bytes(n).  n == 0 returns 0 and enqueues nothing.
+ *
+ * legion_topk_keys, the key rule alone: for i in [0, n), e = eids[i]: eligible_out[i] = 1 and key_out[i] = K(e) for an eligible entry;
+ * 0 and all-ones for one that is not, and for e outside [0, E), for which nothing is read.  Returns 0, or -1 for: n < 0; n > 2^31 - 1; a
+ * mode outside 0 .. 2; w == NULL outside SAMPLE; a null graph, eids_devptr, key_out or eligible_out.  n == 0 enqueues nothing.
+ * Not offered: k above 64 (a wave holds the picks, one per lane); the pool's sampling modes (weighted sampling inside BatchGenerate
+ * stays with replacement); out-edges; heterogeneous graphs; the server, the launcher and the wire. */
+#define LEGION_TOPK_MAX_K 64
+#define LEGION_TOPK_LARGEST  0      /* select_topk, ascending=False */
+#define LEGION_TOPK_SMALLEST 1      /* select_topk, ascending=True  */
+#define LEGION_TOPK_SAMPLE   2      /* sample_neighbors(prob=w, replace=False) */
+int64_t legion_row_topk_scratch_bytes(int32_t n);
+int32_t legion_row_topk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n, int32_t k,
+                        int32_t mode, const float* w_devptr /* float32[E], or NULL in SAMPLE */, int64_t salt,
+                        int32_t* src_out /* int32[n x k] */, int64_t* eid_out /* int64[n x k], or NULL */,
+                        int32_t* count_out /* int32[n], or NULL */, void* scratch, int64_t scratch_bytes);
+int32_t legion_topk_keys(legion_stream_t stream, LegionGraphStorage* graph, const int64_t* eids_devptr /* int64[n] */, int64_t n,
+                         int32_t mode, const float* w_devptr /* float32[E], or NULL in SAMPLE */, int64_t salt,
+                         uint64_t* key_out /* uint64[n] */, uint8_t* eligible_out /* uint8[n] */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

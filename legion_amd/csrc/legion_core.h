@@ -1036,6 +1036,27 @@ void launch_induced_edges(hipStream_t s, const InducedParams& p);
 // indptr[i] = #{ p in [0, L) : dst[p] < i } for i in [0, n], L = count[0] clamped to [0, cap]
 void launch_dst_offsets(hipStream_t s, const int32_t* dst, int64_t cap, const int64_t* count, int32_t n, int64_t* indptr);
 
+// the k best entries of each row (kernels_topk.hip; the rule: legion_row_topk and legion_topk_keys in legion_hip.h, its text
+// topk_rule.h).  The arguments are the caller's to check (topk_rule.h).
+struct TopkParams {
+    const int64_t* indptr;          // the FULL CSR
+    const int32_t* col;
+    const float* w;                 // float32[E], or null (SAMPLE: every weight 1)
+    const int32_t* rows;            // int32[n]
+    int32_t* src;                   // int32[n x k]
+    int64_t* eid;                   // int64[n x k], or null
+    int32_t* count;                 // int32[n], or null
+    int32_t* long_rows;             // the scratch: int32[n + 1]: how many rows were listed, then their positions in rows
+    int32_t node_num;
+    int32_t n;
+    int32_t k;                      // 1 .. 64
+    int32_t mode;                   // LEGION_TOPK_*
+    uint64_t key;                   // labor_key(salt)
+};
+void launch_row_topk(hipStream_t s, const TopkParams& p);
+void launch_topk_keys(hipStream_t s, const int32_t* col, int64_t num_edges, const float* w, const int64_t* eids, int64_t n, int32_t mode,
+                      uint64_t key, uint64_t* key_out, uint8_t* eligible_out);
+
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {
     WalkParams walk;                // indptr, col, edge_cdf, node_num, base; seeds = the n seeds; length = T; restart_prob = the

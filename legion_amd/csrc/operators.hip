@@ -20,6 +20,7 @@
 #include "link_rule.h"
 #include "in_edges_rule.h"
 #include "labor_rule.h"
+#include "topk_rule.h"
 #include "induced_rule.h"
 
 #include <iostream>
@@ -591,6 +592,49 @@ extern "C" int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage
     p.src = src_out;
     p.eid = eid_out;
     lg::launch_labor_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// The k best entries of each row (the rules: legion_hip.h; the keys, the refusals and the scratch size: topk_rule.h).  As above: every
+// check comes before the launch.
+extern "C" int64_t legion_row_topk_scratch_bytes(int32_t n)
+{
+    return topk_scratch_bytes(n);
+}
+
+extern "C" int32_t legion_row_topk(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n, int32_t k,
+                                   int32_t mode, const float* w_devptr, int64_t salt, int32_t* src_out, int64_t* eid_out, int32_t* count_out,
+                                   void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (topk_refusal(n, k, mode, w_devptr != nullptr, graph && rows_devptr && src_out && scratch, scratch_bytes) != TopkRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    lg::TopkParams p{};
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.w = w_devptr;
+    p.rows = rows_devptr;
+    p.src = src_out;
+    p.eid = eid_out;
+    p.count = count_out;
+    p.long_rows = static_cast<int32_t*>(scratch);
+    p.node_num = graph->NodeNum();
+    p.n = n;
+    p.k = k;
+    p.mode = mode;
+    p.key = labor_key(salt);
+    lg::launch_row_topk(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int32_t legion_topk_keys(legion_stream_t stream, LegionGraphStorage* graph_, const int64_t* eids_devptr, int64_t n, int32_t mode,
+                                    const float* w_devptr, int64_t salt, uint64_t* key_out, uint8_t* eligible_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (topk_keys_refusal(n, mode, w_devptr != nullptr, graph && eids_devptr && key_out && eligible_out) != TopkRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    lg::launch_topk_keys(static_cast<hipStream_t>(stream), graph->GetCSRNodeMatrixCPU(), graph->EdgeNum(), w_devptr, eids_devptr, n, mode,
+                         labor_key(salt), key_out, eligible_out);
     return 0;
 }
 

@@ -741,6 +741,113 @@ class GraphStorage:
         out = (input_nodes, dst, src_local)
         return out + (eids,) if return_eids else out
 
+    TOPK_MAX_K = 64                                  # LEGION_TOPK_MAX_K
+    TOPK_LARGEST, TOPK_SMALLEST, TOPK_SAMPLE = 0, 1, 2      # LEGION_TOPK_*
+
+    @staticmethod
+    def _check_topk(k, name, salt, return_eids):
+        """The keywords of select_topk / sample_distinct by the rules of legion_row_topk, before anything touches a device: ValueError
+        with the reason."""
+        _need_bool("return_eids", return_eids)
+        _need_int(name, k)
+        _need_int("salt", salt)
+        if not 1 <= k <= GraphStorage.TOPK_MAX_K:
+            raise ValueError(f"{name} must lie in [1, {GraphStorage.TOPK_MAX_K}], not {k}")
+        if not -2 ** 63 <= salt <= 2 ** 63 - 1:
+            raise ValueError(f"salt must be an int64, not {salt}")
+
+    def _topk_weights(self, weights):
+        """weights as float32 [E] on the graph's device, aligned with col: ValueError otherwise."""
+        if isinstance(weights, np.ndarray):
+            if weights.dtype != np.float32:
+                raise ValueError(f"weights must be float32, not {weights.dtype}")
+            weights = torch.from_numpy(np.ascontiguousarray(weights))
+        if not isinstance(weights, torch.Tensor):
+            raise ValueError(f"weights must be a float32 tensor or array, not {type(weights).__name__}")
+        if weights.dtype != torch.float32:
+            raise ValueError(f"weights must be float32, not {weights.dtype}")
+        if weights.dim() != 1 or weights.numel() != self.edge_num:
+            raise ValueError(f"weights must have one entry per edge ({self.edge_num}), not shape {tuple(weights.shape)}")
+        return weights.to(self.col.device).contiguous()
+
+    def _row_topk(self, rows, n, k, mode, w, salt, return_eids, stream):
+        """(src [n, k], counts [n], eids [n, k] or None) of rows (on the device, contiguous, checked)."""
+        dev = self.col.device
+        src = torch.empty((n, int(k)), dtype=torch.int32, device=dev)
+        counts = torch.empty((n,), dtype=torch.int32, device=dev)
+        eids = torch.empty((n, int(k)), dtype=torch.int64, device=dev) if return_eids else None
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return src, counts, eids
+        nbytes = int(self._lib.legion_row_topk_scratch_bytes(n))
+        scratch = torch.empty((nbytes // 4,), dtype=torch.int32, device=dev)
+        _enqueue(self._lib, "legion_row_topk", "select_topk / sample_distinct", dev, stream,
+                 (self.handle, _ptr(rows), n, int(k), int(mode), _ptr(w), int(salt), _ptr(src), _ptr(eids), _ptr(counts), _ptr(scratch),
+                  nbytes), (rows, w, src, eids, counts, scratch))
+        return src, counts, eids
+
+    def select_topk(self, rows, k, weights, *, ascending=False, return_eids=False, stream=None):
+        """The k heaviest (ascending: lightest) in-edges of each of rows (DGL's dgl.sampling.select_topk; the rule: legion_row_topk in
+        legion_hip.h).  rows as in row_offsets; k in [1, TOPK_MAX_K]; weights float32 [E], aligned with col, a tensor on any device or
+        a numpy array.  Returns (src, counts) and with return_eids also eids: src int32 [n, k], per row the sources of its best
+        entries, best first, equal weights in the order of their positions, -1 past the row's counts[i] = min(k, live entries whose
+        weight is not NaN); eids int64 [n, k], their positions in col, -1 likewise.  -0 equals +0, and +-inf order as numbers.  A row
+        outside the graph has no entries.  No sync.  Enqueued on `stream` (default: the current one)."""
+        _need_bool("ascending", ascending)
+        self._check_topk(k, "k", 0, return_eids)
+        rows, n = self._check_rows(rows)
+        w = self._topk_weights(weights)
+        mode = self.TOPK_SMALLEST if ascending else self.TOPK_LARGEST
+        out = self._row_topk(rows.to(self.col.device).contiguous(), n, k, mode, w, 0, return_eids, stream)
+        return out if return_eids else out[:2]
+
+    def sample_distinct(self, rows, fanout, *, weights=None, salt=0, return_eids=False, stream=None):
+        """Weighted neighbour sampling WITHOUT replacement of the in-edges of rows (DGL's sample_neighbors(g, rows, fanout, prob=weights),
+        whose replace defaults to False; the rule: legion_row_topk in legion_hip.h, mode LEGION_TOPK_SAMPLE).  Every entry e has an
+        exponential variate E, a hash of (e, salt); a row keeps its fanout entries of smallest E / w, which is a weighted sample
+        without replacement (Efraimidis and Spirakis).  rows as in row_offsets; fanout in [1, TOPK_MAX_K]; weights as in select_topk,
+        None: every weight 1 (uniform sampling without replacement); a weight that is not finite and > 0 is never picked, nor is a
+        dead entry.  Returns (src, counts) and with return_eids also eids, shaped as select_topk's: counts[i] = min(fanout, entries
+        that can be picked).  The same arguments give the same result, and the same row listed twice gets the same picks: a new salt
+        per batch is the caller's to choose.  The pool's sampling modes are not involved: weighted sampling inside a MemoryPool stays
+        with replacement.  No sync.  Enqueued on `stream` (default: the current one)."""
+        self._check_topk(fanout, "fanout", salt, return_eids)
+        rows, n = self._check_rows(rows)
+        w = self._topk_weights(weights) if weights is not None else None
+        out = self._row_topk(rows.to(self.col.device).contiguous(), n, fanout, self.TOPK_SAMPLE, w, salt, return_eids, stream)
+        return out if return_eids else out[:2]
+
+    def sample_distinct_block(self, seeds, fanout, *, weights=None, salt=0, return_eids=False, stream=None):
+        """The block of one layer sampled by sample_distinct (DGL's NeighborSampler with one fan-out and prob=): the picks with src >= 0,
+        then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph.  Returns (input_nodes, dst_local, src_local)
+        and with return_eids also eids, in labor_block's layout: input_nodes int32 [U], the seeds first and in their order, then the
+        other picked sources in order of first appearance; dst_local, src_local int32 [K], indices into input_nodes (dst_local[p] is
+        also the index into seeds, non-decreasing); eids int64 [K].  input_nodes is what FeatureStorage.set_ids takes, and the seeds
+        of the next layer out.  A new salt per batch and per layer is the caller's to choose.  ValueError if the seeds and their picks
+        could be more than UNIQUE_MAX_IDS ids, and if a seed repeats or lies outside the graph, as full_neighbor_block.  Synchronises
+        `stream` (default: the current one)."""
+        self._check_topk(fanout, "fanout", salt, return_eids)
+        seeds, n = self._check_rows(seeds, "seeds")
+        _check_unique(n)
+        if n + n * int(fanout) > UNIQUE_MAX_IDS:
+            raise ValueError(f"{n} seeds and up to {n * int(fanout)} picks are {n + n * int(fanout)} ids in one call, at most {UNIQUE_MAX_IDS}")
+        w = self._topk_weights(weights) if weights is not None else None
+        seeds = seeds.to(self.col.device).contiguous()
+        src, _, eids = self._row_topk(seeds, n, fanout, self.TOPK_SAMPLE, w, salt, return_eids, stream)
+
+        def mask():
+            keep = src >= 0
+            dst = torch.nonzero(keep)[:, 0].to(torch.int32)
+            return dst, src[keep], eids[keep] if return_eids else None
+
+        if stream is None:
+            dst, picked, eids = mask()
+        else:
+            with torch.cuda.stream(stream):
+                dst, picked, eids = mask()
+        input_nodes, src_local = self._block_tail(seeds, n, picked, stream)
+        out = (input_nodes, dst, src_local)
+        return out + (eids,) if return_eids else out
+
     @staticmethod
     def _check_nodes(nodes, limit=NODE_SET_MAX_IDS):
         """The nodes of induced_edges / node_subgraph by the rules of legion_node_set_build, before anything touches a device:

@@ -156,6 +156,9 @@ SIGNATURES = {
     "legion_labor_scratch_bytes": (c_i64, [c_i64]),
     "legion_labor_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_i64]),
     "legion_labor_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
+    "legion_row_topk_scratch_bytes": (c_i64, [c_i32]),
+    "legion_row_topk": (c_i32, [c_p, c_p, c_p, c_i32, c_i32, c_i32, c_p, c_i64, c_p, c_p, c_p, c_p, c_i64]),
+    "legion_topk_keys": (c_i32, [c_p, c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p, c_p]),
     "legion_node_set_bytes": (c_i64, [c_i32]),
     "legion_node_set_build": (c_i32, [c_p, c_p, c_i32, c_p, c_i64, c_p]),
     "legion_node_set_lookup": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
