@@ -11,10 +11,10 @@
 //   * find_edges: a lane searches for four edge ids at once, 256 apart, their chains of dependent loads interleaved -- the op is bound
 //     by latency times loads in flight.  Measured against one and two ids per lane and against the top eight levels of the search
 //     staged in LDS, which gained nothing beside it and is not built;
-//   * unique_ids: six launches (the first clears the table) over an open-addressing table in the caller's scratch, none of which waits for another workgroup:
-//       insert   a lane claims its id's slot by a 32-bit compare-and-swap on the key (linear probing from a multiplicative hash, at
-//                most `slots` probes: the table has at least 2 m slots, so a free one exists) and takes atomicMin of its index on the
-//                slot's first index -- whichever lane claims, the minimum is the first appearance.  The slot is remembered per id;
+//   * unique_ids: six launches (the first clears the table) over the id table of node_set.h in the caller's scratch, none of which waits for another workgroup:
+//       insert   a lane claims its id's slot by a 32-bit compare-and-swap on the key (linear probing from the home slot, at most `slots`
+//                probes: the table has at least 2 m slots, so a free one exists) and takes atomicMin of its index on the slot's first
+//                index -- whichever lane claims, the minimum is the first appearance.  The slot is remembered per id;
 //       count    first touches (first[slot[i]] == i) per tile of 256 ids;
 //       scan     ONE workgroup: the exclusive prefix sums of the tile counts in place, and the total to count_out (tile_scan.h);
 //       apply    a tile ranks its first touches (ballot prefix inside a wave, four wave totals through LDS), writes unique[rank]
@@ -24,6 +24,7 @@
 // Bound: find_edges and the edge exclusion by the part's rate of dependent random requests; unique_ids by its atomics; no MFMA.
 #include "legion_core.h"
 #include "draw_rule.h"
+#include "node_set.h"
 #include "tile_scan.h"
 #include "walk_step.h"
 
@@ -137,8 +138,8 @@ void launch_negative_sample(hipStream_t s, const NegativeParams& p)
 }
 
 // ------------------------------------------------------------------------------------------
-// unique_ids.  Scratch (link_rule.h: unique_ids_scratch_bytes), int32 each: keys[slots], first[slots], slot[m], rank_at[m], tiles[T].
-// keys and first are cleared to all-ones by the call: an empty key is -1, a first index nobody has lowered 0xFFFFFFFF.
+// unique_ids.  Scratch (link_rule.h: unique_ids_scratch_bytes), int32 each: the id table [2 x slots] (node_set.h), slot[m], rank_at[m],
+// tiles[T].  The call clears the table.
 // ------------------------------------------------------------------------------------------
 struct UniquePlan {
     const int32_t* ids;
@@ -156,10 +157,9 @@ struct UniquePlan {
     int32_t shift;               // 32 - log2(slots)
 };
 
-// keys and first, all-ones (a kernel of the call's own: it is captured with the rest and ordered like it)
 __global__ __launch_bounds__(LG_LINK_THREADS) void unique_clear_kernel(uint32_t* table, int64_t words)
 {
-    for (int64_t i = (int64_t)blockIdx.x * LG_LINK_THREADS + threadIdx.x; i < words; i += (int64_t)gridDim.x * LG_LINK_THREADS) table[i] = 0xFFFFFFFFu;
+    id_table_clear(table, words, nullptr);
 }
 
 __global__ __launch_bounds__(LG_LINK_THREADS) void unique_insert_kernel(UniquePlan p)
@@ -168,10 +168,10 @@ __global__ __launch_bounds__(LG_LINK_THREADS) void unique_insert_kernel(UniquePl
         const int32_t id = p.ids[i];
         int32_t at = -1;
         if (id >= 0) {
-            uint32_t h = ((uint32_t)id * 2654435769u) >> p.shift;
+            uint32_t h = id_table_home(id, p.shift);
             for (uint32_t probe = 0; probe <= p.mask; probe++) {      // at most `slots` probes; a free slot exists (slots >= 2 m)
-                const int32_t old = atomicCAS(p.keys + h, -1, id);
-                if (old == -1 || old == id) { at = (int32_t)h; break; }
+                const int32_t old = atomicCAS(p.keys + h, ID_TABLE_EMPTY_KEY, id);
+                if (old == ID_TABLE_EMPTY_KEY || old == id) { at = (int32_t)h; break; }
                 h = (h + 1u) & p.mask;
             }
             if (at >= 0) atomicMin(p.first + at, (uint32_t)i);
@@ -233,7 +233,7 @@ __global__ __launch_bounds__(LG_LINK_THREADS) void unique_scatter_kernel(UniqueP
     const int32_t U = p.count[0];
     for (int64_t i = (int64_t)blockIdx.x * LG_LINK_THREADS + threadIdx.x; i < p.m; i += (int64_t)gridDim.x * LG_LINK_THREADS) {
         const int32_t at = p.slot[i];
-        p.local[i] = at >= 0 ? p.rank_at[p.first[at]] : -1;           // first[at] <= i < m: a first touch, whose rank apply has written
+        p.local[i] = at >= 0 ? p.rank_at[p.first[at]] : -1;         // first[at] <= i < m: a first touch, whose rank apply has written
         if (i >= U) p.unique[i] = -1;
     }
 }
@@ -247,17 +247,16 @@ void launch_unique_ids(hipStream_t s, const int32_t* ids, int32_t m, int32_t* un
     p.unique = unique;
     p.local = local;
     p.count = count;
-    p.keys = static_cast<int32_t*>(scratch);
-    p.first = reinterpret_cast<uint32_t*>(p.keys + slots);
+    const IdTable t = id_table_carve(scratch, slots);
+    p.keys = t.keys;
+    p.first = t.first;
+    p.mask = t.mask;
+    p.shift = t.shift;
     p.slot = p.keys + 2 * slots;
     p.rank_at = p.slot + m;
     p.tiles = p.rank_at + m;
     p.m = m;
     p.n_tiles = (int32_t)n_tiles;
-    p.mask = (uint32_t)(slots - 1);
-    int32_t bits = 0;
-    while (((int64_t)1 << bits) < slots) bits++;
-    p.shift = 32 - bits;                                              // slots in [2^8, 2^21]
     if (m > 0) {
         const dim3 grid = walk_grid(m);
         unique_clear_kernel<<<walk_grid(2 * slots), LG_LINK_THREADS, 0, s>>>(reinterpret_cast<uint32_t*>(p.keys), 2 * slots);

@@ -7,6 +7,7 @@
 #include <cstdint>
 
 #include "../../include/legion_hip.h"
+#include "kept_rule.h"
 
 // the function of kernels_synth.hip and legion_amd/synth.py::splitmix64_np
 constexpr uint64_t splitmix64(uint64_t x)
@@ -35,16 +36,11 @@ constexpr bool labor_keep(uint32_t h, int64_t d, int32_t fanout)
 
 enum class LaborRefusal { Ok, Count, TooMany, Slots, Fanout, Capacity, Scratch };
 
-// the tiles of 1 024 slots whose kept counts are summed: at most 2^20
-constexpr int64_t labor_tiles(int64_t m) { return (m + 1023) / 1024; }
-// the sums of 256 tile counts the one-workgroup scan takes: at most 4 096
-constexpr int64_t labor_groups(int64_t m) { return (labor_tiles(m) + 255) / 256; }
-
-// one int64 per tile plus one (the total), plus one int64 per 256 tiles
+// the compaction's scratch (kept_rule.h) for a legal m
 constexpr int64_t labor_scratch_bytes(int64_t m)
 {
     if (m < 0 || m > LEGION_LABOR_MAX_SLOTS) return -1;
-    return 8 * (labor_tiles(m) + 1 + labor_groups(m));
+    return kept_scratch_bytes(m);
 }
 
 // what both calls check, in this order
@@ -70,7 +66,6 @@ constexpr LaborRefusal labor_edges_refusal(int32_t n, int64_t m, int32_t fanout,
 }
 
 static_assert(LEGION_IN_EDGES_MAX_ROWS == (1 << 20) && LEGION_LABOR_MAX_SLOTS == (1 << 30), "labor_refusal_text spells the limits out");
-static_assert(labor_groups(LEGION_LABOR_MAX_SLOTS) == 4096, "2^20 tile counts make 4 096 second-level sums, the one-workgroup scan's reach");
 constexpr const char* labor_refusal_text(LaborRefusal r)
 {
     switch (r) {

@@ -989,23 +989,37 @@ struct InEdgesParams {
 };
 void launch_in_edges(hipStream_t s, const InEdgesParams& p);
 
+// the slots of a row expansion that a predicate keeps, compacted in order (kept_slots.h): what the count and the write pass of
+// LABOR and of induced subgraphs take beside their RowSlots
+struct KeptParams {
+    int64_t* tiles;                 // the scratch: int64[n_tiles + 1 + n_groups]: the tiles' kept counts, then their exclusive prefix sums
+                                    // with the total K at [n_tiles]; behind it the sums per 256 tiles
+    int64_t* count;                 // int64[1] (the count pass)
+    int32_t* dst;                   // int32[cap] (the write pass, as src and eid)
+    int32_t* src;                   // int32[cap]
+    int64_t* eid;                   // int64[cap], or null
+    int64_t n_tiles, n_groups;      // kept_tiles(m), kept_groups(m) (kept_rule.h)
+    int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
+};
+
 // layer-neighbour sampling, LABOR-0 (kernels_labor.hip; the rule: legion_labor_count and legion_labor_edges in legion_hip.h, its text
 // labor_rule.h).  The arguments are the caller's to check (labor_rule.h).
 struct LaborParams {
     RowSlots slots;                 // m <= 2^30
-    int64_t* tiles;                 // the scratch: int64[n_tiles + 1 + n_groups]: the tiles' kept counts, then their exclusive prefix sums
-                                    // with the total K at [n_tiles]; behind it the sums per 256 tiles
-    int64_t* count;                 // int64[1] (launch_labor_count)
-    int32_t* dst;                   // int32[cap] (launch_labor_edges, as src and eid)
-    int32_t* src;                   // int32[cap]
-    int64_t* eid;                   // int64[cap], or null
+    KeptParams kept;
     int32_t fanout;                 // >= 1
-    int64_t n_tiles, n_groups;      // labor_tiles(m), labor_groups(m)
-    int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
     uint64_t key;                   // labor_key(salt)
 };
 void launch_labor_count(hipStream_t s, const LaborParams& p);
 void launch_labor_edges(hipStream_t s, const LaborParams& p);
+
+// the open-addressing table of ids of unique_ids and of a vertex set (id_table_rule.h; carved and claimed in node_set.h)
+struct IdTable {
+    int32_t* keys;                  // int32[S]: an empty key is all-ones
+    uint32_t* first;                // uint32[S]: the least index whose id claimed the slot, all-ones: none
+    uint32_t mask;                  // S - 1
+    int32_t shift;                  // 32 - log2 S
+};
 
 // a vertex set and induced subgraphs (kernels_induced.hip; the rules: legion_node_set_build .. legion_dst_offsets in legion_hip.h, their
 // text induced_rule.h).  The arguments are the caller's to check (induced_rule.h).
@@ -1022,14 +1036,8 @@ void launch_node_set_build(hipStream_t s, const int32_t* nodes, int32_t k, void*
 void launch_node_set_lookup(hipStream_t s, const NodeSetView& set, const int32_t* ids, int64_t m, int32_t* local);
 struct InducedParams {
     RowSlots slots;                 // m <= 2^30
-    NodeSetView set;
-    int64_t* tiles;                 // the scratch, as LaborParams::tiles
-    int64_t* count;                 // int64[1] (launch_induced_count)
-    int32_t* dst;                   // int32[cap] (launch_induced_edges, as src and eid)
-    int32_t* src;                   // int32[cap]: positions in the set
-    int64_t* eid;                   // int64[cap], or null
-    int64_t n_tiles, n_groups;      // induced_tiles(m), induced_groups(m)
-    int64_t cap;                    // entries of dst, src and eid, <= 2^31 - 1
+    NodeSetView set;                // (between the two, where it stood: induced_count_kernel spills 29 SGPRs so, 34 with set first)
+    KeptParams kept;                // src: positions in the set
 };
 void launch_induced_count(hipStream_t s, const InducedParams& p);
 void launch_induced_edges(hipStream_t s, const InducedParams& p);

@@ -6,6 +6,7 @@
 #include <cstdint>
 
 #include "../../include/legion_hip.h"
+#include "id_table_rule.h"
 
 enum class LinkRefusal { Ok, Count, Fanout, DrawIndex, Exclude, Tries, Unsorted, TooMany, Scratch, Alias };
 
@@ -26,13 +27,8 @@ constexpr LinkRefusal negative_sample_refusal(int32_t n, int32_t k, int64_t base
     return LinkRefusal::Ok;
 }
 
-// the slots of the open-addressing table of m ids: the power of two that is at least 2 m, and at least 256 (m legal)
-constexpr int64_t unique_ids_table_slots(int32_t m)
-{
-    int64_t s = 256;
-    while (s < 2 * (int64_t)m) s <<= 1;
-    return s;
-}
+// the slots of the table of m ids (id_table_rule.h)
+constexpr int64_t unique_ids_table_slots(int32_t m) { return id_table_slots(m); }
 
 constexpr int64_t unique_ids_tiles(int32_t m) { return ((int64_t)m + 255) / 256; }
 
@@ -41,7 +37,7 @@ constexpr int64_t unique_ids_tiles(int32_t m) { return ((int64_t)m + 255) / 256;
 constexpr int64_t unique_ids_scratch_bytes(int32_t m)
 {
     if (m < 0 || m > LEGION_UNIQUE_MAX_IDS) return -1;
-    return 4 * (2 * unique_ids_table_slots(m) + 2 * (int64_t)m + unique_ids_tiles(m));
+    return id_table_bytes(unique_ids_table_slots(m)) + 4 * (2 * (int64_t)m + unique_ids_tiles(m));
 }
 
 constexpr bool link_ranges_overlap(uint64_t a, uint64_t a_bytes, uint64_t b, uint64_t b_bytes)

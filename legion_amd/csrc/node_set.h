@@ -1,12 +1,31 @@
-// node_set.h -- the probe of a vertex set (legion_node_set_build's table, include/legion_hip.h; its sizes and its hash: induced_rule.h),
-// once: what the lookup kernel and the edge kernels of kernels_induced.hip share.  Device code; include inside namespace lg's files after
-// legion_core.h.
+// node_set.h -- the open-addressing table of ids (its sizes and its hash: id_table_rule.h), each piece once: the carve of the table out of
+// a buffer and its clear, which unique_ids (kernels_link.hip) and the build of a vertex set (kernels_induced.hip) share (the two insert
+// kernels keep their own claim loops: DESIGN.md 4.22), and the probe of a vertex set (legion_node_set_build's table,
+// include/legion_hip.h), which the lookup kernel and the edge kernels of kernels_induced.hip share.  Device code and the carve; include
+// inside namespace lg's files after legion_core.h.
 #pragma once
 
 #include "legion_core.h"
-#include "induced_rule.h"
+#include "id_table_rule.h"
+#include "walk_step.h"
 
 namespace lg {
+
+// the table of `slots` slots at the head of a buffer of id_table_bytes(slots) bytes: keys, then first
+inline IdTable id_table_carve(void* table, int64_t slots)
+{
+    int32_t* keys = static_cast<int32_t*>(table);
+    return IdTable{.keys = keys, .first = reinterpret_cast<uint32_t*>(keys + slots), .mask = (uint32_t)(slots - 1), .shift = id_table_shift(slots)};
+}
+
+// The body of a clear kernel (a kernel of the call's own: it is captured with the rest and ordered like it): the table's 2 S words
+// all-ones -- an empty key is -1, a first index nobody has lowered 0xFFFFFFFF -- and, unless null, the distinct count 0.  Its kernels
+// run LG_ROW_THREADS and LG_LINK_THREADS lanes, which row_slots.h and kernels_link.hip assert equal to LG_WALK_THREADS
+__device__ __forceinline__ void id_table_clear(uint32_t* table, int64_t words, int32_t* distinct)
+{
+    for (int64_t i = (int64_t)blockIdx.x * LG_WALK_THREADS + threadIdx.x; i < words; i += (int64_t)gridDim.x * LG_WALK_THREADS) table[i] = 0xFFFFFFFFu;
+    if (distinct && blockIdx.x == 0 && threadIdx.x == 0) distinct[0] = 0;
+}
 
 // pos(v[j]) for K ids at once, their chains of dependent loads interleaved (as upper_counts<K> interleaves its searches): the first
 // position of v[j] in the nodes the set was built from, -1 for v[j] < 0 (tested before any probe: a dead column entry has the bit
@@ -23,7 +42,7 @@ __device__ __forceinline__ void node_set_positions(const NodeSetView& s, const i
         pos[j] = -1;
         hit[j] = false;
         open[j] = v[j] >= 0;
-        h[j] = node_set_home(v[j], s.shift) & s.mask;                 // (below S by the shift already; the mask keeps that whatever s holds)
+        h[j] = id_table_home(v[j], s.shift) & s.mask;                 // (below S by the shift already; the mask keeps that whatever s holds)
         more |= open[j];
     }
     if (s.wide) {
@@ -46,7 +65,7 @@ __device__ __forceinline__ void node_set_positions(const NodeSetView& s, const i
                     for (uint32_t c = 0; c < 4; c++) {
                         if (open[j] && c >= from) {
                             if (q[c] == v[j]) { hit[j] = true; open[j] = false; h[j] = base + c; }
-                            else if (q[c] == NODE_SET_EMPTY_KEY) open[j] = false;
+                            else if (q[c] == ID_TABLE_EMPTY_KEY) open[j] = false;
                         }
                     }
                     if (open[j]) { h[j] = (base + 4u) & s.mask; more = true; }
@@ -58,12 +77,12 @@ __device__ __forceinline__ void node_set_positions(const NodeSetView& s, const i
             more = false;
             int32_t key[K];
 #pragma unroll
-            for (int32_t j = 0; j < K; j++) key[j] = open[j] ? s.keys[h[j]] : NODE_SET_EMPTY_KEY;
+            for (int32_t j = 0; j < K; j++) key[j] = open[j] ? s.keys[h[j]] : ID_TABLE_EMPTY_KEY;
 #pragma unroll
             for (int32_t j = 0; j < K; j++) {
                 if (open[j]) {
                     if (key[j] == v[j]) { hit[j] = true; open[j] = false; }
-                    else if (key[j] == NODE_SET_EMPTY_KEY) open[j] = false;
+                    else if (key[j] == ID_TABLE_EMPTY_KEY) open[j] = false;
                     else { h[j] = (h[j] + 1u) & s.mask; more = true; }
                 }
             }

@@ -22,6 +22,7 @@
 #include "labor_rule.h"
 #include "topk_rule.h"
 #include "induced_rule.h"
+#include "node_set.h"
 
 #include <iostream>
 
@@ -545,6 +546,14 @@ extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* g
     return 0;
 }
 
+// what a pass of a kept-slot compaction takes beside the row slots (kept_slots.h).  The count pass: count, and cap 0 without outputs;
+// the write pass: no count
+static lg::KeptParams kept_params(int64_t m, const void* scratch, int64_t* count, int64_t cap, int32_t* dst, int32_t* src, int64_t* eid)
+{
+    return lg::KeptParams{.tiles = static_cast<int64_t*>(const_cast<void*>(scratch)), .count = count, .dst = dst, .src = src, .eid = eid,
+                          .n_tiles = kept_tiles(m), .n_groups = kept_groups(m), .cap = cap};
+}
+
 // Layer-neighbour sampling (the rules: legion_hip.h; the hash, the predicate, the refusals and the scratch size: labor_rule.h).  As
 // above: every check comes before the launch.
 extern "C" int64_t legion_labor_scratch_bytes(int64_t m)
@@ -552,17 +561,9 @@ extern "C" int64_t legion_labor_scratch_bytes(int64_t m)
     return labor_scratch_bytes(m);
 }
 
-static lg::LaborParams labor_params(GraphStorage* graph, const int32_t* rows, int32_t n, const int64_t* offsets, int64_t m, int32_t fanout,
-                                    int64_t salt, void* scratch)
+static lg::LaborParams labor_params(const lg::RowSlots& slots, const lg::KeptParams& kept, int32_t fanout, int64_t salt)
 {
-    lg::LaborParams p{};
-    p.slots = row_slots(graph, rows, n, offsets, m);
-    p.tiles = static_cast<int64_t*>(scratch);
-    p.fanout = fanout;
-    p.n_tiles = labor_tiles(m);
-    p.n_groups = labor_groups(m);
-    p.key = labor_key(salt);
-    return p;
+    return lg::LaborParams{.slots = slots, .kept = kept, .fanout = fanout, .key = labor_key(salt)};
 }
 
 extern "C" int32_t legion_labor_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
@@ -572,9 +573,8 @@ extern "C" int32_t legion_labor_count(legion_stream_t stream, LegionGraphStorage
     GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
     if (!graph || !rows_devptr || !offsets_devptr || !count_out || !scratch) return -1;
     if (labor_count_refusal(n, m, fanout, scratch_bytes) != LaborRefusal::Ok) return -1;
-    lg::LaborParams p = labor_params(graph, rows_devptr, n, offsets_devptr, m, fanout, salt, scratch);
-    p.count = count_out;
-    lg::launch_labor_count(static_cast<hipStream_t>(stream), p);
+    const lg::KeptParams kept = kept_params(m, scratch, count_out, 0, nullptr, nullptr, nullptr);
+    lg::launch_labor_count(static_cast<hipStream_t>(stream), labor_params(row_slots(graph, rows_devptr, n, offsets_devptr, m), kept, fanout, salt));
     return 0;
 }
 
@@ -586,12 +586,8 @@ extern "C" int32_t legion_labor_edges(legion_stream_t stream, LegionGraphStorage
     if (!graph || !rows_devptr || !offsets_devptr || !scratch || !dst_out || !src_out) return -1;
     if (labor_edges_refusal(n, m, fanout, scratch_bytes, cap) != LaborRefusal::Ok) return -1;
     if (cap == 0) return 0;
-    lg::LaborParams p = labor_params(graph, rows_devptr, n, offsets_devptr, m, fanout, salt, const_cast<void*>(scratch));
-    p.cap = cap;
-    p.dst = dst_out;
-    p.src = src_out;
-    p.eid = eid_out;
-    lg::launch_labor_edges(static_cast<hipStream_t>(stream), p);
+    const lg::KeptParams kept = kept_params(m, scratch, nullptr, cap, dst_out, src_out, eid_out);
+    lg::launch_labor_edges(static_cast<hipStream_t>(stream), labor_params(row_slots(graph, rows_devptr, n, offsets_devptr, m), kept, fanout, salt));
     return 0;
 }
 
@@ -645,14 +641,12 @@ extern "C" int64_t legion_node_set_bytes(int32_t k)
     return node_set_bytes(k);
 }
 
-// the table in the caller's memory (k, set_bytes legal)
+// the table in the caller's memory (k, set_bytes legal).  NodeSetView repeats IdTable's fields, const, and is not built around one:
+// the order of a kernel's arguments moved registers in these files, so the kernels' view stays as it was
 static lg::NodeSetView node_set_view(const void* set, int32_t k)
 {
-    const int64_t slots = node_set_slots(k);
-    const int32_t* keys = static_cast<const int32_t*>(set);
-    return lg::NodeSetView{.keys = keys, .first = reinterpret_cast<const uint32_t*>(keys + slots), .mask = (uint32_t)(slots - 1),
-                           .shift = node_set_shift(slots), .k = k,
-                           .wide = ((uintptr_t)set & 15u) == 0 ? 1 : 0};
+    const lg::IdTable t = lg::id_table_carve(const_cast<void*>(set), node_set_slots(k));
+    return lg::NodeSetView{.keys = t.keys, .first = t.first, .mask = t.mask, .shift = t.shift, .k = k, .wide = ((uintptr_t)set & 15u) == 0 ? 1 : 0};
 }
 
 extern "C" int32_t legion_node_set_build(legion_stream_t stream, const int32_t* nodes_devptr, int32_t k, void* set, int64_t set_bytes,
@@ -679,16 +673,9 @@ extern "C" int64_t legion_induced_scratch_bytes(int64_t m)
     return induced_scratch_bytes(m);
 }
 
-static lg::InducedParams induced_params(GraphStorage* graph, const int32_t* rows, int32_t n, const int64_t* offsets, int64_t m, const void* set,
-                                        int32_t k, void* scratch)
+static lg::InducedParams induced_params(const lg::RowSlots& slots, const lg::KeptParams& kept, const void* set, int32_t k)
 {
-    lg::InducedParams p{};
-    p.slots = row_slots(graph, rows, n, offsets, m);
-    p.set = node_set_view(set, k);
-    p.tiles = static_cast<int64_t*>(scratch);
-    p.n_tiles = induced_tiles(m);
-    p.n_groups = induced_groups(m);
-    return p;
+    return lg::InducedParams{.slots = slots, .set = node_set_view(set, k), .kept = kept};
 }
 
 extern "C" int32_t legion_induced_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
@@ -698,9 +685,8 @@ extern "C" int32_t legion_induced_count(legion_stream_t stream, LegionGraphStora
     GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
     if (!graph || !rows_devptr || !offsets_devptr || !set || !count_out || !scratch) return -1;
     if (induced_count_refusal(n, m, k, set_bytes, scratch_bytes) != InducedRefusal::Ok) return -1;
-    lg::InducedParams p = induced_params(graph, rows_devptr, n, offsets_devptr, m, set, k, scratch);
-    p.count = count_out;
-    lg::launch_induced_count(static_cast<hipStream_t>(stream), p);
+    const lg::KeptParams kept = kept_params(m, scratch, count_out, 0, nullptr, nullptr, nullptr);
+    lg::launch_induced_count(static_cast<hipStream_t>(stream), induced_params(row_slots(graph, rows_devptr, n, offsets_devptr, m), kept, set, k));
     return 0;
 }
 
@@ -713,12 +699,8 @@ extern "C" int32_t legion_induced_edges(legion_stream_t stream, LegionGraphStora
     if (!graph || !rows_devptr || !offsets_devptr || !set || !scratch || !dst_out || !src_local_out) return -1;
     if (induced_edges_refusal(n, m, k, set_bytes, scratch_bytes, cap) != InducedRefusal::Ok) return -1;
     if (cap == 0) return 0;
-    lg::InducedParams p = induced_params(graph, rows_devptr, n, offsets_devptr, m, set, k, const_cast<void*>(scratch));
-    p.cap = cap;
-    p.dst = dst_out;
-    p.src = src_local_out;
-    p.eid = eid_out;
-    lg::launch_induced_edges(static_cast<hipStream_t>(stream), p);
+    const lg::KeptParams kept = kept_params(m, scratch, nullptr, cap, dst_out, src_local_out, eid_out);
+    lg::launch_induced_edges(static_cast<hipStream_t>(stream), induced_params(row_slots(graph, rows_devptr, n, offsets_devptr, m), kept, set, k));
     return 0;
 }
 

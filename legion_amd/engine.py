@@ -680,20 +680,27 @@ class GraphStorage:
         if M > GraphStorage.LABOR_MAX_SLOTS:
             raise ValueError(f"the rows hold {M} entries, at most 2^30 a call")
 
-    def _labor_edges(self, rows, n, fanout, salt, return_eids, stream, limit=None):
-        """(dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + K may be."""
+    def _kept_pass(self, c_name, name, stream, args, keep):
+        """One pass of a kept-slot op as a call (head, tail, tensors): c_name enqueued on `stream` with `args` between the head (the
+        graph, the rows, their offsets, M) and the tail, `keep` kept alive behind the first two tensors."""
+        return lambda head, tail, tensors: _enqueue(self._lib, c_name, name, self.col.device, stream, head + args + tail,
+                                                    tensors[:2] + keep + tensors[2:])
+
+    def _kept_edges(self, rows, n, return_eids, stream, scratch_bytes, count_call, edges_call, limit=None):
+        """(dst, src, eids or None, K's device tensor or None) of the entries of rows (on the device, contiguous, checked) that a
+        predicate keeps.  scratch_bytes: the op's C function of M; count_call, edges_call: its two passes (_kept_pass); limit: the
+        most n + K may be."""
         dev = self.col.device
         offsets = self._row_offsets(rows, n, stream)
         M = _read_scalar(offsets[n], stream)
         self._check_labor_slots(M)
-        K = 0
+        head = (self.handle, _ptr(rows), n, _ptr(offsets), M)
+        K, count = 0, None
         if n > 0 and M > 0:
-            nbytes = int(self._lib.legion_labor_scratch_bytes(M))
+            nbytes = int(scratch_bytes(M))
             scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
             count = torch.empty((1,), dtype=torch.int64, device=dev)
-            _enqueue(self._lib, "legion_labor_count", "labor_edges", dev, stream,
-                     (self.handle, _ptr(rows), n, _ptr(offsets), M, int(fanout), int(salt), _ptr(count), _ptr(scratch), nbytes),
-                     (rows, offsets, count, scratch))
+            count_call(head, (_ptr(count), _ptr(scratch), nbytes), (rows, offsets, count, scratch))
             K = _read_scalar(count[0], stream)
         if limit is not None and n + K > limit:
             raise ValueError(f"{n} seeds and their {K} kept entries are {n + K} ids in one call, at most {limit}")
@@ -701,10 +708,14 @@ class GraphStorage:
         src = torch.empty((K,), dtype=torch.int32, device=dev)
         eids = torch.empty((K,), dtype=torch.int64, device=dev) if return_eids else None
         if K > 0:
-            _enqueue(self._lib, "legion_labor_edges", "labor_edges", dev, stream,
-                     (self.handle, _ptr(rows), n, _ptr(offsets), M, int(fanout), int(salt), _ptr(scratch), nbytes, K, _ptr(dst),
-                      _ptr(src), _ptr(eids)), (rows, offsets, scratch, dst, src, eids))
-        return dst, src, eids
+            edges_call(head, (_ptr(scratch), nbytes, K, _ptr(dst), _ptr(src), _ptr(eids)), (rows, offsets, scratch, dst, src, eids))
+        return dst, src, eids, count
+
+    def _labor_edges(self, rows, n, fanout, salt, return_eids, stream, limit=None):
+        """(dst, src, eids or None) of rows (on the device, contiguous, checked); limit: the most n + K may be."""
+        args = ("labor_edges", stream, (int(fanout), int(salt)), ())
+        return self._kept_edges(rows, n, return_eids, stream, self._lib.legion_labor_scratch_bytes,
+                                self._kept_pass("legion_labor_count", *args), self._kept_pass("legion_labor_edges", *args), limit)[:3]
 
     def labor_edges(self, rows, fanout, *, salt=0, return_eids=False, stream=None):
         """Layer-neighbour sampling of the in-edges of rows (LABOR-0; DGL's dgl.sampling.sample_labors; the rule: legion_labor_count
@@ -869,27 +880,9 @@ class GraphStorage:
 
     def _induced_edges(self, rows, n, ns, return_eids, stream):
         """(dst, src_local, eids or None, K's device tensor or None) of rows (on the device, contiguous, checked) against the set ns."""
-        dev = self.col.device
-        offsets = self._row_offsets(rows, n, stream)
-        M = _read_scalar(offsets[n], stream)
-        self._check_labor_slots(M)
-        K, count = 0, None
-        if n > 0 and M > 0:
-            nbytes = int(self._lib.legion_induced_scratch_bytes(M))
-            scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
-            count = torch.empty((1,), dtype=torch.int64, device=dev)
-            _enqueue(self._lib, "legion_induced_count", "induced_edges", dev, stream,
-                     (self.handle, _ptr(rows), n, _ptr(offsets), M, _ptr(ns.table), ns.set_bytes, ns.k, _ptr(count), _ptr(scratch), nbytes),
-                     (rows, offsets, ns.table, count, scratch))
-            K = _read_scalar(count[0], stream)
-        dst = torch.empty((K,), dtype=torch.int32, device=dev)
-        src = torch.empty((K,), dtype=torch.int32, device=dev)
-        eids = torch.empty((K,), dtype=torch.int64, device=dev) if return_eids else None
-        if K > 0:
-            _enqueue(self._lib, "legion_induced_edges", "induced_edges", dev, stream,
-                     (self.handle, _ptr(rows), n, _ptr(offsets), M, _ptr(ns.table), ns.set_bytes, ns.k, _ptr(scratch), nbytes, K, _ptr(dst),
-                      _ptr(src), _ptr(eids)), (rows, offsets, ns.table, scratch, dst, src, eids))
-        return dst, src, eids, count
+        args = ("induced_edges", stream, (_ptr(ns.table), ns.set_bytes, ns.k), (ns.table,))
+        return self._kept_edges(rows, n, return_eids, stream, self._lib.legion_induced_scratch_bytes,
+                                self._kept_pass("legion_induced_count", *args), self._kept_pass("legion_induced_edges", *args))
 
     def induced_edges(self, rows, nodes, *, return_eids=False, stream=None):
         """The in-edges of rows whose source is a member of a vertex set (the rule: legion_induced_count and legion_induced_edges in

@@ -1,10 +1,13 @@
-// Pins the rule of the vertex set and of induced subgraphs (legion_amd/csrc/induced_rule.h: the table's slots, shift, home slot and size,
+// Pins the rule of the vertex set and of induced subgraphs (legion_amd/csrc/induced_rule.h and, under it, id_table_rule.h and
+// kept_rule.h: the table's slots, shift, home slot and size,
 // which calls legion_node_set_build, legion_node_set_lookup, legion_induced_count, legion_induced_edges and legion_dst_offsets refuse, and
 // the scratch size) over a literal table.  The home slots were computed with Python integers ((v * 2654435769 mod 2^32) >> shift), the
 // codes written down from the rules as include/legion_hip.h documents them; none comes from the header.
 //   g++ -O1 -std=c++17 induced_rule_test.cpp -o t && ./t
 #include <cstdio>
 
+#include "../../legion_amd/csrc/id_table_rule.h"      // these two first: a changed copy of one shadows the one induced_rule.h includes
+#include "../../legion_amd/csrc/kept_rule.h"
 #include "../../legion_amd/csrc/induced_rule.h"
 
 static_assert(LEGION_IN_EDGES_MAX_ROWS == 1048576 && LEGION_INDUCED_MAX_SLOTS == 1073741824 && LEGION_NODE_SET_MAX_IDS == 1048576,

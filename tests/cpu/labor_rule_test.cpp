@@ -1,10 +1,11 @@
 // Pins the rule of layer-neighbour sampling (legion_amd/csrc/labor_rule.h: the hash, the integer predicate, which calls
-// legion_labor_count and legion_labor_edges refuse, and the scratch size) over a literal table.  The hash values were computed with
-// legion_amd/synth.py::splitmix64_np, the predicate's with Python integers, the codes written down from the rules as
+// legion_labor_count and legion_labor_edges refuse, and the scratch size, whose formula is kept_rule.h's) over a literal table.  The
+// hash values were computed with legion_amd/synth.py::splitmix64_np, the predicate's with Python integers, the codes written down from the rules as
 // include/legion_hip.h documents them; none comes from the header.
 //   g++ -O1 -std=c++17 labor_rule_test.cpp -o t && ./t
 #include <cstdio>
 
+#include "../../legion_amd/csrc/kept_rule.h"      // first: a changed copy of it shadows the one labor_rule.h includes
 #include "../../legion_amd/csrc/labor_rule.h"
 
 static_assert(LEGION_IN_EDGES_MAX_ROWS == 1048576 && LEGION_LABOR_MAX_SLOTS == 1073741824, "the tables below spell the limits out");

@@ -4,6 +4,7 @@
 //   g++ -O1 -std=c++17 link_rule_test.cpp -o t && ./t
 #include <cstdio>
 
+#include "../../legion_amd/csrc/id_table_rule.h"      // first: a changed copy of it shadows the one link_rule.h includes
 #include "../../legion_amd/csrc/link_rule.h"
 
 static_assert(LEGION_NEGATIVE_MAX_TRIES == 256 && LEGION_UNIQUE_MAX_IDS == 1048576, "the tables below spell both limits out");
@@ -58,6 +59,12 @@ static const BytesCase sizes[] = {
     {1048576, 25182208}, {-1, -1}, {1048577, -1},
 };
 
+struct HomeCase { int32_t v; int32_t shift; uint32_t want; };
+static const HomeCase homes[] = {
+    // where the probe of an id starts in unique_ids' table: ((uint32)v * 2654435769) >> shift, computed with Python integers
+    {1, 24, 158}, {144, 24, 255}, {123456, 19, 33}, {70001, 14, 261420}, {1000003, 11, 1767345}, {2147483647, 11, 1849616},
+};
+
 static int code(LinkRefusal r)
 {
     switch (r) {
@@ -102,6 +109,13 @@ int main()
         n++;
         if (unique_ids_scratch_bytes(c.m) != c.want) {
             printf("MISMATCH scratch bytes of %d: got %lld, want %lld\n", c.m, (long long)unique_ids_scratch_bytes(c.m), (long long)c.want);
+            bad++;
+        }
+    }
+    for (const HomeCase& c : homes) {
+        n++;
+        if (id_table_home(c.v, c.shift) != c.want) {
+            printf("MISMATCH home of %d at shift %d: got %u, want %u\n", c.v, c.shift, id_table_home(c.v, c.shift), c.want);
             bad++;
         }
     }

@@ -9,16 +9,16 @@ import pytest
 
 from tests.rule_table import assert_catches, assert_passes, run_table
 
-# a rule of the header -> what it is replaced with
+# a rule -> the header that states it (induced_rule.h, or id_table_rule.h and kept_rule.h under it) and what it is replaced with
 DROPPED = {
-    "the set-size check": ("    if (k < 0 || k > LEGION_NODE_SET_MAX_IDS) return InducedRefusal::SetSize;\n", "", 4),
-    "the set-bytes check": ("    if (set_bytes < node_set_bytes(k)) return InducedRefusal::SetBytes;\n", "", 4),
-    "the capacity check": ("if (cap < 0 || cap > (int64_t)0x7FFFFFFF) return", "if (false) return", 2),
-    "the table at least twice the nodes": ("while (s < 2 * (int64_t)k) s <<= 1;", "while (s < (int64_t)k) s <<= 1;", 1),
-    "the table at least 256 slots": ("int64_t s = 256;", "int64_t s = 128;", 1),
-    "the hash": ("constexpr uint32_t NODE_SET_HASH = 2654435769u;", "constexpr uint32_t NODE_SET_HASH = 2654435761u;", 1),
-    "the total's entry of the scratch": ("8 * (induced_tiles(m) + 1 + induced_groups(m))", "8 * (induced_tiles(m) + induced_groups(m))", 1),
-    "the lookup's count check": ("    if (m < 0 || m > (int64_t)0x7FFFFFFF) return InducedRefusal::Slots;\n", "", 1),
+    "the set-size check": ("induced_rule.h", "    if (k < 0 || k > LEGION_NODE_SET_MAX_IDS) return InducedRefusal::SetSize;\n", "", 4),
+    "the set-bytes check": ("induced_rule.h", "    if (set_bytes < node_set_bytes(k)) return InducedRefusal::SetBytes;\n", "", 4),
+    "the capacity check": ("induced_rule.h", "if (cap < 0 || cap > (int64_t)0x7FFFFFFF) return", "if (false) return", 2),
+    "the table at least twice the nodes": ("id_table_rule.h", "while (s < 2 * (int64_t)k) s <<= 1;", "while (s < (int64_t)k) s <<= 1;", 1),
+    "the table at least 256 slots": ("id_table_rule.h", "int64_t s = 256;", "int64_t s = 128;", 1),
+    "the hash": ("id_table_rule.h", "constexpr uint32_t ID_TABLE_HASH = 2654435769u;", "constexpr uint32_t ID_TABLE_HASH = 2654435761u;", 1),
+    "the total's entry of the scratch": ("kept_rule.h", "8 * (kept_tiles(m) + 1 + kept_groups(m))", "8 * (kept_tiles(m) + kept_groups(m))", 1),
+    "the lookup's count check": ("induced_rule.h", "    if (m < 0 || m > (int64_t)0x7FFFFFFF) return InducedRefusal::Slots;\n", "", 1),
 }
 
 
@@ -28,5 +28,5 @@ def test_the_rule_over_a_table(tmp_path):
 
 @pytest.mark.parametrize("name", sorted(DROPPED))
 def test_the_table_catches_a_dropped_rule(tmp_path, name):
-    """Without one rule of the header the table says MISMATCH, so the test above is able to fail."""
-    assert_catches(run_table(tmp_path, "induced_rule", ("induced_rule.h",) + DROPPED[name]))
+    """Without one rule of the headers the table says MISMATCH, so the test above is able to fail."""
+    assert_catches(run_table(tmp_path, "induced_rule", DROPPED[name]))

@@ -9,13 +9,13 @@ import pytest
 
 from tests.rule_table import assert_catches, assert_passes, run_table
 
-# a rule of the header -> what it is replaced with
+# a rule -> the header that states it (labor_rule.h, or kept_rule.h under it) and what it is replaced with
 DROPPED = {
-    "the fan-out check": ("    if (fanout < 1) return LaborRefusal::Fanout;\n", "", 2),
-    "the capacity check": ("if (cap < 0 || cap > (int64_t)0x7FFFFFFF) return", "if (false) return", 1),
-    "the salt hashed first": ("return splitmix64((uint64_t)salt); }", "return (uint64_t)salt; }", 1),
-    "the high half of the degree": ("(uint64_t)h * dh + ", "", 1),
-    "the total's entry of the scratch": ("8 * (labor_tiles(m) + 1 + labor_groups(m))", "8 * (labor_tiles(m) + labor_groups(m))", 1),
+    "the fan-out check": ("labor_rule.h", "    if (fanout < 1) return LaborRefusal::Fanout;\n", "", 2),
+    "the capacity check": ("labor_rule.h", "if (cap < 0 || cap > (int64_t)0x7FFFFFFF) return", "if (false) return", 1),
+    "the salt hashed first": ("labor_rule.h", "return splitmix64((uint64_t)salt); }", "return (uint64_t)salt; }", 1),
+    "the high half of the degree": ("labor_rule.h", "(uint64_t)h * dh + ", "", 1),
+    "the total's entry of the scratch": ("kept_rule.h", "8 * (kept_tiles(m) + 1 + kept_groups(m))", "8 * (kept_tiles(m) + kept_groups(m))", 1),
 }
 
 
@@ -25,5 +25,5 @@ def test_the_rule_over_a_table(tmp_path):
 
 @pytest.mark.parametrize("name", sorted(DROPPED))
 def test_the_table_catches_a_dropped_rule(tmp_path, name):
-    """Without one rule of the header the table says MISMATCH, so the test above is able to fail."""
-    assert_catches(run_table(tmp_path, "labor_rule", ("labor_rule.h",) + DROPPED[name]))
+    """Without one rule of the headers the table says MISMATCH, so the test above is able to fail."""
+    assert_catches(run_table(tmp_path, "labor_rule", DROPPED[name]))
