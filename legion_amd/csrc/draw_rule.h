@@ -1,5 +1,6 @@
 // draw_rule.h -- the sampler's draw, shared by its kernels (kernels_sample.hip) and the random walk (kernels_walk.hip): the
-// table-driven minstd power, the uniform pick and the weighted pick's target and search step.  Device code only; every source that
+// table-driven minstd power, the uniform pick, the weighted pick's target and search step, and the distinct picks' draw and
+// resolution (Floyd's algorithm: the sampler alone uses it).  Device code only; every source that
 // includes it carries its own copy of the power tables (20 KiB of constant device memory).
 #pragma once
 
@@ -79,6 +80,32 @@ __device__ __forceinline__ void weighted_step(float v, double t, int32_t& lo, in
     const int32_t half = n >> 1;
     if ((double)v <= t) { lo += half + 1; n -= half + 1; }
     else n = half;
+}
+
+// ------------------------------------------------------------------------------------------
+// Sampling without replacement (SampleMode::replace == 0, DGL's replace=False).  Frontier entry q of a hop with fan-out f owns
+// slots q*f + k, k < f, as with replacement; its row of degree D yields min(f, D) picks:
+//   D <= f: position k (every neighbour in CSR order, no draw);
+//   D >  f: Floyd's algorithm in slot order -- t_k = draw(q*f + k, j_k + 1) with j_k = D - f + k, and pick_k = t_k unless one
+//           of pick_0 .. pick_{k-1} took it, then j_k.  A uniform f-subset of [0, D): distinct adjacency positions.
+// The draws are independent (one per slot, in parallel); only the resolution is serial per entry, ~f^2/2 comparisons.
+// ------------------------------------------------------------------------------------------
+__device__ __forceinline__ int32_t floyd_draw(uint32_t x, int32_t deg, int32_t f, int32_t k)      // t_k from slot's x = minstd_pow(idx + 1)
+{
+    return draw_from_x(x, deg - f + k + 1);
+}
+
+// the picks of one entry with D > f: p[0 .. n) hold t_0 .. t_{n-1} and are replaced, in place, by pick_0 .. pick_{n-1}
+// (n <= f: a super tile resolves the slots it owns and those before them; later picks never change earlier ones)
+template <typename T>
+__device__ __forceinline__ void floyd_resolve(T* p, int32_t n, int32_t jbase)                      // jbase = D - f
+{
+    for (int32_t k = 1; k < n; k++) {
+        const int32_t t = p[k];
+        bool taken = false;
+        for (int32_t i = 0; i < k; i++) taken |= (p[i] == t);
+        if (taken) p[k] = jbase + k;
+    }
 }
 
 }  // namespace lg

@@ -10,6 +10,7 @@
 //       direct-mapped int32/int8 tables indexed by vertex id (N*4 B is trivial in 288 GB HBM)
 //   FeatFillUp                               SS/cache/cache_impl.cuh:183-188
 //   GetNeighborCount / TopoFillUp            SS/storage/graph_storage_impl.cuh:33-53
+//   per-vertex row headers (RowHdr), HotnessMeasure (SS/cache/cache_impl.cuh:190-198) and the bcht::find contract: at the end
 #include "legion_core.h"
 
 #include <cstring>
@@ -357,6 +358,95 @@ void topo_fill_up(hipStream_t s, const int32_t* QT, int32_t Kg, int32_t Ki, int3
     if (capacity <= 0) return;
     topo_fill_up_kernel<<<grid_for((int64_t)capacity * 64, 256, 8192), 256, 0, s>>>(QT, Kg, Ki, capacity, n,
                                                                                    csr_index, csr_dst, d_index, d_dst);
+    hipCheckError();
+}
+
+// ------------------------------------------------------------------------------------------
+// per-vertex row headers (GraphStorage): every vertex starts in the full CSR (slot P) ...
+// ------------------------------------------------------------------------------------------
+__global__ void init_row_hdr_kernel(RowHdr* __restrict__ hdr, const int64_t* __restrict__ csr_index, int32_t n,
+                                    int32_t slot)
+{
+    for (int32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
+        RowHdr h;
+        h.start = csr_index[v];
+        h.deg = (int32_t)(csr_index[v + 1] - h.start);
+        h.slot = slot;
+        hdr[v] = h;
+    }
+}
+
+void init_row_headers(hipStream_t s, RowHdr* hdr, const int64_t* csr_index, int32_t n, int32_t slot)
+{
+    int32_t grid = (n + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    if (grid < 1) grid = 1;
+    init_row_hdr_kernel<<<grid, 256, 0, s>>>(hdr, csr_index, n, slot);
+    hipCheckError();
+}
+
+// ... and the vertices GPU `Ki` of the clique caches (QT[r*Kg + Ki], r < capacity) point into its CSR
+__global__ void cache_row_hdr_kernel(RowHdr* __restrict__ hdr, const int32_t* __restrict__ QT, int32_t Kg, int32_t Ki,
+                                     int32_t capacity, int32_t n, const int64_t* __restrict__ d_index, int32_t slot)
+{
+    for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < capacity; r += gridDim.x * blockDim.x) {
+        const int64_t t = (int64_t)r * Kg + Ki;
+        if (t >= n) continue;
+        RowHdr h;
+        h.start = d_index[r];
+        h.deg = (int32_t)(d_index[r + 1] - h.start);
+        h.slot = slot;
+        hdr[QT[t]] = h;
+    }
+}
+
+void cache_row_headers(hipStream_t s, RowHdr* hdr, const int32_t* QT, int32_t Kg, int32_t Ki, int32_t capacity,
+                       int32_t n, const int64_t* d_index, int32_t slot)
+{
+    if (capacity <= 0) return;
+    int32_t grid = (capacity + 255) / 256;
+    if (grid > 4096) grid = 4096;
+    cache_row_hdr_kernel<<<grid, 256, 0, s>>>(hdr, QT, Kg, Ki, capacity, n, d_index, slot);
+    hipCheckError();
+}
+
+// SS/cache/cache_impl.cuh:190-198
+__global__ void hotness_measure_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ nc,
+                                       unsigned long long* __restrict__ access_map)
+{
+    const int32_t n = nc[INTRABATCH_CON * 2 + 1];
+    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int32_t cid = ids[i];
+        if (cid >= 0) atomicAdd(access_map + cid, 1ull);
+    }
+}
+
+void launch_hotness_measure(hipStream_t s, const int32_t* sampled_ids, const int32_t* node_counter,
+                            unsigned long long* access_map)
+{
+    hotness_measure_kernel<<<1024, 256, 0, s>>>(sampled_ids, node_counter, access_map);
+    hipCheckError();
+}
+
+// the bcht::find contract on the direct-mapped tables (SS/include/hashmap/bcht.hpp:105-165)
+__global__ void find_kernel(const int32_t* __restrict__ keys, int32_t n,
+                            const int32_t* __restrict__ map32, const char* __restrict__ map8,
+                            int32_t* __restrict__ out32, char* __restrict__ out8)
+{
+    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
+        const int32_t k = keys[i];
+        if (out32) out32[i] = (k >= 0 && map32) ? map32[k] : CACHEMISS_FLAG;
+        if (out8) out8[i] = (k >= 0 && map8) ? map8[k] : (char)CACHEMISS_FLAG;
+    }
+}
+
+void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* map32, const char* map8,
+                 int32_t* out32, char* out8)
+{
+    if (n <= 0) return;
+    int32_t grid = (n + 255) / 256;
+    if (grid > 2048) grid = 2048;
+    find_kernel<<<grid, 256, 0, s>>>(keys, n, map32, map8, out32, out8);
     hipCheckError();
 }
 

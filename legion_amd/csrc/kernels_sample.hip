@@ -33,14 +33,18 @@
 //
 // Bound: sample_kernel by the part's rate of random 128-byte requests; the other kernels by their dependent chains
 // (DESIGN.md 4.2); no MFMA.
+// The bit formats the kernels talk through -- the hash and its bucket bits, the claim pair, the claim lists' layout, the table word, the
+// losers' codes, the look-back word -- are claim_rule.h's (through legion_core.h), host-checkable.
 #include "legion_core.h"
 #include "draw_rule.h"
+#include "tile_scan.h"      // wave_inclusive
 
 #include <cstdlib>
 
 namespace lg {
 
-// minstd_pow, draw_from_x (the uniform pick), weighted_target and weighted_step (the weighted pick): draw_rule.h
+// minstd_pow, draw_from_x (the uniform pick), weighted_target and weighted_step (the weighted pick), floyd_draw and floyd_resolve (the
+// distinct picks): draw_rule.h
 __global__ void draw_batch_kernel(const int32_t* idx, const int32_t* deg, int32_t* out, int32_t n)
 {
     int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -54,33 +58,8 @@ void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, in
     hipCheckError();
 }
 
-// ------------------------------------------------------------------------------------------
-// Sampling without replacement (SampleMode::replace == 0, DGL's replace=False).  Frontier entry q of a hop with fan-out f owns
-// slots q*f + k, k < f, as with replacement; its row of degree D yields min(f, D) picks:
-//   D <= f: position k (every neighbour in CSR order, no draw);
-//   D >  f: Floyd's algorithm in slot order -- t_k = draw(q*f + k, j_k + 1) with j_k = D - f + k, and pick_k = t_k unless one
-//           of pick_0 .. pick_{k-1} took it, then j_k.  A uniform f-subset of [0, D): distinct adjacency positions.
-// The draws are independent (one per slot, in parallel); only the resolution is serial per entry, ~f^2/2 comparisons.
-// ------------------------------------------------------------------------------------------
-__device__ __forceinline__ int32_t floyd_draw(uint32_t x, int32_t deg, int32_t f, int32_t k)      // t_k from slot's x = minstd_pow(idx + 1)
-{
-    return draw_from_x(x, deg - f + k + 1);
-}
-
-// the picks of one entry with D > f: p[0 .. n) hold t_0 .. t_{n-1} and are replaced, in place, by pick_0 .. pick_{n-1}
-// (n <= f: a super tile resolves the slots it owns and those before them; later picks never change earlier ones)
-template <typename T>
-__device__ __forceinline__ void floyd_resolve(T* p, int32_t n, int32_t jbase)                      // jbase = D - f
-{
-    for (int32_t k = 1; k < n; k++) {
-        const int32_t t = p[k];
-        bool taken = false;
-        for (int32_t i = 0; i < k; i++) taken |= (p[i] == t);
-        if (taken) p[k] = jbase + k;
-    }
-}
-
-// the rule stand-alone (tests): entry i has its first slot at base[i] and degree deg[i]; out[i*f + k] = pick_k or -1
+// the distinct picks (floyd_draw + floyd_resolve, draw_rule.h) stand-alone (tests): entry i has its first slot at base[i] and degree
+// deg[i]; out[i*f + k] = pick_k or -1
 __global__ void draw_distinct_batch_kernel(const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n)
 {
     const int32_t i = blockIdx.x * blockDim.x + threadIdx.x;
@@ -204,10 +183,6 @@ void launch_batch_generate(hipStream_t s, const SeedParams& p, const LanePtrs* d
 // the kernels' view of one lane: the launch-wide hop parameters + that lane's buffers
 typedef int32_t lg_v4i __attribute__((ext_vector_type(4)));
 typedef int32_t lg_v2i __attribute__((ext_vector_type(2)));
-template <int NB> __device__ __forceinline__ int64_t lg_claim_at(int32_t b, int32_t k)      // entry k of bucket b's claim list (LanePtrs)
-{
-    return ((((int64_t)(k >> LG_CLAIM_CHUNK_BITS) * NB) + b) << LG_CLAIM_CHUNK_BITS) + (k & (LG_CLAIM_CHUNK - 1));
-}
 struct SampleArgs {
     int32_t op_id, count, partition_count, max_slots;
     int32_t* const* csr_dst_node_ids;
@@ -308,6 +283,31 @@ __device__ __forceinline__ HopGeom hop_geometry(const SampleArgs& a)
     g.ntiles = (g.total + LG_TILE - 1) / LG_TILE;
     g.nsuper = (g.total + LG_SUPER - 1) / LG_SUPER;
     return g;
+}
+
+// ------------------------------------------------------------------------------------------
+// Claims staged in LDS by bucket, then written out in runs (sample_kernel<.., STAGED>: a super tile; place_kernel: a partition tile).
+// With 64 buckets a super tile's ~450 claims are ~7 per bucket, with 256 a bucket's share of a super tile is 1-2.  Written straight
+// from the registers a wave's 64 claims would go to ~40 (64 buckets) or ~60 (256) different lists: 8-byte stores all over the lane's
+// pair array, +60 % memory requests in a kernel that is bound by them (that sweep cost the hop-3 launch of [15,10,5] at B = 8000 as
+// much again as its scattered column loads).  So the caller ranks its claims per bucket by LDS atomics and stores them -- lg_pair
+// (vertex, slot) -- at s_stage[s_off[bucket] + rank], s_off being the exclusive prefix of the buckets' counts: the block is grouped
+// by bucket.  write_staged then writes it out entry by entry: consecutive entries of a bucket go to consecutive places of its list
+// (s_list[bucket]: the first place the caller reserved there, one reservation per non-empty bucket), so a bucket's share of the block
+// leaves as one run -- a wave's store covers ~9 runs instead of ~40.  An entry past the list's capacity is not written: the list's
+// count says so, and the bucket's de-duplication workgroup then reads the hop's slots instead.  Every thread of the workgroup calls it,
+// behind the barrier that ends the staging; the caller's next barrier releases the stage.
+// ------------------------------------------------------------------------------------------
+template <int NB, int THREADS>
+__device__ __forceinline__ void write_staged(const unsigned long long* s_stage, int32_t tot, const int32_t* s_off, const int32_t* s_list,
+                                             LG_G unsigned long long* claim_pairs, int32_t claim_cap)
+{
+    for (int32_t i = threadIdx.x; i < tot; i += THREADS) {
+        const unsigned long long pr = s_stage[i];
+        const int32_t bk = lg_bucket(lg_pair_vertex(pr), NB);
+        const int32_t at = s_list[bk] + (i - s_off[bk]);
+        if (at < claim_cap) claim_pairs[lg_claim_at(bk, at, NB)] = pr;
+    }
 }
 
 // ------------------------------------------------------------------------------------------
@@ -529,7 +529,7 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                     // slot_dst / slot_fs are read once, by the compaction two kernels later: non-temporal stores (+0.5 % on the whole job,
                     // round 4, five alternating runs per build: they do not push the column arrays' lines out of the caches)
                     __builtin_nontemporal_store(dst[u], &a.slot_dst[idx]);
-                    a.slot_pos[idx] = -1;      // "no position yet": compact_kernel publishes a first touch's position here (plain store: no difference)
+                    a.slot_pos[idx] = LG_POS_NONE;      // "no position yet": compact_kernel publishes a first touch's position here (plain store: no difference)
                     if (a.slot_fs != nullptr && dst[u] >= 0) __builtin_nontemporal_store(fs[u], &a.slot_fs[idx]);     // (read for first-touch slots only)
                     if constexpr (EIDS)
                         if (dst[u] >= 0) __builtin_nontemporal_store(pk[u], &a.slot_pick[idx]);                       // (read for slots with an edge only)
@@ -543,25 +543,21 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                 for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
                     bkt[u] = -1;
                     if (dst[u] >= 0) {
-                        bkt[u] = (int32_t)(lg_tab_hash(dst[u]) & (NB - 1));
+                        bkt[u] = lg_bucket(dst[u], NB);
                         rank[u] = atomicAdd(&s_bcnt[bkt[u]], 1);
                     }
                 }
                 __syncthreads();
                 if (STAGED) {
-                    // 64 buckets: a super tile's ~450 claims are ~7 per bucket.  Written straight from the registers (as below) a wave's 64
-                    // claims would go to ~40 different lists: 8-byte stores all over the lane's pair array, +60 % memory requests in a
-                    // kernel that is bound by them.  So the claims are ranked and STAGED in LDS grouped by bucket -- in the row-header
+                    // 64 buckets: the super tile's claims are staged by bucket and written out in runs (write_staged) -- in the row-header
                     // stage, which nobody reads any more once every pick has been loaded: no LDS added, the kernel keeps its 8 workgroups
-                    // per CU -- and written out entry by entry: consecutive entries of a bucket go to consecutive places of its list, a
-                    // wave's store covers ~9 runs instead of ~40.  One reservation per non-empty bucket and super tile.  (Round 4 did this
+                    // per CU.  This kernel reserves too: one reservation per non-empty bucket and super tile.  (Round 4 did this
                     // with a second kernel over partition tiles of 8 super tiles, place_kernel: 93-107 us per 64-lane group of B = 8000
                     // for 250 MB of traffic; the 256-bucket class, where a bucket's share of a super tile is 1-2 claims, still does.)
                     unsigned long long* s_stage = reinterpret_cast<unsigned long long*>(s_hdr);      // LG_SUPER pairs = 8 KB of the 16 KB
                     if (tid < 64) {                                    // wave 0: exclusive prefix of the bucket counts + the reservations
                         const int32_t c = tid < NB ? s_bcnt[tid] : 0;
-                        int32_t inc = c;
-                        for (int d = 1; d < 64; d <<= 1) { const int32_t o = __shfl_up(inc, d); if (tid >= d) inc += o; }
+                        const int32_t inc = wave_inclusive(c, tid);
                         if (tid < NB) {
                             s_boff[tid] = inc - c;
                             s_list[tid] = c > 0 ? __hip_atomic_fetch_add(a.claim_cnt + tid * LG_CLAIM_CNT_STRIDE, c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0;
@@ -571,15 +567,9 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
 #pragma unroll
                     for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
                         if (bkt[u] >= 0)
-                            s_stage[s_boff[bkt[u]] + rank[u]] = ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
+                            s_stage[s_boff[bkt[u]] + rank[u]] = lg_pair(dst[u], (uint32_t)(idx0 + u * LG_TILE + tid));
                     __syncthreads();
-                    const int32_t tot = s_boff[NB - 1] + s_bcnt[NB - 1];
-                    for (int32_t i = tid; i < tot; i += LG_TILE) {
-                        const unsigned long long pr = s_stage[i];
-                        const int32_t bk = (int32_t)(lg_tab_hash((int32_t)(pr >> 32)) & (NB - 1));
-                        const int32_t at = s_list[bk] + (i - s_boff[bk]);
-                        if (at < a.claim_cap) a.claim_pairs[lg_claim_at<NB>(bk, at)] = pr;
-                    }
+                    write_staged<NB, LG_TILE>(s_stage, s_boff[NB - 1] + s_bcnt[NB - 1], s_boff, s_list, a.claim_pairs, a.claim_cap);
                 } else {
                     // one list per bucket: the super tile's claims of a bucket take the next places of that bucket's list (one
                     // reservation per bucket and super tile).  A claim past the list's capacity is not written: the count says so, and
@@ -594,8 +584,7 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
                         if (bkt[u] >= 0) {
                             const int32_t at = s_boff[bkt[u]] + rank[u];
                             if (at < a.claim_cap)
-                                a.claim_pairs[lg_claim_at<NB>(bkt[u], at)] =
-                                    ((unsigned long long)(uint32_t)dst[u] << 32) | (uint32_t)(idx0 + u * LG_TILE + tid);
+                                a.claim_pairs[lg_claim_at(bkt[u], at, NB)] = lg_pair(dst[u], (uint32_t)(idx0 + u * LG_TILE + tid));
                         }
                 }
             }
@@ -603,7 +592,7 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
             if (!SINGLE) {
 #pragma unroll
                 for (int u = 0; u < LG_SLOTS_PER_LANE; u++)
-                    if (dst[u] >= 0) atomicAdd(&s_bcnt[lg_tab_hash(dst[u]) & (NB - 1)], 1);
+                    if (dst[u] >= 0) atomicAdd(&s_bcnt[lg_bucket(dst[u], NB)], 1);
             }
             __syncthreads();
         }
@@ -624,13 +613,9 @@ __global__ __launch_bounds__(LG_TILE) __attribute__((amdgpu_num_sgpr(LG_SAMPLE_S
 
 // ------------------------------------------------------------------------------------------
 // K1a (256-bucket class, partition tiles of at most LG_PLACE_MAX_K super tiles): the pairs of a partition
-// tile, written to the buckets' claim lists.  With 256 buckets a wave's 64 pairs go to ~60 different lists: written straight
-// from the sampling kernel they are 8-byte stores all over the lane's pair array (that sweep cost the hop-3 launch of [15,10,5]
-// at B = 8000 as much again as its scattered column loads).  Here the partition tile's pairs are ranked and staged in LDS grouped
-// by bucket (8 KB per super tile), and the staged block is then written out entry by entry: consecutive entries of a bucket go
-// to consecutive places of that bucket's list (the places sample_kernel reserved), so a bucket's share of the partition tile
-// leaves as one run.  The sampling kernel keeps its occupancy for the scattered loads (no staging there); this kernel reads
-// slot_dst as a plain stream.
+// tile, written to the buckets' claim lists: staged by bucket in LDS of its own (8 KB per super tile) and written out in runs
+// (write_staged) to the places sample_kernel reserved.  The sampling kernel keeps its occupancy for the scattered loads (no
+// staging there); this kernel reads slot_dst as a plain stream.
 // ------------------------------------------------------------------------------------------
 // Workgroups of 1024 threads (one slot per thread and super tile): with the 64 KB stage of K = 8 two of them share a CU, i.e. 32
 // waves per CU keep this stream's loads in flight (round 4's 256-thread workgroups left 8 waves per CU: 107 us per 64-lane
@@ -654,7 +639,7 @@ __global__ __launch_bounds__(LG_PLACE_THREADS) void place_kernel(HopParams hp, c
         if (tid < NB) r = ((const LG_G lg_v2i*)a.run_off)[(int64_t)m * NB + tid];
         int32_t inc = r.y;
         if (tid < 256) {
-            for (int d = 1; d < 64; d <<= 1) { const int32_t o = __shfl_up(inc, d); if ((tid & 63) >= d) inc += o; }
+            inc = wave_inclusive(inc, tid & 63);
             if ((tid & 63) == 63) s_wtot[tid >> 6] = inc;
         }
         __syncthreads();
@@ -673,34 +658,30 @@ __global__ __launch_bounds__(LG_PLACE_THREADS) void place_kernel(HopParams hp, c
 #pragma unroll
             for (int u = 0; u < 4; u++) {
                 if (d[u] < 0) continue;
-                const int32_t bk = (int32_t)(lg_tab_hash(d[u]) & (NB - 1));
+                const int32_t bk = lg_bucket(d[u], NB);
                 const int32_t rk = atomicAdd(&s_cnt[bk], 1);
-                s_stage[s_off[bk] + rk] = ((unsigned long long)(uint32_t)d[u] << 32) | (uint32_t)((m * K + sub0 + u) * LG_SUPER + tid);
+                s_stage[s_off[bk] + rk] = lg_pair(d[u], (uint32_t)((m * K + sub0 + u) * LG_SUPER + tid));
             }
         }
         __syncthreads();
-        for (int32_t i = tid; i < tot; i += LG_PLACE_THREADS) {
-            const unsigned long long pr = s_stage[i];
-            const int32_t bk = (int32_t)(lg_tab_hash((int32_t)(pr >> 32)) & (NB - 1));
-            const int32_t at = s_list[bk] + (i - s_off[bk]);
-            if (at < a.claim_cap) a.claim_pairs[lg_claim_at<NB>(bk, at)] = pr;
-        }
+        write_staged<NB, LG_PLACE_THREADS>(s_stage, tot, s_off, s_list, a.claim_pairs, a.claim_cap);
         __syncthreads();                           // (the next partition tile re-uses the stage and the counts)
     }
 }
 
 // ------------------------------------------------------------------------------------------
 // K1b (lds form): de-duplication of a hop's claims, one workgroup per (bucket, lane), entirely in LDS.
-//   table word = [ vertex : 32 | pending : 1 | value : 31 ], empty = all ones, ordered linear probing with atomicMin.
+//   table word = [ vertex : 32 | pending : 1 | value : 31 ], empty = all ones (lg_tab_known / lg_tab_claim, claim_rule.h), ordered
+//   linear probing with atomicMin.
 //   1. the batch's known vertices that hash into this bucket go in with their position: the seeds from sampled_ids, the
 //      nodes earlier hops added from the bucket's known list (list_known_kernel) -- or all of them from sampled_ids when the
 //      list outgrew its capacity;
 //   2. the bucket's claims go in as pending | slot: per vertex the lowest value survives -- a known position beats any
 //      slot, a lower slot beats a higher one;
 //   3. every claim looks its vertex up: the claim that IS the surviving word is a first touch and stays unmarked; every
-//      other claim's slot is marked a loser -- slot_dst[slot] = -2 - vertex (LG_SLOT_LOSER: any int32 vertex id fits, and the
+//      other claim's slot is marked a loser -- slot_dst[slot] = -2 - vertex (LG_SLOT_LOSER: vertex ids up to 2^31 - 2 fit, and the
 //      compaction reads the mark in the stream it reads anyway) -- and gets, in slot_pos, the vertex's final position or
-//      -2 - (the winning slot: always a LOWER slot of this hop, and itself a first touch).
+//      -2 - (the winning slot: always a LOWER slot of this hop, and itself a first touch) -- lg_tab_loser_pos.
 // A bucket whose vertices cannot fit the table is processed in P passes over sub-buckets (further hash bits), so the
 // result never depends on how the hash spreads the batch.  Nothing survives the hop: nothing to clear, no state that
 // scales with the graph.
@@ -740,9 +721,7 @@ __global__ __launch_bounds__(LG_DEDUP_THREADS, (CL <= LG_DEDUP_CLAIMS_MID ? 8 : 
 void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 {
     constexpr int NB = 1 << BB;
-    constexpr uint32_t PENDING = 0x80000000u;
     constexpr int TABLE = 1 << TB;
-    auto slot_of = [](uint32_t h) { return (h * 0x9E3779B1u) >> (32 - TB); };
     __shared__ unsigned long long s_tab[TABLE];
     __shared__ int32_t s_full;
     const int32_t tid = threadIdx.x, b = (int32_t)blockIdx.x;
@@ -754,9 +733,9 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 #pragma unroll
     for (int u = 0; u < CL; u++) {
         const int32_t k = u * LG_DEDUP_THREADS + tid;
-        rp[u] = k < a.claim_cap ? a.claim_pairs[lg_claim_at<NB>(b, k)] : ~0ull;
+        rp[u] = k < a.claim_cap ? a.claim_pairs[lg_claim_at(b, k, NB)] : LG_PAIR_EMPTY;
     }
-    unsigned long long kl0 = (a.known_pairs != nullptr && tid < a.known_cap) ? a.known_pairs[(int64_t)b * a.known_cap + tid] : ~0ull;
+    unsigned long long kl0 = (a.known_pairs != nullptr && tid < a.known_cap) ? a.known_pairs[(int64_t)b * a.known_cap + tid] : LG_PAIR_EMPTY;
     const int32_t n_listed = a.known_pairs != nullptr ? a.known_cnt[b] : 0;
     const int32_t total = a.claim_cnt[b * LG_CLAIM_CNT_STRIDE];      // (the count of the bucket's claims even when the list could not take them all)
     const int32_t kid0 = tid < a.ids_cap ? a.sampled_ids[tid] : -1;
@@ -764,10 +743,10 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
     const int32_t n_seed = min(max(a.node_counter[INTRABATCH_CON * 3], 0), n_known);
 
     auto insert = [&](unsigned long long w, uint32_t h) {
-        uint32_t p = slot_of(h);
+        uint32_t p = lg_tab_home(h, TB);
         for (int it = 0; it < TABLE; it++) {
             const unsigned long long old = __hip_atomic_fetch_min(&s_tab[p], w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
-            if (old == ~0ull || (uint32_t)(old >> 32) == (uint32_t)(w >> 32)) return;    // placed, or merged with the same vertex
+            if (old == LG_PAIR_EMPTY || lg_pair_vertex(old) == lg_pair_vertex(w)) return;    // placed, or merged with the same vertex
             if (old > w) w = old;                                                          // displaced a larger word: carry it on
             p = (p + 1) & (TABLE - 1);
         }
@@ -781,8 +760,8 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
     const LG_G unsigned long long* klist = a.known_pairs + (int64_t)b * a.known_cap;
 #pragma unroll
     for (int u = 0; u < CL; u++)
-        if (u * LG_DEDUP_THREADS + tid >= total) rp[u] = ~0ull;
-    if (!listed || tid >= n_listed) kl0 = ~0ull;
+        if (u * LG_DEDUP_THREADS + tid >= total) rp[u] = LG_PAIR_EMPTY;
+    if (!listed || tid >= n_listed) kl0 = LG_PAIR_EMPTY;
     // passes: distinct vertices <= known + claims; keep the expected load of a pass at or below LG_LDS_FILL_16THS / 16 of the
     // table.  The bucket's share of the scanned ids is ESTIMATED (an even spread + a quarter; counting it would cost every
     // workgroup one more round trip to memory), and the hash is assumed to spread the bucket evenly over its sub-buckets: when
@@ -801,24 +780,34 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
 #pragma unroll
         for (int u = 0; u < CL; u++) {
             const int32_t k = k0 + u * LG_DEDUP_THREADS + tid;
-            pr[u] = ~0ull;
+            pr[u] = LG_PAIR_EMPTY;
             if (k >= n_src) continue;
             if (from_slots) {
                 int32_t d = a.slot_dst[k];
                 if (d == -1) continue;
                 if (d < -1) d = LG_SLOT_LOSER(d);                // (an earlier pass may have marked the slot)
-                if ((lg_tab_hash(d) & (NB - 1)) == (uint32_t)b) pr[u] = ((unsigned long long)(uint32_t)d << 32) | (uint32_t)k;
+                if (lg_bucket(d, NB) == b) pr[u] = lg_pair(d, (uint32_t)k);
             } else {
-                pr[u] = a.claim_pairs[lg_claim_at<NB>(b, k)];
+                pr[u] = a.claim_pairs[lg_claim_at(b, k, NB)];
             }
         }
     };
+    // the thread's CL claims of the sweep that starts at claim k0: from the registers when resident, through fetch otherwise.  (The loops
+    // below keep their `for`: with the loop inside the helper and the body handed in, every instance's code moved by ~4 % and two of
+    // them, <8, 10> and <8, 5>, by a VGPR -- DESIGN.md 4.23)
+    auto sweep_claims = [&](int32_t k0, unsigned long long (&pr)[CL]) {
+        if (resident) {
+#pragma unroll
+            for (int u = 0; u < CL; u++) pr[u] = rp[u];
+        } else
+            fetch(k0, pr);
+    };
 
     for (;;) {
-        const uint32_t pmask = (uint32_t)passes - 1u;
+        const uint32_t npass = (uint32_t)passes;
         bool overflow = false;
-        for (uint32_t pass = 0; pass <= pmask; pass++) {
-            for (int32_t i = tid; i < TABLE; i += LG_DEDUP_THREADS) s_tab[i] = ~0ull;
+        for (uint32_t pass = 0; pass < npass; pass++) {
+            for (int32_t i = tid; i < TABLE; i += LG_DEDUP_THREADS) s_tab[i] = LG_PAIR_EMPTY;
             if (tid == 0) s_full = 0;
             lds_barrier();
             for (int32_t i0 = 0; i0 < n_scan; i0 += LG_DEDUP_THREADS) {
@@ -826,31 +815,27 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
                 const int32_t id = i >= n_scan ? -1 : (i0 == 0 ? kid0 : a.sampled_ids[i]);      // (the first one came early)
                 if (id < 0) continue;
                 const uint32_t h = lg_tab_hash(id);
-                if ((h & (NB - 1)) != (uint32_t)b || ((h >> BB) & pmask) != pass) continue;
-                insert(((unsigned long long)(uint32_t)id << 32) | (uint32_t)i, h);
+                if (lg_hash_bucket(h, NB) != b || lg_sub_bucket(h, BB, npass) != pass) continue;
+                insert(lg_tab_known(id, (uint32_t)i), h);
             }
             if (listed)
                 for (int32_t i0 = 0; i0 < n_listed; i0 += LG_DEDUP_THREADS) {
                     const int32_t i = i0 + tid;
-                    const unsigned long long pr = i0 == 0 ? kl0 : (i < n_listed ? klist[i] : ~0ull);
-                    if (pr == ~0ull) continue;
-                    const uint32_t h = lg_tab_hash((int32_t)(pr >> 32));
-                    if (((h >> BB) & pmask) != pass) continue;
-                    insert(pr, h);
+                    const unsigned long long pr = i0 == 0 ? kl0 : (i < n_listed ? klist[i] : LG_PAIR_EMPTY);
+                    if (pr == LG_PAIR_EMPTY) continue;
+                    const uint32_t h = lg_tab_hash(lg_pair_vertex(pr));
+                    if (lg_sub_bucket(h, BB, npass) != pass) continue;
+                    insert(pr, h);                             // (a known list's pair IS the table word of a known vertex: lg_tab_known)
                 }
             for (int32_t k0 = 0; k0 < n_src; k0 += CL * LG_DEDUP_THREADS) {
                 unsigned long long pr[CL];
-                if (resident) {
-#pragma unroll
-                    for (int u = 0; u < CL; u++) pr[u] = rp[u];
-                } else
-                    fetch(k0, pr);
+                sweep_claims(k0, pr);
 #pragma unroll
                 for (int u = 0; u < CL; u++) {
-                    if (pr[u] == ~0ull) continue;
-                    const uint32_t h = lg_tab_hash((int32_t)(pr[u] >> 32));
-                    if (((h >> BB) & pmask) != pass) continue;
-                    insert((pr[u] & 0xFFFFFFFF00000000ull) | PENDING | (uint32_t)pr[u], h);
+                    if (pr[u] == LG_PAIR_EMPTY) continue;
+                    const uint32_t h = lg_tab_hash(lg_pair_vertex(pr[u]));
+                    if (lg_sub_bucket(h, BB, npass) != pass) continue;
+                    insert(lg_tab_claim(lg_pair_vertex(pr[u]), lg_pair_value(pr[u])), h);
                 }
             }
             lds_barrier();
@@ -859,27 +844,24 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
             if (s_full != 0) { overflow = true; break; }
             for (int32_t k0 = 0; k0 < n_src; k0 += CL * LG_DEDUP_THREADS) {
                 unsigned long long pr[CL];
-                if (resident) {
-#pragma unroll
-                    for (int u = 0; u < CL; u++) pr[u] = rp[u];
-                } else
-                    fetch(k0, pr);
+                sweep_claims(k0, pr);
 #pragma unroll
                 for (int u = 0; u < CL; u++) {
-                    if (pr[u] == ~0ull) continue;
-                    const uint32_t id = (uint32_t)(pr[u] >> 32), slot = (uint32_t)pr[u];
-                    const uint32_t h = lg_tab_hash((int32_t)id);
-                    if (((h >> BB) & pmask) != pass) continue;
-                    uint32_t p = slot_of(h);
-                    uint32_t v = 0xFFFFFFFFu;
+                    if (pr[u] == LG_PAIR_EMPTY) continue;
+                    const int32_t id = lg_pair_vertex(pr[u]);
+                    const uint32_t slot = lg_pair_value(pr[u]);
+                    const uint32_t h = lg_tab_hash(id);
+                    if (lg_sub_bucket(h, BB, npass) != pass) continue;
+                    uint32_t p = lg_tab_home(h, TB);
+                    uint32_t v = lg_pair_value(LG_PAIR_EMPTY);
                     for (int it = 0; it < TABLE; it++) {
                         const unsigned long long w = s_tab[p];
-                        if ((uint32_t)(w >> 32) == id) { v = (uint32_t)w; break; }
+                        if (lg_pair_vertex(w) == id) { v = lg_pair_value(w); break; }
                         p = (p + 1) & (TABLE - 1);
                     }
-                    if (v != (PENDING | slot)) {          // not the lowest slot of a new vertex
-                        a.slot_dst[slot] = LG_SLOT_LOSER((int32_t)id);
-                        a.slot_pos[slot] = (v & PENDING) ? -2 - (int32_t)(v & ~PENDING) : (int32_t)v;
+                    if (!lg_tab_first_touch(v, slot)) {          // not the lowest slot of a new vertex
+                        a.slot_dst[slot] = LG_SLOT_LOSER(id);
+                        a.slot_pos[slot] = lg_tab_loser_pos(v);
                     }
                 }
             }
@@ -928,14 +910,27 @@ void dedup_lists_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
                                               // per lane, to 7 (72) still 12; at 6 it uses no scratch
 #endif
 #define LG_SPIN_LIMIT (1 << 24)       // polls of one word before a waiter gives up with LG_ERR_CHAIN (seconds; a wait is microseconds)
-#define LG_ST_AGG (1ull << 62)
-#define LG_ST_PREF (2ull << 62)
-__device__ __forceinline__ unsigned long long st_word(unsigned long long status, int32_t e, int32_t n)
+// (the status word: st_word / st_edges / st_nodes / st_status, LG_ST_AGG, LG_ST_PREF -- claim_rule.h)
+
+// The bounded poll of one word another workgroup will write: relaxed agent-scope loads with a sleep in between until ready(word) holds.
+// A waiter never hangs: after LG_SPIN_LIMIT polls it raises LG_ERR_CHAIN for its lane and goes on with `fallback`.
+template <typename T, typename Ready>
+__device__ __forceinline__ T poll_word(const LG_G T* p, Ready ready, T fallback, LG_G int32_t* hop_scratch, LG_G int32_t* err_flag)
 {
-    return status | ((unsigned long long)(uint32_t)e << 31) | (unsigned long long)(uint32_t)n;
+    T w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    for (int32_t spin = 0; !ready(w); spin++) {
+        if (spin == LG_SPIN_LIMIT) {
+            raise_error(hop_scratch, err_flag, LG_ERR_CHAIN);
+            return fallback;
+        }
+        __builtin_amdgcn_s_sleep(1);
+        w = __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    return w;
 }
-__device__ __forceinline__ int32_t st_edges(unsigned long long w) { return (int32_t)((w >> 31) & 0x7FFFFFFFull); }
-__device__ __forceinline__ int32_t st_nodes(unsigned long long w) { return (int32_t)(w & 0x7FFFFFFFull); }
+
+// the ballot bits of the lanes below `lane` (0 .. 63)
+__device__ __forceinline__ unsigned long long lanes_below(int32_t lane) { return lane == 0 ? 0ull : (~0ull >> (64 - lane)); }
 
 // EIDS (edge-id mode, SampleMode::edge_ids): every edge e also gets agg_edge_ids[e] = indptr_full[vertex the slot sampled for] + the
 // position the slot drew (slot_pick, sample_kernel<.., EIDS>): the edge's place in the FULL CSR's column array, also for a row that
@@ -968,7 +963,7 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
     LG_G unsigned long long* state = a.tile_state;
     const int32_t tid = threadIdx.x;
     const int32_t wave = tid >> 6, lane = tid & 63;
-    const unsigned long long lt = (lane == 0) ? 0ull : (~0ull >> (64 - lane));
+    const unsigned long long lt = lanes_below(lane);
 
     // The next tile's ticket is drawn BEFORE this tile's stores are issued and the barriers inside the loop order LDS only: memory
     // operations of a wave complete in order, so a ticket drawn after the stores (and a barrier that fences global memory) waits
@@ -1027,11 +1022,7 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
         int32_t te = 0, tn = 0;
         if (wave == 0) {
             const int32_t ce = lane < NW ? s_cnt[0][lane] : 0, cn = lane < NW ? s_cnt[1][lane] : 0;
-            int32_t ie = ce, in = cn;
-            for (int d = 1; d < NW; d <<= 1) {
-                const int32_t oe = __shfl_up(ie, d), on = __shfl_up(in, d);
-                if (lane >= d) { ie += oe; in += on; }
-            }
+            const int32_t ie = wave_inclusive(ce, lane, NW), in = wave_inclusive(cn, lane, NW);
             te = __shfl(ie, NW - 1);
             tn = __shfl(in, NW - 1);
             if (lane < NW) {
@@ -1053,7 +1044,7 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
                 const bool first = (mf[u] >> lane) & 1ull;
                 if (!first) fsv[u] = LG_FS_UNKNOWN;
                 if (!LAST) nh[u] = load_hdr(a.row_hdr + v[u]);     // next hop's frontier header
-                lost_pos[u] = first ? 0 : a.slot_pos[idx];         // final already, or -2 - (slot it lost to)
+                lost_pos[u] = first ? 0 : a.slot_pos[idx];         // final already, or lg_pos_lost_to(the slot it lost to)
             }
         }
         if (wave == 0) {
@@ -1063,19 +1054,9 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
                 for (;;) {
                     const int32_t me = j - lane;
                     unsigned long long w = LG_ST_PREF;                    // below tile 0: an inclusive prefix of nothing
-                    if (me >= 0) {
-                        w = __hip_atomic_load(state + me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        for (int32_t spin = 0; (w >> 62) == 0; spin++) {
-                            if (spin == LG_SPIN_LIMIT) {       // cannot happen (the tile's workgroup is running): give up, never hang
-                                raise_error(a.hop_scratch, a.err_flag, LG_ERR_CHAIN);
-                                w = LG_ST_AGG;
-                                break;
-                            }
-                            __builtin_amdgcn_s_sleep(1);
-                            w = __hip_atomic_load(state + me, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                        }
-                    }
-                    const unsigned long long pm = __ballot((w >> 62) == 2);
+                    if (me >= 0)       // (the limit cannot be met: the tile's workgroup is running; then an aggregate of nothing)
+                        w = poll_word(state + me, [](unsigned long long s) { return st_status(s) != 0; }, LG_ST_AGG, a.hop_scratch, a.err_flag);
+                    const unsigned long long pm = __ballot(st_status(w) == st_status(LG_ST_PREF));
                     const int first_p = pm ? __builtin_ctzll(pm) : 64;   // lanes up to the nearest inclusive prefix count
                     if (lane <= first_p) { xe += st_edges(w); xn += st_nodes(w); }
                     if (pm) break;
@@ -1109,24 +1090,14 @@ void compact_kernel(HopParams hp, const LanePtrs* __restrict__ lanes)
             // a slot that lost to ANOTHER slot of the hop: that slot IS the winner (chains have length one), and it is a LOWER slot
 #pragma unroll
             for (int u = 0; u < LG_SLOTS_PER_LANE; u++) {
-                if (v[u] < 0 || lost_pos[u] >= -1) continue;
-                const int32_t w = -2 - lost_pos[u];
+                if (v[u] < 0 || lost_pos[u] >= LG_POS_NONE) continue;      // (final or none: not "lost to a slot")
+                const int32_t w = lg_pos_winner(lost_pos[u]);
                 if (w >= idx0) {            // of this super tile: its position follows from the ballots at hand
                     const int32_t ww = (w - idx0) >> 6, lw = w & 63;
-                    lost_pos[u] = node_base + xn + s_pre[1][ww] + __popcll(s_mf[ww] & (lw == 0 ? 0ull : (~0ull >> (64 - lw))));
+                    lost_pos[u] = node_base + xn + s_pre[1][ww] + __popcll(s_mf[ww] & lanes_below(lw));
                 } else {                    // of an earlier one: wait for the position its workgroup publishes
-                    const LG_G int32_t* wp = a.slot_pos + w;
-                    int32_t np = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    for (int32_t spin = 0; np < 0; spin++) {
-                        if (spin == LG_SPIN_LIMIT) {           // (as above: an error bit instead of a hung GPU)
-                            raise_error(a.hop_scratch, a.err_flag, LG_ERR_CHAIN);
-                            np = 0;
-                            break;
-                        }
-                        __builtin_amdgcn_s_sleep(1);
-                        np = __hip_atomic_load(wp, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-                    }
-                    lost_pos[u] = np;
+                    // (as above: an error bit and position 0 instead of a hung GPU)
+                    lost_pos[u] = poll_word((const LG_G int32_t*)(a.slot_pos + w), [](int32_t np) { return np >= 0; }, 0, a.hop_scratch, a.err_flag);
                 }
             }
         }
@@ -1243,7 +1214,7 @@ __global__ __launch_bounds__(LG_TILE) void list_known_kernel(HopParams hp, const
         for (int32_t i = tid; i < NB; i += LG_TILE) s_kcnt[i] = 0;
         __syncthreads();
         for (int32_t i = c0 + tid; i < c1; i += LG_TILE)
-            atomicAdd(&s_kcnt[lg_tab_hash(a.sampled_ids[base + i]) & (NB - 1)], 1);
+            atomicAdd(&s_kcnt[lg_bucket(a.sampled_ids[base + i], NB)], 1);
         __syncthreads();
         for (int32_t i = tid; i < NB; i += LG_TILE) {
             const int32_t c = s_kcnt[i];
@@ -1253,10 +1224,10 @@ __global__ __launch_bounds__(LG_TILE) void list_known_kernel(HopParams hp, const
         __syncthreads();
         for (int32_t i = c0 + tid; i < c1; i += LG_TILE) {
             const int32_t id = a.sampled_ids[base + i];
-            const int32_t bk = (int32_t)(lg_tab_hash(id) & (NB - 1));
+            const int32_t bk = lg_bucket(id, NB);
             const int32_t at = s_kbase[bk] + atomicAdd(&s_kcnt[bk], 1);
             if (at < a.known_cap)
-                a.known_pairs[(int64_t)bk * a.known_cap + at] = ((unsigned long long)(uint32_t)id << 32) | (uint32_t)(base + i);
+                a.known_pairs[(int64_t)bk * a.known_cap + at] = lg_pair(id, (uint32_t)(base + i));
         }
         __syncthreads();
     }
@@ -1340,55 +1311,6 @@ void launch_random_sample(hipStream_t s, const HopParams& p, int32_t bucket_bits
 }
 
 // ------------------------------------------------------------------------------------------
-// per-vertex row headers (GraphStorage): every vertex starts in the full CSR (slot P) ...
-// ------------------------------------------------------------------------------------------
-__global__ void init_row_hdr_kernel(RowHdr* __restrict__ hdr, const int64_t* __restrict__ csr_index, int32_t n,
-                                    int32_t slot)
-{
-    for (int32_t v = blockIdx.x * blockDim.x + threadIdx.x; v < n; v += gridDim.x * blockDim.x) {
-        RowHdr h;
-        h.start = csr_index[v];
-        h.deg = (int32_t)(csr_index[v + 1] - h.start);
-        h.slot = slot;
-        hdr[v] = h;
-    }
-}
-
-void init_row_headers(hipStream_t s, RowHdr* hdr, const int64_t* csr_index, int32_t n, int32_t slot)
-{
-    int32_t grid = (n + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    if (grid < 1) grid = 1;
-    init_row_hdr_kernel<<<grid, 256, 0, s>>>(hdr, csr_index, n, slot);
-    hipCheckError();
-}
-
-// ... and the vertices GPU `Ki` of the clique caches (QT[r*Kg + Ki], r < capacity) point into its CSR
-__global__ void cache_row_hdr_kernel(RowHdr* __restrict__ hdr, const int32_t* __restrict__ QT, int32_t Kg, int32_t Ki,
-                                     int32_t capacity, int32_t n, const int64_t* __restrict__ d_index, int32_t slot)
-{
-    for (int32_t r = blockIdx.x * blockDim.x + threadIdx.x; r < capacity; r += gridDim.x * blockDim.x) {
-        const int64_t t = (int64_t)r * Kg + Ki;
-        if (t >= n) continue;
-        RowHdr h;
-        h.start = d_index[r];
-        h.deg = (int32_t)(d_index[r + 1] - h.start);
-        h.slot = slot;
-        hdr[QT[t]] = h;
-    }
-}
-
-void cache_row_headers(hipStream_t s, RowHdr* hdr, const int32_t* QT, int32_t Kg, int32_t Ki, int32_t capacity,
-                       int32_t n, const int64_t* d_index, int32_t slot)
-{
-    if (capacity <= 0) return;
-    int32_t grid = (capacity + 255) / 256;
-    if (grid > 4096) grid = 4096;
-    cache_row_hdr_kernel<<<grid, 256, 0, s>>>(hdr, QT, Kg, Ki, capacity, n, d_index, slot);
-    hipCheckError();
-}
-
-// ------------------------------------------------------------------------------------------
 // end of batch (IOComplete).  The reference zeroes position_map for every node of the batch
 // (ClearPosMap, operator_impl.cu:542-548) and memsets the N/8-byte bitmap at the next batch's
 // start (:151).  Here there is nothing to clear: no per-vertex state exists.  What is left of the op: the batch's counters
@@ -1415,46 +1337,6 @@ __global__ void end_of_batch_kernel(const LanePtrs* __restrict__ lanes, int32_t*
 void launch_end_of_batch(hipStream_t s, const LanePtrs* d_lanes, int32_t n_lanes, int32_t* iter_state)
 {
     end_of_batch_kernel<<<dim3(1, n_lanes), 64, 0, s>>>(d_lanes, iter_state);
-    hipCheckError();
-}
-
-// SS/cache/cache_impl.cuh:190-198
-__global__ void hotness_measure_kernel(const int32_t* __restrict__ ids, const int32_t* __restrict__ nc,
-                                       unsigned long long* __restrict__ access_map)
-{
-    const int32_t n = nc[INTRABATCH_CON * 2 + 1];
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int32_t cid = ids[i];
-        if (cid >= 0) atomicAdd(access_map + cid, 1ull);
-    }
-}
-
-void launch_hotness_measure(hipStream_t s, const int32_t* sampled_ids, const int32_t* node_counter,
-                            unsigned long long* access_map)
-{
-    hotness_measure_kernel<<<1024, 256, 0, s>>>(sampled_ids, node_counter, access_map);
-    hipCheckError();
-}
-
-// the bcht::find contract on the direct-mapped tables (SS/include/hashmap/bcht.hpp:105-165)
-__global__ void find_kernel(const int32_t* __restrict__ keys, int32_t n,
-                            const int32_t* __restrict__ map32, const char* __restrict__ map8,
-                            int32_t* __restrict__ out32, char* __restrict__ out8)
-{
-    for (int32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < n; i += gridDim.x * blockDim.x) {
-        const int32_t k = keys[i];
-        if (out32) out32[i] = (k >= 0 && map32) ? map32[k] : CACHEMISS_FLAG;
-        if (out8) out8[i] = (k >= 0 && map8) ? map8[k] : (char)CACHEMISS_FLAG;
-    }
-}
-
-void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* map32, const char* map8,
-                 int32_t* out32, char* out8)
-{
-    if (n <= 0) return;
-    int32_t grid = (n + 255) / 256;
-    if (grid > 2048) grid = 2048;
-    find_kernel<<<grid, 256, 0, s>>>(keys, n, map32, map8, out32, out8);
     hipCheckError();
 }
 

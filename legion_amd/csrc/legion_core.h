@@ -26,6 +26,7 @@
 #include "sample_mode.h"
 #include "sample_plan.h"
 #include "pool_plan.h"
+#include "claim_rule.h"      // lg_tab_hash, the claim pair, lg_claim_at, LG_SLOT_LOSER: the formats the sampler's kernels talk through
 
 #define INTERBATCH_CON LEGION_INTERBATCH_CON
 #define INTRABATCH_CON LEGION_INTRABATCH_CON
@@ -74,12 +75,6 @@ static inline int64_t lg_feature_row_bytes(int32_t dtype, int32_t D)
 {
     return dtype == LEGION_FEATURE_BF16 ? (int64_t)lg_feature_pitch(dtype, D) * 2 : (int64_t)D * 4;
 }
-__host__ __device__ inline uint32_t lg_tab_hash(int32_t id)
-{
-    uint32_t x = (uint32_t)id;
-    x ^= x >> 16; x *= 0x7feb352du; x ^= x >> 15; x *= 0x846ca68bu; x ^= x >> 16;
-    return x;
-}
 
 // per-hop scratch written by the scan kernel, read by scatter / localise (device int32[16])
 enum HopScratch {
@@ -122,9 +117,7 @@ static_assert(BATCH_OP_STRIDE == INTRABATCH_CON, "batch_ops.h numbers the ops of
 // Feature-cache slot of a sampled neighbour, carried from the sampler to the gather (see "column slots", GraphStorage):
 // a value >= 0 or CACHEMISS_FLAG is what node_map[id] holds; LG_FS_UNKNOWN means "not carried: look it up"
 #define LG_FS_UNKNOWN (-3)
-// slot_dst[slot] of a hop: -1 no edge; v >= 0 the sampled neighbour; v < -1 the neighbour -2 - v, marked by the de-duplication as
-// NOT the first touch of a new vertex (an involution: the same expression marks and unmarks; every int32 vertex id fits)
-#define LG_SLOT_LOSER(v) (-2 - (v))
+// (slot_dst[slot] of a hop and its loser mark LG_SLOT_LOSER: claim_rule.h)
 
 // Per-vertex row header: where the adjacency of v lives (slot of the CSR pointer tables: P = the
 // full CSR, d < P = GPU d's cached CSR), its first edge and its degree.  One 16-byte read resolves
@@ -895,13 +888,6 @@ struct SeedParams {
 void launch_batch_generate(hipStream_t s, const SeedParams& p, const LanePtrs* d_lanes, int32_t n_lanes);
 
 void launch_end_of_batch(hipStream_t s, const LanePtrs* d_lanes, int32_t n_lanes, int32_t* iter_state);
-void launch_hotness_measure(hipStream_t s, const int32_t* sampled_ids, const int32_t* node_counter,
-                            unsigned long long* access_map);
-void init_row_headers(hipStream_t s, RowHdr* hdr, const int64_t* csr_index, int32_t n, int32_t slot);
-void cache_row_headers(hipStream_t s, RowHdr* hdr, const int32_t* QT, int32_t Kg, int32_t Ki, int32_t capacity,
-                       int32_t n, const int64_t* d_index, int32_t slot);
-void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* map32,
-                 const char* map8, int32_t* out32, char* out8);
 void launch_draw_batch(hipStream_t s, const int32_t* idx, const int32_t* deg, int32_t* out, int32_t n);
 void launch_draw_distinct_batch(hipStream_t s, const int32_t* base, const int32_t* deg, int32_t f, int32_t* out, int32_t n);
 // the weighted pick rule on its own (tests): out[i] = pick of slot idx[i] in the row {row_start[i], deg[i]} of cdf, or -1
@@ -1092,6 +1078,13 @@ double allreduce_u64_clique(const std::vector<int32_t>& devs, const std::vector<
                             const std::vector<unsigned long long*>& recv, int64_t count);
 
 // set-up kernels (kernels_cache.hip)
+void launch_hotness_measure(hipStream_t s, const int32_t* sampled_ids, const int32_t* node_counter,
+                            unsigned long long* access_map);
+void init_row_headers(hipStream_t s, RowHdr* hdr, const int64_t* csr_index, int32_t n, int32_t slot);
+void cache_row_headers(hipStream_t s, RowHdr* hdr, const int32_t* QT, int32_t Kg, int32_t Ki, int32_t capacity,
+                       int32_t n, const int64_t* d_index, int32_t slot);
+void launch_find(hipStream_t s, const int32_t* keys, int32_t n, const int32_t* map32,
+                 const char* map8, int32_t* out32, char* out8);
 void aggregate_access(hipStream_t s, unsigned long long* agg, const unsigned long long* add, int32_t n);
 void sort_hotness_desc(hipStream_t s, unsigned long long* keys_inout, int32_t* order_out, int32_t n);
 void inclusive_scan_u64(hipStream_t s, const unsigned long long* in, unsigned long long* out, int32_t n);

@@ -10,7 +10,7 @@
 
 #define LG_DISTINCT_MAX_FANOUT LEGION_DISTINCT_MAX_FANOUT   // largest fan-out of sampling without replacement (the sampler's LDS span of an entry's picks)
 
-// how a slot picks its adjacency position: draw_from_x / floyd_draw + floyd_resolve / the search of the prefix table (kernels_sample.hip)
+// how a slot picks its adjacency position: draw_from_x / floyd_draw + floyd_resolve / the search of the prefix table (draw_rule.h)
 enum class SampleDraw { Uniform, Distinct, Weighted };
 
 struct SampleMode {                 // MemoryPool's, and by value in HopParams: every lane of a launch samples with one mode

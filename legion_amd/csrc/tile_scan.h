@@ -1,7 +1,8 @@
 // tile_scan.h -- the scan pieces of a workgroup of 256 lanes (four waves of 64) over int32_t or int64_t sums, each once: the sum and the
 // exclusive prefix of one value per lane, and ONE workgroup's exclusive scan of at most 4 096 values in place.  Their users: row_offsets
-// and LABOR's second level (the int64 launches of kernels_in_edges.hip) and unique_ids (kernels_link.hip).  The sampler's and the weight
-// table's scans have other shapes and stay where they are.  Device code; include inside namespace lg's files after legion_core.h.
+// and LABOR's second level (the int64 launches of kernels_in_edges.hip) and unique_ids (kernels_link.hip).  The sampler's scans have
+// other shapes (one wave over its bucket counts) and share the wave step only, wave_inclusive; the weight table's stays where it is.
+// Device code; include inside namespace lg's files after legion_core.h.
 #pragma once
 
 #include <cstdint>
@@ -23,16 +24,24 @@ __device__ __forceinline__ T tile_sum(T v, T* s_wave)
     return sum;
 }
 
+// the sum of v over this lane of the wave and the lanes below it (lane = threadIdx.x & 63), exact in the first `width` lanes (a power of
+// two): every active lane of the wave calls it.  The sampler's three scans (kernels_sample.hip) use it too
+template <typename T>
+__device__ __forceinline__ T wave_inclusive(T v, int32_t lane, int32_t width = 64)
+{
+    for (int32_t off = 1; off < width; off <<= 1) {
+        const T y = __shfl_up(v, off, 64);
+        if (lane >= off) v += y;
+    }
+    return v;
+}
+
 // the sum of v over the lanes of the workgroup below this one (both barriers inside: every lane of the workgroup calls it)
 template <typename T>
 __device__ __forceinline__ T tile_exclusive(T v, T* s_wave)
 {
-    T inc = v;                                                        // inclusive over the wave
     const int32_t lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int32_t off = 1; off < 64; off <<= 1) {
-        const T y = __shfl_up(inc, off, 64);
-        if (lane >= off) inc += y;
-    }
+    const T inc = wave_inclusive(v, lane);
     if (lane == 63) s_wave[wave] = inc;
     __syncthreads();
     T before = inc - v;

@@ -1,4 +1,4 @@
-"""What the one-time set-up kernels (kernels_cache.hip, the tail of kernels_sample.hip, kernels_weights.hip) build, stated in plain numpy
+"""What the one-time set-up kernels (kernels_cache.hip, kernels_weights.hip) build, stated in plain numpy
 over whole arrays: the hotness order, the id -> slot maps of a clique fill and of the hybrid tier, a member's cached feature rows and cached
 CSR, the column-slot pairs, the row headers, and the per-row prefix-sum table.  tests/test_setup_ref_cpu.py holds every statement against
 the C oracle at a small size; the large GPU cases (tests/test_gpu_setup_stride.py, tests/test_gpu_weights_stride.py) then use both.

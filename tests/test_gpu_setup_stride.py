@@ -1,4 +1,4 @@
-"""The cache set-up chain (kernels_cache.hip, the tail of kernels_sample.hip) past every capped grid, against the C oracle and the numpy
+"""The cache set-up chain (kernels_cache.hip: the row headers, the hotness count and the find included) past every capped grid, against the C oracle and the numpy
 statements of tests/setup_ref.py, integer for integer and bit for bit.
 
 One world: N = 2^20 + 2^16 + 777 vertices of degree 2 and 3 alternating (E about 2.8 M: the later rows' edges lie past the 2 097 152 of one
