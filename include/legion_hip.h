@@ -127,6 +127,35 @@ const float* legion_graph_edge_cdf(const LegionGraphStorage* g);
  * `stream`; the result is read back -- set-up: the call synchronises that stream -- and remembered in the graph, so a repeat call
  * returns it without work.  1: sorted, 0: not, -1: a null graph.  legion_node2vec_walk asks for a remembered 1. */
 int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g, legion_stream_t stream);
+/* The reverse CSR (DGL's dgl.reverse; through it g.out_edges, g.out_degrees and g.successors), new in this build; no reference
+ * counterpart.  A row of the library's CSR is the destination side of an edge and a column entry its source side, so every op reads a
+ * vertex's in-edges; the reverse is a CSR of the same shape whose rows hold the out-edges, and every op works on it as it stands.
+ * (Where an op below lists out-edges under "Not offered", with or without "there is no reverse CSR", it speaks of that call on the
+ * graph it is given: the call on the reverse of the graph is the op over out-edges.)
+ * The rule.  N = node_num, E the column entries.  A LIVE entry is an e with 0 <= col[e] < N; dead entries (-1) and entries outside the
+ * graph are dropped, as everywhere else.  row(e) is the one v with indptr[v] <= e < indptr[v + 1] (-1 where an indptr that does not
+ * run from 0 to E leaves none).
+ *   rindptr int64[N + 1]:  rindptr[u] = #{ live e : col[e] < u };  rindptr[N] = E', the number of live entries;
+ *   reid    int64[E']:     the live e with col[e] == u, ASCENDING, at rindptr[u] <= p < rindptr[u + 1];
+ *   rcol    int32[E']:     rcol[p] = row(reid[p]).
+ * "Ascending" makes the result a function of the graph alone -- bit-identical from run to run, whatever order the atomics of the
+ * build arrived in -- and every reverse row sorted by vertex id, parallel edges in the order of their edge ids: the rows of the reverse
+ * are sorted in legion_graph_check_rows_sorted's sense.  If the graph has sorted rows and no dead entries, the reverse of the reverse
+ * is the graph itself and reid(reverse)[reid(reverse of reverse)[p]] == p.
+ * legion_graph_build_reverse reads the FULL CSR on the device current at the call and enqueues on `stream`.  It is set-up, like
+ * legion_graph_set_edge_weights and legion_graph_check_rows_sorted: it synchronises that stream (E', and the list of the rows too long
+ * for one workgroup's sort, are read back) and must not be captured.  The three arrays are plain allocations of the library, owned by
+ * the graph and freed by legion_graph_destroy; every temporary (N-sized cursors, the lists, a scratch as long as the long rows
+ * together -- nothing E-sized) is freed before the call returns.  Returns 0; a second call returns 0 without work.  Returns -1, with
+ * nothing enqueued and nothing allocated, for a null graph or N > LEGION_REVERSE_MAX_NODES (the reach of the two-level scan: 2^20 sums
+ * of 256 counts).  N == 0 or E == 0 gives rindptr all zero and E' = 0.
+ * legion_graph_reverse_csr returns E' and the three device pointers; before a build, and for a null graph, -1 and nulls.  Any
+ * out-pointer may be null.
+ * Not offered: N above 2^28; the reverse of a cached topology or of a partition; to_bidirected; pairing an edge with its reverse edge
+ * id (seed-edge exclusion); heterogeneous graphs; the server, the launcher and the wire. */
+#define LEGION_REVERSE_MAX_NODES (1 << 28)
+int32_t legion_graph_build_reverse(LegionGraphStorage* g, legion_stream_t stream);
+int64_t legion_graph_reverse_csr(const LegionGraphStorage* g, const int64_t** rindptr, const int32_t** rcol, const int64_t** reid);
 
 /* FeatureStorage: SS/storage/feature_storage.cu:18-90.  ids/labels are HOST arrays copied to
  * device `dev_id`; mode selects the training / validation / testing set. */

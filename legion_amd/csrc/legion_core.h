@@ -393,6 +393,11 @@ public:
     // it; RowsSorted: 1 / 0, or -1 before any check.  node2vec's membership test is a binary search of a row (legion_node2vec_walk).
     virtual int32_t CheckRowsSorted(hipStream_t s) = 0;
     virtual int32_t RowsSorted() const = 0;
+    // The reverse CSR (new): the transpose of the full CSR (the rule: legion_graph_build_reverse in legion_hip.h), three plain
+    // allocations on the device current at the first BuildReverse, which builds on `s` (set-up: it synchronises s) and returns 0; a
+    // second call returns 0 without work.  ReverseCSR: the live entries E' and the arrays, or -1 and nulls before a build.
+    virtual int32_t BuildReverse(hipStream_t s) = 0;
+    virtual int64_t ReverseCSR(const int64_t** rindptr, const int32_t** rcol, const int64_t** reid) const = 0;
     // "Column slots" (new): a copy of the full column array in which every entry is the pair {neighbour id, feature-cache
     // slot of that neighbour = node_map[id]} (8 bytes).  The sampler's scattered 4-byte pick costs a whole 64-byte sector
     // either way; read as 8 bytes it brings the neighbour's cache slot along for free, and the gather no longer fetches a
@@ -974,6 +979,12 @@ struct InEdgesParams {
     int64_t* eid;                   // int64[m], or null
 };
 void launch_in_edges(hipStream_t s, const InEdgesParams& p);
+
+// the reverse CSR (kernels_reverse.hip; the rule: legion_graph_build_reverse in legion_hip.h, its classes and refusals reverse_rule.h).
+// The arguments are the caller's to check.  Builds on s and synchronises it; returns the live entries E' and three allocations of
+// d_alloc_space on the current device: rindptr int64[node_num + 1], rcol int32[E'], reid int64[E'].  Its temporaries are freed
+int64_t build_reverse_csr(hipStream_t s, const int64_t* indptr, const int32_t* col, int32_t node_num, int64_t num_edges, int64_t** rindptr_out,
+                          int32_t** rcol_out, int64_t** reid_out);
 
 // the slots of a row expansion that a predicate keeps, compacted in order (kept_slots.h): what the count and the write pass of
 // LABOR and of induced subgraphs take beside their RowSlots

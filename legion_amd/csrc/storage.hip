@@ -9,6 +9,7 @@
 // device-dereferenceable pointers; the caller places them in HBM when they fit and in mapped
 // pinned memory otherwise.  Nothing here assumes which.
 #include "legion_core.h"
+#include "reverse_rule.h"
 #include <unistd.h>
 #include <algorithm>
 #include <map>
@@ -618,8 +619,35 @@ public:
     }
     int32_t RowsSorted() const override { return rows_sorted_; }
 
+    // the reverse CSR (legion_core.h): built once on the current device, owned here
+    int32_t BuildReverse(hipStream_t s) override
+    {
+        if (rev_edges_ >= 0) return 0;
+        HIP_CALL(hipGetDevice(&rev_dev_));
+        rev_edges_ = lg::build_reverse_csr(s, csr_node_index_cpu_, csr_dst_node_ids_cpu_, node_num_, edge_num_, &rev_indptr_, &rev_col_, &rev_eid_);
+        return 0;
+    }
+    int64_t ReverseCSR(const int64_t** rindptr, const int32_t** rcol, const int64_t** reid) const override
+    {
+        const bool built = rev_edges_ >= 0;
+        if (rindptr) *rindptr = built ? rev_indptr_ : nullptr;
+        if (rcol) *rcol = built ? rev_col_ : nullptr;
+        if (reid) *reid = built ? rev_eid_ : nullptr;
+        return built ? rev_edges_ : -1;
+    }
+
     void Finalize() override
     {
+        if (rev_edges_ >= 0) {
+            SetGPUDevice(rev_dev_);
+            HIP_CALL(hipDeviceSynchronize());
+            d_free_space(rev_indptr_);
+            d_free_space(rev_col_);
+            d_free_space(rev_eid_);
+            rev_indptr_ = rev_eid_ = nullptr;
+            rev_col_ = nullptr;
+            rev_edges_ = -1;
+        }
         if (edge_cdf_ != nullptr) {
             SetGPUDevice(edge_cdf_dev_);
             HIP_CALL(hipDeviceSynchronize());
@@ -683,6 +711,11 @@ private:
     int edge_cdf_dev_ = 0;
     int32_t rows_sorted_ = -1;           // CheckRowsSorted's answer, -1 before the first check
     bool weighted_used_ = false;         // a weighted hop has been enqueued against this graph: the table stays as it is
+    int64_t* rev_indptr_ = nullptr;      // [N + 1] the reverse CSR (BuildReverse), null before it
+    int32_t* rev_col_ = nullptr;         // [E']
+    int64_t* rev_eid_ = nullptr;         // [E']
+    int64_t rev_edges_ = -1;             // E', -1 before the build
+    int rev_dev_ = 0;
 };
 
 extern "C" GraphStorage* NewCompleteGraphStorage() { return new CompleteGraphStorage(); }
@@ -1040,6 +1073,24 @@ extern "C" int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g_, legion
 {
     GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
     return g ? g->CheckRowsSorted(static_cast<hipStream_t>(stream)) : -1;
+}
+
+// the reverse CSR: built once on `stream` on the current device (set-up: it synchronises that stream), owned by the graph
+extern "C" int32_t legion_graph_build_reverse(LegionGraphStorage* g_, legion_stream_t stream)
+{
+    GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
+    if (reverse_refusal(g != nullptr, g ? g->NodeNum() : 0) != ReverseRefusal::Ok) return -1;
+    return g->BuildReverse(static_cast<hipStream_t>(stream));
+}
+
+extern "C" int64_t legion_graph_reverse_csr(const LegionGraphStorage* g_, const int64_t** rindptr, const int32_t** rcol, const int64_t** reid)
+{
+    const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
+    if (g) return g->ReverseCSR(rindptr, rcol, reid);
+    if (rindptr) *rindptr = nullptr;
+    if (rcol) *rcol = nullptr;
+    if (reid) *reid = nullptr;
+    return -1;
 }
 
 extern "C" void legion_graph_destroy(LegionGraphStorage* g_)

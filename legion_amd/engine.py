@@ -941,6 +941,60 @@ class GraphStorage:
                 indptr = torch.zeros((k + 1,), dtype=torch.int64, device=dev)
         return (indptr, src, eids) if return_eids else (indptr, src)
 
+    REVERSE_MAX_NODES = 2 ** 28                      # LEGION_REVERSE_MAX_NODES
+
+    def reverse(self, stream=None):
+        """The graph with every edge turned round (DGL's dgl.reverse; the rule: legion_graph_build_reverse in legion_hip.h): a
+        GraphStorage whose row u holds the vertices that u's edges point to, sorted by the edges' positions in this graph's col, so
+        its rows are sorted by vertex id (rows_sorted() is True) and every method of this class works on it: a walk on it follows
+        the edges backwards, its in_edges are this graph's out-edges.  Dead (-1) column entries and entries outside the graph are
+        dropped.  .indptr int64 [N + 1], .col int32 [E'] and .eids int64 [E'] -- entry p of the reverse is entry eids[p] of this
+        graph's col -- are views of arrays the library owns; .parent is this graph, which stays alive with it.  Built on the device at
+        the first call (it synchronises `stream`, default the current one, and is not to be captured) and remembered: later calls
+        return the same object.  Edge weights do not travel by themselves: rev.set_edge_weights(w[rev.eids]) gives the reverse the
+        weights w of this graph's edges.  ValueError for more than REVERSE_MAX_NODES vertices."""
+        if getattr(self, "_reverse", None) is None:
+            if self.node_num > self.REVERSE_MAX_NODES:
+                raise ValueError(f"{self.node_num} vertices, at most {self.REVERSE_MAX_NODES} for a reverse")
+            dev = self.col.device
+            with torch.cuda.device(dev):
+                rc = self._lib.legion_graph_build_reverse(self.handle, _stream_handle(stream))
+            if rc != 0:
+                raise RuntimeError("legion_graph_build_reverse refused the graph")
+            a, b, c = ctypes.c_void_p(), ctypes.c_void_p(), ctypes.c_void_p()
+            live = int(self._lib.legion_graph_reverse_csr(self.handle, ctypes.byref(a), ctypes.byref(b), ctypes.byref(c)))
+            rev = GraphStorage(self.partition_count, device_view(a.value, (self.node_num + 1,), torch.int64, dev),
+                               device_view(b.value, (live,), torch.int32, dev))
+            rev.eids = device_view(c.value, (live,), torch.int64, dev)
+            rev.parent = self
+            self._reverse = rev
+        return self._reverse
+
+    def out_degrees(self, nodes, stream=None):
+        """The number of edges that leave each of nodes (DGL's g.out_degrees): int64 [n], by row_offsets on reverse() and a
+        difference; 0 for a node outside the graph.  nodes as rows in row_offsets.  The first call builds the reverse."""
+        nodes, n = self._check_rows(nodes, "nodes")
+        rev = self.reverse(stream)
+        offsets = rev._row_offsets(nodes.to(self.col.device).contiguous(), n, stream)
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            return offsets[1:] - offsets[:-1]
+
+    def out_edges(self, nodes, *, return_eids=False, stream=None):
+        """Every edge that leaves nodes (DGL's g.out_edges(nodes, form='all')): reverse().in_edges(nodes) and one index through
+        .eids.  nodes as rows in row_offsets.  Returns (src, dst) and with return_eids also eids: src, dst int32 [M] and eids int64
+        [M]; src[p] = i, the index into nodes (nodes[src] is the vertex, as in_edges' dst), dst[p] the vertex the edge points to and
+        eids[p] the edge's position in THIS graph's col: col[eids] == nodes[src], and find_edges(eids)'s row is dst.  The edges of
+        nodes[i] are consecutive, ordered by eids.  Like in_edges it synchronises `stream` (default: the current one); the first call
+        builds the reverse."""
+        _need_bool("return_eids", return_eids)
+        nodes, n = self._check_rows(nodes, "nodes")
+        rev = self.reverse(stream)
+        _, src, dst, at = rev._in_edges(nodes.to(self.col.device).contiguous(), n, return_eids, stream)
+        if not return_eids:
+            return src, dst
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            return src, dst, rev.eids[at]
+
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""
         return bool(self._lib.legion_graph_column_slots(self.handle, int(dev_id)))
@@ -955,6 +1009,10 @@ class GraphStorage:
         return index, device_view(b.value, (n,), torch.int32, dev)
 
     def close(self):
+        rev = getattr(self, "_reverse", None)
+        if rev is not None:                          # (its arrays are this graph's: they go with the handle below)
+            rev.close()
+            self._reverse = None
         if self.handle:
             self._lib.legion_graph_destroy(self.handle)
             self.handle = None

@@ -34,6 +34,8 @@ SIGNATURES = {
     "legion_graph_set_edge_weights": (c_i32, [c_p, c_p, c_p]),
     "legion_graph_edge_cdf": (c_p, [c_p]),
     "legion_graph_check_rows_sorted": (c_i32, [c_p, c_p]),
+    "legion_graph_build_reverse": (c_i32, [c_p, c_p]),
+    "legion_graph_reverse_csr": (c_i64, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p)]),
     "legion_feature_create": (c_p, [c_i32, c_i32, c_i32, c_p]),
     "legion_feature_set_ids": (None, [c_p, c_i32, c_i32, c_p, c_p, c_i32]),
     "legion_feature_destroy": (None, [c_p]),
