@@ -152,7 +152,9 @@ int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g, legion_stream_t st
  * legion_graph_reverse_csr returns E' and the three device pointers; before a build, and for a null graph, -1 and nulls.  Any
  * out-pointer may be null.
  * Not offered: N above 2^28; the reverse of a cached topology or of a partition; to_bidirected; pairing an edge with its reverse edge
- * id (seed-edge exclusion); heterogeneous graphs; the server, the launcher and the wire. */
+ * id (seed-edge exclusion); heterogeneous graphs; the server, the launcher and the wire.
+ * (The pairing exists since: legion_reverse_edge_ids, below, searches a row of this reverse CSR -- or of a graph with sorted rows -- for
+ * an edge's reverse edge id; "not offered" speaks of this call, which pairs nothing.) */
 #define LEGION_REVERSE_MAX_NODES (1 << 28)
 int32_t legion_graph_build_reverse(LegionGraphStorage* g, legion_stream_t stream);
 int64_t legion_graph_reverse_csr(const LegionGraphStorage* g, const int64_t** rindptr, const int32_t** rcol, const int64_t** reid);
@@ -653,7 +655,10 @@ int32_t legion_negative_sample(legion_stream_t stream, LegionGraphStorage* graph
  * m > LEGION_UNIQUE_MAX_IDS; scratch_bytes below legion_unique_ids_scratch_bytes(m); unique_out, local_out or count_out overlapping
  * ids.  m == 0 returns 0 and writes count_out[0] = 0 only.
  * Not offered by these three: excluding the seed edges from the sampled neighbourhood (a consumer masks by agg_edge_ids); device-resident
- * seed sets for BatchGenerate (legion_feature_set_ids still takes host arrays); the server, the launcher and the wire. */
+ * seed sets for BatchGenerate (legion_feature_set_ids still takes host arrays); the server, the launcher and the wire.
+ * (The exclusion exists since, as calls of its own: legion_reverse_edge_ids, legion_edge_set_build and legion_edge_filter_count /
+ * legion_edge_filter_edges, below, drop the seed edges and their reverses from an edge list -- a pool's consumer hands them the batch's
+ * agg_dst_ids, agg_src_ids and agg_edge_ids; these three ops still exclude nothing.) */
 #define LEGION_UNIQUE_MAX_IDS 1048576
 int64_t legion_unique_ids_scratch_bytes(int32_t m);
 int32_t legion_unique_ids(legion_stream_t stream, const int32_t* ids_devptr /* int32[m] */, int32_t m, int32_t* unique_out /* int32[m] */,
@@ -818,6 +823,88 @@ int32_t legion_induced_edges(legion_stream_t stream, LegionGraphStorage* graph, 
                              int64_t* eid_out /* int64[cap], or NULL */);
 int32_t legion_dst_offsets(legion_stream_t stream, const int32_t* dst_devptr /* int32[cap] */, int64_t cap,
                            const int64_t* count_devptr /* int64[1] */, int32_t n, int64_t* indptr_out /* int64[n + 1] */);
+/* Seed-edge exclusion (DGL's as_edge_prediction_sampler(exclude="self" | "reverse_id"), which runs ExcludeCertainEdges after
+ * sample_neighbors), new in this build; no reference counterpart.  Without it a link-prediction model sees the edge it is asked to
+ * predict.  Three pieces: the reverse edge id of an edge, a set of edge ids as an object of its own, and the filter that drops the set's
+ * members from an edge list.  All buffers are device memory.  Each op is enqueued on `stream`, on the device current at the call; nothing
+ * synchronises with the host, and each call may be captured into a graph.  An edge id is a position in col of the FULL CSR, int64: ids
+ * pass 2^32, and neither a key nor a hash is ever cut to 32 bits.  A CSR row is the dst side and a column entry the src side, as above.
+ *
+ * legion_reverse_edge_ids.  N = node_num, E the column entries.  For i in [0, n), e = eids[i]:
+ *   1. e < 0 or e >= E: reverse_out[i] = -1 -- no memory is read for e;
+ *   2. u = col[e]; u < 0 (a dead entry) or u >= N: reverse_out[i] = -1;
+ *   3. v = row(e), the one v with indptr[v] <= e < indptr[v + 1] (legion_find_edges' upper bound); none in [0, N): -1;
+ *   4. reverse_out[i] = the LEAST e' in row u (indptr[u] <= e' < indptr[u + 1]) with col[e'] == v; -1 if there is none.
+ * So edge e is v <- u and e' is u <- v.  A self-loop maps to the least parallel self-loop of its row, usually itself.  PARALLEL EDGES ALL
+ * MAP TO THE FIRST REVERSE EDGE: the k-th of several u -> v is not paired with the k-th of several v -> u, so rev(rev(e)) == e holds only
+ * where e is the least of its parallel edges.  For exclusion that is what is wanted of one id per edge; a caller that must exclude every
+ * parallel reverse edge excludes by vertex pair, which is not offered.  The result is a function of the graph alone: bit-identical from
+ * run to run.  reverse_out is int64[n].
+ * via chooses where rule 4 searches; both give the same reverse_out on a graph with sorted rows:
+ *   via == 0: a lower-bound search for v of row u of the graph itself.  Needs sorted rows: refused unless
+ *             legion_graph_check_rows_sorted has returned 1 for the graph, as legion_negative_sample's exclude & 2 is;
+ *   via == 1: a lower-bound search for u of row v of the reverse CSR, returning reid[position].  Reverse rows are sorted by vertex and,
+ *             within a vertex, by ascending edge id, so the first match is the least e'.  Needs legion_graph_build_reverse to have
+ *             built; works on unsorted rows.  The reverse CSR lives on the device that was current at its build: a via == 1 call is
+ *             made with that device current (it is not checked).
+ * One kernel: the upper bound over indptr, then the lower bound of the row, four ids per lane with their chains of dependent loads
+ * interleaved; rows of up to 2^31 - 1 entries.  Whatever eids holds, nothing outside eids, indptr, col and the reverse CSR is read.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null graph, eids_devptr or reverse_out; n < 0; n > 2^31 - 1; via
+ * outside {0, 1}; via == 0 on a graph whose rows have not been checked or are unsorted; via == 1 before the reverse is built.  n == 0
+ * returns 0 and enqueues nothing.
+ *
+ * The set.  eids is int64[k], 0 <= k <= LEGION_EDGE_SET_MAX_IDS (a million seed edges and their reverses).  An id is a member iff it is
+ * >= 0 and occurs in eids: negative entries are never inserted and never members, which covers the -1 of "no reverse edge".  Duplicates
+ * are fine.  The set lives in caller-held device memory, 8-byte aligned, of at least legion_edge_set_bytes(k) bytes: int64 keys[S], S the
+ * smallest power of two that is at least 256 and at least 2 k; -1 for k outside [0, LEGION_EDGE_SET_MAX_IDS].  It is an open-addressing
+ * table: the home slot of e is ((uint64)e * 0x9E3779B97F4A7C15) >> (64 - log2 S), probing is linear and wraps, at most S probes, an
+ * empty key is all-ones.
+ * legion_edge_set_build clears the table on `stream` itself and inserts every non-negative entry by a 64-bit compare-and-swap on the
+ * key.  Which slot a key lands in depends on the order in which the device takes the entries; membership does not, and nothing else of
+ * the table is specified.  k == 0 clears and nothing else.  Two sets in flight on different streams need memory of their own.
+ * legion_edge_set_contains: member_out[i] = 1 if ids[i] is a member, else 0, for i in [0, m); member_out is int32[m].  e >= 0 is tested
+ * before any probe; a probe stops at the key, at an empty key, or after S probes.  Whatever the set holds, nothing outside keys[0 .. S)
+ * is read.  k and set_bytes are those of the build.
+ * _build returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a null eids_devptr or set; k outside
+ * [0, LEGION_EDGE_SET_MAX_IDS]; set_bytes below legion_edge_set_bytes(k).  _contains likewise for: a null set, eids_devptr or member_out;
+ * k and set_bytes as above; m outside [0, 2^31 - 1].  m == 0 returns 0 and enqueues nothing.
+ *
+ * The filter.  The input is an edge list dst int32[m], src int32[m], eid int64[m]: the triples of legion_in_edges, legion_labor_edges,
+ * legion_induced_edges and the block ops.  Entry p is KEPT iff dst[p] >= 0 and eid[p] is not a member of the set.  So the -1 tail of a
+ * capacity call drops out, and a dead entry (src == -1) is kept unless its id is excluded.  The kept entries are written in the order of
+ * the list (stable) to dst_out / src_out / eid_out.  legion_edge_filter_count leaves in scratch the exclusive prefix sums of the kept
+ * counts per tile of 1 024 entries and their total K, and writes K to count_out[0] (int64[1]); legion_edge_filter_edges, given the same
+ * list and set and the scratch as _count left it, writes the kept triples to [0, min(K, cap)) and -1 / -1 / -1 to [K, cap): a capacity as
+ * in legion_labor_edges -- a triple whose position falls outside [0, cap) is dropped whatever the scratch holds, and the fill is clamped
+ * to [0, cap].  scratch: device memory, 8-byte aligned, of at least legion_edge_filter_scratch_bytes(m) bytes, LABOR's formula; -1 for m
+ * outside [0, LEGION_EDGE_FILTER_MAX_EDGES].
+ * Both return 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: a null dst_devptr, src_devptr, eid_devptr, set,
+ * scratch, count_out, dst_out or src_out (eid_out may be null); m outside [0, LEGION_EDGE_FILTER_MAX_EDGES]; k outside
+ * [0, LEGION_EDGE_SET_MAX_IDS]; set_bytes below legion_edge_set_bytes(k); cap outside [0, 2^31 - 1]; scratch_bytes below
+ * legion_edge_filter_scratch_bytes(m); an output that overlaps an input (cap entries against m entries; with cap == 0 or
+ * m == 0 there is no byte to share, and nothing overlaps).  m == 0: _count writes
+ * count_out[0] = 0 and a zero total only.  cap == 0 returns 0 and enqueues nothing.
+ * Not offered: rank-matched pairing of parallel edges (the k-th u -> v with the k-th v -> u); exclusion by vertex pair;
+ * exclude="reverse_types" and heterogeneous graphs; the filter inside the pool's hops or the launch group (a consumer of a pool with edge
+ * ids calls legion_edge_filter_count / _edges on the batch's arrays); a whole-graph reverse-id map; the server, the launcher and the
+ * wire. */
+#define LEGION_EDGE_SET_MAX_IDS 2097152
+#define LEGION_EDGE_FILTER_MAX_EDGES 1073741824
+int32_t legion_reverse_edge_ids(legion_stream_t stream, LegionGraphStorage* graph, const int64_t* eids_devptr /* int64[n] */, int64_t n,
+                                int32_t via, int64_t* reverse_out /* int64[n] */);
+int64_t legion_edge_set_bytes(int32_t k);
+int32_t legion_edge_set_build(legion_stream_t stream, const int64_t* eids_devptr /* int64[k] */, int32_t k, void* set, int64_t set_bytes);
+int32_t legion_edge_set_contains(legion_stream_t stream, const void* set /* as legion_edge_set_build left it */, int64_t set_bytes, int32_t k,
+                                 const int64_t* eids_devptr /* int64[m] */, int64_t m, int32_t* member_out /* int32[m] */);
+int64_t legion_edge_filter_scratch_bytes(int64_t m);
+int32_t legion_edge_filter_count(legion_stream_t stream, const int32_t* dst_devptr /* int32[m] */, const int32_t* src_devptr /* int32[m] */,
+                                 const int64_t* eid_devptr /* int64[m] */, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                                 int64_t* count_out /* int64[1] */, void* scratch, int64_t scratch_bytes);
+int32_t legion_edge_filter_edges(legion_stream_t stream, const int32_t* dst_devptr /* int32[m] */, const int32_t* src_devptr /* int32[m] */,
+                                 const int64_t* eid_devptr /* int64[m] */, int64_t m, const void* set, int64_t set_bytes, int32_t k,
+                                 const void* scratch /* as legion_edge_filter_count left it */, int64_t scratch_bytes, int64_t cap,
+                                 int32_t* dst_out /* int32[cap] */, int32_t* src_out /* int32[cap] */,
+                                 int64_t* eid_out /* int64[cap], or NULL */);
 /* The k best entries of each row (DGL's dgl.sampling.select_topk, and sample_neighbors(prob=w, replace=False): weighted sampling
  * WITHOUT replacement), new in this build; no reference counterpart.  One selection kernel, the k smallest keys of a row; only the key
  * differs between the modes.  Orientation, N, rows, the buffers, the stream, capture and the FULL CSR are as for legion_in_edges: a CSR

@@ -18,7 +18,7 @@ BIN = os.path.join(HERE, "bin", "sampling_server")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels_sample.hip", "kernels_gather.hip", "kernels_cache.hip", "kernels_weights.hip", "kernels_walk.hip", "kernels_pinsage.hip", "kernels_node2vec.hip", "kernels_link.hip", "kernels_in_edges.hip", "kernels_labor.hip", "kernels_induced.hip", "kernels_topk.hip", "kernels_reverse.hip", "kernels_synth.hip",
+SOURCES = ["kernels_sample.hip", "kernels_gather.hip", "kernels_cache.hip", "kernels_weights.hip", "kernels_walk.hip", "kernels_pinsage.hip", "kernels_node2vec.hip", "kernels_link.hip", "kernels_in_edges.hip", "kernels_labor.hip", "kernels_induced.hip", "kernels_topk.hip", "kernels_reverse.hip", "kernels_exclude.hip", "kernels_synth.hip",
            "storage.hip", "tuning.hip", "link_counters.hip", "collective.hip", "markers.hip", "cache.hip", "operators.hip", "pipeline.hip", "ipc_env.hip", "server.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-Wall",
          "-Wno-unused-result", "-Wno-unused-function"] + os.environ.get("LEGION_EXTRA_HIPCC_FLAGS", "").split()

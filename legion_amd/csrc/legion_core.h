@@ -1041,6 +1041,42 @@ void launch_induced_edges(hipStream_t s, const InducedParams& p);
 // indptr[i] = #{ p in [0, L) : dst[p] < i } for i in [0, n], L = count[0] clamped to [0, cap]
 void launch_dst_offsets(hipStream_t s, const int32_t* dst, int64_t cap, const int64_t* count, int32_t n, int64_t* indptr);
 
+// seed-edge exclusion (kernels_exclude.hip; the rules: legion_reverse_edge_ids .. legion_edge_filter_edges in legion_hip.h, their text
+// exclude_rule.h).  The arguments are the caller's to check (exclude_rule.h).
+struct ReverseIdsParams {
+    const int64_t* indptr;          // the FULL CSR: row(e) and col[e] come from it
+    const int32_t* col;
+    const int64_t* t_indptr;        // the CSR whose rows are searched: the graph's own (via 0) or the reverse CSR (via 1)
+    const int32_t* t_col;
+    const int64_t* t_eid;           // reid of the reverse CSR (via 1); via 0: a position in t_col is the edge id
+    const int64_t* eids;            // int64[n]
+    int64_t* out;                   // int64[n]
+    int64_t num_edges;
+    int64_t n;                      // <= 2^31 - 1
+    int32_t node_num;
+    int32_t via;                    // 0, 1
+};
+void launch_reverse_edge_ids(hipStream_t s, const ReverseIdsParams& p);
+// a set of edge ids in the caller's memory: int64 keys[S], an empty key all-ones
+struct EdgeSetView {
+    const int64_t* keys;
+    uint64_t mask;                  // S - 1
+    int32_t shift;                  // 64 - log2 S
+};
+// set: edge_set_bytes(k) bytes, cleared here on s
+void launch_edge_set_build(hipStream_t s, const int64_t* eids, int32_t k, void* set);
+void launch_edge_set_contains(hipStream_t s, const EdgeSetView& set, const int64_t* eids, int64_t m, int32_t* out);
+struct EdgeFilterParams {
+    const int32_t* dst;             // int32[m]: the list to filter
+    const int32_t* src;             // int32[m]
+    const int64_t* eid;             // int64[m]
+    int64_t m;                      // <= 2^30
+    EdgeSetView set;
+    KeptParams kept;
+};
+void launch_edge_filter_count(hipStream_t s, const EdgeFilterParams& p);
+void launch_edge_filter_edges(hipStream_t s, const EdgeFilterParams& p);
+
 // the k best entries of each row (kernels_topk.hip; the rule: legion_row_topk and legion_topk_keys in legion_hip.h, its text
 // topk_rule.h).  The arguments are the caller's to check (topk_rule.h).
 struct TopkParams {

@@ -22,6 +22,7 @@
 #include "labor_rule.h"
 #include "topk_rule.h"
 #include "induced_rule.h"
+#include "exclude_rule.h"
 #include "node_set.h"
 
 #include <iostream>
@@ -710,6 +711,101 @@ extern "C" int32_t legion_dst_offsets(legion_stream_t stream, const int32_t* dst
     if (!dst_devptr || !count_devptr || !indptr_out) return -1;
     if (dst_offsets_refusal(cap, n) != InducedRefusal::Ok) return -1;
     lg::launch_dst_offsets(static_cast<hipStream_t>(stream), dst_devptr, cap, count_devptr, n, indptr_out);
+    return 0;
+}
+
+// Seed-edge exclusion (the rules: legion_hip.h; the set's size, the refusals and the scratch size: exclude_rule.h).  As above: every
+// check comes before the launch.
+extern "C" int32_t legion_reverse_edge_ids(legion_stream_t stream, LegionGraphStorage* graph_, const int64_t* eids_devptr, int64_t n,
+                                           int32_t via, int64_t* reverse_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (!graph || !eids_devptr || !reverse_out) return -1;
+    const int64_t* rindptr = nullptr;
+    const int32_t* rcol = nullptr;
+    const int64_t* reid = nullptr;
+    const bool have_reverse = graph->ReverseCSR(&rindptr, &rcol, &reid) >= 0;
+    if (reverse_edge_ids_refusal(n, via, graph->RowsSorted(), have_reverse) != ExcludeRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    lg::ReverseIdsParams p;
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.t_indptr = via == 0 ? p.indptr : rindptr;
+    p.t_col = via == 0 ? p.col : rcol;
+    p.t_eid = via == 0 ? nullptr : reid;
+    p.eids = eids_devptr;
+    p.out = reverse_out;
+    p.num_edges = graph->EdgeNum();
+    p.n = n;
+    p.node_num = graph->NodeNum();
+    p.via = via;
+    lg::launch_reverse_edge_ids(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+extern "C" int64_t legion_edge_set_bytes(int32_t k)
+{
+    return edge_set_bytes(k);
+}
+
+// the set in the caller's memory (k, set_bytes legal)
+static lg::EdgeSetView edge_set_view(const void* set, int32_t k)
+{
+    const int64_t slots = edge_set_slots(k);
+    return lg::EdgeSetView{.keys = static_cast<const int64_t*>(set), .mask = (uint64_t)(slots - 1), .shift = edge_set_shift(slots)};
+}
+
+extern "C" int32_t legion_edge_set_build(legion_stream_t stream, const int64_t* eids_devptr, int32_t k, void* set, int64_t set_bytes)
+{
+    if (!eids_devptr || !set) return -1;
+    if (edge_set_build_refusal(k, set_bytes) != ExcludeRefusal::Ok) return -1;
+    lg::launch_edge_set_build(static_cast<hipStream_t>(stream), eids_devptr, k, set);
+    return 0;
+}
+
+extern "C" int32_t legion_edge_set_contains(legion_stream_t stream, const void* set, int64_t set_bytes, int32_t k, const int64_t* eids_devptr,
+                                            int64_t m, int32_t* member_out)
+{
+    if (!set || !eids_devptr || !member_out) return -1;
+    if (edge_set_contains_refusal(k, set_bytes, m) != ExcludeRefusal::Ok) return -1;
+    if (m == 0) return 0;
+    lg::launch_edge_set_contains(static_cast<hipStream_t>(stream), edge_set_view(set, k), eids_devptr, m, member_out);
+    return 0;
+}
+
+extern "C" int64_t legion_edge_filter_scratch_bytes(int64_t m)
+{
+    return edge_filter_scratch_bytes(m);
+}
+
+static lg::EdgeFilterParams edge_filter_params(const int32_t* dst, const int32_t* src, const int64_t* eid, int64_t m, const void* set, int32_t k,
+                                               const lg::KeptParams& kept)
+{
+    return lg::EdgeFilterParams{.dst = dst, .src = src, .eid = eid, .m = m, .set = edge_set_view(set, k), .kept = kept};
+}
+
+extern "C" int32_t legion_edge_filter_count(legion_stream_t stream, const int32_t* dst_devptr, const int32_t* src_devptr, const int64_t* eid_devptr,
+                                            int64_t m, const void* set, int64_t set_bytes, int32_t k, int64_t* count_out, void* scratch,
+                                            int64_t scratch_bytes)
+{
+    if (!dst_devptr || !src_devptr || !eid_devptr || !set || !count_out || !scratch) return -1;
+    if (edge_filter_count_refusal(m, k, set_bytes, scratch_bytes) != ExcludeRefusal::Ok) return -1;
+    const lg::KeptParams kept = kept_params(m, scratch, count_out, 0, nullptr, nullptr, nullptr);
+    lg::launch_edge_filter_count(static_cast<hipStream_t>(stream), edge_filter_params(dst_devptr, src_devptr, eid_devptr, m, set, k, kept));
+    return 0;
+}
+
+extern "C" int32_t legion_edge_filter_edges(legion_stream_t stream, const int32_t* dst_devptr, const int32_t* src_devptr, const int64_t* eid_devptr,
+                                            int64_t m, const void* set, int64_t set_bytes, int32_t k, const void* scratch, int64_t scratch_bytes,
+                                            int64_t cap, int32_t* dst_out, int32_t* src_out, int64_t* eid_out)
+{
+    if (!dst_devptr || !src_devptr || !eid_devptr || !set || !scratch || !dst_out || !src_out) return -1;
+    const uint64_t in[3] = {(uint64_t)(uintptr_t)dst_devptr, (uint64_t)(uintptr_t)src_devptr, (uint64_t)(uintptr_t)eid_devptr};
+    const uint64_t out[3] = {(uint64_t)(uintptr_t)dst_out, (uint64_t)(uintptr_t)src_out, (uint64_t)(uintptr_t)eid_out};
+    if (edge_filter_edges_refusal(m, k, set_bytes, scratch_bytes, cap, in, out) != ExcludeRefusal::Ok) return -1;
+    if (cap == 0) return 0;
+    const lg::KeptParams kept = kept_params(m, scratch, nullptr, cap, dst_out, src_out, eid_out);
+    lg::launch_edge_filter_edges(static_cast<hipStream_t>(stream), edge_filter_params(dst_devptr, src_devptr, eid_devptr, m, set, k, kept));
     return 0;
 }
 

@@ -299,6 +299,99 @@ class NodeSet:
         return local
 
 
+EDGE_SET_MAX_IDS = 2 ** 21                           # LEGION_EDGE_SET_MAX_IDS
+EDGE_FILTER_MAX_EDGES = 2 ** 30                      # LEGION_EDGE_FILTER_MAX_EDGES
+
+
+class EdgeIdSet:
+    """A set of edge ids on the device (the rule: legion_edge_set_build / legion_edge_set_contains in legion_hip.h): an
+    open-addressing table of int64 keys that answers "is e a member?".  eids: int64 positions in a graph's col, a CUDA tensor (its
+    device is used) or anything torch.as_tensor takes (`device`, default: the current one); at most EDGE_SET_MAX_IDS of them
+    (ValueError before anything touches a device); they may repeat, and negative entries -- the -1 of an edge without a reverse -- are
+    members of nothing.  .eids: the ids on the device; .k: their number.  The table is built on `stream` (default: the current one);
+    a set is what exclude_edges and the block ops' exclude_eids take, and may be used any number of times."""
+
+    def __init__(self, eids, device=None, stream=None):
+        eids = _as_1d(eids, torch.int64, "eids")
+        k = int(eids.numel())
+        if k > EDGE_SET_MAX_IDS:
+            raise ValueError(f"{k} edge ids in one set, at most {EDGE_SET_MAX_IDS}")
+        self._lib = _libmod.load()
+        if eids.is_cuda:
+            dev = eids.device
+        else:
+            dev = torch.device(device) if device is not None else torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.eids = eids.to(dev).contiguous()
+        self.k = k
+        self.set_bytes = int(self._lib.legion_edge_set_bytes(k))
+        self.table = torch.empty((self.set_bytes // 8,), dtype=torch.int64, device=dev)
+        src = self.eids if k > 0 else self.table             # (an empty tensor has no address to hand over; k == 0 reads nothing)
+        _enqueue(self._lib, "legion_edge_set_build", "EdgeIdSet", dev, stream, (_ptr(src), k, _ptr(self.table), self.set_bytes),
+                 (self.eids, self.table))
+
+    def contains(self, eids, stream=None):
+        """Is eids[i] a member, for every i: int32 [m] of 0 / 1; 0 for a negative id.  eids: int64, a CUDA tensor or anything
+        torch.as_tensor takes.  No sync.  Enqueued on `stream` (default: the current one)."""
+        eids = _as_1d(eids, torch.int64, "eids")
+        m = int(eids.numel())
+        eids = eids.to(self.device).contiguous()
+        member = torch.empty((m,), dtype=torch.int32, device=self.device)
+        if m == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return member
+        _enqueue(self._lib, "legion_edge_set_contains", "EdgeIdSet.contains", self.device, stream,
+                 (_ptr(self.table), self.set_bytes, self.k, _ptr(eids), m, _ptr(member)), (self.table, eids, member))
+        return member
+
+
+def _need_edge_set(edge_set, name="edge_set"):
+    if not isinstance(edge_set, EdgeIdSet):
+        raise ValueError(f"{name} must be an EdgeIdSet, not {type(edge_set).__name__}")
+
+
+def _filter_edges(dst, src, eids, edge_set, stream):
+    """exclude_edges' work on checked arguments: dst, src, eids on the set's device, contiguous, of one length m <= 2^30.  Returns
+    (dst, src, eids, K's device tensor or None)."""
+    L, dev, m = edge_set._lib, edge_set.device, int(dst.numel())
+    K, count = 0, None
+    if m > 0:
+        nbytes = int(L.legion_edge_filter_scratch_bytes(m))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+        count = torch.empty((1,), dtype=torch.int64, device=dev)
+        head = (_ptr(dst), _ptr(src), _ptr(eids), m, _ptr(edge_set.table), edge_set.set_bytes, edge_set.k)
+        _enqueue(L, "legion_edge_filter_count", "exclude_edges", dev, stream, head + (_ptr(count), _ptr(scratch), nbytes),
+                 (dst, src, eids, edge_set.table, count, scratch))
+        K = _read_scalar(count[0], stream)
+    out = (torch.empty((K,), dtype=torch.int32, device=dev), torch.empty((K,), dtype=torch.int32, device=dev),
+           torch.empty((K,), dtype=torch.int64, device=dev))
+    if K > 0:
+        _enqueue(L, "legion_edge_filter_edges", "exclude_edges", dev, stream,
+                 head + (_ptr(scratch), nbytes, K, _ptr(out[0]), _ptr(out[1]), _ptr(out[2])), (dst, src, eids, edge_set.table, scratch) + out)
+    return out + (count,)
+
+
+def exclude_edges(dst, src, eids, edge_set, stream=None):
+    """An edge list without the edges of a set (DGL's ExcludeCertainEdges after sample_neighbors; the rule: legion_edge_filter_count
+    and legion_edge_filter_edges in legion_hip.h).  dst, src: int32 [m]; eids: int64 [m] -- the triples in_edges, labor_edges,
+    induced_edges and the block ops return with return_eids, or a pool's agg_dst_ids, agg_src_ids and agg_edge_ids; CUDA tensors or
+    anything torch.as_tensor takes; at most EDGE_FILTER_MAX_EDGES entries.  edge_set: an EdgeIdSet (GraphStorage.seed_edge_exclusion
+    makes one of a batch's seed edges).  Entry p is kept iff dst[p] >= 0 and eids[p] is no member: the -1 tail of a capacity call
+    drops out, a dead entry (src == -1) stays unless its id is excluded.  Returns (dst, src, eids) of the kept entries, in their
+    order, sized exactly: the kept number is read back to the host once, so the call synchronises `stream` (default: the current
+    one), on which everything is enqueued.  A capturing caller uses the C ABI with a capacity instead."""
+    dst = _as_1d(dst, torch.int32, "dst")
+    src = _as_1d(src, torch.int32, "src")
+    eids = _as_1d(eids, torch.int64, "eids")
+    _need_edge_set(edge_set)
+    m = int(dst.numel())
+    if int(src.numel()) != m or int(eids.numel()) != m:
+        raise ValueError(f"dst, src and eids must have one length, not {m}, {int(src.numel())} and {int(eids.numel())}")
+    if m > EDGE_FILTER_MAX_EDGES:
+        raise ValueError(f"{m} edges in one call, at most {EDGE_FILTER_MAX_EDGES}")
+    dev = edge_set.device
+    return _filter_edges(dst.to(dev).contiguous(), src.to(dev).contiguous(), eids.to(dev).contiguous(), edge_set, stream)[:3]
+
+
 class GraphStorage:
     """Full CSR (slot P of the pointer tables) from device tensors: indptr int64[N+1], col int32[E]."""
 
@@ -643,7 +736,24 @@ class GraphStorage:
             raise ValueError("the seeds of a block must be distinct vertices of the graph: one repeats or lies outside it")
         return unique[:U], local[n:]
 
-    def full_neighbor_block(self, seeds, *, return_eids=False, stream=None):
+    def _check_exclude_eids(self, exclude_eids):
+        """A block op's exclude_eids, before anything touches a device: None or an EdgeIdSet on the graph's device, else ValueError."""
+        if exclude_eids is None:
+            return
+        _need_edge_set(exclude_eids, "exclude_eids")
+        if exclude_eids.device != self.col.device:
+            raise ValueError(f"the EdgeIdSet lives on {exclude_eids.device}, the graph on {self.col.device}")
+
+    def _without_excluded(self, n, dst, src, eids, exclude_eids, stream):
+        """What the block ops share of exclude_eids: the list (on the device, with edge ids) through the filter (_filter_edges), then
+        the check the op made without a limit.  Returns (dst, src, eids, K's device tensor or None)."""
+        dst, src, eids, count = _filter_edges(dst.contiguous(), src.contiguous(), eids.contiguous(), exclude_eids, stream)
+        K = int(dst.numel())
+        if n + K > UNIQUE_MAX_IDS:
+            raise ValueError(f"{n} seeds and their {K} entries left are {n + K} ids in one call, at most {UNIQUE_MAX_IDS}")
+        return dst, src, eids, count
+
+    def full_neighbor_block(self, seeds, *, return_eids=False, exclude_eids=None, stream=None):
         """The block of all in-edges of seeds (DGL's MultiLayerFullNeighborSampler(1), or dgl.in_subgraph followed by to_block): in_edges,
         then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph, as rows in row_offsets.  Returns (input_nodes,
         dst_local, src_local, offsets) and with return_eids also eids: input_nodes int32 [U], the distinct vertices, the seeds first
@@ -652,12 +762,24 @@ class GraphStorage:
         returns them.  input_nodes is what FeatureStorage.set_ids takes, or what a feature table is indexed with.  ValueError if the
         seeds and their entries are more than UNIQUE_MAX_IDS ids (before any device work beyond the offsets), and if a seed repeats or
         lies outside the graph: a block's dst nodes are distinct.  Reads back offsets[n], the seeds' local indices and the number of
-        distinct vertices: it synchronises `stream` (default: the current one)."""
+        distinct vertices: it synchronises `stream` (default: the current one).  exclude_eids: an EdgeIdSet (seed_edge_exclusion makes
+        one of a batch's seed edges) whose members are dropped from the edges before the block is made (DGL's exclude= of
+        as_edge_prediction_sampler): M is then the number of edges left, offsets their rows' prefix sums, and the id limit applies to
+        what is left; None: nothing is dropped."""
         _need_bool("return_eids", return_eids)
+        self._check_exclude_eids(exclude_eids)
         seeds, n = self._check_rows(seeds, "seeds")
         _check_unique(n)
         seeds = seeds.to(self.col.device).contiguous()
-        offsets, dst, src, eids = self._in_edges(seeds, n, return_eids, stream, limit=UNIQUE_MAX_IDS)
+        if exclude_eids is None:
+            offsets, dst, src, eids = self._in_edges(seeds, n, return_eids, stream, limit=UNIQUE_MAX_IDS)
+        else:
+            _, dst, src, eids = self._in_edges(seeds, n, True, stream)
+            if int(dst.numel()) > EDGE_FILTER_MAX_EDGES:
+                raise ValueError(f"the seeds hold {int(dst.numel())} entries, at most 2^30 a call with exclude_eids")
+            dst, src, eids, count = self._without_excluded(n, dst, src, eids, exclude_eids, stream)
+            offsets = self._dst_offsets(dst, count, n, stream)
+            eids = eids if return_eids else None
         input_nodes, src_local = self._block_tail(seeds, n, src, stream)
         out = (input_nodes, dst, src_local, offsets)
         return out + (eids,) if return_eids else out
@@ -733,7 +855,7 @@ class GraphStorage:
         out = self._labor_edges(rows.to(self.col.device).contiguous(), n, fanout, salt, return_eids, stream)
         return out if return_eids else out[:2]
 
-    def labor_block(self, seeds, fanout, *, salt=0, return_eids=False, stream=None):
+    def labor_block(self, seeds, fanout, *, salt=0, return_eids=False, exclude_eids=None, stream=None):
         """The block of a LABOR-0 layer (DGL's LaborSampler with one fan-out): labor_edges, then unique_ids over [seeds | src].  seeds:
         distinct int32 vertices of the graph.  Returns (input_nodes, dst_local, src_local) and with return_eids also eids: input_nodes
         int32 [U], the seeds first and in their order, then the other kept sources in order of first appearance; dst_local, src_local
@@ -742,12 +864,19 @@ class GraphStorage:
         batch is LABOR's layer dependency (the same r_t in all layers: a vertex kept in one layer tends to be kept in the next, which
         is what keeps the input nodes few); a new salt per batch is the caller's to choose.  ValueError if the seeds and their kept
         entries are more than UNIQUE_MAX_IDS ids, and if a seed repeats or lies outside the graph, as full_neighbor_block.
-        Synchronises `stream` (default: the current one)."""
+        Synchronises `stream` (default: the current one).  exclude_eids: as in full_neighbor_block -- the set's members are dropped
+        from the kept edges (the sampling itself does not look at the set: as DGL, which excludes after sample_neighbors)."""
         self._check_labor(fanout, salt, return_eids)
+        self._check_exclude_eids(exclude_eids)
         seeds, n = self._check_rows(seeds, "seeds")
         _check_unique(n)
         seeds = seeds.to(self.col.device).contiguous()
-        dst, src, eids = self._labor_edges(seeds, n, fanout, salt, return_eids, stream, limit=UNIQUE_MAX_IDS)
+        if exclude_eids is None:
+            dst, src, eids = self._labor_edges(seeds, n, fanout, salt, return_eids, stream, limit=UNIQUE_MAX_IDS)
+        else:
+            dst, src, eids = self._labor_edges(seeds, n, fanout, salt, True, stream)
+            dst, src, eids = self._without_excluded(n, dst, src, eids, exclude_eids, stream)[:3]
+            eids = eids if return_eids else None
         input_nodes, src_local = self._block_tail(seeds, n, src, stream)
         out = (input_nodes, dst, src_local)
         return out + (eids,) if return_eids else out
@@ -827,7 +956,7 @@ class GraphStorage:
         out = self._row_topk(rows.to(self.col.device).contiguous(), n, fanout, self.TOPK_SAMPLE, w, salt, return_eids, stream)
         return out if return_eids else out[:2]
 
-    def sample_distinct_block(self, seeds, fanout, *, weights=None, salt=0, return_eids=False, stream=None):
+    def sample_distinct_block(self, seeds, fanout, *, weights=None, salt=0, return_eids=False, exclude_eids=None, stream=None):
         """The block of one layer sampled by sample_distinct (DGL's NeighborSampler with one fan-out and prob=): the picks with src >= 0,
         then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph.  Returns (input_nodes, dst_local, src_local)
         and with return_eids also eids, in labor_block's layout: input_nodes int32 [U], the seeds first and in their order, then the
@@ -835,26 +964,32 @@ class GraphStorage:
         also the index into seeds, non-decreasing); eids int64 [K].  input_nodes is what FeatureStorage.set_ids takes, and the seeds
         of the next layer out.  A new salt per batch and per layer is the caller's to choose.  ValueError if the seeds and their picks
         could be more than UNIQUE_MAX_IDS ids, and if a seed repeats or lies outside the graph, as full_neighbor_block.  Synchronises
-        `stream` (default: the current one)."""
+        `stream` (default: the current one).  exclude_eids: as in full_neighbor_block -- the set's members are dropped from the picks
+        (a row then has fewer than its counts: as DGL, which excludes after sample_neighbors)."""
         self._check_topk(fanout, "fanout", salt, return_eids)
+        self._check_exclude_eids(exclude_eids)
         seeds, n = self._check_rows(seeds, "seeds")
         _check_unique(n)
         if n + n * int(fanout) > UNIQUE_MAX_IDS:
             raise ValueError(f"{n} seeds and up to {n * int(fanout)} picks are {n + n * int(fanout)} ids in one call, at most {UNIQUE_MAX_IDS}")
         w = self._topk_weights(weights) if weights is not None else None
         seeds = seeds.to(self.col.device).contiguous()
-        src, _, eids = self._row_topk(seeds, n, fanout, self.TOPK_SAMPLE, w, salt, return_eids, stream)
+        with_eids = return_eids or exclude_eids is not None
+        src, _, eids = self._row_topk(seeds, n, fanout, self.TOPK_SAMPLE, w, salt, with_eids, stream)
 
         def mask():
             keep = src >= 0
             dst = torch.nonzero(keep)[:, 0].to(torch.int32)
-            return dst, src[keep], eids[keep] if return_eids else None
+            return dst, src[keep], eids[keep] if with_eids else None
 
         if stream is None:
             dst, picked, eids = mask()
         else:
             with torch.cuda.stream(stream):
                 dst, picked, eids = mask()
+        if exclude_eids is not None:
+            dst, picked, eids = self._without_excluded(n, dst, picked, eids, exclude_eids, stream)[:3]
+            eids = eids if return_eids else None
         input_nodes, src_local = self._block_tail(seeds, n, picked, stream)
         out = (input_nodes, dst, src_local)
         return out + (eids,) if return_eids else out
@@ -994,6 +1129,64 @@ class GraphStorage:
             return src, dst
         with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
             return src, dst, rev.eids[at]
+
+    def _dst_offsets(self, dst, count, n, stream):
+        """The row pointers int64 [n + 1] of a non-decreasing dst (on the device) whose length is count's value (a device tensor, or
+        None with an empty dst): legion_dst_offsets."""
+        dev, K = self.col.device, int(dst.numel())
+        if K > 0:
+            indptr = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+            _enqueue(self._lib, "legion_dst_offsets", "dst_offsets", dev, stream, (_ptr(dst), K, _ptr(count), n, _ptr(indptr)),
+                     (dst, count, indptr))
+            return indptr
+        with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            return torch.zeros((n + 1,), dtype=torch.int64, device=dev)
+
+    REVERSE_IDS_MAX = 2 ** 31 - 1                    # legion_reverse_edge_ids' n
+
+    def reverse_edge_ids(self, eids, stream=None):
+        """The reverse edge id of each edge (the pairing behind DGL's exclude="reverse_id"; the rule: legion_reverse_edge_ids in
+        legion_hip.h).  eids: int64 positions in col, a CUDA tensor or anything torch.as_tensor takes.  Returns int64 [n]: for the edge
+        e = eids[i] from u = col[e] into v, its row, the LEAST position e' in row u with col[e'] == v -- the first edge from v into
+        u; -1 for an e outside [0, E), for a dead entry or one that points outside the graph, and where no reverse edge exists.
+        Parallel edges all map to the first reverse edge (no rank-matched pairing: reverse_edge_ids of the result gives e back only
+        for the least of its parallel edges); a self-loop maps to the least self-loop of its row.  The same graph gives the same
+        answer, bit for bit.  With sorted rows (rows_sorted() is asked here) the graph's own rows are searched; otherwise reverse() is
+        built -- set-up: it synchronises `stream` -- and its rows are.  Enqueued on `stream` (default: the current one)."""
+        eids = _as_1d(eids, torch.int64, "eids")
+        n = int(eids.numel())
+        if n > self.REVERSE_IDS_MAX:
+            raise ValueError(f"{n} edge ids in one call, at most 2^31 - 1")
+        dev = self.col.device
+        eids = eids.to(dev).contiguous()
+        out = torch.empty((n,), dtype=torch.int64, device=dev)
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return out
+        via = 0 if self.rows_sorted(stream) else 1
+        if via == 1:
+            self.reverse(stream)
+        _enqueue(self._lib, "legion_reverse_edge_ids", "reverse_edge_ids", dev, stream, (self.handle, _ptr(eids), n, via, _ptr(out)), (eids, out))
+        return out
+
+    def seed_edge_exclusion(self, eids, exclude="self", stream=None):
+        """The set of edges a link-prediction batch must not see (DGL's as_edge_prediction_sampler(exclude=...)): an EdgeIdSet to hand
+        to full_neighbor_block, labor_block and sample_distinct_block as exclude_eids, or to exclude_edges.  eids: the batch's seed
+        edges, int64, at most EDGE_SET_MAX_IDS with their reverses.  exclude="self": the set holds the seed edges; "reverse_id": the
+        seed edges and reverse_edge_ids of them (an edge without a reverse adds nothing).  Anything else is a ValueError, before
+        anything touches a device.  Enqueued on `stream` (default: the current one); no sync beyond reverse_edge_ids' set-up."""
+        if not isinstance(exclude, str) or exclude not in ("self", "reverse_id"):
+            raise ValueError(f'exclude must be "self" or "reverse_id", not {exclude!r}')
+        eids = _as_1d(eids, torch.int64, "eids")
+        k = int(eids.numel()) * (2 if exclude == "reverse_id" else 1)
+        if k > EDGE_SET_MAX_IDS:
+            raise ValueError(f"{k} edge ids in one set, at most {EDGE_SET_MAX_IDS}")
+        dev = self.col.device
+        eids = eids.to(dev).contiguous()
+        if exclude == "reverse_id":
+            rev = self.reverse_edge_ids(eids, stream=stream)
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                eids = torch.cat([eids, rev])
+        return EdgeIdSet(eids, device=dev, stream=stream)
 
     def column_slots(self, dev_id=0):
         """True when logical GPU dev_id samples from the {neighbour id, feature-cache slot} copy of the column array."""

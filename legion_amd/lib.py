@@ -168,6 +168,13 @@ SIGNATURES = {
     "legion_induced_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_p, c_p, c_i64]),
     "legion_induced_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_p]),
     "legion_dst_offsets": (c_i32, [c_p, c_p, c_i64, c_p, c_i32, c_p]),
+    "legion_reverse_edge_ids": (c_i32, [c_p, c_p, c_p, c_i64, c_i32, c_p]),
+    "legion_edge_set_bytes": (c_i64, [c_i32]),
+    "legion_edge_set_build": (c_i32, [c_p, c_p, c_i32, c_p, c_i64]),
+    "legion_edge_set_contains": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
+    "legion_edge_filter_scratch_bytes": (c_i64, [c_i64]),
+    "legion_edge_filter_count": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i32, c_p, c_p, c_i64]),
+    "legion_edge_filter_edges": (c_i32, [c_p, c_p, c_p, c_p, c_i64, c_p, c_i64, c_i32, c_p, c_i64, c_i64, c_p, c_p, c_p]),
     "legion_pool_profile_begin": (None, [c_p, c_i32]),
     "legion_pool_profile_end": (c_i32, [c_p, ctypes.POINTER(ctypes.c_float), P_I32, c_i32]),
     # 5. synthetic workloads
