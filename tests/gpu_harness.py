@@ -8,15 +8,20 @@ from oracle import ffi
 
 class GpuSide:
     def __init__(self, wl, batch_size, fanout, cache_memory=0, feature_rows=None, pipeline_depth=1,
-                 replace=True, edge_ids=False, feature_dtype="float32", feature_out_dtype="float32"):
-        """replace / edge_ids / feature_out_dtype: MemoryPool's, given to every pool of every partition (so before the first hop);
-        feature_dtype: FeatureStorage's.  The defaults are the reference's behaviour."""
+                 replace=True, edge_ids=False, feature_dtype="float32", feature_out_dtype="float32", weights=None, weighted=False):
+        """replace / edge_ids / weighted / feature_out_dtype: MemoryPool's, given to every pool of every partition (so before the
+        first hop); feature_dtype: FeatureStorage's; weights: float32[E] for GraphStorage.set_edge_weights, whose table is built
+        (and waited for: a Pipeline samples on streams of its own) before any pool exists.  The defaults are the reference's
+        behaviour."""
         dev = torch.device("cuda:0")
         self.wl, self.fanout, self.batch_size = wl, list(fanout), batch_size
         self.indptr = torch.from_numpy(wl.indptr).to(dev)
         self.col = torch.from_numpy(wl.col).to(dev)
         self.features = torch.from_numpy(wl.features).to(dev) if wl.features is not None else None
         self.graph = engine.GraphStorage(wl.P, self.indptr, self.col)
+        if weights is not None:
+            self.graph.set_edge_weights(weights)
+            torch.cuda.synchronize()
         self.feature = engine.FeatureStorage(wl.P, self.features, wl.N, wl.D, feature_dtype=feature_dtype)
         for (p, mode), (ids, labels) in wl.sets.items():
             self.feature.set_ids(p, mode, ids, labels)
@@ -25,7 +30,7 @@ class GpuSide:
         for p in range(wl.P):
             self.cache.init_controller(p)
             pool = engine.MemoryPool(p, wl.N, batch_size, fanout, wl.D, pipeline_depth, feature_out_dtype=feature_out_dtype,
-                                     replace=replace, edge_ids=edge_ids)
+                                     replace=replace, edge_ids=edge_ids, weighted=weighted)
             rows = feature_rows if feature_rows is not None else pool.num_ids
             if wl.D > 0:
                 pool.alloc_features(rows)

@@ -1,32 +1,65 @@
-"""What the GPU must produce for one batch under any combination of the four opt-in modes (sampling without replacement, edge
-ids, bfloat16 feature storage, bfloat16 rows to the trainer), composed from the references the suite already has:
+"""What the GPU must produce for one batch under any combination of the opt-in modes (the draw: with replacement, without, or
+weighted; edge ids; bfloat16 feature storage; bfloat16 rows to the trainer), composed from the references the suite already has:
 
-  ids, labels, counters, COO (helpers.KEYS_EXACT)   replace=True: the oracle (gpu_harness.CpuSide); replace=False: distinct_ref
-  agg_edge_ids                                      edge_ids_ref (which tests/test_mode_ref_cpu.py holds equal to the two above)
+  ids, labels, counters, COO (helpers.KEYS_EXACT)   replace=True: the oracle (gpu_harness.CpuSide); replace=False: distinct_ref;
+                                                    weighted: weighted_ref (which tests/test_mode_ref_cpu.py holds equal to the
+                                                    oracle under unit weights)
+  agg_edge_ids                                      edge_ids_ref (which tests/test_mode_ref_cpu.py holds equal to the first two);
+                                                    weighted: weighted_ref's own
   rows                                              table[sampled_ids], the table being the float32 features or, for a bf16 storage,
                                                     torch's CPU rounding of them; for bf16 rows out the same rounding once more (a
                                                     no-op on a rounded table)
 
 Every path is a copy or one round to nearest even, so everything is compared as bit patterns.  A helper of the tests, not a test
 file."""
+import collections
 import copy
 import itertools
 
 import numpy as np
 import torch
 
-from tests import distinct_ref, edge_ids_ref
+from tests import distinct_ref, edge_ids_ref, weighted_ref
 from tests.gpu_harness import CpuSide
 from tests.helpers import compare_batches
 
-# replace x edge_ids x storage x out, indexed 0..15
-COMBOS = [dict(replace=r, edge_ids=e, storage=s, out=o)
+# replace x edge_ids x storage x out, indexed 0..15; then the weighted draw (with replacement: the library refuses weighted and
+# distinct together) x edge_ids x storage x out, indexed 16..23.  "draw" names the draw: replace / distinct / weighted
+COMBOS = [dict(replace=r, edge_ids=e, storage=s, out=o, draw="replace" if r else "distinct")
           for r, e, s, o in itertools.product((True, False), (False, True), ("float32", "bfloat16"), ("float32", "bfloat16"))]
+COMBOS += [dict(replace=True, edge_ids=e, storage=s, out=o, draw="weighted")
+           for e, s, o in itertools.product((False, True), ("float32", "bfloat16"), ("float32", "bfloat16"))]
 
 
 def combo_name(c):
-    return (f"{'replace' if c['replace'] else 'distinct'}{'+eids' if c['edge_ids'] else ''} "
-            f"storage {c['storage']} out {c['out']}")
+    return f"{c['draw']}{'+eids' if c['edge_ids'] else ''} storage {c['storage']} out {c['out']}"
+
+
+# a case's per-edge weights and the prefix-sum table the graph builds from them
+EdgeWeights = collections.namedtuple("EdgeWeights", "w table")
+SPECIAL_WEIGHTS = np.array([0.0, -1.0, np.nan, np.inf, -0.0], dtype=np.float32)        # each counts as 0
+
+
+def case_weights(indptr, seed):
+    """The weights of the case `seed` over the CSR indptr: multiples of 1/8 (weighted_ref.hash_weights: a fifth of them zero), so
+    every prefix sum is exact and the table is weighted_ref.cdf's bit for bit; about 5 % of the entries one of the values that
+    are sanitised to 0; and every weight of a few rows of positive degree 0 (such a row yields no edge)."""
+    indptr = np.asarray(indptr, dtype=np.int64)
+    E = int(indptr[-1])
+    rng = np.random.RandomState(6000 + seed)
+    w = weighted_ref.hash_weights(E, seed=seed)
+    odd = rng.rand(E) < 0.05
+    w[odd] = rng.choice(SPECIAL_WEIGHTS, int(odd.sum()))
+    rows = np.nonzero(np.diff(indptr) > 0)[0]
+    for v in rng.choice(rows, min(3 + rows.size // 64, rows.size), replace=False):
+        w[indptr[v]:indptr[v + 1]] = 0
+    return EdgeWeights(w, weighted_ref.cdf(indptr, w))
+
+
+def unit_weights(indptr):
+    """Weight 1 on every edge: the weighted draw is then the uniform one."""
+    w = np.ones(int(indptr[-1]), np.float32)
+    return EdgeWeights(w, weighted_ref.cdf(indptr, w))
 
 
 def rounded(f):
@@ -59,13 +92,21 @@ def expected_rows(wl, sampled_ids, storage, out):
     return bf16_bits(rows) if out == "bfloat16" else rows.view(np.uint32)
 
 
-def expected_batch(wl, dev, it, mode, batch, fanout, *, replace, edge_ids, storage, out, serve=True, edge_access=None,
-                   node_access=None, cpu=None):
+def expected_batch(wl, dev, it, mode, batch, fanout, *, replace, edge_ids, storage, out, draw=None, weights=None, serve=True,
+                   edge_access=None, node_access=None, cpu=None):
     """The batch `it` of partition dev's seed set `mode`: KEYS_EXACT, "agg_edge_ids" (int64) if edge_ids, and -- for a served batch
     -- "rows".  serve=False is a PreSC batch (no gathers); edge_access / node_access: uint64[N] hotness counts of the partition,
-    added to in place.  cpu: the CpuSide the oracle runs through when replace=True (a throw-away one otherwise)."""
+    added to in place.  draw: COMBOS' (None: by replace); weights: the EdgeWeights of a weighted draw.  cpu: the CpuSide the oracle
+    runs through when replace=True (a throw-away one otherwise; the weighted draw does not use it)."""
     ids, labels = wl.sets[(dev, mode)]
-    if replace:
+    weighted = draw == "weighted"
+    assert draw in (None, "weighted", "replace" if replace else "distinct") and (replace or not weighted)
+    if weighted:
+        want = weighted_ref.run_batch(wl.indptr, wl.col, weights.table, ids, labels, batch, it, fanout, serve, edge_access, node_access)
+        weighted_ref.check_edges(wl.indptr, wl.col, weights.w, want)
+        if not edge_ids:
+            del want["agg_edge_ids"]
+    elif replace:
         side = cpu if cpu is not None else cpu_side(wl, batch, fanout, storage)
         if node_access is not None:
             side.node_access[dev] = node_access
@@ -78,7 +119,7 @@ def expected_batch(wl, dev, it, mode, batch, fanout, *, replace, edge_ids, stora
             side.close()
     else:
         want = distinct_ref.run_batch(wl.indptr, wl.col, ids, labels, batch, it, fanout, serve, edge_access, node_access)
-    if edge_ids:
+    if edge_ids and not weighted:
         e = edge_ids_ref.run_batch(wl.indptr, wl.col, ids, labels, batch, it, fanout, replace)
         for k in ("sampled_ids", "agg_src_ids", "agg_dst_ids"):      # the same edges, so the ids line up (counters differ in PreSC)
             assert np.array_equal(e[k], want[k]), f"the references disagree on {k}"
@@ -135,18 +176,34 @@ def _carried_picks_matter(q, f, D, super_tile):
     return any(t[kk] in picks[:first] for kk in range(first, f))
 
 
-def batch_stats(wl, want, fanout, super_tile=1024, distinct=False):
+def row_weight_counts(indptr, w):
+    """int64[N]: per row, how many of its entries have a (sanitised) weight > 0."""
+    below = np.concatenate([[0], np.cumsum(weighted_ref.sanitise(w) > 0)]).astype(np.int64)
+    indptr = np.asarray(indptr, dtype=np.int64)
+    return below[indptr[1:]] - below[indptr[:-1]]
+
+
+def batch_stats(wl, want, fanout, super_tile=1024, distinct=False, weights=None):
     """What a reference batch exercised, for the conditions that keep a fuzz from passing vacuously -- from the reference alone:
     frontier entries with D > f and with D = 0, entries with D > f whose f slots q*f .. q*f + f - 1 straddle a multiple of the
     sampler's super tile, (distinct=True: and, of these, the entries whose later picks depend on the earlier super tile's: "carry"), sampled
     dead column entries (slots that drew col < 0: every slot k < min(f, D) gives an edge otherwise), and whether the batch is the
-    empty one."""
+    empty one.  weights (the EdgeWeights of a weighted batch): also the frontier entries with D > 0 whose row total is 0
+    ("zero_total": none of their slots draws) and the frontier rows that hold a zero-weight entry beside positive ones ("mixed")."""
     ec = want["edge_counter"]
     deg = np.diff(wl.indptr)
     s = dict(over=0, zero=0, straddle=0, carry=0, dead=0, empty=int(want["sampled_ids"].size == 0 and int(want["node_counter"][9]) <= 0))
+    positive = None
+    if weights is not None:
+        positive = row_weight_counts(wl.indptr, weights.w)
+        s.update(zero_total=0, mixed=0)
     for h, (f, fr) in enumerate(zip(fanout, hop_frontiers(want, len(fanout)))):
         fr = np.asarray(fr, dtype=np.int64)
         D = np.where(fr >= 0, deg[np.maximum(fr, 0)], 0)
+        if positive is not None:
+            n_pos = np.where(fr >= 0, positive[np.maximum(fr, 0)], 0)
+            s["zero_total"] += int(((D > 0) & (n_pos == 0)).sum())
+            s["mixed"] += int(((n_pos > 0) & (n_pos < D)).sum())
         q = np.arange(fr.size, dtype=np.int64)
         s["over"] += int((D > f).sum())
         s["zero"] += int((D == 0).sum())
@@ -154,7 +211,8 @@ def batch_stats(wl, want, fanout, super_tile=1024, distinct=False):
         s["straddle"] += int(across.sum())
         if distinct:
             s["carry"] += sum(_carried_picks_matter(int(i), f, int(D[i]), super_tile) for i in np.nonzero(across)[0])
-        s["dead"] += int(np.minimum(D, f).sum()) - (int(ec[9 + h + 1]) - int(ec[9 + h]))
+        drawing = D if positive is None else np.where(n_pos > 0, D, 0)                # (a row whose total is 0 draws nothing)
+        s["dead"] += int(np.minimum(drawing, f).sum()) - (int(ec[9 + h + 1]) - int(ec[9 + h]))
     return s
 
 

@@ -733,6 +733,78 @@ def test_owner_bucketed_bulk_transfer_matches_direct_peer_loads(hip, monkeypatch
     gpu.close(); cpu.close()
 
 
+@pytest.mark.parametrize("mode,P,mode_bits,capacity,replica_rows,D", [("edge_ids", 2, 1, (150, 90), 0, 32), ("distinct", 4, 2, (64, 33), 40, 32),
+                                                                      ("weighted", 4, 1, (100, 50), 0, 7)])
+def test_bulk_transfer_with_the_opt_in_sampler_modes(hip, col_slots, mode, P, mode_bits, capacity, replica_rows, D):
+    """peer_gather = bulk under each opt-in sampler mode (edge ids, without replacement, weighted), on three of the shapes of
+    test_owner_bucketed_bulk_transfer_matches_direct_peer_loads: every lane's batch, rows and agg_edge_ids are those of a pipeline
+    of the same mode that reads its peers' stripes by direct loads, hit masks and cache slots included, and those of the composed
+    CPU reference (tests/mode_ref.py); rows did travel by the bulk path."""
+    from legion_amd import engine
+    from oracle import ffi
+    from tests import mode_ref
+    wl = Workload(scale=11, edge_factor=8, dim=D, partition_count=P, n_seeds=1600)
+    fanout, batch, G = [5, 4], 48, 3
+    combo = dict(replace=mode != "distinct", edge_ids=mode == "edge_ids", storage="float32", out="float32",
+                 draw=mode if mode in ("distinct", "weighted") else "replace")
+    weights = mode_ref.case_weights(wl.indptr, 2000) if mode == "weighted" else None
+    sampler = dict(replace=combo["replace"], edge_ids=combo["edge_ids"], weighted=mode == "weighted")
+    gpu = GpuSide(wl, batch, fanout, weights=weights.w if weights else None, **sampler)
+    steps = min((wl.sets[(p, 0)][0].size - 1) // batch for p in range(P))
+    for p in range(P):
+        for it in range(steps):
+            gpu.run(p, it, 0, is_presc=True)             # (the mode's own hotness: tests/test_gpu_fuzz_modes.py holds it to the reference)
+    gpu.cache.candidate_selection(mode_bits, gpu.graph)
+    gpu.cache.set_capacity(*capacity)
+    if replica_rows:
+        gpu.cache.set_replica_memory(replica_rows * D * 4)
+    gpu.cache.fill_up(gpu.feature, gpu.graph)
+    assert all(gpu.graph.column_slots(p) == col_slots for p in range(P))
+    Kg = min(1 << mode_bits, P)
+    rows = ffi.num_ids_for(batch, fanout)
+    direct = [engine.Pipeline(gpu.graph, gpu.feature, gpu.cache, p, batch, fanout, G, rows, use_graph=False, slots=2, **sampler) for p in range(P)]
+    pipes = [engine.Pipeline(gpu.graph, gpu.feature, gpu.cache, p, batch, fanout, G, rows, use_graph=False, slots=2, arena="shared", **sampler)
+             for p in range(P)]
+    for pl in pipes:
+        pl.bulk_enable()
+    for p in range(P):                                   # every member knows the other members of ITS clique
+        for q in range(p // Kg * Kg, p // Kg * Kg + Kg):
+            if q != p:
+                pipes[p].bulk_link(pipes[q])
+    n_groups = min(2, (steps - 1) // G)
+    assert n_groups >= 1
+    cpu = mode_ref.cpu_side(wl, batch, fanout)
+    listed = 0
+    for grp in range(n_groups):
+        slots = [pipes[p].bulk_phase_a(grp * G) for p in range(P)]          # (phase A synchronises its stream: the lists are final)
+        assert len(set(slots)) == 1
+        listed += sum(pipes[p].bulk_listed(slots[0]) for p in range(P))
+        for p in range(P):
+            pipes[p].bulk_phase_b(slots[0])                                  # every member pushes what the others listed for it
+        for p in range(P):
+            ds = direct[p].submit(grp * G, 0)
+            direct[p].wait(ds)
+            for lane in range(G):
+                at = f"bulk {mode} gpu {p} group {grp} lane {lane}: "
+                pools = pipes[p].pools[slots[0]][lane], direct[p].pools[ds][lane]
+                assert pools[0].weighted is sampler["weighted"] and pools[0].replace is sampler["replace"] and pools[0].edge_ids is sampler["edge_ids"]
+                g, d = (engine.read_batch(pool) for pool in pools)
+                compare_batches(g, d, at + "against direct peer loads: ")
+                assert g["float_features"].shape[0] == g["sampled_ids"].size and ("agg_edge_ids" in g) == ("agg_edge_ids" in d) == combo["edge_ids"]
+                if combo["edge_ids"]:
+                    assert np.array_equal(g["agg_edge_ids"], d["agg_edge_ids"]), at + "agg_edge_ids against direct peer loads"
+                for name, n in (("cache_search_buffer", max(int(g["node_counter"][1]), 0)), ("tmp_part_ind", int(g["edge_counter"][10] - g["edge_counter"][9]))):
+                    assert np.array_equal(pools[0].buffer(name)[:n].cpu().numpy(), pools[1].buffer(name)[:n].cpu().numpy()), at + name
+                want = mode_ref.expected_batch(wl, p, grp * G + lane, 0, batch, fanout, cpu=cpu, weights=weights, **combo)
+                mode_ref.compare_mode_batch(g, want, wl, at)
+    assert listed > 0                                    # rows did travel by the bulk path
+    assert all(pool.error() == 0 for pl in pipes + direct for lanes in pl.pools for pool in lanes)
+    cpu.close()
+    for pl in pipes + direct:
+        pl.close()
+    gpu.close()
+
+
 @pytest.mark.parametrize("use_graph,weave,fanout", [(False, False, [3]), (True, False, [3]), (False, True, [3]), (True, True, [3]),
                                                     (False, False, [3, 2]), (False, True, [3, 2]), (True, True, [3, 2])],
                          ids=["eager-1hop", "replay-1hop", "weave-eager-1hop", "weave-replay-1hop",
