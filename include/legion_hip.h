@@ -1016,6 +1016,9 @@ void legion_consume_batch(legion_stream_t stream, const float* feats, int64_t n_
  * is the host-side address to fill and to pass to legion_host_free. */
 void* legion_host_alloc(int64_t num_bytes, void** host_ptr_out);
 void legion_host_free(void* host_ptr);
+/* legion_host_alloc for a caller that has a smaller size to fall back to: returns NULL (and leaves *host_ptr_out NULL) where the
+ * driver refuses to pin that much -- how much it pins is not something a process can read anywhere -- instead of ending the process. */
+void* legion_host_try_alloc(int64_t num_bytes, void** host_ptr_out);
 
 /* One process per GPU: logical GPU d of this process is physical GPU (base + d) % device_count.
  * Call once before creating any object (bench.py passes LOCAL_RANK). */

@@ -71,20 +71,24 @@ public:
             }
             shm_ = (volatile shmStruct*)info_.addr;
             memset((void*)shm_, 0, sizeof(*shm_));
-            // the counter mirror: a shm object of its own that the GPUs write straight into
+            // the counter mirror: a shm object of its own.  A GPU cannot write into it (a shm mapping would have to be registered
+            // with HIP, which not every machine allows): the GPUs write a batch's counters into a block of pinned host memory
+            // allocated here, and IPCPost copies the slot's 32 words into the mirror before it posts
             ext_info_.addr = nullptr;
             ext_info_.shmFd = -1;
             ext_name_ = wire_name(wire_mirror_name, ipc_suffix().c_str());
             if (lg::tuning().shm_mirror && sharedMemoryCreate(ext_name_.c_str(), sizeof(shmExt), &ext_info_) == 0) {
                 ext_ = (volatile shmExt*)ext_info_.addr;
                 memset((void*)ext_, 0, sizeof(shmExt));
-                if (hipHostRegister(ext_info_.addr, sizeof(shmExt), hipHostRegisterPortable | hipHostRegisterMapped) == hipSuccess) {
+                void* host = nullptr;
+                if (hipHostMalloc(&host, sizeof(CounterStage), hipHostMallocPortable | hipHostMallocMapped) == hipSuccess) {
                     void* dptr = nullptr;
-                    if (hipHostGetDevicePointer(&dptr, ext_info_.addr, 0) == hipSuccess && dptr != nullptr) {
-                        ext_dev_ = (shmExt*)dptr;
-                        registered_ = true;
+                    if (hipHostGetDevicePointer(&dptr, host, 0) == hipSuccess && dptr != nullptr) {
+                        memset(host, 0, sizeof(CounterStage));
+                        stage_ = (CounterStage*)host;
+                        stage_dev_ = (CounterStage*)dptr;
                     } else {
-                        (void)hipHostUnregister(ext_info_.addr);
+                        (void)hipHostFree(host);
                     }
                 }
                 (void)hipGetLastError();
@@ -245,15 +249,15 @@ public:
     int32_t* GetNodeCounter(int32_t d, int32_t p) override { return (int32_t*)node_counter_[d][p % pipeline_depth_]; }
     int32_t* GetEdgeCounter(int32_t d, int32_t p) override { return (int32_t*)edge_counter_[d][p % pipeline_depth_]; }
 
-    // device address of the host-visible counter mirror of (device, pipe slot), or null when the slab could not be
-    // registered (then the trainer end falls back to copying the counters from the device buffers)
+    // device address of the host-visible counter block of (device, pipe slot) -- what IPCPost copies into the mirror -- or null when
+    // there is no mirror (then the trainer end falls back to copying the counters from the device buffers)
     int32_t* GetCounterMirror(int32_t d, int32_t p) override
     {
-        return ext_dev_ ? &ext_dev_->counters[d][p % pipeline_depth_][0] : nullptr;
+        return stage_dev_ ? &stage_dev_->counters[d][p % pipeline_depth_][0] : nullptr;
     }
     void PublishMirror() override
     {
-        if (!ext_dev_) return;
+        if (!stage_dev_) return;
         for (int32_t d = 0; d < MAX_DEVICE; d++) ext_->feature_out_dtype[d] = feature_out_dtype;
         ext_->ext_version = LEGION_SHM_EXT_VERSION;
         __sync_synchronize();
@@ -266,7 +270,7 @@ public:
     }
     bool PublishArena(int32_t dev_id, void* base, int64_t bytes) override
     {
-        if (!ext_ || !ext_dev_ || base == nullptr || bytes <= 0) return false;
+        if (!ext_ || !stage_dev_ || base == nullptr || bytes <= 0) return false;
         int32_t n_chunks = 0;
         const int64_t chunk_bytes = lg_scattered_info(base, &n_chunks);
         if (chunk_bytes > 0) {          // an arena of shuffled chunks: handed over as file descriptors (shmExt, version 3)
@@ -291,7 +295,8 @@ public:
     void SetView(int32_t dev_id, int32_t pipe, const int64_t* off5, const int32_t* counters32) override
     {
         if (!ext_) return;
-        if (counters32) for (int i = 0; i < 32; i++) ext_->counters[dev_id][pipe][i] = counters32[i];
+        if (counters32 && stage_) for (int i = 0; i < 32; i++) stage_->counters[dev_id][pipe][i] = counters32[i];     // (IPCPost carries them into the mirror)
+        else if (counters32) for (int i = 0; i < 32; i++) ext_->counters[dev_id][pipe][i] = counters32[i];
         if (off5) for (int i = 0; i < 5; i++) ext_->view[dev_id][pipe][i] = off5[i];
         ext_->view_on[dev_id][pipe] = off5 ? 1 : 0;
     }
@@ -313,7 +318,14 @@ public:
     }
     bool IPCTryWait(int32_t dev_id, int32_t current_pipe) override { return sem_trywait(semr_[dev_id][current_pipe]) == 0; }
 
-    void IPCPost(int32_t dev_id, int32_t current_pipe) override { sem_post(semw_[dev_id][current_pipe]); }
+    // the batch in the slot is complete (the caller saw its event): what the GPU -- or SetView -- left in the slot's counter block
+    // becomes the mirror's, then the trainer is woken
+    void IPCPost(int32_t dev_id, int32_t current_pipe) override
+    {
+        if (stage_ && ext_)
+            for (int i = 0; i < 32; i++) ext_->counters[dev_id][current_pipe][i] = ((volatile CounterStage*)stage_)->counters[dev_id][current_pipe][i];
+        sem_post(semw_[dev_id][current_pipe]);
+    }
     void IPCWait(int32_t dev_id, int32_t current_pipe) override { sem_wait(semr_[dev_id][current_pipe]); }
 
     // ipc_service.cu:293-321
@@ -342,9 +354,8 @@ public:
             delete local_;
             local_ = nullptr;
         } else {
-            if (registered_) (void)hipHostUnregister(ext_info_.addr);
-            registered_ = false;
-            ext_dev_ = nullptr;
+            if (stage_) (void)hipHostFree(stage_);
+            stage_ = stage_dev_ = nullptr;
             ext_ = nullptr;
             sharedMemoryClose(&info_);
             if (!shm_name_.empty()) shm_unlink(shm_name_.c_str());
@@ -360,9 +371,10 @@ public:
 
 private:
     volatile shmStruct* shm_ = nullptr;
-    volatile shmExt* ext_ = nullptr;    // the counter mirror (its own shm object) ...
-    shmExt* ext_dev_ = nullptr;         // ... as the GPUs see it (registered host memory)
-    bool registered_ = false;
+    struct CounterStage { int32_t counters[MAX_DEVICE][INTERBATCH_CON][32]; };       // shmExt::counters, in pinned host memory
+    volatile shmExt* ext_ = nullptr;    // the counter mirror (its own shm object)
+    CounterStage* stage_ = nullptr;     // the block the GPUs write and IPCPost copies from ...
+    CounterStage* stage_dev_ = nullptr; // ... as the GPUs see it
     shmStruct* local_ = nullptr;
     sharedMemoryInfo info_, ext_info_ = {nullptr, 0, -1};
     std::string shm_name_, ext_name_;

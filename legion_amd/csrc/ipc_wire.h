@@ -47,7 +47,7 @@ static_assert(offsetof(shmStruct, memHandle) == 12 &&
               sizeof(shmStruct) == 12 + LEGION_MAX_DEVICE * LEGION_INTERBATCH_CON * LEGION_MEMORY_USAGE * 64,
               "the reference's slab layout is the wire format");
 
-/* This build's extra lives in a shm object of its own, the mirror: registered with HIP and written by the GPU on the server side,
+/* This build's extra lives in a shm object of its own, the mirror: written by the server (its GPUs' counters reach it through pinned host memory, ipc_env.hip),
  * opened by this build's trainer end when it exists (never created there) and believed when its magic says so.
  *   version 1: per (device, pipe slot) the 16 + 16 counters of the batch in that slot in HOST memory, so the trainer end needs no
  *     device-to-host copy per batch (the reference does two blocking 64-byte cudaMemcpy per get_next, TB/ipc_cuda_kernel.cu:186-187).

@@ -21,6 +21,12 @@
 #include <string>
 #include <thread>
 #include <sys/time.h>
+#include <sys/wait.h>
+#include <dlfcn.h>
+#include <fcntl.h>
+#include <signal.h>
+#include <spawn.h>
+extern char** environ;
 
 #include "../trainer/vmm_map.h"        // vmm_map_chunks(): a range of this process built from another process's chunks (+ ipc_wire.h: the messages)
 
@@ -81,8 +87,15 @@ std::map<void*, ScatterLive> g_scatter_live;
 }
 static void* alloc_scattered(int64_t num_bytes, int32_t chunk_mb, bool exportable);
 extern "C" void* d_alloc_scattered(int64_t num_bytes, int32_t chunk_mb) { return alloc_scattered(num_bytes, chunk_mb, false); }
-// ... whose chunks can be handed to another process as file descriptors (the server's lane arena: lg_scattered_export_fd)
-extern "C" void* d_alloc_scattered_exportable(int64_t num_bytes, int32_t chunk_mb) { return alloc_scattered(num_bytes, chunk_mb, true); }
+// ... whose chunks can be handed to another process as file descriptors (the server's lane arena: lg_scattered_export_fd).  On a
+// machine where descriptors of device memory do not cross a process boundary (lg_fd_handover_works, below) the allocation is a
+// plain one instead -- lg_scattered_info says 0 for it, and every owner then hands it over as a hipIpcMemHandle.
+extern "C" int32_t lg_fd_handover_works(void);
+extern "C" void* d_alloc_scattered_exportable(int64_t num_bytes, int32_t chunk_mb)
+{
+    if (!lg_fd_handover_works()) return d_alloc_space(num_bytes);
+    return alloc_scattered(num_bytes, chunk_mb, true);
+}
 static void* alloc_scattered(int64_t num_bytes, int32_t chunk_mb, bool exportable)
 {
     int dev = 0;
@@ -94,7 +107,12 @@ static void* alloc_scattered(int64_t num_bytes, int32_t chunk_mb, bool exportabl
     if (exportable) prop.requestedHandleType = hipMemHandleTypePosixFileDescriptor;
     size_t g0 = 0;
     HIP_CALL(hipMemGetAllocationGranularity(&g0, &prop, hipMemAllocationGranularityRecommended));          // (4 KB on this stack)
-    const size_t want = (size_t)(chunk_mb > 0 ? chunk_mb : 2) << 20;
+    // At most 4096 chunks per allocation: every chunk is a handle of its own to the driver, and a process has only so many (a
+    // guest's driver ran out -- hipMemCreate: out of memory with half the HBM free -- past some 50 000 chunks of 2 MB).  A large
+    // arena gets larger chunks, whole multiples of 2 MB; from 2 MB to 128 MB the placement is worth the same to the gathers (above).
+    const size_t mb2 = (size_t)2 << 20;
+    const size_t floor_bytes = (((size_t)(num_bytes > 0 ? num_bytes : 16) + 4095) / 4096 + mb2 - 1) / mb2 * mb2;
+    const size_t want = std::max((size_t)(chunk_mb > 0 ? chunk_mb : 2) << 20, floor_bytes);
     const size_t g = (want + g0 - 1) / g0 * g0;
     const size_t n = ((size_t)(num_bytes > 0 ? num_bytes : 16) + g - 1) / g;
     ScatterLive live;
@@ -285,6 +303,56 @@ extern "C" void lg_scattered_unmap_remote(void* base)
     vmm_unmap_chunks(base, m.n_chunks, m.n_chunks, (long long)m.chunk_bytes);
 }
 
+// Whether another process can map device memory of this one from file descriptors, found out once per process by trying: one
+// exportable chunk is served to a helper program of the package (bin/vmm_convention_probe --map, a fresh child process), which
+// imports and maps it.  hipMemImportFromShareableHandle fails across processes on some virtual machines (the import of a chunk the
+// same process exported works there, and so does hipIpcOpenMemHandle), and neither the exporter nor a file says so beforehand.
+// No helper, or a helper that does not answer in 30 s, counts as "does not work": the plain allocation always does.
+extern "C" int32_t lg_fd_handover_works(void)
+{
+    static std::mutex mu;
+    static int known = -1;
+    std::lock_guard<std::mutex> lk(mu);
+    if (known >= 0) return known;
+    known = 0;
+    Dl_info self;
+    if (dladdr((void*)&lg_fd_handover_works, &self) == 0 || self.dli_fname == nullptr) return known;
+    std::string helper(self.dli_fname);
+    const size_t slash = helper.rfind('/');
+    helper = (slash == std::string::npos ? std::string(".") : helper.substr(0, slash)) + "/bin/vmm_convention_probe";
+    if (access(helper.c_str(), X_OK) != 0) return known;
+    int dev = 0;
+    HIP_CALL(hipGetDevice(&dev));
+    void* chunk = alloc_scattered(1, 2, true);
+    int32_t n_chunks = 0;
+    const int64_t chunk_bytes = lg_scattered_info(chunk, &n_chunks);
+    char name[WIRE_NAME_MAX];
+    snprintf(name, sizeof(name), "legion_handover_probe_%d", (int)getpid());
+    if (chunk_bytes > 0 && lg_scattered_serve(chunk, name)) {
+        const std::string a_chunks = std::to_string(n_chunks), a_bytes = std::to_string((long long)chunk_bytes), a_dev = std::to_string(dev);
+        char* const argv[] = {(char*)helper.c_str(), (char*)"--map", name, (char*)a_chunks.c_str(), (char*)a_bytes.c_str(), (char*)a_dev.c_str(), nullptr};
+        posix_spawn_file_actions_t fa;
+        posix_spawn_file_actions_init(&fa);
+        posix_spawn_file_actions_addopen(&fa, 0, "/dev/null", O_RDONLY, 0);
+        posix_spawn_file_actions_addopen(&fa, 1, "/dev/null", O_WRONLY, 0);      // (the answer is the exit status)
+        pid_t child = -1;
+        if (posix_spawn(&child, helper.c_str(), &fa, nullptr, argv, environ) == 0) {
+            int status = 0;
+            bool ended = false;
+            for (int ms = 0; ms < 30000 && !ended; ms += 5) {
+                ended = waitpid(child, &status, WNOHANG) == child;
+                if (!ended) usleep(5000);
+            }
+            if (!ended) { kill(child, SIGKILL); (void)waitpid(child, &status, 0); }
+            else known = (WIFEXITED(status) && WEXITSTATUS(status) == 0) ? 1 : 0;
+        }
+        posix_spawn_file_actions_destroy(&fa);
+    }
+    d_free_space(chunk);
+    if (!known) { printf("legion_hip: device memory does not cross a process boundary as file descriptors here: arenas other processes map are plain allocations\n"); fflush(stdout); }
+    return known;
+}
+
 static bool d_free_scattered(void* ptr)
 {
     ScatterLive live;
@@ -413,6 +481,20 @@ extern "C" void* legion_host_alloc(int64_t num_bytes, void** host_ptr_out)
     void* host_ptr = nullptr;
     void* dev_ptr = nullptr;
     HIP_CALL(hipHostMalloc(&host_ptr, num_bytes > 0 ? (size_t)num_bytes : 16, hipHostMallocMapped));
+    HIP_CALL(hipHostGetDevicePointer(&dev_ptr, host_ptr, 0));
+    if (host_ptr_out) *host_ptr_out = host_ptr;
+    return dev_ptr;
+}
+
+extern "C" void* legion_host_try_alloc(int64_t num_bytes, void** host_ptr_out)
+{
+    void* host_ptr = nullptr;
+    void* dev_ptr = nullptr;
+    if (host_ptr_out) *host_ptr_out = nullptr;
+    if (hipHostMalloc(&host_ptr, num_bytes > 0 ? (size_t)num_bytes : 16, hipHostMallocMapped) != hipSuccess) {
+        (void)hipGetLastError();
+        return nullptr;
+    }
     HIP_CALL(hipHostGetDevicePointer(&dev_ptr, host_ptr, 0));
     if (host_ptr_out) *host_ptr_out = host_ptr;
     return dev_ptr;

@@ -107,6 +107,13 @@ def _torch_device(dev_id):
     return torch.device("cuda", (base + int(dev_id)) % max(torch.cuda.device_count(), 1))
 
 
+def fd_handover_works():
+    """Whether another process can map this one's device memory from file descriptors on this machine (found out once per process by
+    trying, storage.hip lg_fd_handover_works); where it cannot, the arenas other processes map are plain allocations, handed over as
+    hipIpcMemHandles."""
+    return bool(_libmod.load().lg_fd_handover_works())
+
+
 class PinnedArray:
     """A numpy-visible array in mapped pinned host memory that the GPU reads in place over PCIe: the
     spill-over tier for tables that do not fit HBM (the reference's only tier for the full CSR/features)."""
@@ -131,6 +138,18 @@ class PinnedArray:
         self.dev_ptr = self._lib.legion_host_alloc(nbytes, ctypes.byref(host))
         self.host_ptr = host.value
         return self
+
+    @classmethod
+    def try_empty(cls, shape, dtype):
+        """empty(), or None where the driver refuses to pin that much host memory (empty() ends the process there)."""
+        self = cls.__new__(cls)
+        self._lib = _libmod.load()
+        self.shape, self.dtype = tuple(int(s) for s in shape), np.dtype(dtype)
+        nbytes = int(np.prod(self.shape, dtype=np.int64)) * self.dtype.itemsize
+        host = ctypes.c_void_p()
+        self.dev_ptr = self._lib.legion_host_try_alloc(nbytes, ctypes.byref(host))
+        self.host_ptr = host.value
+        return self if self.host_ptr else None
 
     def numpy(self):
         n = int(np.prod(self.shape, dtype=np.int64))

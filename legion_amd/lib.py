@@ -194,7 +194,9 @@ SIGNATURES = {
     "legion_tuning_get": (None, [c_p]),
     "legion_tuning_set": (None, [c_p]),
     "legion_host_alloc": (c_p, [c_i64, ctypes.POINTER(c_p)]),
+    "legion_host_try_alloc": (c_p, [c_i64, ctypes.POINTER(c_p)]),
     "legion_host_free": (None, [c_p]),
+    "lg_fd_handover_works": (c_i32, []),
     "legion_set_device_base": (None, [c_i32]),
     "legion_get_device_base": (c_i32, []),
     "legion_version": (ctypes.c_char_p, []),

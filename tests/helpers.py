@@ -1,5 +1,7 @@
 """Shared builders for the parity tests: small synthetic workloads run through the oracle (CPU)
 and through liblegion_hip.so (GPU) with identical inputs."""
+import functools
+
 import numpy as np
 
 from legion_amd import synth
@@ -35,6 +37,28 @@ class Workload:
             for p in range(partition_count):
                 mine = ids[part_of == p]
                 self.sets[(p, mode)] = (np.ascontiguousarray(mine), np.ascontiguousarray(self.labels_all[mine]))
+
+
+@functools.lru_cache(maxsize=None)
+def link_counters_advance():
+    """Whether the GPU's cumulative PCIe counter (engine.link_counters) moves at all under traffic.  Where the driver hands a guest a
+    gpu_metrics table whose accumulators stand still, the table decodes, and every reading of it is the same: a 256 MiB copy from
+    pinned host memory, which a live counter cannot miss, leaves it where it was."""
+    import time
+    import torch
+    from legion_amd import engine
+    if engine.link_counters(0) is None:
+        return False
+    dev = torch.device("cuda:0")
+    host = engine.PinnedArray.empty((1 << 26,), np.int32)
+    sink = torch.empty(1 << 26, dtype=torch.int32, device=dev)
+    torch.cuda.synchronize(); time.sleep(0.05)
+    before = engine.link_counters(0)
+    sink.copy_(host.tensor(dev))
+    torch.cuda.synchronize(); time.sleep(0.05)                          # the table is refreshed every millisecond or so
+    after = engine.link_counters(0)
+    host.close()
+    return after is not None and after[0] != before[0]
 
 
 def compare_batches(got, want, ctx=""):

@@ -18,8 +18,9 @@ from tests.server_proc import start_server  # noqa: E402
 def vram_held_mib():
     """What THIS process holds in VRAM according to the driver (amdgpu fdinfo of its drm / kfd descriptors, one entry per drm
     client).  hipMemGetInfo answers from the runtime's own book-keeping, which does not follow another process's chunks being
-    mapped and unmapped here (tools/micro/vmm_release_probe.cpp)."""
-    seen, total = set(), 0
+    mapped and unmapped here (tools/micro/vmm_release_probe.cpp).  None where the driver's fdinfo carries no memory figures at all (a
+    guest's): the caller then measures with what the whole GPU holds."""
+    seen, total = set(), None
     for name in os.listdir("/proc/self/fdinfo"):
         try:
             text = open(f"/proc/self/fdinfo/{name}").read()
@@ -33,8 +34,15 @@ def vram_held_mib():
                 vram = int(ln.split()[1])
         if vram is not None and cid not in seen:
             seen.add(cid)
-            total += vram >> 10
+            total = (total or 0) + (vram >> 10)
     return total
+
+
+def gpu_held_mib(torch):
+    """What the whole GPU holds, from the driver's free-memory figure: this process and the server are all that run on it.  A dead
+    server's arena that this process still maps stays allocated, so it shows here from the second life on."""
+    free, total = torch.cuda.mem_get_info(0)
+    return (total - free) >> 20
 
 
 def main():
@@ -67,6 +75,8 @@ def main():
                 torch.cuda.synchronize()
                 ipc_service.synchronize()
             mid_free, mid_held = torch.cuda.mem_get_info(0)[0], vram_held_mib()
+            if mid_held is None:
+                mid_held = gpu_held_mib(torch)
             ipc_service.finalize()
             server.wait(timeout=120)
             assert server.returncode == 0, open(os.path.join(work, f"server{life}.log")).read()[-2000:]
@@ -78,6 +88,8 @@ def main():
                  digests=np.array(digests, dtype=np.uint64), sizes=np.array(sizes, dtype=np.int32))
         torch.cuda.empty_cache()
         free, held = torch.cuda.mem_get_info(0)[0], vram_held_mib()
+        if held is None:
+            held = gpu_held_mib(torch)
         print(f"life {life}: {total} batches; VRAM held by this process (driver's fdinfo) while attached {mid_held} MiB, after finalize + server "
               f"exit {held} MiB; hipMemGetInfo free {mid_free >> 20} -> {free >> 20} MiB", flush=True)
         if level is None:

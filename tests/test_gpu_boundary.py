@@ -338,7 +338,10 @@ def test_one_trainer_process_outlives_eight_server_lives(hip, tmp_path):
                              stdin=subprocess.DEVNULL, timeout=560)
         logs = "".join(open(work / f).read()[-1200:] for f in sorted(os.listdir(work)) if f.startswith("server"))
         assert res.returncode == 0 and "all lives clean" in res.stdout, res.stdout[-4000:] + "\n---- servers ----\n" + logs[-3000:]
-        assert "hand-over by views of the lane arena" in logs and "chunks): batches arrive as views" in res.stdout, res.stdout[-2000:]
+        # (where descriptors of device memory cross no process boundary the server's arena is a plain allocation, opened by its IPC handle)
+        from legion_amd import engine
+        attached = "chunks): batches arrive as views" if engine.fd_handover_works() else "MiB): batches arrive as views"
+        assert "hand-over by views of the lane arena" in logs and attached in res.stdout, res.stdout[-2000:]
         # ---- the oracle's batches of one server life (every life serves the same schedule) ----
         import ctypes
         g = ffi.OracleGraph(1, indptr, col)
