@@ -959,6 +959,73 @@ int32_t legion_row_topk(legion_stream_t stream, LegionGraphStorage* graph, const
 int32_t legion_topk_keys(legion_stream_t stream, LegionGraphStorage* graph, const int64_t* eids_devptr /* int64[n] */, int64_t n,
                          int32_t mode, const float* w_devptr /* float32[E], or NULL in SAMPLE */, int64_t salt,
                          uint64_t* key_out /* uint64[n] */, uint8_t* eligible_out /* uint8[n] */);
+
+/* Typed edges and a fan-out per edge type (DGL's dgl.sampling.sample_etype_neighbors(g, nodes, etype_field, fanouts, etype_sorted=True)
+ * and g.in_degrees(v, etype=); kernels_etype.hip, the rule's text etype_rule.h).
+ *
+ * legion_graph_set_edge_types.  etype[e] < T = num_types is the type of entry e of the full CSR's col, aligned with it as the w of
+ * legion_graph_set_edge_weights; inside a row the types do not decrease (etype[e - 1] <= etype[e] for adjacent entries of one row; a
+ * dead entry, col[e] = -1, carries a type and holds its place like any other).  1 <= T <= LEGION_ETYPE_MAX_TYPES: a lane of a wave
+ * stands for a type.  The call checks both on the current device in one pass over the graph; it is set-up: it synchronises `stream`
+ * and reads the verdict back.  The graph BORROWS the pointer: the array stays the caller's, alive and unchanged while the graph is
+ * typed; a second call replaces the types.  Returns 0, or, in this order and with the graph left UNTYPED: LEGION_ETYPE_NO_GRAPH,
+ * LEGION_ETYPE_NO_POINTER, LEGION_ETYPE_BAD_COUNT (T outside [1, 64]), LEGION_ETYPE_TYPE_RANGE (some etype[e] >= T),
+ * LEGION_ETYPE_UNSORTED (the types decrease inside some row).  legion_graph_num_edge_types: T, 0 for an untyped or a null graph.
+ *
+ * The segments of a row.  Segment t of row r is the run of its entries of type t: [b_t, b_{t+1}) with b_t the first position of the
+ * row whose type is >= t and b_T its end; D_t is its length.
+ *
+ * legion_etype_degrees.  deg_out[i T + t] = D_t of row rows[i] for i in [0, n), t in [0, T); a row id outside [0, node_num) has 0 in
+ * every type and reads nothing.  Returns 0, or -1 -- nothing enqueued -- for, in this order: n < 0; n > LEGION_IN_EDGES_MAX_ROWS; an
+ * untyped (or null) graph; a null rows_devptr or deg_out.  n == 0 returns 0 and enqueues nothing.  No sync.
+ *
+ * legion_etype_sample_count / legion_etype_sample_edges.  fanouts: HOST int32[T], f_t in [-1, LEGION_ETYPE_MAX_FANOUT], read before
+ * the call returns and handed to the kernels as arguments.  The pair (row, type t) yields s slots: 0 if f_t == 0 or D_t == 0; D_t if
+ * f_t == -1; D_t if replace == 0 and D_t <= f_t; f_t otherwise.  A pair with s == D_t is TAKEN WHOLE: slot k is position b_t + k, in
+ * CSR order, without a draw (so also with replace == 1 and D_t == f_t).  Otherwise, with
+ *     draw(row, t, k, R) = ((splitmix64(key ^ ((uint64)row << 32 | t << 16 | k)) >> 32) * R) >> 32,  key = splitmix64((uint64)salt),
+ * whose bias is below R / 2^32: with replace == 1 slot k is b_t + draw(row, t, k, D_t); with replace == 0 the slots follow Floyd's
+ * algorithm in slot order: j = D_t - f_t + k, c = draw(row, t, k, j + 1), and the pick is c unless an earlier slot of the pair picked
+ * c, else j -- f_t distinct positions, every subset equally likely.  The picks are a pure function of (graph, types, row, fanouts,
+ * replace, salt): a row listed twice gets the same picks, and a fresh salt per batch is the caller's to choose.
+ * _count writes offsets_out[i], the exclusive prefix sums of the rows' slot totals, and M = offsets_out[n].  _edges, given those
+ * offsets, writes slot q = offsets[i] + (the slots of row i's earlier types) + k, inside [0, cap) only: dst_out[q] = i (the row's
+ * position in rows, as legion_in_edges), src_out[q] = col[e] (-1 for a dead entry: dead entries are not dropped, the consumer masks
+ * src >= 0), eid_out[q] = e, the int64 position in col, etype_out[q] = t; [M, cap) holds -1, and 255 in etype_out.  The order is row
+ * position, then type, then slot.  A row id outside [0, node_num) has no slots.  Whatever offsets holds, no load leaves rows, indptr,
+ * col, etype and offsets, and no store leaves [0, cap).
+ * scratch: device memory, 8-byte aligned, of at least legion_etype_sample_scratch_bytes(n) = 8 ceil(n / 256) bytes (-1 for n outside
+ * [0, LEGION_IN_EDGES_MAX_ROWS]).  Nothing synchronises; both calls can be captured into a graph.
+ * Both return 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: n < 0; n > LEGION_IN_EDGES_MAX_ROWS; an untyped
+ * (or null) graph; a fan-out outside [-1, 64]; replace not 0 or 1; (_edges) cap outside [0, 2^31 - 1]; a null rows_devptr, fanouts,
+ * offsets, scratch (_count), dst_out or src_out (_edges); (_count) scratch_bytes below legion_etype_sample_scratch_bytes(n).  cap == 0
+ * returns 0 and enqueues nothing.
+ *
+ * Not offered: type arrays that are not sorted inside the rows (DGL's slow path); more than 64 types, or a fan-out above 64 for a
+ * type; per-type WEIGHTED sampling; typed vertices and metapath walks; types on the reverse CSR, whose rows are sorted by edge id;
+ * the mode inside the pool, the server, the launcher and the wire.  Rows sorted by (type, col) are not sorted by col:
+ * legion_graph_check_rows_sorted answers 0 for them, and legion_node2vec_walk and legion_reverse_edge_ids (via 0) refuse as before. */
+#define LEGION_ETYPE_MAX_TYPES 64
+#define LEGION_ETYPE_MAX_FANOUT 64
+#define LEGION_ETYPE_NO_GRAPH   (-1)
+#define LEGION_ETYPE_NO_POINTER (-2)
+#define LEGION_ETYPE_BAD_COUNT  (-3)
+#define LEGION_ETYPE_TYPE_RANGE (-4)
+#define LEGION_ETYPE_UNSORTED   (-5)
+int32_t legion_graph_set_edge_types(LegionGraphStorage* g, legion_stream_t stream, const uint8_t* etype_devptr /* uint8[E] */,
+                                    int32_t num_types);
+int32_t legion_graph_num_edge_types(const LegionGraphStorage* g);
+int32_t legion_etype_degrees(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                             int64_t* deg_out /* int64[n x T] */);
+int64_t legion_etype_sample_scratch_bytes(int32_t n);
+int32_t legion_etype_sample_count(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                                  const int32_t* fanouts /* HOST int32[T] */, int32_t replace, int64_t* offsets_out /* int64[n + 1] */,
+                                  void* scratch, int64_t scratch_bytes);
+int32_t legion_etype_sample_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
+                                  const int32_t* fanouts /* HOST int32[T] */, int32_t replace, int64_t salt,
+                                  const int64_t* offsets_devptr /* int64[n + 1] */, int64_t cap, int32_t* dst_out /* int32[cap] */,
+                                  int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */,
+                                  uint8_t* etype_out /* uint8[cap], or NULL */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -393,6 +393,14 @@ public:
     // it; RowsSorted: 1 / 0, or -1 before any check.  node2vec's membership test is a binary search of a row (legion_node2vec_walk).
     virtual int32_t CheckRowsSorted(hipStream_t s) = 0;
     virtual int32_t RowsSorted() const = 0;
+    // Typed edges (new): etype, uint8[E] indexed like the full column array, BORROWED from the caller (the rule:
+    // legion_graph_set_edge_types in legion_hip.h, its text etype_rule.h).  SetEdgeTypes checks on the device current at the call that
+    // every type is below num_types and that no row's types decrease (kernels_etype.hip), reads the verdict back through `s` (set-up: it
+    // synchronises s) and returns 0 or LEGION_ETYPE_TYPE_RANGE / _UNSORTED, after which the graph is untyped.  NumEdgeTypes: 0 untyped.
+    virtual int32_t SetEdgeTypes(hipStream_t s, const uint8_t* etype, int32_t num_types) = 0;
+    virtual void ClearEdgeTypes() = 0;                                // untyped again: what every refusal of the C entry point leaves
+    virtual const uint8_t* EdgeTypes() const = 0;
+    virtual int32_t NumEdgeTypes() const = 0;
     // The reverse CSR (new): the transpose of the full CSR (the rule: legion_graph_build_reverse in legion_hip.h), three plain
     // allocations on the device current at the first BuildReverse, which builds on `s` (set-up: it synchronises s) and returns 0; a
     // second call returns 0 without work.  ReverseCSR: the live entries E' and the arrays, or -1 and nulls before a build.
@@ -1097,6 +1105,37 @@ struct TopkParams {
 void launch_row_topk(hipStream_t s, const TopkParams& p);
 void launch_topk_keys(hipStream_t s, const int32_t* col, int64_t num_edges, const float* w, const int64_t* eids, int64_t n, int32_t mode,
                       uint64_t key, uint64_t* key_out, uint8_t* eligible_out);
+
+// typed edges and a fan-out per type (kernels_etype.hip; the rule: legion_graph_set_edge_types .. legion_etype_sample_edges in
+// legion_hip.h, its text etype_rule.h).  The arguments are the caller's to check (etype_rule.h).
+struct EtypeRows {
+    const int64_t* indptr;          // the FULL CSR
+    const int32_t* col;
+    const uint8_t* etype;           // uint8[E]: GraphStorage::EdgeTypes()
+    const int32_t* rows;            // int32[n]
+    int32_t node_num;
+    int32_t n;
+    int32_t num_types;              // 1 .. 64
+};
+struct EtypeSampleParams {
+    EtypeRows g;
+    uint64_t planes[7];             // the fan-outs: EtypeFanouts::plane (etype_rule.h)
+    uint64_t key;                   // labor_key(salt)
+    int64_t* offsets;               // int64[n + 1]: written by the count pass, read by the write pass
+    int32_t* dst;                   // int32[cap] (the write pass, as src, eid and etype_out)
+    int32_t* src;
+    int64_t* eid;                   // or null
+    uint8_t* etype_out;             // or null
+    int64_t cap;                    // <= 2^31 - 1
+    int32_t replace;                // 0, 1
+};
+// counts: three zeroed words: entries of type >= num_types, adjacent entries that decrease in type, those of them at a row's start
+void launch_etype_check(hipStream_t s, const int64_t* indptr, const uint8_t* etype, int32_t n_rows, int64_t num_edges, int32_t num_types,
+                        unsigned long long* counts);
+void launch_etype_degrees(hipStream_t s, const EtypeRows& g, int64_t* deg);
+// scratch: etype_scratch_bytes(n) bytes, 8-byte aligned; n_tiles: row_offsets_tiles(n)
+void launch_etype_count(hipStream_t s, const EtypeSampleParams& p, void* scratch, int64_t n_tiles);
+void launch_etype_edges(hipStream_t s, const EtypeSampleParams& p);
 
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {

@@ -21,6 +21,7 @@
 #include "in_edges_rule.h"
 #include "labor_rule.h"
 #include "topk_rule.h"
+#include "etype_rule.h"
 #include "induced_rule.h"
 #include "exclude_rule.h"
 #include "node_set.h"
@@ -632,6 +633,71 @@ extern "C" int32_t legion_topk_keys(legion_stream_t stream, LegionGraphStorage* 
     if (n == 0) return 0;
     lg::launch_topk_keys(static_cast<hipStream_t>(stream), graph->GetCSRNodeMatrixCPU(), graph->EdgeNum(), w_devptr, eids_devptr, n, mode,
                          labor_key(salt), key_out, eligible_out);
+    return 0;
+}
+
+// A fan-out per edge type (the rules: legion_hip.h; the draw, the slot count, the refusals and the scratch size: etype_rule.h).  As
+// above: every check comes before the launch.
+static lg::EtypeRows etype_rows(GraphStorage* graph, const int32_t* rows, int32_t n)
+{
+    return lg::EtypeRows{.indptr = graph->GetCSRNodeIndexCPU(), .col = graph->GetCSRNodeMatrixCPU(), .etype = graph->EdgeTypes(), .rows = rows,
+                         .node_num = graph->NodeNum(), .n = n, .num_types = graph->NumEdgeTypes()};
+}
+
+extern "C" int32_t legion_etype_degrees(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n, int64_t* deg_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (etype_degrees_refusal(n, graph ? graph->NumEdgeTypes() : 0, rows_devptr && deg_out) != EtypeRefusal::Ok) return -1;
+    lg::launch_etype_degrees(static_cast<hipStream_t>(stream), etype_rows(graph, rows_devptr, n), deg_out);
+    return 0;
+}
+
+extern "C" int64_t legion_etype_sample_scratch_bytes(int32_t n)
+{
+    return etype_scratch_bytes(n);
+}
+
+static lg::EtypeSampleParams etype_sample_params(GraphStorage* graph, const int32_t* rows, int32_t n, const int32_t* fanouts, int32_t replace,
+                                                 int64_t salt, int64_t* offsets)
+{
+    lg::EtypeSampleParams p{};
+    p.g = etype_rows(graph, rows, n);
+    const EtypeFanouts packed = etype_pack_fanouts(fanouts, p.g.num_types);
+    for (int32_t b = 0; b < 7; b++) p.planes[b] = packed.plane[b];
+    p.key = labor_key(salt);
+    p.offsets = offsets;
+    p.replace = replace;
+    return p;
+}
+
+extern "C" int32_t legion_etype_sample_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                             const int32_t* fanouts, int32_t replace, int64_t* offsets_out, void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (etype_count_refusal(n, graph ? graph->NumEdgeTypes() : 0, fanouts, replace, rows_devptr && fanouts && offsets_out && scratch,
+                            scratch_bytes) != EtypeRefusal::Ok)
+        return -1;
+    lg::launch_etype_count(static_cast<hipStream_t>(stream), etype_sample_params(graph, rows_devptr, n, fanouts, replace, 0, offsets_out), scratch,
+                           row_offsets_tiles(n));
+    return 0;
+}
+
+extern "C" int32_t legion_etype_sample_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr, int32_t n,
+                                             const int32_t* fanouts, int32_t replace, int64_t salt, const int64_t* offsets_devptr, int64_t cap,
+                                             int32_t* dst_out, int32_t* src_out, int64_t* eid_out, uint8_t* etype_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (etype_edges_refusal(n, graph ? graph->NumEdgeTypes() : 0, fanouts, replace, cap, rows_devptr && fanouts && offsets_devptr && dst_out && src_out) !=
+        EtypeRefusal::Ok)
+        return -1;
+    if (cap == 0) return 0;
+    lg::EtypeSampleParams p = etype_sample_params(graph, rows_devptr, n, fanouts, replace, salt, const_cast<int64_t*>(offsets_devptr));
+    p.dst = dst_out;
+    p.src = src_out;
+    p.eid = eid_out;
+    p.etype_out = etype_out;
+    p.cap = cap;
+    lg::launch_etype_edges(static_cast<hipStream_t>(stream), p);
     return 0;
 }
 

@@ -10,6 +10,7 @@
 // pinned memory otherwise.  Nothing here assumes which.
 #include "legion_core.h"
 #include "reverse_rule.h"
+#include "etype_rule.h"
 #include <unistd.h>
 #include <algorithm>
 #include <map>
@@ -701,6 +702,33 @@ public:
     }
     int32_t RowsSorted() const override { return rows_sorted_; }
 
+    // typed edges (legion_core.h): three counts on the current device, read back; the array stays the caller's
+    int32_t SetEdgeTypes(hipStream_t s, const uint8_t* etype, int32_t num_types) override
+    {
+        ClearEdgeTypes();
+        unsigned long long h[3] = {0, 0, 0};
+        if (edge_num_ > 0) {
+            unsigned long long* d = (unsigned long long*)d_alloc_space(sizeof(h));
+            HIP_CALL(hipMemsetAsync(d, 0, sizeof(h), s));
+            lg::launch_etype_check(s, csr_node_index_cpu_, etype, node_num_, edge_num_, num_types, d);
+            HIP_CALL(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s));
+            HIP_CALL(hipStreamSynchronize(s));
+            d_free_space(d);
+        }
+        const int32_t verdict = etype_set_verdict(h[0], h[1], h[2]);
+        if (verdict != 0) return verdict;
+        etype_ = etype;
+        num_types_ = num_types;
+        return 0;
+    }
+    void ClearEdgeTypes() override
+    {
+        etype_ = nullptr;
+        num_types_ = 0;
+    }
+    const uint8_t* EdgeTypes() const override { return etype_; }
+    int32_t NumEdgeTypes() const override { return num_types_; }
+
     // the reverse CSR (legion_core.h): built once on the current device, owned here
     int32_t BuildReverse(hipStream_t s) override
     {
@@ -792,6 +820,8 @@ private:
     int32_t cdf_long_cap_ = 0;
     int edge_cdf_dev_ = 0;
     int32_t rows_sorted_ = -1;           // CheckRowsSorted's answer, -1 before the first check
+    const uint8_t* etype_ = nullptr;     // [E] the caller's edge types (SetEdgeTypes), null while the graph is untyped
+    int32_t num_types_ = 0;
     bool weighted_used_ = false;         // a weighted hop has been enqueued against this graph: the table stays as it is
     int64_t* rev_indptr_ = nullptr;      // [N + 1] the reverse CSR (BuildReverse), null before it
     int32_t* rev_col_ = nullptr;         // [E']
@@ -1155,6 +1185,24 @@ extern "C" int32_t legion_graph_check_rows_sorted(LegionGraphStorage* g_, legion
 {
     GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
     return g ? g->CheckRowsSorted(static_cast<hipStream_t>(stream)) : -1;
+}
+
+// typed edges: the caller's uint8 etype[E], checked on `stream` on the current device (set-up: it synchronises that stream), borrowed
+extern "C" int32_t legion_graph_set_edge_types(LegionGraphStorage* g_, legion_stream_t stream, const uint8_t* etype_devptr, int32_t num_types)
+{
+    GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
+    const int32_t refused = etype_set_refusal(g != nullptr, etype_devptr != nullptr, num_types);
+    if (refused != 0) {
+        if (g) g->ClearEdgeTypes();                                   // every refusal leaves the graph untyped
+        return refused;
+    }
+    return g->SetEdgeTypes(static_cast<hipStream_t>(stream), etype_devptr, num_types);
+}
+
+extern "C" int32_t legion_graph_num_edge_types(const LegionGraphStorage* g_)
+{
+    const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
+    return g ? g->NumEdgeTypes() : 0;
 }
 
 // the reverse CSR: built once on `stream` on the current device (set-up: it synchronises that stream), owned by the graph

@@ -445,6 +445,47 @@ class GraphStorage:
             raise RuntimeError("legion_graph_set_edge_weights: a weighted hop has been enqueued against this graph already")
         self._weights = w                            # (alive until the build has run; replaced by the next call)
 
+    ETYPE_MAX_TYPES = 64                             # LEGION_ETYPE_MAX_TYPES
+    ETYPE_MAX_FANOUT = 64                            # LEGION_ETYPE_MAX_FANOUT
+    _ETYPE_REFUSALS = {-3: "num_types lies outside [1, 64]", -4: "an edge type is not below num_types",
+                       -5: "the edge types decrease inside a row: rows must be sorted by type"}
+
+    def set_edge_types(self, etypes, num_types, stream=None):
+        """Per-edge types for sample_etype_neighbors and etype_degrees (DGL's etype_field of a homogenised heterogeneous graph, with
+        etype_sorted=True; the rule: legion_graph_set_edge_types in legion_hip.h): uint8[E], aligned with col, a torch tensor (any
+        device) or a numpy array; every type below num_types, which lies in [1, ETYPE_MAX_TYPES]; inside a row the types do not
+        decrease (a dead entry carries a type like any other).  Both are checked on the device in one pass over the graph: the call
+        synchronises `stream` (default: the current one).  ValueError with the reason otherwise, and the graph is then untyped.  A
+        second call replaces the types.  The graph reads the tensor in place; it is kept alive here."""
+        # untyped from here on, whatever is raised below (a null pointer is the C ABI's own refusal, and clears the types)
+        self._lib.legion_graph_set_edge_types(self.handle, _stream_handle(stream), None, 0)
+        self._etypes = None
+        _need_int("num_types", num_types)
+        if isinstance(etypes, np.ndarray):
+            if etypes.dtype != np.uint8:
+                raise ValueError(f"edge types must be uint8, not {etypes.dtype}")
+            etypes = torch.from_numpy(np.ascontiguousarray(etypes))
+        if not isinstance(etypes, torch.Tensor):
+            raise ValueError(f"edge types must be a uint8 tensor or array, not {type(etypes).__name__}")
+        if etypes.dtype != torch.uint8:
+            raise ValueError(f"edge types must be uint8, not {etypes.dtype}")
+        if etypes.dim() != 1 or etypes.numel() != self.edge_num:
+            raise ValueError(f"edge types must have one entry per edge ({self.edge_num}), not shape {tuple(etypes.shape)}")
+        if not 1 <= num_types <= self.ETYPE_MAX_TYPES:
+            raise ValueError(f"num_types must lie in [1, {self.ETYPE_MAX_TYPES}], not {num_types}")
+        with torch.cuda.device(self.col.device), torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+            t = etypes.to(self.col.device).contiguous()               # (the copy runs on the stream the check runs on)
+            src = t if self.edge_num > 0 else self.indptr             # (an empty tensor has no address to hand over; E == 0 reads nothing)
+            rc = self._lib.legion_graph_set_edge_types(self.handle, _stream_handle(stream), _ptr(src), int(num_types))
+        if rc != 0:
+            raise ValueError(f"legion_graph_set_edge_types: {self._ETYPE_REFUSALS.get(rc, rc)}")
+        self._etypes = t                             # (alive while the graph is typed; replaced by the next call)
+
+    @property
+    def num_edge_types(self):
+        """T of the last set_edge_types, 0 while the graph is untyped."""
+        return int(self._lib.legion_graph_num_edge_types(self.handle))
+
     def edge_cdf(self):
         """The prefix-sum table, float32[E] as a device view (indexed like col), or None before set_edge_weights."""
         ptr = self._lib.legion_graph_edge_cdf(self.handle)
@@ -1011,6 +1052,127 @@ class GraphStorage:
             eids = eids if return_eids else None
         input_nodes, src_local = self._block_tail(seeds, n, picked, stream)
         out = (input_nodes, dst, src_local)
+        return out + (eids,) if return_eids else out
+
+    def _check_etype(self, fanouts, replace, salt, return_eids, return_etypes=True):
+        """The keywords of sample_etype_neighbors by the rules of legion_etype_sample_count, before anything touches a device:
+        ValueError with the reason.  Returns the fan-outs as the C ABI's host int32[T]."""
+        _need_bool("replace", replace)
+        _need_bool("return_eids", return_eids)
+        _need_bool("return_etypes", return_etypes)
+        _need_int("salt", salt)
+        T = self.num_edge_types
+        if T == 0:
+            raise ValueError("the graph has no edge types (set_edge_types)")
+        fanouts = list(fanouts) if isinstance(fanouts, (list, tuple, np.ndarray)) else fanouts
+        if not isinstance(fanouts, list) or len(fanouts) != T:
+            raise ValueError(f"fanouts must be a sequence of {T} integers, one per edge type")
+        for f in fanouts:
+            _need_int("a fan-out", f)
+            if not -1 <= f <= self.ETYPE_MAX_FANOUT:
+                raise ValueError(f"a fan-out must lie in [-1, {self.ETYPE_MAX_FANOUT}], not {f}")
+        if not -2 ** 63 <= salt <= 2 ** 63 - 1:
+            raise ValueError(f"salt must be an int64, not {salt}")
+        return _i32_array(fanouts)
+
+    def etype_degrees(self, rows, stream=None):
+        """The in-degree of each of rows per edge type (DGL's g.in_degrees(rows, etype=t) for every t; the rule: legion_etype_degrees
+        in legion_hip.h).  rows as in row_offsets.  Returns int64 [n, T]: the entries of type t in row rows[i], dead ones counted; 0
+        in every type for a row outside the graph.  ValueError on an untyped graph.  No sync.  Enqueued on `stream` (default: the
+        current one)."""
+        T = self.num_edge_types
+        if T == 0:
+            raise ValueError("the graph has no edge types (set_edge_types)")
+        rows, n = self._check_rows(rows)
+        rows = rows.to(self.col.device).contiguous()
+        deg = torch.empty((n, T), dtype=torch.int64, device=self.col.device)
+        if n > 0:
+            _enqueue(self._lib, "legion_etype_degrees", "etype_degrees", self.col.device, stream, (self.handle, _ptr(rows), n, _ptr(deg)),
+                     (rows, deg))
+        return deg
+
+    def _etype_edges(self, rows, n, fan, replace, salt, return_eids, return_etypes, stream, limit=None):
+        """(dst, src, eids or None, etypes or None) of rows (on the device, contiguous, checked); fan: _check_etype's; limit: the most
+        n + M may be."""
+        dev = self.col.device
+        empty = lambda dtype, want=True: torch.empty((0,), dtype=dtype, device=dev) if want else None
+        if n == 0:                                   # (an empty tensor has no address to hand over)
+            return empty(torch.int32), empty(torch.int32), empty(torch.int64, return_eids), empty(torch.uint8, return_etypes)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        nbytes = int(self._lib.legion_etype_sample_scratch_bytes(n))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+        head = (self.handle, _ptr(rows), n, fan, int(replace))
+        _enqueue(self._lib, "legion_etype_sample_count", "sample_etype_neighbors", dev, stream, head + (_ptr(offsets), _ptr(scratch), nbytes),
+                 (rows, offsets, scratch))
+        M = _read_scalar(offsets[n], stream)
+        if M > 2 ** 31 - 1:
+            raise ValueError(f"the rows yield {M} slots, at most 2^31 - 1 a call")
+        if limit is not None and n + M > limit:
+            raise ValueError(f"{n} seeds and their {M} slots are {n + M} ids in one call, at most {limit}")
+        dst = torch.empty((M,), dtype=torch.int32, device=dev)
+        src = torch.empty((M,), dtype=torch.int32, device=dev)
+        eids = torch.empty((M,), dtype=torch.int64, device=dev) if return_eids else None
+        etypes = torch.empty((M,), dtype=torch.uint8, device=dev) if return_etypes else None
+        if M > 0:
+            _enqueue(self._lib, "legion_etype_sample_edges", "sample_etype_neighbors", dev, stream,
+                     head + (int(salt), _ptr(offsets), M, _ptr(dst), _ptr(src), _ptr(eids), _ptr(etypes)), (rows, offsets, dst, src, eids, etypes))
+        return dst, src, eids, etypes
+
+    def sample_etype_neighbors(self, rows, fanouts, *, replace=False, salt=0, return_eids=False, return_etypes=True, stream=None):
+        """Neighbour sampling with a fan-out per edge type (DGL's dgl.sampling.sample_etype_neighbors on a graph whose rows are sorted
+        by type; the rule: legion_etype_sample_count and legion_etype_sample_edges in legion_hip.h).  rows as in row_offsets; fanouts:
+        num_edge_types integers in [-1, ETYPE_MAX_FANOUT], fanouts[t] for the entries of type t: 0 takes none, -1 all of them, f at
+        most f (replace: exactly f, drawn with replacement, where the row has entries of the type); a row with no more than f entries
+        of a type keeps them all, in CSR order.  Returns (dst, src) and, in this order, with return_eids eids and with return_etypes
+        etypes: int32 [M], int32 [M], int64 [M], uint8 [M], ordered by the row's position in rows, then type, then slot: dst[p] is the
+        index into rows (rows[dst] is the vertex), src[p] = col[eids[p]] -- DEAD ENTRIES ARE NOT DROPPED: src[p] == -1 where a pick is
+        a dead entry, and the caller masks src >= 0 -- eids[p] the position in col, etypes[p] its type.  The picks are a function of
+        (row, fanouts, replace, salt) alone: the same row listed twice gets the same picks, and a new salt per batch is the caller's to
+        choose.  The outputs are sized exactly, so M is read back to the host once: the call synchronises `stream` (default: the
+        current one), on which everything is enqueued.  A capturing caller uses the C ABI with a capacity instead."""
+        fan = self._check_etype(fanouts, replace, salt, return_eids, return_etypes)
+        rows, n = self._check_rows(rows)
+        out = self._etype_edges(rows.to(self.col.device).contiguous(), n, fan, replace, salt, return_eids, return_etypes, stream)
+        return tuple(x for x in out if x is not None)
+
+    def sample_etype_block(self, seeds, fanouts, *, replace=False, salt=0, return_eids=False, exclude_eids=None, stream=None):
+        """The block of one layer sampled by sample_etype_neighbors (DGL's NeighborSampler with a fan-out dict on a heterogeneous graph
+        kept homogenised): the picks with src >= 0, then unique_ids over [seeds | src].  seeds: distinct int32 vertices of the graph.
+        Returns (input_nodes, dst_local, src_local, etypes) and with return_eids also eids, in labor_block's layout: input_nodes int32
+        [U], the seeds first and in their order, then the other picked sources in order of first appearance; dst_local, src_local
+        int32 [K], indices into input_nodes (dst_local[p] is also the index into seeds, non-decreasing); etypes uint8 [K], the type of
+        each edge (what an R-GCN layer selects its weights by); eids int64 [K].  input_nodes is what FeatureStorage.set_ids takes, and
+        the seeds of the next layer out.  ValueError if the seeds and their slots are more than UNIQUE_MAX_IDS ids, and if a seed
+        repeats or lies outside the graph, as full_neighbor_block.  Synchronises `stream` (default: the current one).  exclude_eids: as
+        in full_neighbor_block -- the set's members are dropped from the picks (as DGL, which excludes after sampling)."""
+        fan = self._check_etype(fanouts, replace, salt, return_eids)
+        self._check_exclude_eids(exclude_eids)
+        seeds, n = self._check_rows(seeds, "seeds")
+        _check_unique(n)
+        seeds = seeds.to(self.col.device).contiguous()
+        with_eids = return_eids or exclude_eids is not None
+        limit = UNIQUE_MAX_IDS if exclude_eids is None else None
+        dst, src, eids, etypes = self._etype_edges(seeds, n, fan, replace, salt, with_eids, True, stream, limit=limit)
+
+        def mask():
+            keep = src >= 0
+            return dst[keep], src[keep], eids[keep] if with_eids else None, etypes[keep]
+
+        if stream is None:
+            dst, src, eids, etypes = mask()
+        else:
+            with torch.cuda.stream(stream):
+                dst, src, eids, etypes = mask()
+        if exclude_eids is not None:
+            if int(dst.numel()) > EDGE_FILTER_MAX_EDGES:
+                raise ValueError(f"the seeds yield {int(dst.numel())} slots, at most 2^30 a call with exclude_eids")
+            dst, src, eids = self._without_excluded(n, dst, src, eids, exclude_eids, stream)[:3]
+            # the filter keeps order and the kept edges' ids: their types are read back through the graph's own array
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                etypes = self._etypes[eids]
+            eids = eids if return_eids else None
+        input_nodes, src_local = self._block_tail(seeds, n, src, stream)
+        out = (input_nodes, dst, src_local, etypes)
         return out + (eids,) if return_eids else out
 
     @staticmethod
