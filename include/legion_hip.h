@@ -1026,6 +1026,68 @@ int32_t legion_etype_sample_edges(legion_stream_t stream, LegionGraphStorage* gr
                                   const int64_t* offsets_devptr /* int64[n + 1] */, int64_t cap, int32_t* dst_out /* int32[cap] */,
                                   int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */,
                                   uint8_t* etype_out /* uint8[cap], or NULL */);
+
+/* Temporal neighbour sampling: a timestamp per edge and a time bound per seed (GraphBolt's temporal_sample_neighbors, PyG's
+ * NeighborLoader(time_attr=, temporal_strategy="uniform" | "last"), TGL's most recent k neighbours; kernels_temporal.hip, the rule's
+ * text temporal_rule.h).
+ *
+ * legion_graph_set_edge_times.  time[e], int64, is the timestamp of entry e of the full CSR's col, aligned with it as the etype of
+ * legion_graph_set_edge_types.  The graph BORROWS the pointer: the array stays the caller's, alive and unchanged while the graph has
+ * times; a second call replaces them, a null time_devptr removes them.  The call looks through the array once on the current device:
+ * if inside every row the times do not decrease (time[e - 1] <= time[e] for adjacent entries of one row) the graph is TIME-SORTED and
+ * the ops below run their sorted class, otherwise their scan class: an unsorted array is not refused.  It is set-up: it synchronises
+ * `stream` and reads the answer back.  Returns 0, or -1 for a null graph.  legion_graph_edge_times_sorted: 1 sorted, 0 unsorted, -1
+ * for a graph without times or a null graph.
+ *
+ * The candidates of a row.  For row rows[i] observed at bounds[i] they are the entries e of the row with time[e] < bounds[i], a strict,
+ * signed 64-bit comparison (for an inclusive one pass t + 1).  A dead entry, col[e] = -1, carries a time and counts like any other.
+ * C is their number, and a candidate's RANK is its index among the row's candidates in CSR order.  A row id outside [0, node_num) has
+ * C = 0 and reads nothing.  On a time-sorted graph the candidates are the row's first C entries.
+ *
+ * legion_temporal_sample_count / legion_temporal_sample_edges.  fanout is -1 or lies in [1, LEGION_TEMPORAL_MAX_FANOUT].  A row yields
+ * s slots: 0 if C == 0; C if fanout == -1; C if replace == 0 and C <= fanout; fanout otherwise.  Slot k picks a rank:
+ *   - strategy LEGION_TEMPORAL_LAST: rank C - s + k, the s most recent candidates in CSR order.  Defined on a time-sorted graph only,
+ *     and with replace == 0;
+ *   - strategy LEGION_TEMPORAL_UNIFORM, s == C: rank k, the row TAKEN WHOLE without a draw (so also with replace == 1 and C == fanout);
+ *   - strategy LEGION_TEMPORAL_UNIFORM otherwise, with draw(row, k, R) the draw of legion_etype_sample_edges at t = 0, a function of
+ *     (salt, the row's vertex, k): with replace == 1 the rank is draw(row, k, C); with replace == 0 the slots follow Floyd's algorithm
+ *     in slot order: j = C - fanout + k, c = draw(row, k, j + 1), and the rank is c unless an earlier slot of the row picked c, else
+ *     j -- fanout distinct ranks, every subset equally likely.  A C at or above 2^32 draws below 2^32.
+ * The picks are a pure function of (graph, times, row, bound, fanout, strategy, replace, salt), the same in both classes: the rule is
+ * stated over ranks.  A row listed twice with one bound gets the same picks; a fresh salt per batch is the caller's to choose.
+ * _count writes cand_out[i] = C of row i, offsets_out[i], the exclusive prefix sums of the rows' slots, and M = offsets_out[n].
+ * _edges, given both, writes slot q = offsets[i] + k, inside [0, cap) only: dst_out[q] = i (the row's position in rows, as
+ * legion_in_edges), src_out[q] = col[e] (-1 for a dead entry: dead entries are not dropped, the consumer masks src >= 0), eid_out[q]
+ * = e, the int64 position in col, time_out[q] = time[e]; [M, cap) holds -1.  Whatever cand and offsets hold, no load leaves rows,
+ * bounds, indptr, col, time, cand and offsets, and no store leaves [0, cap).
+ * scratch: device memory, 8-byte aligned, of at least legion_temporal_sample_scratch_bytes(n) = 8 ceil(n / 256) bytes (-1 for n
+ * outside [0, LEGION_IN_EDGES_MAX_ROWS]).  Nothing synchronises and nothing is allocated; both calls can be captured into a graph.
+ * Both return 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: n < 0; n > LEGION_IN_EDGES_MAX_ROWS; a graph
+ * without times (or null); fanout 0, below -1 or above 64; a strategy that is neither constant; replace not 0 or 1; LAST with replace
+ * == 1; LAST on a graph that is not time-sorted; (_edges) cap outside [0, 2^31 - 1]; a null rows_devptr, bounds_devptr, cand,
+ * offsets, scratch (_count), dst_out or src_out (_edges); (_count) scratch_bytes below legion_temporal_sample_scratch_bytes(n).
+ * cap == 0 returns 0 and enqueues nothing.
+ *
+ * Not offered: LAST on rows that are not sorted by time (a selection by key on unsorted rows is legion_row_topk's); de-duplicated
+ * temporal blocks (the entity is a (vertex, time) pair, which the int32 legion_unique_ids cannot key); typed and temporal sampling
+ * together (rows sorted by type are not sorted by time); per-vertex timestamps; an inclusive comparison (pass t + 1); the mode inside
+ * the pool, the server, the launcher and the wire. */
+#define LEGION_TEMPORAL_UNIFORM 0
+#define LEGION_TEMPORAL_LAST 1
+#define LEGION_TEMPORAL_MAX_FANOUT 64
+int32_t legion_graph_set_edge_times(LegionGraphStorage* g, legion_stream_t stream, const int64_t* time_devptr /* int64[E], or NULL */);
+int32_t legion_graph_edge_times_sorted(const LegionGraphStorage* g);
+int64_t legion_temporal_sample_scratch_bytes(int32_t n);
+int32_t legion_temporal_sample_count(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */,
+                                     const int64_t* bounds_devptr /* int64[n] */, int32_t n, int32_t fanout, int32_t strategy,
+                                     int32_t replace, int64_t* cand_out /* int64[n] */, int64_t* offsets_out /* int64[n + 1] */,
+                                     void* scratch, int64_t scratch_bytes);
+int32_t legion_temporal_sample_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */,
+                                     const int64_t* bounds_devptr /* int64[n] */, int32_t n, int32_t fanout, int32_t strategy,
+                                     int32_t replace, int64_t salt, const int64_t* cand_devptr /* int64[n] */,
+                                     const int64_t* offsets_devptr /* int64[n + 1] */, int64_t cap, int32_t* dst_out /* int32[cap] */,
+                                     int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */,
+                                     int64_t* time_out /* int64[cap], or NULL */);
 /* Measurement aid (no reference counterpart): while enabled, FeatureCacheLookup records a HIP event
  * on its own stream before and after the gather launch.  _end returns how many gathers were timed
  * and fills their elapsed ms and op ids; call it after synchronising the stream. */

@@ -401,6 +401,14 @@ public:
     virtual void ClearEdgeTypes() = 0;                                // untyped again: what every refusal of the C entry point leaves
     virtual const uint8_t* EdgeTypes() const = 0;
     virtual int32_t NumEdgeTypes() const = 0;
+    // Edge times (new): time, int64[E] indexed like the full column array, BORROWED from the caller (the rule:
+    // legion_graph_set_edge_times in legion_hip.h, its text temporal_rule.h).  SetEdgeTimes finds out on the device current at the call
+    // whether every row is non-decreasing in time (kernels_temporal.hip), reads the answer back through `s` (set-up: it synchronises s)
+    // and records it: an unsorted array is accepted, and selects the scan class.  EdgeTimesSorted: 1 / 0, or -1 while there are none.
+    virtual void SetEdgeTimes(hipStream_t s, const int64_t* time) = 0;
+    virtual void ClearEdgeTimes() = 0;
+    virtual const int64_t* EdgeTimes() const = 0;
+    virtual int32_t EdgeTimesSorted() const = 0;
     // The reverse CSR (new): the transpose of the full CSR (the rule: legion_graph_build_reverse in legion_hip.h), three plain
     // allocations on the device current at the first BuildReverse, which builds on `s` (set-up: it synchronises s) and returns 0; a
     // second call returns 0 without work.  ReverseCSR: the live entries E' and the arrays, or -1 and nulls before a build.
@@ -1136,6 +1144,35 @@ void launch_etype_degrees(hipStream_t s, const EtypeRows& g, int64_t* deg);
 // scratch: etype_scratch_bytes(n) bytes, 8-byte aligned; n_tiles: row_offsets_tiles(n)
 void launch_etype_count(hipStream_t s, const EtypeSampleParams& p, void* scratch, int64_t n_tiles);
 void launch_etype_edges(hipStream_t s, const EtypeSampleParams& p);
+
+// temporal neighbour sampling (kernels_temporal.hip; the rule: legion_graph_set_edge_times .. legion_temporal_sample_edges in
+// legion_hip.h, its text temporal_rule.h).  The arguments are the caller's to check (temporal_rule.h).
+struct TemporalParams {
+    const int64_t* indptr;          // the FULL CSR
+    const int32_t* col;
+    const int64_t* time;            // int64[E]: GraphStorage::EdgeTimes()
+    const int32_t* rows;            // int32[n]
+    const int64_t* bounds;          // int64[n]
+    int32_t node_num;
+    int32_t n;
+    int32_t fanout;                 // -1, 1 .. 64
+    int32_t strategy;               // LEGION_TEMPORAL_UNIFORM, _LAST
+    int32_t replace;                // 0, 1
+    int32_t sorted;                 // GraphStorage::EdgeTimesSorted(): 1 the sorted class, 0 the scan class
+    uint64_t key;                   // labor_key(salt)
+    int64_t* cand;                  // int64[n]: the rows' candidate counts, written by the count pass, read by the write pass
+    int64_t* offsets;               // int64[n + 1]: as cand
+    int32_t* dst;                   // int32[cap] (the write pass, as src, eid and time_out)
+    int32_t* src;
+    int64_t* eid;                   // or null
+    int64_t* time_out;              // or null
+    int64_t cap;                    // <= 2^31 - 1
+};
+// counts: two zeroed words: adjacent entries that decrease in time, those of them at a row's start
+void launch_time_check(hipStream_t s, const int64_t* indptr, const int64_t* time, int32_t n_rows, int64_t num_edges, unsigned long long* counts);
+// scratch: temporal_scratch_bytes(n) bytes, 8-byte aligned; n_tiles: row_offsets_tiles(n)
+void launch_temporal_count(hipStream_t s, const TemporalParams& p, void* scratch, int64_t n_tiles);
+void launch_temporal_edges(hipStream_t s, const TemporalParams& p);
 
 // PinSAGE's neighbour sampler (kernels_pinsage.hip; the rule: legion_pinsage_neighbors in legion_hip.h)
 struct PinsageParams {

@@ -22,6 +22,7 @@
 #include "labor_rule.h"
 #include "topk_rule.h"
 #include "etype_rule.h"
+#include "temporal_rule.h"
 #include "induced_rule.h"
 #include "exclude_rule.h"
 #include "node_set.h"
@@ -698,6 +699,69 @@ extern "C" int32_t legion_etype_sample_edges(legion_stream_t stream, LegionGraph
     p.etype_out = etype_out;
     p.cap = cap;
     lg::launch_etype_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// Temporal neighbour sampling (the rules: legion_hip.h; the candidates, the slot count, the ranks, the refusals and the scratch size:
+// temporal_rule.h).  As above: every check comes before the launch.
+extern "C" int64_t legion_temporal_sample_scratch_bytes(int32_t n)
+{
+    return temporal_scratch_bytes(n);
+}
+
+static lg::TemporalParams temporal_params(GraphStorage* graph, const int32_t* rows, const int64_t* bounds, int32_t n, int32_t fanout, int32_t strategy,
+                                          int32_t replace, int64_t salt, int64_t* cand, int64_t* offsets)
+{
+    lg::TemporalParams p{};
+    p.indptr = graph->GetCSRNodeIndexCPU();
+    p.col = graph->GetCSRNodeMatrixCPU();
+    p.time = graph->EdgeTimes();
+    p.rows = rows;
+    p.bounds = bounds;
+    p.node_num = graph->NodeNum();
+    p.n = n;
+    p.fanout = fanout;
+    p.strategy = strategy;
+    p.replace = replace;
+    p.sorted = graph->EdgeTimesSorted();
+    p.key = labor_key(salt);
+    p.cand = cand;
+    p.offsets = offsets;
+    return p;
+}
+
+extern "C" int32_t legion_temporal_sample_count(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr,
+                                                const int64_t* bounds_devptr, int32_t n, int32_t fanout, int32_t strategy, int32_t replace,
+                                                int64_t* cand_out, int64_t* offsets_out, void* scratch, int64_t scratch_bytes)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (temporal_count_refusal(n, graph ? graph->EdgeTimesSorted() : -1, fanout, strategy, replace,
+                               rows_devptr && bounds_devptr && cand_out && offsets_out && scratch, scratch_bytes) != TemporalRefusal::Ok)
+        return -1;
+    lg::launch_temporal_count(static_cast<hipStream_t>(stream),
+                              temporal_params(graph, rows_devptr, bounds_devptr, n, fanout, strategy, replace, 0, cand_out, offsets_out), scratch,
+                              row_offsets_tiles(n));
+    return 0;
+}
+
+extern "C" int32_t legion_temporal_sample_edges(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* rows_devptr,
+                                                const int64_t* bounds_devptr, int32_t n, int32_t fanout, int32_t strategy, int32_t replace,
+                                                int64_t salt, const int64_t* cand_devptr, const int64_t* offsets_devptr, int64_t cap, int32_t* dst_out,
+                                                int32_t* src_out, int64_t* eid_out, int64_t* time_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (temporal_edges_refusal(n, graph ? graph->EdgeTimesSorted() : -1, fanout, strategy, replace, cap,
+                               rows_devptr && bounds_devptr && cand_devptr && offsets_devptr && dst_out && src_out) != TemporalRefusal::Ok)
+        return -1;
+    if (cap == 0) return 0;
+    lg::TemporalParams p = temporal_params(graph, rows_devptr, bounds_devptr, n, fanout, strategy, replace, salt, const_cast<int64_t*>(cand_devptr),
+                                           const_cast<int64_t*>(offsets_devptr));
+    p.dst = dst_out;
+    p.src = src_out;
+    p.eid = eid_out;
+    p.time_out = time_out;
+    p.cap = cap;
+    lg::launch_temporal_edges(static_cast<hipStream_t>(stream), p);
     return 0;
 }
 

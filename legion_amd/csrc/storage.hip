@@ -11,6 +11,7 @@
 #include "legion_core.h"
 #include "reverse_rule.h"
 #include "etype_rule.h"
+#include "temporal_rule.h"
 #include <unistd.h>
 #include <algorithm>
 #include <map>
@@ -729,6 +730,30 @@ public:
     const uint8_t* EdgeTypes() const override { return etype_; }
     int32_t NumEdgeTypes() const override { return num_types_; }
 
+    // edge times (legion_core.h): two counts on the current device, read back; the array stays the caller's
+    void SetEdgeTimes(hipStream_t s, const int64_t* time) override
+    {
+        ClearEdgeTimes();
+        unsigned long long h[2] = {0, 0};
+        if (edge_num_ > 0) {
+            unsigned long long* d = (unsigned long long*)d_alloc_space(sizeof(h));
+            HIP_CALL(hipMemsetAsync(d, 0, sizeof(h), s));
+            lg::launch_time_check(s, csr_node_index_cpu_, time, node_num_, edge_num_, d);
+            HIP_CALL(hipMemcpyAsync(h, d, sizeof(h), hipMemcpyDeviceToHost, s));
+            HIP_CALL(hipStreamSynchronize(s));
+            d_free_space(d);
+        }
+        time_ = time;
+        times_sorted_ = temporal_sorted_verdict(h[0], h[1]);
+    }
+    void ClearEdgeTimes() override
+    {
+        time_ = nullptr;
+        times_sorted_ = -1;
+    }
+    const int64_t* EdgeTimes() const override { return time_; }
+    int32_t EdgeTimesSorted() const override { return times_sorted_; }
+
     // the reverse CSR (legion_core.h): built once on the current device, owned here
     int32_t BuildReverse(hipStream_t s) override
     {
@@ -822,6 +847,8 @@ private:
     int32_t rows_sorted_ = -1;           // CheckRowsSorted's answer, -1 before the first check
     const uint8_t* etype_ = nullptr;     // [E] the caller's edge types (SetEdgeTypes), null while the graph is untyped
     int32_t num_types_ = 0;
+    const int64_t* time_ = nullptr;      // [E] the caller's edge times (SetEdgeTimes), null while the graph has none
+    int32_t times_sorted_ = -1;          // 1: every row is non-decreasing in time, 0: some row is not, -1: no times
     bool weighted_used_ = false;         // a weighted hop has been enqueued against this graph: the table stays as it is
     int64_t* rev_indptr_ = nullptr;      // [N + 1] the reverse CSR (BuildReverse), null before it
     int32_t* rev_col_ = nullptr;         // [E']
@@ -1203,6 +1230,23 @@ extern "C" int32_t legion_graph_num_edge_types(const LegionGraphStorage* g_)
 {
     const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
     return g ? g->NumEdgeTypes() : 0;
+}
+
+// edge times: the caller's int64 time[E], looked through on `stream` on the current device (set-up: it synchronises that stream),
+// borrowed; null removes them
+extern "C" int32_t legion_graph_set_edge_times(LegionGraphStorage* g_, legion_stream_t stream, const int64_t* time_devptr)
+{
+    GraphStorage* g = reinterpret_cast<GraphStorage*>(g_);
+    if (!g) return -1;
+    if (time_devptr) g->SetEdgeTimes(static_cast<hipStream_t>(stream), time_devptr);
+    else g->ClearEdgeTimes();
+    return 0;
+}
+
+extern "C" int32_t legion_graph_edge_times_sorted(const LegionGraphStorage* g_)
+{
+    const GraphStorage* g = reinterpret_cast<const GraphStorage*>(g_);
+    return g ? g->EdgeTimesSorted() : -1;
 }
 
 // the reverse CSR: built once on `stream` on the current device (set-up: it synchronises that stream), owned by the graph

@@ -486,6 +486,40 @@ class GraphStorage:
         """T of the last set_edge_types, 0 while the graph is untyped."""
         return int(self._lib.legion_graph_num_edge_types(self.handle))
 
+    TEMPORAL_MAX_FANOUT = 64                         # LEGION_TEMPORAL_MAX_FANOUT
+    _TEMPORAL_STRATEGIES = {"uniform": 0, "last": 1}                  # LEGION_TEMPORAL_UNIFORM, LEGION_TEMPORAL_LAST
+
+    def set_edge_times(self, times, stream=None):
+        """Per-edge timestamps for sample_temporal_neighbors, sample_temporal_layers and temporal_degrees (the rule:
+        legion_graph_set_edge_times in legion_hip.h): int64 [E] on the graph's device, aligned with col; anything else is a ValueError,
+        and the graph then has no times.  One pass over the graph finds out whether every row is non-decreasing in time
+        (edge_times_sorted): the call synchronises `stream` (default: the current one).  Unsorted rows are accepted and sampled by the
+        slower scan class.  A second call replaces the times.  The graph reads the tensor in place; it is kept alive here."""
+        self._lib.legion_graph_set_edge_times(self.handle, _stream_handle(stream), None)
+        self._times = None
+        if not isinstance(times, torch.Tensor) or times.dtype != torch.int64:
+            raise ValueError(f"edge times must be an int64 tensor, not {getattr(times, 'dtype', type(times).__name__)}")
+        if times.dim() != 1 or times.numel() != self.edge_num:
+            raise ValueError(f"edge times must have one entry per edge ({self.edge_num}), not shape {tuple(times.shape)}")
+        if times.device != self.col.device:
+            raise ValueError(f"edge times must be on the graph's device ({self.col.device}), not {times.device}")
+        t = times.contiguous()
+        with torch.cuda.device(self.col.device):
+            src = t if self.edge_num > 0 else self.indptr              # (an empty tensor has no address to hand over; E == 0 reads nothing)
+            rc = self._lib.legion_graph_set_edge_times(self.handle, _stream_handle(stream), _ptr(src))
+        if rc != 0:
+            raise RuntimeError("legion_graph_set_edge_times refused a graph")
+        self._times = t                              # (alive while the graph has times; replaced by the next call)
+
+    @property
+    def has_edge_times(self):
+        return int(self._lib.legion_graph_edge_times_sorted(self.handle)) >= 0
+
+    @property
+    def edge_times_sorted(self):
+        """True if every row of the graph is non-decreasing in time (the sorted class), False otherwise or without times."""
+        return int(self._lib.legion_graph_edge_times_sorted(self.handle)) == 1
+
     def edge_cdf(self):
         """The prefix-sum table, float32[E] as a device view (indexed like col), or None before set_edge_weights."""
         ptr = self._lib.legion_graph_edge_cdf(self.handle)
@@ -1174,6 +1208,123 @@ class GraphStorage:
         input_nodes, src_local = self._block_tail(seeds, n, src, stream)
         out = (input_nodes, dst, src_local, etypes)
         return out + (eids,) if return_eids else out
+
+    def _check_temporal(self, fanout, strategy, replace, salt, return_eids, return_times):
+        """The keywords of sample_temporal_neighbors by the rules of legion_temporal_sample_count, before anything touches a device:
+        ValueError with the reason.  Returns the strategy's constant."""
+        _need_bool("replace", replace)
+        _need_bool("return_eids", return_eids)
+        _need_bool("return_times", return_times)
+        _need_int("salt", salt)
+        _need_int("fanout", fanout)
+        if not self.has_edge_times:
+            raise ValueError("the graph has no edge times (set_edge_times)")
+        if fanout != -1 and not 1 <= fanout <= self.TEMPORAL_MAX_FANOUT:
+            raise ValueError(f"fanout must be -1 or lie in [1, {self.TEMPORAL_MAX_FANOUT}], not {fanout}")
+        if not isinstance(strategy, str) or strategy not in self._TEMPORAL_STRATEGIES:
+            raise ValueError(f"strategy must be 'uniform' or 'last', not {strategy!r}")
+        if strategy == "last" and replace:
+            raise ValueError("strategy 'last' draws nothing: replace must be False")
+        if strategy == "last" and not self.edge_times_sorted:
+            raise ValueError("strategy 'last' needs every row sorted by time (edge_times_sorted)")
+        if not -2 ** 63 <= salt <= 2 ** 63 - 1:
+            raise ValueError(f"salt must be an int64, not {salt}")
+        return self._TEMPORAL_STRATEGIES[strategy]
+
+    def _check_row_times(self, rows, row_times, name="rows"):
+        """(rows, bounds, n) on the device, contiguous: rows as in row_offsets, row_times int64, one per row."""
+        rows, n = self._check_rows(rows, name)
+        bounds = _as_1d(row_times, torch.int64, name[:-1] + "_times")
+        if int(bounds.numel()) != n:
+            raise ValueError(f"{name[:-1]}_times must have one entry per row ({n}), not {int(bounds.numel())}")
+        return rows.to(self.col.device).contiguous(), bounds.to(self.col.device).contiguous(), n
+
+    def _temporal_count(self, rows, bounds, n, fanout, strategy, replace, stream):
+        """(cand, offsets) of rows (on the device, contiguous, checked), n > 0."""
+        dev = self.col.device
+        cand = torch.empty((n,), dtype=torch.int64, device=dev)
+        offsets = torch.empty((n + 1,), dtype=torch.int64, device=dev)
+        nbytes = int(self._lib.legion_temporal_sample_scratch_bytes(n))
+        scratch = torch.empty((nbytes // 8,), dtype=torch.int64, device=dev)
+        _enqueue(self._lib, "legion_temporal_sample_count", "sample_temporal_neighbors", dev, stream,
+                 (self.handle, _ptr(rows), _ptr(bounds), n, int(fanout), strategy, int(replace), _ptr(cand), _ptr(offsets), _ptr(scratch), nbytes),
+                 (rows, bounds, cand, offsets, scratch))
+        return cand, offsets
+
+    def temporal_degrees(self, rows, row_times, stream=None):
+        """The candidates of each of rows: int64 [n], the entries of row rows[i] whose time is below row_times[i], dead ones counted;
+        0 for a row outside the graph (the count call of legion_temporal_sample_count with fanout -1).  rows as in row_offsets,
+        row_times int64, one per row.  ValueError on a graph without times.  No sync.  Enqueued on `stream` (default: the current one)."""
+        if not self.has_edge_times:
+            raise ValueError("the graph has no edge times (set_edge_times)")
+        rows, bounds, n = self._check_row_times(rows, row_times)
+        if n == 0:
+            return torch.empty((0,), dtype=torch.int64, device=self.col.device)
+        return self._temporal_count(rows, bounds, n, -1, 0, False, stream)[0]
+
+    def _temporal_edges(self, rows, bounds, n, fanout, strategy, replace, salt, return_eids, return_times, stream):
+        """(dst, src, eids or None, times or None) of rows and bounds (on the device, contiguous, checked)."""
+        dev = self.col.device
+        empty = lambda dtype, want=True: torch.empty((0,), dtype=dtype, device=dev) if want else None
+        if n == 0:                                   # (an empty tensor has no address to hand over)
+            return empty(torch.int32), empty(torch.int32), empty(torch.int64, return_eids), empty(torch.int64, return_times)
+        cand, offsets = self._temporal_count(rows, bounds, n, fanout, strategy, replace, stream)
+        M = _read_scalar(offsets[n], stream)
+        if M > 2 ** 31 - 1:
+            raise ValueError(f"the rows yield {M} slots, at most 2^31 - 1 a call")
+        dst = torch.empty((M,), dtype=torch.int32, device=dev)
+        src = torch.empty((M,), dtype=torch.int32, device=dev)
+        eids = torch.empty((M,), dtype=torch.int64, device=dev) if return_eids else None
+        times = torch.empty((M,), dtype=torch.int64, device=dev) if return_times else None
+        if M > 0:
+            _enqueue(self._lib, "legion_temporal_sample_edges", "sample_temporal_neighbors", dev, stream,
+                     (self.handle, _ptr(rows), _ptr(bounds), n, int(fanout), strategy, int(replace), int(salt), _ptr(cand), _ptr(offsets), M,
+                      _ptr(dst), _ptr(src), _ptr(eids), _ptr(times)), (rows, bounds, cand, offsets, dst, src, eids, times))
+        return dst, src, eids, times
+
+    def sample_temporal_neighbors(self, rows, row_times, fanout, *, strategy="uniform", replace=False, salt=0, return_eids=False,
+                                  return_times=False, stream=None):
+        """Neighbour sampling under a time bound per row (GraphBolt's temporal_sample_neighbors, PyG's NeighborLoader(time_attr=,
+        temporal_strategy=); the rule: legion_temporal_sample_count and legion_temporal_sample_edges in legion_hip.h).  rows as in
+        row_offsets; row_times int64, one per row: row rows[i] sees only its entries whose time is BELOW row_times[i] (strict; pass
+        t + 1 for an inclusive bound), its candidates.  fanout: -1 takes every candidate, f in [1, TEMPORAL_MAX_FANOUT] at most f
+        (replace: exactly f, drawn with replacement, where the row has a candidate); a row with no more than f candidates keeps them
+        all, in CSR order.  strategy "uniform" draws among the candidates; "last" takes the f most recent ones in CSR order and needs
+        edge_times_sorted and replace=False.  Returns (dst, src) and, in this order, with return_eids eids and with return_times times:
+        int32 [M], int32 [M], int64 [M], int64 [M], ordered by the row's position in rows, then slot: dst[p] is the index into rows
+        (rows[dst] is the vertex), src[p] = col[eids[p]] -- DEAD ENTRIES ARE NOT DROPPED: src[p] == -1 where a pick is a dead entry,
+        and the caller masks src >= 0 -- eids[p] the position in col, times[p] its timestamp.  The picks are a function of (row, bound,
+        fanout, strategy, replace, salt) alone, the same whether the graph's rows are sorted by time or not: the same row listed twice
+        with one bound gets the same picks, and a new salt per batch is the caller's to choose.  The outputs are sized exactly, so M
+        is read back to the host once: the call synchronises `stream` (default: the current one), on which everything is enqueued.  A
+        capturing caller uses the C ABI with a capacity instead."""
+        strat = self._check_temporal(fanout, strategy, replace, salt, return_eids, return_times)
+        rows, bounds, n = self._check_row_times(rows, row_times)
+        out = self._temporal_edges(rows, bounds, n, fanout, strat, replace, salt, return_eids, return_times, stream)
+        return tuple(x for x in out if x is not None)
+
+    def sample_temporal_layers(self, seeds, seed_times, fanouts, *, strategy="uniform", replace=False, salt=0, return_eids=False,
+                               return_times=False, stream=None):
+        """The multi-hop tree of sample_temporal_neighbors that TGAT and TGL consume: hop 0 samples the seeds at seed_times with
+        fanouts[0]; hop h + 1 samples rows = the src of hop h, each at the bound of the row it was picked for (bounds[dst]), with
+        fanouts[h + 1].  A dead src (-1) is a row outside the graph and yields nothing.  Nothing is de-duplicated: the entity is a
+        (vertex, time) pair.  Returns a list with sample_temporal_neighbors' tuple per hop; dst of hop h + 1 indexes the picks of hop
+        h.  Synchronises `stream` (default: the current one) once per hop."""
+        fanouts = list(fanouts) if isinstance(fanouts, (list, tuple, np.ndarray)) else fanouts
+        if not isinstance(fanouts, list) or not fanouts:
+            raise ValueError("fanouts must be a non-empty sequence of integers, one per hop")
+        strat = [self._check_temporal(f, strategy, replace, salt, return_eids, return_times) for f in fanouts][0]
+        rows, bounds, n = self._check_row_times(seeds, seed_times, "seeds")
+        hops = []
+        for f in fanouts:
+            if n > self.IN_EDGES_MAX_ROWS:
+                raise ValueError(f"hop {len(hops)} has {n} rows, at most {self.IN_EDGES_MAX_ROWS} a call")
+            out = self._temporal_edges(rows, bounds, n, f, strat, replace, salt, return_eids, return_times, stream)
+            hops.append(tuple(x for x in out if x is not None))
+            with torch.cuda.stream(stream if stream is not None else torch.cuda.current_stream()):
+                rows, bounds = out[1], bounds[out[0].long()]
+            n = int(rows.numel())
+        return hops
 
     @staticmethod
     def _check_nodes(nodes, limit=NODE_SET_MAX_IDS):

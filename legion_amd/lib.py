@@ -36,6 +36,8 @@ SIGNATURES = {
     "legion_graph_check_rows_sorted": (c_i32, [c_p, c_p]),
     "legion_graph_set_edge_types": (c_i32, [c_p, c_p, c_p, c_i32]),
     "legion_graph_num_edge_types": (c_i32, [c_p]),
+    "legion_graph_set_edge_times": (c_i32, [c_p, c_p, c_p]),
+    "legion_graph_edge_times_sorted": (c_i32, [c_p]),
     "legion_graph_build_reverse": (c_i32, [c_p, c_p]),
     "legion_graph_reverse_csr": (c_i64, [c_p, ctypes.POINTER(c_p), ctypes.POINTER(c_p), ctypes.POINTER(c_p)]),
     "legion_feature_create": (c_p, [c_i32, c_i32, c_i32, c_p]),
@@ -167,6 +169,9 @@ SIGNATURES = {
     "legion_etype_sample_scratch_bytes": (c_i64, [c_i32]),
     "legion_etype_sample_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32, c_p, c_p, c_i64]),
     "legion_etype_sample_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i32, c_i64, c_p, c_i64, c_p, c_p, c_p, c_p]),
+    "legion_temporal_sample_scratch_bytes": (c_i64, [c_i32]),
+    "legion_temporal_sample_count": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_p, c_p, c_p, c_i64]),
+    "legion_temporal_sample_edges": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_i32, c_i32, c_i64, c_p, c_p, c_i64, c_p, c_p, c_p, c_p]),
     "legion_node_set_bytes": (c_i64, [c_i32]),
     "legion_node_set_build": (c_i32, [c_p, c_p, c_i32, c_p, c_i64, c_p]),
     "legion_node_set_lookup": (c_i32, [c_p, c_p, c_i64, c_i32, c_p, c_i64, c_p]),
