@@ -535,7 +535,8 @@ void legion_draw_weighted_batch(legion_stream_t stream, const int32_t* idx, cons
  * base < 0; base + num_walks * length > 2^31 - 1 (the draw index, the restart offset included, stays where the power tables reach);
  * weighted outside {0, 1}; weighted == 1 on a graph without a table; restart_prob NaN or outside [0, 1].  num_walks == 0 returns 0
  * and enqueues nothing.  A weighted walk counts as a weighted hop for legion_graph_set_edge_weights: the table cannot be replaced
- * afterwards.  node2vec's p / q bias is legion_node2vec_walk, below.  Not offered: metapaths; the server, the launcher and the wire. */
+ * afterwards.  node2vec's p / q bias is legion_node2vec_walk, a metapath over typed edges legion_metapath_walk, both below.  Not offered: the
+ * server, the launcher and the wire. */
 int32_t legion_random_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
                            int32_t length, int32_t weighted, float restart_prob, int64_t base, int32_t* traces_out,
                            int64_t* edge_ids_out /* may be NULL */);
@@ -597,7 +598,8 @@ int32_t legion_node2vec_walk(legion_stream_t stream, LegionGraphStorage* graph, 
  * R < 1, T < 1 or k < 1; R * T > LEGION_PINSAGE_MAX_VISITS or k > LEGION_PINSAGE_MAX_VISITS; base < 0;
  * base + num_seeds * R * T > 2^31 - 1 (in 64 bits); weighted outside {0, 1}; weighted == 1 on a graph without a table; termination_prob
  * NaN or outside [0, 1].  num_seeds == 0 returns 0 and enqueues nothing.  A weighted call counts as a weighted hop for
- * legion_graph_set_edge_weights, like a weighted walk.  Not offered: metapaths (heterogeneous graphs); the server, the launcher, the wire. */
+ * legion_graph_set_edge_weights, like a weighted walk.  Over a metapath of a typed graph: legion_pinsage_metapath_neighbors, below.  Not
+ * offered: the server, the launcher, the wire. */
 #define LEGION_PINSAGE_MAX_VISITS 1024
 int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_seeds,
                                  int32_t num_walks_per_seed, int32_t walk_length, int32_t num_neighbors, int32_t weighted,
@@ -1002,7 +1004,7 @@ int32_t legion_topk_keys(legion_stream_t stream, LegionGraphStorage* graph, cons
  * returns 0 and enqueues nothing.
  *
  * Not offered: type arrays that are not sorted inside the rows (DGL's slow path); more than 64 types, or a fan-out above 64 for a
- * type; per-type WEIGHTED sampling; typed vertices and metapath walks; types on the reverse CSR, whose rows are sorted by edge id;
+ * type; per-type WEIGHTED sampling; typed vertices (metapath walks over edge types: legion_metapath_walk); types on the reverse CSR, whose rows are sorted by edge id;
  * the mode inside the pool, the server, the launcher and the wire.  Rows sorted by (type, col) are not sorted by col:
  * legion_graph_check_rows_sorted answers 0 for them, and legion_node2vec_walk and legion_reverse_edge_ids (via 0) refuse as before. */
 #define LEGION_ETYPE_MAX_TYPES 64
@@ -1026,6 +1028,59 @@ int32_t legion_etype_sample_edges(legion_stream_t stream, LegionGraphStorage* gr
                                   const int64_t* offsets_devptr /* int64[n + 1] */, int64_t cap, int32_t* dst_out /* int32[cap] */,
                                   int32_t* src_out /* int32[cap] */, int64_t* eid_out /* int64[cap], or NULL */,
                                   uint8_t* etype_out /* uint8[cap], or NULL */);
+
+/* Metapath random walks and PinSAGE over a metapath on typed edges (DGL's dgl.sampling.random_walk(g, nodes, metapath=[...]) and
+ * PinSAGESampler(g, ntype, other_type, ...)), new in this build; no reference counterpart; kernels_metapath.hip, the rule's text
+ * metapath_rule.h.  The graph has edge types (legion_graph_set_edge_types, T types, every row sorted by type).
+ *
+ * legion_metapath_walk.  metapath: HOST uint8[period], read before the call returns and handed to the kernel as arguments;
+ * 1 <= period (L) <= LEGION_METAPATH_MAX_PERIOD, every entry < T.  A walk of `length` steps uses type t_j = metapath[(j - 1) mod L] at
+ * step j = 1 .. length: DGL's explicit list is L == length, metapath2vec's repeated pattern a short L and a long length.  Buffers,
+ * stream, capture and draws are legion_random_walk's: traces_out int32[num_walks x (length + 1)], edge_ids_out int64[num_walks x length]
+ * or NULL; the walk reads the FULL CSR and the graph's type array, nothing else.
+ * Walk w:  traces[w][0] = seeds[w], copied as given.  Step j = 1 .. length has v = traces[w][j - 1], n = base + w * length + (j - 1):
+ *   1. ended walk: v < 0 or v >= node_num (a bad seed too): traces[w][j] = -1, and so is every later entry -- no memory is read for v;
+ *   2. restart, only if restart_prob > 0: y = minstd((uint32)(n + 1) + 2^31), r2 = (double)(y - 1) / 2147483646.0; r2 < (double)restart_prob:
+ *      the walk ends before this transition.  With restart_prob == 0 nothing is drawn;
+ *   3. row: s = indptr[v], D = indptr[v + 1] - s; D == 0: the walk ends;
+ *   4. segment and pick: lo = #{ i < D : etype[s + i] < t_j }, hi = #{ i < D : etype[s + i] <= t_j }, R = hi - lo; R == 0 (the row has
+ *      no entry of the step's type): the walk ends; else x = minstd(n + 1), r = (double)(x - 1) / 2147483646.0, pick = lo + (int)(r * R):
+ *      uniform inside the type's segment.  (A draw over the whole row followed by a filter on type is another distribution.)
+ *   5. next vertex: u = col[s + pick]; u < 0 (a dead column entry): the walk ends; else traces[w][j] = u and edge_ids[w][j - 1] = s + pick;
+ *   6. wherever traces[w][j] == -1, edge_ids[w][j - 1] == -1.
+ * Steps 1, 2, 3, 5 and 6 are legion_random_walk's word for word, and so is the draw index.  On a graph with T = 1 and metapath = [0]
+ * the op is legion_random_walk with weighted = 0, bit for bit: traces and edge ids, with and without restart.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: num_walks < 0, length < 1 or base < 0; period outside
+ * [1, LEGION_METAPATH_MAX_PERIOD]; base + num_walks * length > 2^31 - 1; an untyped (or null) graph; a metapath entry >= T;
+ * restart_prob NaN or outside [0, 1]; a null seeds_devptr, traces_out or metapath.  num_walks == 0 returns 0 and enqueues nothing.
+ *
+ * legion_pinsage_metapath_neighbors.  For each of num_seeds seeds: num_walks_per_seed (R) walks of num_traversals (Q) traversals of the
+ * L-step metapath; the vertices reached at the END of a traversal are counted, and the num_neighbors (k) most visited returned with
+ * their counts, as legion_pinsage_neighbors returns them (neighbors_out, counts_out: int32[num_seeds x k]; count descending, vertex id
+ * ascending, -1 / 0 past the number of distinct vertices).  For the bipartite item-user graph the metapath is [item->user, user->item].
+ * Walk r of seed i is global walk w = i * R + r and has Q * L steps; step j draws at n = base + w * Q * L + (j - 1) and is steps 1-5
+ * above with t_j = metapath[(j - 1) mod L], except for the restart draw of step 2: it is taken, with restart_prob = termination_prob,
+ * only before the first step of traversals 2 .. Q, that is at (j - 1) mod L == 0, j > 1 (DGL's restart_prob[L::L] = termination_prob).
+ * A visit is recorded only at j mod L == 0; a walk that ends inside a traversal records nothing from there on.  At T = 1,
+ * metapath = [0] the op is legion_pinsage_neighbors with weighted = 0 and walk_length = Q, bit for bit.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for, in this order: num_seeds < 0, R < 1, Q < 1, k < 1 or base < 0; period
+ * outside [1, LEGION_METAPATH_MAX_PERIOD]; R * Q > LEGION_PINSAGE_MAX_VISITS or k > LEGION_PINSAGE_MAX_VISITS;
+ * base + num_seeds * R * Q * L > 2^31 - 1 (in 64 bits); an untyped (or null) graph; a metapath entry >= T; termination_prob NaN or outside
+ * [0, 1]; a null seeds_devptr, neighbors_out, counts_out or metapath.  num_seeds == 0 returns 0 and enqueues nothing.
+ *
+ * Both calls enqueue on `stream`, allocate nothing, do not synchronise with the host and may be captured into a graph.
+ * Not offered: WEIGHTED metapath walks (a segment's total is a difference of two float32 prefix sums, which gives up the table's
+ * bit-for-bit guarantees); typed vertices and DGL's per-position node types; periods above 64; types on the graph of
+ * legion_graph_build_reverse; the mode in the pool, the server, the launcher and the wire. */
+#define LEGION_METAPATH_MAX_PERIOD 64
+int32_t legion_metapath_walk(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_walks,
+                             const uint8_t* metapath /* HOST uint8[period] */, int32_t period, int32_t length, float restart_prob,
+                             int64_t base, int32_t* traces_out /* int32[n x (length + 1)] */,
+                             int64_t* edge_ids_out /* int64[n x length], or NULL */);
+int32_t legion_pinsage_metapath_neighbors(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* seeds_devptr, int32_t num_seeds,
+                                          const uint8_t* metapath /* HOST uint8[period] */, int32_t period, int32_t num_walks_per_seed,
+                                          int32_t num_traversals, int32_t num_neighbors, float termination_prob, int64_t base,
+                                          int32_t* neighbors_out /* int32[n x k] */, int32_t* counts_out /* int32[n x k] */);
 
 /* Temporal neighbour sampling: a timestamp per edge and a time bound per seed (GraphBolt's temporal_sample_neighbors, PyG's
  * NeighborLoader(time_attr=, temporal_strategy="uniform" | "last"), TGL's most recent k neighbours; kernels_temporal.hip, the rule's

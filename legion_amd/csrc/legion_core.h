@@ -1185,6 +1185,28 @@ struct PinsageParams {
 };
 void launch_pinsage_neighbors(hipStream_t s, const PinsageParams& p);
 
+// metapath walks and PinSAGE over a metapath on typed edges (kernels_metapath.hip; the rule: legion_metapath_walk and
+// legion_pinsage_metapath_neighbors in legion_hip.h, its text metapath_rule.h).  The arguments are the caller's to check.
+struct MetapathParams {
+    WalkParams walk;                // as for launch_random_walk, edge_cdf null; length = every step of a walk
+    const uint8_t* etype;           // uint8[num_edges]: GraphStorage::EdgeTypes()
+    int64_t num_edges;              // E: the short class reads whole words only inside etype[0, E)
+    uint64_t path[8];               // the metapath: MetapathWords::w (metapath_rule.h)
+    int32_t period;                 // L
+    int32_t num_types;              // T
+};
+void launch_metapath_walk(hipStream_t s, const MetapathParams& p);
+struct PinsageMetapathParams {
+    MetapathParams m;               // walk.seeds = the n seeds; walk.num_walks = n; walk.length = Q * L; walk.restart_prob = the
+                                    // termination probability; traces, edge_ids unused
+    int32_t walks_per_seed;         // R
+    int32_t num_traversals;         // Q
+    int32_t num_neighbors;          // k
+    int32_t* neighbors;             // int32[n x k]
+    int32_t* counts;                // int32[n x k]
+};
+void launch_pinsage_metapath_neighbors(hipStream_t s, const PinsageMetapathParams& p);
+
 // a roctx range for the enclosing scope (markers.hip): visible to rocprofv3 --marker-trace, near-free otherwise
 struct Range {
     explicit Range(const char* fmt, ...) __attribute__((format(printf, 2, 3)));

@@ -16,6 +16,7 @@
 //     legion_core.h), so BatchGenerate has nothing to memset and IOComplete nothing to restore.
 #include "legion_core.h"
 #include "walk_rule.h"
+#include "metapath_rule.h"
 #include "node2vec_rule.h"
 #include "link_rule.h"
 #include "in_edges_rule.h"
@@ -456,6 +457,55 @@ extern "C" int32_t legion_pinsage_neighbors(legion_stream_t stream, LegionGraphS
                               .walks_per_seed = num_walks_per_seed, .num_neighbors = num_neighbors, .neighbors = neighbors_out,
                               .counts = counts_out};
     lg::launch_pinsage_neighbors(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// Metapath walks and PinSAGE over a metapath on typed edges (the rule: legion_hip.h; the refusals and how the metapath travels:
+// metapath_rule.h).  As above: every check comes before the launch.  A null graph has no types: it is refused as an untyped one.
+static lg::MetapathParams metapath_params(GraphStorage* graph, const int32_t* seeds, int32_t count, const uint8_t* metapath, int32_t period,
+                                          int32_t length, float prob, int64_t base, int32_t* traces, int64_t* edge_ids)
+{
+    lg::MetapathParams p{};
+    p.walk = walk_params(graph, seeds, count, length, 0, prob, base, traces, edge_ids);
+    p.etype = graph->EdgeTypes();
+    p.num_edges = graph->EdgeNum();
+    const MetapathWords words = metapath_pack(metapath, period);
+    for (int32_t w = 0; w < 8; w++) p.path[w] = words.w[w];
+    p.period = period;
+    p.num_types = graph->NumEdgeTypes();
+    return p;
+}
+
+extern "C" int32_t legion_metapath_walk(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr, int32_t num_walks,
+                                        const uint8_t* metapath, int32_t period, int32_t length, float restart_prob, int64_t base,
+                                        int32_t* traces_out, int64_t* edge_ids_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (metapath_walk_refusal(num_walks, metapath, period, length, base, graph ? graph->NumEdgeTypes() : 0, restart_prob,
+                              seeds_devptr && traces_out) != MetapathRefusal::Ok)
+        return -1;
+    if (num_walks == 0) return 0;
+    lg::launch_metapath_walk(static_cast<hipStream_t>(stream),
+                             metapath_params(graph, seeds_devptr, num_walks, metapath, period, length, restart_prob, base, traces_out, edge_ids_out));
+    return 0;
+}
+
+extern "C" int32_t legion_pinsage_metapath_neighbors(legion_stream_t stream, LegionGraphStorage* graph_, const int32_t* seeds_devptr,
+                                                     int32_t num_seeds, const uint8_t* metapath, int32_t period, int32_t num_walks_per_seed,
+                                                     int32_t num_traversals, int32_t num_neighbors, float termination_prob, int64_t base,
+                                                     int32_t* neighbors_out, int32_t* counts_out)
+{
+    GraphStorage* graph = reinterpret_cast<GraphStorage*>(graph_);
+    if (pinsage_metapath_refusal(num_seeds, metapath, period, num_walks_per_seed, num_traversals, num_neighbors, base,
+                                 graph ? graph->NumEdgeTypes() : 0, termination_prob,
+                                 seeds_devptr && neighbors_out && counts_out) != MetapathRefusal::Ok)
+        return -1;
+    if (num_seeds == 0) return 0;
+    const lg::PinsageMetapathParams p{.m = metapath_params(graph, seeds_devptr, num_seeds, metapath, period, num_traversals * period,
+                                                           termination_prob, base, nullptr, nullptr),
+                                      .walks_per_seed = num_walks_per_seed, .num_traversals = num_traversals, .num_neighbors = num_neighbors,
+                                      .neighbors = neighbors_out, .counts = counts_out};
+    lg::launch_pinsage_metapath_neighbors(static_cast<hipStream_t>(stream), p);
     return 0;
 }
 

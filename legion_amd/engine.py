@@ -669,6 +669,73 @@ class GraphStorage:
                   float(termination_prob), int(base), _ptr(neighbors), _ptr(counts)), (seeds, neighbors, counts))
         return neighbors, counts
 
+    METAPATH_MAX_PERIOD = 64                         # LEGION_METAPATH_MAX_PERIOD
+
+    def _check_metapath(self, metapath):
+        """The metapath of the two ops below by the rules of legion_metapath_walk, before anything touches a device: 1 to
+        METAPATH_MAX_PERIOD integers below num_edge_types, on a typed graph.  Returns it as the C call's HOST uint8 array."""
+        T = self.num_edge_types
+        if T < 1:
+            raise ValueError("the graph has no edge types (set_edge_types)")
+        if isinstance(metapath, (str, bytes)) or not hasattr(metapath, "__len__"):
+            raise ValueError(f"metapath must be a sequence of edge types, not {metapath!r}")
+        if not 1 <= len(metapath) <= self.METAPATH_MAX_PERIOD:
+            raise ValueError(f"metapath must have 1 to {self.METAPATH_MAX_PERIOD} entries, not {len(metapath)}")
+        for t in metapath:
+            _need_int("a metapath entry", t)
+            if not 0 <= t < T:
+                raise ValueError(f"metapath entries must lie in [0, {T}), not {t}")
+        return (ctypes.c_uint8 * len(metapath))(*[int(t) for t in metapath])
+
+    def metapath_random_walk(self, seeds, metapath, *, repeats=1, restart_prob=0.0, return_eids=False, base=0, stream=None):
+        """Random walks along a metapath of edge types (DGL's dgl.sampling.random_walk(g, nodes, metapath=...); the rule:
+        legion_metapath_walk in legion_hip.h).  Step j picks uniformly among the current row's entries of type
+        metapath[(j - 1) % len(metapath)]; a row without that type ends the walk.  The walk takes len(metapath) * repeats steps:
+        repeats > 1 is metapath2vec's repeated pattern.  Returns traces, int32 [n, len(metapath) * repeats + 1], and with return_eids
+        also eids, int64 [n, len(metapath) * repeats].  seeds, restart_prob, base, stream and the -1 entries as in random_walk; on a
+        graph of one type with metapath [0] the walks are random_walk's, bit for bit.  Weighted metapath walks are not offered."""
+        seeds = _as_1d(seeds, torch.int32, "seeds")
+        n = int(seeds.numel())
+        path = self._check_metapath(metapath)
+        _need_int("repeats", repeats)
+        if repeats < 1:
+            raise ValueError(f"repeats must be at least 1, not {repeats}")
+        length = len(path) * int(repeats)
+        self._check_walk(n, length, False, restart_prob, return_eids, base)
+        dev = self.col.device
+        seeds = seeds.to(dev).contiguous()
+        traces = torch.empty((n, length + 1), dtype=torch.int32, device=dev)
+        eids = torch.empty((n, length), dtype=torch.int64, device=dev) if return_eids else None
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return (traces, eids) if return_eids else traces
+        _enqueue(self._lib, "legion_metapath_walk", "metapath_random_walk", dev, stream,
+                 (self.handle, _ptr(seeds), n, path, len(path), length, float(restart_prob), int(base), _ptr(traces), _ptr(eids)),
+                 (seeds, traces, eids))
+        return (traces, eids) if return_eids else traces
+
+    def pinsage_metapath_neighbors(self, seeds, metapath, num_random_walks, num_traversals, num_neighbors, *, termination_prob=0.5, base=0,
+                                   stream=None):
+        """PinSAGE's importance neighbourhoods over a metapath (DGL's PinSAGESampler(g, ntype, other_type, ...), whose metapath is
+        [item->user, user->item]; the rule: legion_pinsage_metapath_neighbors in legion_hip.h).  From each seed num_random_walks walks
+        of num_traversals traversals of the metapath; the vertex reached at the end of each traversal is a visit, and before each
+        traversal but the first a walk ends with termination_prob.  Returns (neighbors, counts) as pinsage_neighbors does; with one
+        edge type and metapath [0] they are pinsage_neighbors' at walk_length = num_traversals, bit for bit."""
+        seeds = _as_1d(seeds, torch.int32, "seeds")
+        n = int(seeds.numel())
+        path = self._check_metapath(metapath)
+        self._check_pinsage(n, num_random_walks, num_traversals, num_neighbors, termination_prob, False, base)
+        _need_draw_indices(base, n * num_random_walks * num_traversals * len(path), "num_seeds * num_random_walks * num_traversals * len(metapath)")
+        dev = self.col.device
+        seeds = seeds.to(dev).contiguous()
+        neighbors = torch.empty((n, int(num_neighbors)), dtype=torch.int32, device=dev)
+        counts = torch.empty((n, int(num_neighbors)), dtype=torch.int32, device=dev)
+        if n == 0:                                   # (nothing to enqueue; an empty tensor has no address to hand over)
+            return neighbors, counts
+        _enqueue(self._lib, "legion_pinsage_metapath_neighbors", "pinsage_metapath_neighbors", dev, stream,
+                 (self.handle, _ptr(seeds), n, path, len(path), int(num_random_walks), int(num_traversals), int(num_neighbors),
+                  float(termination_prob), int(base), _ptr(neighbors), _ptr(counts)), (seeds, neighbors, counts))
+        return neighbors, counts
+
     NEGATIVE_MAX_TRIES = 256                         # LEGION_NEGATIVE_MAX_TRIES
 
     def find_edges(self, eids, stream=None):
