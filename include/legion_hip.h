@@ -706,6 +706,53 @@ int32_t legion_row_offsets(legion_stream_t stream, LegionGraphStorage* graph, co
 int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph, const int32_t* rows_devptr /* int32[n] */, int32_t n,
                         const int64_t* offsets_devptr /* int64[n + 1] */, int64_t m, int32_t* dst_out /* int32[m] */,
                         int32_t* src_out /* int32[m] */, int64_t* eid_out /* int64[m], or NULL */);
+/* Fused neighbour aggregation of feature rows (DGL's update_all(copy_u, sum / mean / max) and u_mul_e_sum), new in this build; no
+ * reference counterpart.  What every consumer of a per-destination source list does next -- read the sources' feature rows and reduce
+ * them per destination -- in one pass: each source row is read once, only the n results are written, and no M x D gathered copy
+ * exists.  All buffers are device memory.  The call is enqueued on `stream`, on the device current at the call; nothing is read back
+ * and it may be captured into a graph.
+ *
+ * For n segments given by offsets (int64[n + 1], non-decreasing, offsets[0] >= 0) over ids (int32[M], global vertex ids):
+ *   out[d, :] = reduce over e in [offsets[d], offsets[d + 1]) with 0 <= ids[e] < N of w[e] * X[ids[e], :]
+ *   1. reduce is LEGION_REDUCE_SUM, LEGION_REDUCE_MEAN or LEGION_REDUCE_MAX;
+ *   2. w = weights (float32[M]) if not NULL, allowed with LEGION_REDUCE_SUM only, else 1;
+ *   3. an entry whose id is negative or >= N contributes nothing and is not counted (legion_pinsage_neighbors pads with -1); no
+ *      memory is read for it;
+ *   4. LEGION_REDUCE_MEAN divides the sum by the number of live entries (converted to float32), a correctly rounded float32 division;
+ *   5. a segment with no live entry gives a row of zeros for every reduce (DGL's zero in-degree);
+ *   6. accumulation is float32 whatever the storage and output formats: fmaf(w, x, acc), or fmaxf;
+ *   7. X[id] is the row the gather resolves: with node_map (int32[N]) and cache_table given, slot = node_map[id] >= 0 is row `slot`
+ *      of cache_table, anything else row id of full_table.  dtype is the format of both tables (LEGION_FEATURE_F32: rows of D
+ *      float32; LEGION_FEATURE_BF16: rows round_up(D, 8) bf16 apart, widened by bits << 16); tables are 16-byte aligned;
+ *   8. out is [n x D] of out_dtype, stride D, no pad: float32, or bf16 rounded to nearest even from the float32 result;
+ *   9. the result is a pure function of the arguments, bit-identical from run to run: there is no floating-point atomic and every sum
+ *      has one order.  A segment of at most 256 entries is summed by G = 64 / C interleaved groups (C: the lanes that cover a row at 16
+ *      bytes each -- one float32 each where D % 4 != 0 -- rounded up to a power of two, at most 64), group g taking entries g, g + G,
+ *      ... in order, the groups combined by a pairwise tree; a longer one is cut into chunks of 256 entries, each summed so, and the
+ *      chunks' sums are added in chunk order;
+ *  10. memory safety does not rest on the caller's offsets: each is clamped into [0, M] and to its predecessor before use, so nothing is
+ *      read outside offsets[0 .. n], ids, weights and the tables' rows, and nothing is written outside out and scratch.  For offsets
+ *      that are not non-decreasing some rows of out may stay unwritten.
+ * scratch: device memory, 16-byte aligned, of at least legion_aggregate_scratch_bytes(n, M, D) bytes (host-only: the first chunk of
+ * every segment, the scan's sums, and a partial row of D float32 with its count for every chunk of a segment longer than 256 entries:
+ * fewer than M / 128 rows; -1 for arguments the call refuses); two calls in flight on different streams need scratch of their own.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a reduce that is no LEGION_REDUCE_*; a dtype or out_dtype that is no
+ * LEGION_FEATURE_*; weights with a reduce other than LEGION_REDUCE_SUM; a cache_table without a node_map or a node_map without a
+ * cache_table; n < 0, M < 0, D <= 0; n > LEGION_AGGREGATE_MAX_SEGMENTS; a bf16 pitch round_up(D, 8) that is no int32; a null
+ * full_table, offsets, ids, out or scratch; scratch_bytes below legion_aggregate_scratch_bytes(n, M, D).  n == 0 returns 0 and enqueues
+ * nothing.
+ * Not offered: striped cliques, peer stripes, the replica and the hybrid tier (they need the gather's whole source rule: one local
+ * cache table only); min and other reductions; a weight per source vertex; gradients. */
+#define LEGION_REDUCE_SUM 0
+#define LEGION_REDUCE_MEAN 1
+#define LEGION_REDUCE_MAX 2
+#define LEGION_AGGREGATE_MAX_SEGMENTS 268435456
+int64_t legion_aggregate_scratch_bytes(int32_t n, int64_t M, int32_t D);
+int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                              const void* cache_table /* or NULL */, const int32_t* node_map /* int32[N], or NULL */, int32_t D, int32_t N,
+                              const int64_t* offsets /* int64[n + 1] */, int32_t n, const int32_t* ids /* int32[M] */, int64_t M,
+                              const float* weights /* float[M], or NULL */, int32_t reduce, void* out /* [n x D] */, void* scratch,
+                              int64_t scratch_bytes);
 /* Layer-neighbour sampling (LABOR-0 of Balin and Catalyurek, NeurIPS 2023; DGL's dgl.sampling.sample_labors and
  * dgl.dataloading.LaborSampler), new in this build; no reference counterpart.  Every SOURCE vertex t has one random number r_t for the
  * whole call, and the entry t -> s is kept iff r_t < fanout / deg(s): a seed keeps fanout neighbours in expectation, and seeds with

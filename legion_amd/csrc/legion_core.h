@@ -996,6 +996,23 @@ struct InEdgesParams {
 };
 void launch_in_edges(hipStream_t s, const InEdgesParams& p);
 
+// the fused neighbour aggregation (kernels_aggregate.hip; the rule: legion_aggregate_rows in legion_hip.h, its refusals, chunk rule and
+// scratch layout aggregate_rule.h).  The arguments are the caller's to check
+struct AggregateParams {
+    const void* full_table;         // N rows of the stored format
+    const void* cache_table;        // null, or the rows node_map's slots >= 0 address
+    const int32_t* node_map;        // null, or int32[N]
+    const int64_t* offsets;         // int64[n + 1]: whatever they hold, nothing is read outside them, ids and weights
+    const int32_t* ids;             // int32[M]
+    const float* weights;           // null, or float[M]
+    void* out;                      // [n x D] of out_dtype
+    int64_t M;
+    int32_t n, N, D;
+    int32_t dtype, out_dtype;       // LEGION_FEATURE_*
+    int32_t reduce;                 // LEGION_REDUCE_*
+};
+void launch_aggregate_rows(hipStream_t s, const AggregateParams& a, void* scratch);
+
 // the reverse CSR (kernels_reverse.hip; the rule: legion_graph_build_reverse in legion_hip.h, its classes and refusals reverse_rule.h).
 // The arguments are the caller's to check.  Builds on s and synchronises it; returns the live entries E' and three allocations of
 // d_alloc_space on the current device: rindptr int64[node_num + 1], rcol int32[E'], reid int64[E'].  Its temporaries are freed

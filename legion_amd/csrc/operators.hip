@@ -20,6 +20,7 @@
 #include "node2vec_rule.h"
 #include "link_rule.h"
 #include "in_edges_rule.h"
+#include "aggregate_rule.h"
 #include "labor_rule.h"
 #include "topk_rule.h"
 #include "etype_rule.h"
@@ -596,6 +597,31 @@ extern "C" int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* g
     if (m == 0) return 0;
     const lg::InEdgesParams p{.slots = row_slots(graph, rows_devptr, n, offsets_devptr, m), .dst = dst_out, .src = src_out, .eid = eid_out};
     lg::launch_in_edges(static_cast<hipStream_t>(stream), p);
+    return 0;
+}
+
+// The fused neighbour aggregation (the rule: legion_hip.h; the refusals, the chunk rule and the scratch size: aggregate_rule.h).  As
+// above: every check comes before the launch.
+extern "C" int64_t legion_aggregate_scratch_bytes(int32_t n, int64_t M, int32_t D)
+{
+    return aggregate_scratch_bytes(n, M, D);
+}
+
+extern "C" int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                                         const void* cache_table, const int32_t* node_map, int32_t D, int32_t N, const int64_t* offsets,
+                                         int32_t n, const int32_t* ids, int64_t M, const float* weights, int32_t reduce, void* out,
+                                         void* scratch, int64_t scratch_bytes)
+{
+    const AggregateArgs args{.dtype = dtype, .out_dtype = out_dtype, .reduce = reduce, .n = n, .D = D, .M = M, .scratch_bytes = scratch_bytes,
+                             .full_table = full_table != nullptr, .cache_table = cache_table != nullptr, .node_map = node_map != nullptr,
+                             .offsets = offsets != nullptr, .ids = ids != nullptr, .weights = weights != nullptr, .out = out != nullptr,
+                             .scratch = scratch != nullptr};
+    if (aggregate_refusal(args) != AggregateRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    const lg::AggregateParams a{.full_table = full_table, .cache_table = cache_table, .node_map = node_map, .offsets = offsets, .ids = ids,
+                                .weights = weights, .out = out, .M = M, .n = n, .N = N, .D = D, .dtype = dtype, .out_dtype = out_dtype,
+                                .reduce = reduce};
+    lg::launch_aggregate_rows(static_cast<hipStream_t>(stream), a, scratch);
     return 0;
 }
 

@@ -878,6 +878,29 @@ class GraphStorage:
         out = self._in_edges(rows.to(self.col.device).contiguous(), n, return_eids, stream)
         return out if return_eids else out[:3]
 
+    def _check_full_aggregate(self, feature, reduce, cache):
+        """The arguments of full_neighbor_aggregate, before anything touches a device: ValueError with the reason.  Returns (the
+        graph's logical GPU, the cache's tables as FeatureStorage._check_aggregate returns them)."""
+        if not isinstance(feature, FeatureStorage):
+            raise ValueError(f"feature must be a FeatureStorage, not {type(feature).__name__}")
+        if feature.total_num_nodes < self.node_num:
+            raise ValueError(f"the feature table has {feature.total_num_nodes} rows, the graph {self.node_num} vertices")
+        dev = self.col.device
+        dev_id = (dev.index - int(self._lib.legion_get_device_base())) % max(torch.cuda.device_count(), 1)
+        return dev_id, feature._check_aggregate(reduce, None, cache, dev_id, "float32")
+
+    def full_neighbor_aggregate(self, feature, rows, *, reduce="mean", cache=None, stream=None):
+        """The feature rows of every in-neighbour of rows reduced per row (DGL's update_all(copy_u, mean) over in_edges(rows): exact
+        layer-wise inference of a first SAGE / GCN layer, which is linear in the aggregate): row_offsets, in_edges and
+        FeatureStorage.aggregate, with no relabelling and no de-duplication.  feature: a FeatureStorage over the graph's vertices;
+        rows as in row_offsets; reduce and cache as in FeatureStorage.aggregate.  Returns float32 [n, D]; a row without entries, or
+        with dead ones only, is zeros.  offsets[n] is read back to size the edge list: the call synchronises `stream` (default: the
+        current one), on which everything is enqueued."""
+        _, tables = self._check_full_aggregate(feature, reduce, cache)
+        rows, n = self._check_rows(rows)
+        offsets, _, src, _ = self._in_edges(rows.to(self.col.device).contiguous(), n, False, stream)
+        return feature._aggregate(self.col.device, offsets, src, reduce, None, tables, "float32", stream)
+
     def _block_tail(self, seeds, n, src, stream):
         """The end of a block: unique_ids over [seeds | src] under `stream`.  Returns (input_nodes, src_local); ValueError unless the n
         seeds are distinct vertices of the graph."""
@@ -1669,6 +1692,70 @@ class FeatureStorage:
                                          lab.ctypes.data_as(ctypes.c_void_p) if lab is not None else None,
                                          int(ids.size))
         self.set_sizes[(int(dev_id), int(mode))] = int(ids.size)
+
+    REDUCES = {"sum": 0, "mean": 1, "max": 2}        # LEGION_REDUCE_*
+    AGGREGATE_MAX_SEGMENTS = 2 ** 28                 # LEGION_AGGREGATE_MAX_SEGMENTS
+
+    def _check_aggregate(self, reduce, weights, cache, dev_id, out_dtype):
+        """The keywords of aggregate by the rules of legion_aggregate_rows, before anything touches a device: ValueError with the
+        reason.  Returns (cache table address, node_map address), both None without a usable cache."""
+        if reduce not in self.REDUCES:
+            raise ValueError(f"reduce must be one of {sorted(self.REDUCES)}, not {reduce!r}")
+        if out_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {out_dtype!r}")
+        if weights is not None and reduce != "sum":
+            raise ValueError(f"weights go with reduce='sum' only, not {reduce!r}")
+        _need_int("dev_id", dev_id)
+        if cache is None:
+            return None, None
+        if not isinstance(cache, UnifiedCache):
+            raise ValueError(f"cache must be a UnifiedCache, not {type(cache).__name__}")
+        if cache.device_count > 1:
+            raise ValueError(f"aggregate reads one local cache table: this cache is striped over {cache.device_count} GPUs")
+        if self._lib.legion_cache_hybrid_cpu_cache(cache.handle, int(dev_id)):
+            raise ValueError("aggregate reads one local cache table: this cache is hybrid (hybrid_init)")
+        table = self._lib.legion_cache_feature_cache(cache.handle, int(dev_id))
+        node_map = self._lib.legion_cache_array(cache.handle, int(dev_id), 6)
+        if not table or not node_map or int(self._lib.legion_cache_node_capacity(cache.handle, int(dev_id))) <= 0:
+            return None, None                        # nothing is cached: every row is the full table's
+        return table, node_map
+
+    def _aggregate(self, dev, offsets, ids, reduce, weights, tables, out_dtype, stream):
+        """offsets, ids, weights: on dev, contiguous, checked."""
+        n, M, D = int(offsets.numel()) - 1, int(ids.numel()), self.float_feature_len
+        torch_dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        if n == 0 or M == 0:                         # (an empty tensor has no address to hand over)
+            return torch.zeros((n, D), dtype=torch_dtype, device=dev)
+        out = torch.empty((n, D), dtype=torch_dtype, device=dev)
+        nbytes = int(self._lib.legion_aggregate_scratch_bytes(n, M, D))
+        scratch = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+        _enqueue(self._lib, "legion_aggregate_rows", "aggregate", dev, stream,
+                 (FEATURE_DTYPES[self.feature_dtype], FEATURE_DTYPES[out_dtype], self._lib.legion_feature_table(self.handle),
+                  tables[0], tables[1], D, self.total_num_nodes, _ptr(offsets), n, _ptr(ids), M, _ptr(weights), self.REDUCES[reduce],
+                  _ptr(out), _ptr(scratch), nbytes), (offsets, ids, weights, out, scratch))
+        return out
+
+    def aggregate(self, offsets, ids, *, reduce="sum", weights=None, cache=None, dev_id=0, out_dtype="float32", stream=None):
+        """The feature rows of ids reduced per segment (DGL's update_all(copy_u, sum / mean / max), with weights u_mul_e_sum; the rule:
+        legion_aggregate_rows in legion_hip.h): out[d] = reduce over e in [offsets[d], offsets[d + 1]) of weights[e] * X[ids[e]].
+        offsets: int64 [n + 1], non-decreasing, as row_offsets returns them; ids: int32 [M] global vertex ids, a negative id or one past
+        the table contributes nothing and is not counted by "mean"; weights: None or float32 [M], with reduce="sum" only.  A segment
+        without a live entry is a row of zeros.  cache: None, or a UnifiedCache with one local table on dev_id, whose cached rows are
+        read from it; one striped over several GPUs or hybrid is a ValueError.  Returns [n, D] of out_dtype ("float32" or "bfloat16",
+        rounded from the float32 result) on logical GPU dev_id, bit-identical from run to run.  No sync; enqueued on `stream`
+        (default: the current one)."""
+        tables = self._check_aggregate(reduce, weights, cache, dev_id, out_dtype)
+        offsets = _as_1d(offsets, torch.int64, "offsets")
+        ids = _as_1d(ids, torch.int32, "ids")
+        if offsets.numel() < 1 or offsets.numel() - 1 > self.AGGREGATE_MAX_SEGMENTS:
+            raise ValueError(f"offsets must hold n + 1 entries for 0 <= n <= {self.AGGREGATE_MAX_SEGMENTS}, not {offsets.numel()}")
+        if weights is not None:
+            weights = _as_1d(weights, torch.float32, "weights")
+            if weights.numel() != ids.numel():
+                raise ValueError(f"{weights.numel()} weights for {ids.numel()} ids")
+        dev = _torch_device(dev_id)
+        return self._aggregate(dev, offsets.to(dev).contiguous(), ids.to(dev).contiguous(),
+                               reduce, None if weights is None else weights.to(dev).contiguous(), tables, out_dtype, stream)
 
     def close(self):
         if self.handle:

@@ -161,6 +161,8 @@ SIGNATURES = {
     "legion_row_offsets_scratch_bytes": (c_i64, [c_i32]),
     "legion_row_offsets": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_p, c_i64]),
     "legion_in_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p]),
+    "legion_aggregate_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32]),
+    "legion_aggregate_rows": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_p, c_p, c_i64]),
     "legion_labor_scratch_bytes": (c_i64, [c_i64]),
     "legion_labor_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_i64]),
     "legion_labor_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
