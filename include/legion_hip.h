@@ -742,7 +742,7 @@ int32_t legion_in_edges(legion_stream_t stream, LegionGraphStorage* graph, const
  * full_table, offsets, ids, out or scratch; scratch_bytes below legion_aggregate_scratch_bytes(n, M, D).  n == 0 returns 0 and enqueues
  * nothing.
  * Not offered: striped cliques, peer stripes, the replica and the hybrid tier (they need the gather's whole source rule: one local
- * cache table only); min and other reductions; a weight per source vertex; gradients. */
+ * cache table only); min and other reductions; a weight per source vertex; gradients (applying them to the table: legion_row_update). */
 #define LEGION_REDUCE_SUM 0
 #define LEGION_REDUCE_MEAN 1
 #define LEGION_REDUCE_MAX 2
@@ -753,6 +753,57 @@ int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, int32_t out
                               const int64_t* offsets /* int64[n + 1] */, int32_t n, const int32_t* ids /* int32[M] */, int64_t M,
                               const float* weights /* float[M], or NULL */, int32_t reduce, void* out /* [n x D] */, void* scratch,
                               int64_t scratch_bytes);
+/* Sparse row updates of the float32 feature table (DGL's dgl.nn.NodeEmbedding with dgl.optim.SparseAdagrad / SparseAdam, and plain
+ * SGD), new in this build; no reference counterpart.  The half of "gradients" the library owns: a batch of per-row gradients with
+ * duplicate ids -- what a walk or a link-prediction batch hands back for rows that are learnable embeddings -- is combined per id and
+ * applied to the table and to its cache copy, so that a later gather or aggregate sees the update wherever it resolves the row.  All
+ * buffers are device memory, the tables, grads and the state 16-byte aligned.  The call is enqueued on `stream`, on the device current
+ * at the call; nothing is read back and it may be captured into a graph.
+ *
+ * For ids (int32[m]) and grads (float32[m x D], stride D):
+ *   1. entry i is live when 0 <= ids[i] < N; a dead entry reads and writes nothing;
+ *   2. for every distinct live id v, g_v is the combination of the rows grads[i] with ids[i] == v, accumulated in float32 in
+ *      ascending i: the list of those i is cut into chunks of 256 and combined exactly as rule 9 of legion_aggregate_rows combines a
+ *      segment (G = 64 / C interleaved groups inside a chunk, group g taking entries g, g + G, ... in order, a pairwise tree over the
+ *      groups, then the chunks' sums in chunk order).  combine = LEGION_REDUCE_SUM keeps the sum (torch.optim's rule),
+ *      LEGION_REDUCE_MEAN divides it by the count, a correctly rounded float32 division (DGL's rule);
+ *   3. the old weight w is read from full_table[v];
+ *   4. the new weight is written to full_table[v] and, where node_map (int32[N]) and cache_table are given and node_map[v] >= 0, to
+ *      row node_map[v] of cache_table as well;
+ *   5. every step below is its own correctly rounded float32 operation, in this order, nothing contracted into a fused multiply-add:
+ *        LEGION_UPDATE_SGD      w = w - lr * g;
+ *        LEGION_UPDATE_ADAGRAD  s = state1[v] + g * g;  w = w - (lr * g) / (sqrt(s) + eps);  state1[v] = s;
+ *        LEGION_UPDATE_ADAM     p1 = state_pow[v, 0] * beta1;  p2 = state_pow[v, 1] * beta2;  (the running products beta^t of the row;
+ *                               the caller initialises state_pow to 1)
+ *                               m = beta1 * state1[v] + (1 - beta1) * g;  u = beta2 * state2[v] + (1 - beta2) * (g * g);
+ *                               w = w - (lr * (m / (1 - p1))) / (sqrt(u / (1 - p2)) + eps);
+ *                               state1[v] = m;  state2[v] = u;  state_pow[v] = {p1, p2};  1 - beta is formed once in float32.
+ *      The running products differ from DGL's pow(beta, step) by rounding only;
+ *   6. every row is written by one lane-group of one wave; there is no floating-point atomic, and two calls with the same arguments
+ *      and state give the same bits.
+ * state1, state2: float32[N x D]; state_pow: float32[N x 2].  Adagrad needs state1; Adam needs all three; SGD none.
+ * scratch: device memory, 16-byte aligned, of at least legion_row_update_scratch_bytes(m, N, D) bytes (host-only: two buffers of
+ * {id, position} pairs for the sort, the digit counts of a pass, the groups of equal ids, the first chunk of every group, and a
+ * partial row of D float32 for every chunk of a group longer than 256 entries: fewer than m / 128 rows; -1 for arguments the call
+ * refuses); two calls in flight on different streams need scratch of their own.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a combine that is neither LEGION_REDUCE_SUM nor LEGION_REDUCE_MEAN;
+ * an optimizer that is no LEGION_UPDATE_*; a cache_table without a node_map or a node_map without a cache_table; m < 0, N <= 0,
+ * D <= 0; m > LEGION_ROW_UPDATE_MAX_IDS; a null full_table, ids, grads or scratch; a state pointer the optimizer needs that is null;
+ * scratch_bytes below legion_row_update_scratch_bytes(m, N, D).  m == 0 returns 0 and enqueues nothing.
+ * Not offered: bf16 tables (a bf16 weight swallows small steps: it needs a float32 master row, which is a change of its own);
+ * striped cliques, peer stripes, the replica and the hybrid tier (one local cache table only); weight decay; the pool, the server
+ * and the wire; the backward pass that produces grads. */
+#define LEGION_UPDATE_SGD 0
+#define LEGION_UPDATE_ADAGRAD 1
+#define LEGION_UPDATE_ADAM 2
+#define LEGION_ROW_UPDATE_MAX_IDS 4194304
+int64_t legion_row_update_scratch_bytes(int32_t m, int32_t N, int32_t D);
+int32_t legion_row_update(legion_stream_t stream, float* full_table, float* cache_table /* or NULL */,
+                          const int32_t* node_map /* int32[N], or NULL */, int32_t D, int32_t N, const int32_t* ids /* int32[m] */,
+                          const float* grads /* float[m x D] */, int32_t m, int32_t combine /* LEGION_REDUCE_SUM | _MEAN */,
+                          int32_t optimizer, float lr, float eps, float beta1, float beta2, float* state1 /* float[N x D], or NULL */,
+                          float* state2 /* float[N x D], or NULL */, float* state_pow /* float[N x 2], or NULL */, void* scratch,
+                          int64_t scratch_bytes);
 /* Layer-neighbour sampling (LABOR-0 of Balin and Catalyurek, NeurIPS 2023; DGL's dgl.sampling.sample_labors and
  * dgl.dataloading.LaborSampler), new in this build; no reference counterpart.  Every SOURCE vertex t has one random number r_t for the
  * whole call, and the entry t -> s is kept iff r_t < fanout / deg(s): a seed keeps fanout neighbours in expectation, and seeds with

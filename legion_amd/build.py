@@ -18,10 +18,12 @@ BIN = os.path.join(HERE, "bin", "sampling_server")
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 ARCH = "gfx950"
 
-SOURCES = ["kernels_sample.hip", "kernels_gather.hip", "kernels_cache.hip", "kernels_weights.hip", "kernels_walk.hip", "kernels_pinsage.hip", "kernels_node2vec.hip", "kernels_link.hip", "kernels_in_edges.hip", "kernels_aggregate.hip", "kernels_labor.hip", "kernels_induced.hip", "kernels_topk.hip", "kernels_etype.hip", "kernels_metapath.hip", "kernels_temporal.hip", "kernels_reverse.hip", "kernels_exclude.hip", "kernels_synth.hip",
+SOURCES = ["kernels_sample.hip", "kernels_gather.hip", "kernels_cache.hip", "kernels_weights.hip", "kernels_walk.hip", "kernels_pinsage.hip", "kernels_node2vec.hip", "kernels_link.hip", "kernels_in_edges.hip", "kernels_aggregate.hip", "kernels_update.hip", "kernels_labor.hip", "kernels_induced.hip", "kernels_topk.hip", "kernels_etype.hip", "kernels_metapath.hip", "kernels_temporal.hip", "kernels_reverse.hip", "kernels_exclude.hip", "kernels_synth.hip",
            "storage.hip", "tuning.hip", "link_counters.hip", "collective.hip", "markers.hip", "cache.hip", "operators.hip", "pipeline.hip", "ipc_env.hip", "server.hip"]
 FLAGS = ["-O3", "-std=c++17", "-fPIC", f"--offload-arch={ARCH}", "-fno-fast-math", "-Wall",
          "-Wno-unused-result", "-Wno-unused-function"] + os.environ.get("LEGION_EXTRA_HIPCC_FLAGS", "").split()
+# legion_row_update's epilogue is a chain of single correctly rounded operations: no product and sum of it may become one fma
+SOURCE_FLAGS = {"kernels_update.hip": ["-ffp-contract=off"]}
 
 
 def _newer(target, deps):
@@ -43,7 +45,7 @@ def build_lib(force=False, verbose=True):
         o = os.path.join(objdir, src + ".o")
         objs.append(o)
         if force or _newer(o, [s] + headers):
-            cmd = [HIPCC] + FLAGS + ["-c", s, "-o", o]
+            cmd = [HIPCC] + FLAGS + SOURCE_FLAGS.get(src, []) + ["-c", s, "-o", o]
             if verbose:
                 print(" ".join(cmd), flush=True)
             procs.append((src, subprocess.Popen(cmd)))

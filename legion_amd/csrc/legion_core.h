@@ -1013,6 +1013,24 @@ struct AggregateParams {
 };
 void launch_aggregate_rows(hipStream_t s, const AggregateParams& a, void* scratch);
 
+// the sparse row update (kernels_update.hip; the rule: legion_row_update in legion_hip.h, its refusals, sort passes and scratch layout
+// update_rule.h).  The arguments are the caller's to check
+struct UpdateParams {
+    float* full_table;              // float[N x D]
+    float* cache_table;             // null, or the rows node_map's slots >= 0 address
+    const int32_t* node_map;        // null, or int32[N]
+    const int32_t* ids;             // int32[m]
+    const float* grads;             // float[m x D]
+    float* state1;                  // float[N x D], or null (SGD)
+    float* state2;                  // float[N x D], or null (SGD, Adagrad)
+    float* state_pow;               // float[N x 2], or null (SGD, Adagrad)
+    int32_t m, N, D;
+    int32_t combine;                // LEGION_REDUCE_SUM or LEGION_REDUCE_MEAN
+    int32_t optimizer;              // LEGION_UPDATE_*
+    float lr, eps, beta1, beta2;
+};
+void launch_row_update(hipStream_t s, const UpdateParams& u, void* scratch);
+
 // the reverse CSR (kernels_reverse.hip; the rule: legion_graph_build_reverse in legion_hip.h, its classes and refusals reverse_rule.h).
 // The arguments are the caller's to check.  Builds on s and synchronises it; returns the live entries E' and three allocations of
 // d_alloc_space on the current device: rindptr int64[node_num + 1], rcol int32[E'], reid int64[E'].  Its temporaries are freed

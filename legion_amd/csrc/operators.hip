@@ -21,6 +21,7 @@
 #include "link_rule.h"
 #include "in_edges_rule.h"
 #include "aggregate_rule.h"
+#include "update_rule.h"
 #include "labor_rule.h"
 #include "topk_rule.h"
 #include "etype_rule.h"
@@ -622,6 +623,31 @@ extern "C" int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, 
                                 .weights = weights, .out = out, .M = M, .n = n, .N = N, .D = D, .dtype = dtype, .out_dtype = out_dtype,
                                 .reduce = reduce};
     lg::launch_aggregate_rows(static_cast<hipStream_t>(stream), a, scratch);
+    return 0;
+}
+
+// The sparse row update (the rule: legion_hip.h; the refusals, the sort's passes and the scratch layout: update_rule.h).  As above:
+// every check comes before the launch.
+extern "C" int64_t legion_row_update_scratch_bytes(int32_t m, int32_t N, int32_t D)
+{
+    return update_scratch_bytes(m, N, D);
+}
+
+extern "C" int32_t legion_row_update(legion_stream_t stream, float* full_table, float* cache_table, const int32_t* node_map, int32_t D,
+                                     int32_t N, const int32_t* ids, const float* grads, int32_t m, int32_t combine, int32_t optimizer,
+                                     float lr, float eps, float beta1, float beta2, float* state1, float* state2, float* state_pow,
+                                     void* scratch, int64_t scratch_bytes)
+{
+    const UpdateArgs args{.m = m, .N = N, .D = D, .combine = combine, .optimizer = optimizer, .scratch_bytes = scratch_bytes,
+                          .full_table = full_table != nullptr, .cache_table = cache_table != nullptr, .node_map = node_map != nullptr,
+                          .ids = ids != nullptr, .grads = grads != nullptr, .state1 = state1 != nullptr, .state2 = state2 != nullptr,
+                          .state_pow = state_pow != nullptr, .scratch = scratch != nullptr};
+    if (update_refusal(args) != UpdateRefusal::Ok) return -1;
+    if (m == 0) return 0;
+    const lg::UpdateParams u{.full_table = full_table, .cache_table = cache_table, .node_map = node_map, .ids = ids, .grads = grads,
+                             .state1 = state1, .state2 = state2, .state_pow = state_pow, .m = m, .N = N, .D = D, .combine = combine,
+                             .optimizer = optimizer, .lr = lr, .eps = eps, .beta1 = beta1, .beta2 = beta2};
+    lg::launch_row_update(static_cast<hipStream_t>(stream), u, scratch);
     return 0;
 }
 

@@ -1705,15 +1705,20 @@ class FeatureStorage:
             raise ValueError(f"out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {out_dtype!r}")
         if weights is not None and reduce != "sum":
             raise ValueError(f"weights go with reduce='sum' only, not {reduce!r}")
+        return self._local_cache_tables(cache, dev_id, "aggregate reads")
+
+    def _local_cache_tables(self, cache, dev_id, what):
+        """(cache table address, node_map address) of the one local table of `cache` on dev_id, both None without a usable cache;
+        ValueError for a cache `what` ("aggregate reads", "update_rows writes") cannot serve."""
         _need_int("dev_id", dev_id)
         if cache is None:
             return None, None
         if not isinstance(cache, UnifiedCache):
             raise ValueError(f"cache must be a UnifiedCache, not {type(cache).__name__}")
         if cache.device_count > 1:
-            raise ValueError(f"aggregate reads one local cache table: this cache is striped over {cache.device_count} GPUs")
+            raise ValueError(f"{what} one local cache table: this cache is striped over {cache.device_count} GPUs")
         if self._lib.legion_cache_hybrid_cpu_cache(cache.handle, int(dev_id)):
-            raise ValueError("aggregate reads one local cache table: this cache is hybrid (hybrid_init)")
+            raise ValueError(f"{what} one local cache table: this cache is hybrid (hybrid_init)")
         table = self._lib.legion_cache_feature_cache(cache.handle, int(dev_id))
         node_map = self._lib.legion_cache_array(cache.handle, int(dev_id), 6)
         if not table or not node_map or int(self._lib.legion_cache_node_capacity(cache.handle, int(dev_id))) <= 0:
@@ -1756,6 +1761,68 @@ class FeatureStorage:
         dev = _torch_device(dev_id)
         return self._aggregate(dev, offsets.to(dev).contiguous(), ids.to(dev).contiguous(),
                                reduce, None if weights is None else weights.to(dev).contiguous(), tables, out_dtype, stream)
+
+    OPTIMIZERS = {"sgd": 0, "adagrad": 1, "adam": 2}  # LEGION_UPDATE_*
+    ROW_UPDATE_MAX_IDS = 2 ** 22                      # LEGION_ROW_UPDATE_MAX_IDS
+    STATE_ROWS = {"sgd": (), "adagrad": ("state1",), "adam": ("state1", "state2", "state_pow")}
+
+    def _check_update(self, optimizer, lr, combine, state, eps, betas, cache, dev_id):
+        """The keywords of update_rows by the rules of legion_row_update, before anything touches a device: ValueError with the
+        reason.  Returns the cache's tables as _local_cache_tables returns them."""
+        if self.feature_dtype != "float32":
+            raise ValueError(f"update_rows writes a float32 table: this storage holds {self.feature_dtype} rows")
+        if optimizer not in self.OPTIMIZERS:
+            raise ValueError(f"optimizer must be one of {sorted(self.OPTIMIZERS)}, not {optimizer!r}")
+        if combine not in ("sum", "mean"):
+            raise ValueError(f"combine must be 'sum' or 'mean', not {combine!r}")
+        numbers = [("lr", lr), ("eps", eps)]
+        if not isinstance(betas, (tuple, list)) or len(betas) != 2:
+            raise ValueError(f"betas must be a pair of numbers, not {betas!r}")
+        for name, x in numbers + [("betas", b) for b in betas]:
+            if isinstance(x, bool) or not isinstance(x, (int, float, np.floating, np.integer)):
+                raise ValueError(f"{name} must be a number, not {x!r}")
+        if state is not None and not isinstance(state, dict):
+            raise ValueError(f"state must be None or the dict an earlier call returned, not {type(state).__name__}")
+        return self._local_cache_tables(cache, dev_id, "update_rows writes")
+
+    def update_rows(self, ids, grads, *, optimizer="sgd", lr, combine="mean", state=None, eps=1e-10, betas=(0.9, 0.999), cache=None,
+                    dev_id=0, stream=None):
+        """One sparse optimizer step on the float32 table this storage uses in place (DGL's NodeEmbedding with SparseAdagrad /
+        SparseAdam, or plain SGD; the rule: legion_row_update in legion_hip.h).  ids: int32 [m], duplicates allowed, a negative id or
+        one past the table is skipped; grads: float32 [m, D].  The rows of one id are combined ("mean": DGL's rule, "sum":
+        torch.optim's) in a fixed order and the step is applied to the table row and, with cache (a UnifiedCache with one local table
+        on dev_id; striped or hybrid is a ValueError), to the row's cached copy.  state: None on the first call, then the dict this
+        method returns: state1, state2 float32 [N, D] (zeros) and state_pow float32 [N, 2] (ones), those the optimizer needs, on the
+        table's GPU.  Bit-identical from run to run.  No sync; enqueued on `stream` (default: the current one)."""
+        tables = self._check_update(optimizer, lr, combine, state, eps, betas, cache, dev_id)
+        ids = _as_1d(ids, torch.int32, "ids")
+        if not isinstance(grads, torch.Tensor):
+            grads = torch.as_tensor(grads)
+        m, N, D = int(ids.numel()), self.total_num_nodes, self.float_feature_len
+        if grads.dtype != torch.float32 or tuple(grads.shape) != (m, D):
+            raise ValueError(f"grads must be float32 [{m}, {D}], not {grads.dtype} {tuple(grads.shape)}")
+        if m > self.ROW_UPDATE_MAX_IDS:
+            raise ValueError(f"{m} ids in one call, at most {self.ROW_UPDATE_MAX_IDS}")
+        dev = _torch_device(dev_id)
+        state = {} if state is None else state
+        for name in self.STATE_ROWS[optimizer]:
+            shape = (N, 2) if name == "state_pow" else (N, D)
+            if name not in state:
+                state[name] = (torch.ones if name == "state_pow" else torch.zeros)(shape, dtype=torch.float32, device=dev)
+            t = state[name]
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float32 or tuple(t.shape) != shape or not t.is_contiguous() or t.device != dev:
+                raise ValueError(f"state[{name!r}] must be a contiguous float32 tensor {shape} on {dev}")
+        if m == 0:                                   # (an empty tensor has no address to hand over)
+            return state
+        ids, grads = ids.to(dev).contiguous(), grads.to(dev).contiguous()
+        nbytes = int(self._lib.legion_row_update_scratch_bytes(m, N, D))
+        scratch = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+        rows = [state[name] if name in self.STATE_ROWS[optimizer] else None for name in ("state1", "state2", "state_pow")]
+        _enqueue(self._lib, "legion_row_update", "update_rows", dev, stream,
+                 (self._lib.legion_feature_table(self.handle), tables[0], tables[1], D, N, _ptr(ids), _ptr(grads), m,
+                  self.REDUCES[combine], self.OPTIMIZERS[optimizer], float(lr), float(eps), float(betas[0]), float(betas[1]),
+                  _ptr(rows[0]), _ptr(rows[1]), _ptr(rows[2]), _ptr(scratch), nbytes), (ids, grads, scratch) + tuple(rows))
+        return state
 
     def close(self):
         if self.handle:

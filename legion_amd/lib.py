@@ -13,7 +13,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get("LEGION_HIP_LIB") or os.path.join(_HERE, "liblegion_hip.so")
 
 c_i32, c_i64, c_u64 = ctypes.c_int32, ctypes.c_int64, ctypes.c_uint64
-c_p, c_bool = ctypes.c_void_p, ctypes.c_bool
+c_p, c_bool, c_f32 = ctypes.c_void_p, ctypes.c_bool, ctypes.c_float
 P_I32 = ctypes.POINTER(ctypes.c_int32)
 P_U64 = ctypes.POINTER(ctypes.c_uint64)
 
@@ -163,6 +163,9 @@ SIGNATURES = {
     "legion_in_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p]),
     "legion_aggregate_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32]),
     "legion_aggregate_rows": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_p, c_p, c_i64]),
+    "legion_row_update_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32]),
+    "legion_row_update": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_p, c_p, c_p,
+                                  c_p, c_i64]),
     "legion_labor_scratch_bytes": (c_i64, [c_i64]),
     "legion_labor_count": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_p, c_i64]),
     "legion_labor_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_i32, c_i64, c_p, c_i64, c_i64, c_p, c_p, c_p]),
