@@ -753,6 +753,66 @@ int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, int32_t out
                               const int64_t* offsets /* int64[n + 1] */, int32_t n, const int32_t* ids /* int32[M] */, int64_t M,
                               const float* weights /* float[M], or NULL */, int32_t reduce, void* out /* [n x D] */, void* scratch,
                               int64_t scratch_bytes);
+/* Fused attention aggregation of feature rows (DGL's u_dot_v / edge_softmax / u_mul_e_sum: DotGatConv, PyG's TransformerConv, and with
+ * bias alone GAT's edge_softmax + u_mul_e_sum), new in this build; no reference counterpart.  legion_aggregate_rows with weights that
+ * depend on the rows being read: a logit per entry and head, a softmax per destination, the weighted sum -- in one pass, each source
+ * row read once for all heads, no M x D gathered copy.  Both projections of a dot-product attention layer commute with the neighbour
+ * loop ((W_k x) . q = x . (W_k^T q), sum a (W_v x) = W_v sum a x), so attention over the STORED rows with a dense query per destination
+ * and head is what the layer needs.  All buffers are device memory.  The call is enqueued on `stream`, on the device current at the
+ * call; nothing is read back and it may be captured into a graph.
+ *
+ * For n segments given by offsets (int64[n + 1]) over ids (int32[M]), segment d, head h in [0, heads) and every entry e of the segment
+ * with 0 <= ids[e] < N (a live entry):
+ *   1. s[e, h] = scale * sum_c queries[d, h, c] * X[ids[e], c] + bias[e, h]; either term is 0 where its pointer is NULL (queries:
+ *      float32[n, heads, D]; bias: float32[M, heads]); the product with scale and the sum with bias are one fmaf;
+ *   2. m = max_e s, l = sum_e exp(s - m), out[d, h, :] = (sum_e exp(s - m) * X[ids[e], :]) / l, one correctly rounded float32 division
+ *      per element; lse_out[d, h] = m + logf(l); scores_out[e, h] = s[e, h], and 0 for a dead entry of a segment;
+ *   3. an entry whose id is negative or >= N is dead: it takes no part and no memory is read for it.  A segment with no live entry
+ *      gives a row of zeros and lse = -inf.  Masking is by a dead id, not by a -inf bias;
+ *   4. all arithmetic is float32; the exponential is expf (HIP's device expf, documented maximum error 1 ulp), taken of s - m <= 0 in
+ *      natural units: no logit is pre-multiplied by log2 e, so a weight of exp(0) is exactly 1; lse_out's logarithm is HIP's device
+ *      logf (documented maximum error 2 ulp; logf(1) = 0);
+ *   5. logits must be finite: a NaN or infinite logit makes out, lse_out and scores_out of that (d, h) unspecified; the call stays
+ *      memory-safe, no address depends on a logit;
+ *   6. X[id] is the row legion_aggregate_rows resolves (its rule 7: node_map / cache_table / full_table, float32 or bf16 storage with
+ *      the gather's pitch); out is [n, heads, D] of out_dtype, stride D, no pad: float32, or bf16 rounded to nearest even from the
+ *      float32 result; offsets are clamped and memory safety is as rule 10 of legion_aggregate_rows, over queries, bias, scores_out
+ *      and lse_out as well;
+ *   7. the result is a pure function of the arguments, bit-identical from run to run: there is no floating-point atomic and every sum
+ *      and every merge has one order.  A state is (m, l, acc[D]) per head, empty as (-inf, 0, 0).  A segment of at most 256 entries is
+ *      read by G = 64 / C interleaved groups (C as in rule 9 of legion_aggregate_rows; a lane holds up to 4 units of a row wider than
+ *      64 units), group g taking entries g, g + G, ... in order, in blocks of B rows (B = 4, or 2 where a lane holds 16 or more
+ *      columns): the block's logits (the dot's partial sums over a lane's columns in column order, then a pairwise tree over the C
+ *      lanes), m' = max(m, the block's maximum), then l = l * expf(m - m') + p_0 + ... + p_{B-1} and acc = fmaf(p_k, x_k,
+ *      ... fmaf(p_0, x_0, acc * expf(m - m'))) with p_k = expf(s_k - m'), dead rows as p = 0.  The groups' states merge by a pairwise
+ *      tree over lane distances C, 2C, ... 32: (m, l, acc) = (max(m1, m2), fmaf(l1, w1, l2 * w2), fmaf(acc1, w1, acc2 * w2)) with
+ *      w_i = expf(m_i - m), the lower group as 1; an empty state has w = 0.  A longer segment is cut into chunks of 256 entries, each
+ *      reduced so to a partial record; m is the maximum of the records' m_j, and l and acc are fmaf(l_j, w_j, l) and
+ *      fmaf(acc_j, w_j, acc) with w_j = expf(m_j - m) over the records in chunk order, from 0.
+ * scratch: device memory, 16-byte aligned, of at least legion_attention_scratch_bytes(n, M, D, heads) bytes (host-only: the first chunk
+ * of every segment, the scan's sums, and a partial record of heads x (2 + D) float32 for every chunk of a segment longer than 256
+ * entries: fewer than M / 128 records; -1 for n, M, D or heads the call refuses); two calls in flight on different streams need
+ * scratch of their own.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: a dtype or out_dtype that is no LEGION_FEATURE_*; heads outside
+ * [1, LEGION_ATTENTION_MAX_HEADS]; a cache_table without a node_map or a node_map without a cache_table; queries and bias both NULL;
+ * n < 0, M < 0, D <= 0; n > LEGION_AGGREGATE_MAX_SEGMENTS; a bf16 pitch round_up(D, 8) that is no int32; a width the register plan
+ * cannot hold (a lane keeps heads' x U x W <= 64 accumulators, heads' = heads rounded up to a power of two, W = 4, 1 or 8 columns a unit
+ * as the row is float32 with D % 4 == 0, other float32, or bf16, U = ceil(units / 64) rounded up to a power of two and <= 4: float32
+ * D <= 1024 and heads' x D <= 4096, D <= 256 where D % 4 != 0; bf16 D <= 2048 and heads' x round_up(D, 8) <= 4096); a null full_table,
+ * offsets, ids, out or scratch; scratch_bytes below legion_attention_scratch_bytes(n, M, D, heads).  n == 0 returns 0 and enqueues
+ * nothing.
+ * Not offered: heads as column slices of one row (every head reads the whole row: slice the queries with zeros instead); -inf masks;
+ * the backward pass; striped cliques, peer stripes, the replica and the hybrid tier (one local cache table only); the pool, the server
+ * and the wire. */
+#define LEGION_ATTENTION_MAX_HEADS 8
+int64_t legion_attention_scratch_bytes(int32_t n, int64_t M, int32_t D, int32_t heads);
+int32_t legion_attention_rows(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                              const void* cache_table /* or NULL */, const int32_t* node_map /* int32[N], or NULL */, int32_t D, int32_t N,
+                              const int64_t* offsets /* int64[n + 1] */, int32_t n, const int32_t* ids /* int32[M] */, int64_t M,
+                              const float* queries /* float32[n, heads, D], or NULL */, int32_t heads, float scale,
+                              const float* bias /* float32[M, heads], or NULL */, void* out /* [n, heads, D] of out_dtype */,
+                              float* scores_out /* float32[M, heads], or NULL */, float* lse_out /* float32[n, heads], or NULL */,
+                              void* scratch, int64_t scratch_bytes);
 /* Sparse row updates of the float32 feature table (DGL's dgl.nn.NodeEmbedding with dgl.optim.SparseAdagrad / SparseAdam, and plain
  * SGD), new in this build; no reference counterpart.  The half of "gradients" the library owns: a batch of per-row gradients with
  * duplicate ids -- what a walk or a link-prediction batch hands back for rows that are learnable embeddings -- is combined per id and

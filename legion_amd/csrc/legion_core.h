@@ -1013,6 +1013,19 @@ struct AggregateParams {
 };
 void launch_aggregate_rows(hipStream_t s, const AggregateParams& a, void* scratch);
 
+// the fused attention aggregation (kernels_attention.hip; the rule: legion_attention_rows in legion_hip.h, its refusals, register plan
+// and scratch layout attention_rule.h).  The arguments are the caller's to check
+struct AttentionParams {
+    AggregateParams rows;           // the tables, offsets, ids, out, M, n, N, D and the formats; weights null, reduce unused
+    const float* queries;           // null, or float[n x heads x D]
+    const float* bias;              // null, or float[M x heads]
+    float* scores_out;              // null, or float[M x heads]
+    float* lse_out;                 // null, or float[n x heads]
+    int32_t heads;
+    float scale;
+};
+void launch_attention_rows(hipStream_t s, const AttentionParams& t, void* scratch);
+
 // the sparse row update (kernels_update.hip; the rule: legion_row_update in legion_hip.h, its refusals, sort passes and scratch layout
 // update_rule.h).  The arguments are the caller's to check
 struct UpdateParams {

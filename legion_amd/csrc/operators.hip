@@ -21,6 +21,7 @@
 #include "link_rule.h"
 #include "in_edges_rule.h"
 #include "aggregate_rule.h"
+#include "attention_rule.h"
 #include "update_rule.h"
 #include "labor_rule.h"
 #include "topk_rule.h"
@@ -623,6 +624,33 @@ extern "C" int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, 
                                 .weights = weights, .out = out, .M = M, .n = n, .N = N, .D = D, .dtype = dtype, .out_dtype = out_dtype,
                                 .reduce = reduce};
     lg::launch_aggregate_rows(static_cast<hipStream_t>(stream), a, scratch);
+    return 0;
+}
+
+// The fused attention aggregation (the rule: legion_hip.h; the refusals, the register plan and the scratch size: attention_rule.h).  As
+// above: every check comes before the launch.
+extern "C" int64_t legion_attention_scratch_bytes(int32_t n, int64_t M, int32_t D, int32_t heads)
+{
+    return attention_scratch_bytes(n, M, D, heads);
+}
+
+extern "C" int32_t legion_attention_rows(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
+                                         const void* cache_table, const int32_t* node_map, int32_t D, int32_t N, const int64_t* offsets,
+                                         int32_t n, const int32_t* ids, int64_t M, const float* queries, int32_t heads, float scale,
+                                         const float* bias, void* out, float* scores_out, float* lse_out, void* scratch,
+                                         int64_t scratch_bytes)
+{
+    const AttentionArgs args{.dtype = dtype, .out_dtype = out_dtype, .n = n, .D = D, .heads = heads, .M = M, .scratch_bytes = scratch_bytes,
+                             .full_table = full_table != nullptr, .cache_table = cache_table != nullptr, .node_map = node_map != nullptr,
+                             .offsets = offsets != nullptr, .ids = ids != nullptr, .queries = queries != nullptr, .bias = bias != nullptr,
+                             .out = out != nullptr, .scratch = scratch != nullptr};
+    if (attention_refusal(args) != AttentionRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    const lg::AttentionParams t{.rows = {.full_table = full_table, .cache_table = cache_table, .node_map = node_map, .offsets = offsets,
+                                         .ids = ids, .weights = nullptr, .out = out, .M = M, .n = n, .N = N, .D = D, .dtype = dtype,
+                                         .out_dtype = out_dtype, .reduce = LEGION_REDUCE_SUM},
+                                .queries = queries, .bias = bias, .scores_out = scores_out, .lse_out = lse_out, .heads = heads, .scale = scale};
+    lg::launch_attention_rows(static_cast<hipStream_t>(stream), t, scratch);
     return 0;
 }
 

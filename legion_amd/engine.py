@@ -11,6 +11,7 @@ include/legion_hip.h; PyTorch is used only to own device memory, streams and tor
 There is no CPU path: constructing any of these without a GPU-backed library raises.
 """
 import ctypes
+import math
 
 import numpy as np
 import torch
@@ -901,6 +902,26 @@ class GraphStorage:
         offsets, _, src, _ = self._in_edges(rows.to(self.col.device).contiguous(), n, False, stream)
         return feature._aggregate(self.col.device, offsets, src, reduce, None, tables, "float32", stream)
 
+    def full_neighbor_attention(self, feature, rows, queries, *, scale=None, cache=None, out_dtype="float32", return_lse=False,
+                                stream=None):
+        """Softmax attention of rows over the feature rows of every in-neighbour (DGL's DotGatConv over in_edges(rows): exact
+        layer-wise inference of a dot-product attention layer): row_offsets, in_edges and FeatureStorage.attention, with no
+        relabelling and no de-duplication.  feature and rows as in full_neighbor_aggregate; queries, scale, cache and out_dtype as
+        in FeatureStorage.attention.  Returns [n, H, D] ([n, D] for [n, D] queries), and with return_lse also lse float32 [n, H]; a
+        row without entries, or with dead ones only, is zeros.  offsets[n] is read back to size the edge list: the call
+        synchronises `stream` (default: the current one), on which everything is enqueued."""
+        dev_id, _ = self._check_full_aggregate(feature, "sum", None)
+        rows, n = self._check_rows(rows)
+        if queries is None:
+            raise ValueError("full_neighbor_attention needs queries: a bias per entry has no list to index before the call")
+        queries, _, H, flat, scale, tables = feature._check_attention(n, 0, queries, None, scale, cache, dev_id, out_dtype, False, return_lse)
+        dev = self.col.device
+        offsets, _, src, _ = self._in_edges(rows.to(dev).contiguous(), n, False, stream)
+        out, _, lse = feature._attention(dev, offsets, src, queries.to(dev).contiguous(), None, H, scale, tables, out_dtype, False,
+                                         return_lse, stream)
+        out = out[:, 0] if flat else out
+        return (out, lse) if return_lse else out
+
     def _block_tail(self, seeds, n, src, stream):
         """The end of a block: unique_ids over [seeds | src] under `stream`.  Returns (input_nodes, src_local); ValueError unless the n
         seeds are distinct vertices of the graph."""
@@ -1761,6 +1782,92 @@ class FeatureStorage:
         dev = _torch_device(dev_id)
         return self._aggregate(dev, offsets.to(dev).contiguous(), ids.to(dev).contiguous(),
                                reduce, None if weights is None else weights.to(dev).contiguous(), tables, out_dtype, stream)
+
+    ATTENTION_MAX_HEADS = 8                          # LEGION_ATTENTION_MAX_HEADS
+
+    def _check_attention(self, n, M, queries, bias, scale, cache, dev_id, out_dtype, return_scores, return_lse):
+        """The arguments of attention by the rules of legion_attention_rows, before anything touches a device: ValueError with the
+        reason.  Returns (queries [n, H, D] or None, bias [M, H] or None, H, whether queries came as [n, D], scale, the cache's
+        tables as _local_cache_tables returns them)."""
+        D = self.float_feature_len
+        if out_dtype not in FEATURE_DTYPES:
+            raise ValueError(f"out_dtype must be one of {sorted(FEATURE_DTYPES)}, not {out_dtype!r}")
+        _need_bool("return_scores", return_scores)
+        _need_bool("return_lse", return_lse)
+        if queries is None and bias is None:
+            raise ValueError("attention needs queries, bias or both: there is no logit without them")
+        flat, H = False, None
+        if queries is not None:
+            queries = queries if isinstance(queries, torch.Tensor) else torch.as_tensor(queries)
+            flat = queries.dim() == 2
+            if flat:
+                queries = queries.unsqueeze(1)
+            if queries.dtype != torch.float32 or queries.dim() != 3 or queries.shape[0] != n or queries.shape[2] != D:
+                raise ValueError(f"queries must be float32 [{n}, H, {D}] or [{n}, {D}], not {queries.dtype} {tuple(queries.shape)}")
+            H = int(queries.shape[1])
+        if bias is not None:
+            bias = bias if isinstance(bias, torch.Tensor) else torch.as_tensor(bias)
+            if bias.dim() == 1:
+                bias = bias.unsqueeze(1)
+            if bias.dtype != torch.float32 or bias.dim() != 2 or bias.shape[0] != M or (H is not None and bias.shape[1] != H):
+                raise ValueError(f"bias must be float32 [{M}, {'H' if H is None else H}], not {bias.dtype} {tuple(bias.shape)}")
+            H = int(bias.shape[1])
+        if not 1 <= H <= self.ATTENTION_MAX_HEADS:
+            raise ValueError(f"{H} heads, from 1 to {self.ATTENTION_MAX_HEADS} a call")
+        if scale is None:
+            scale = 1.0 / math.sqrt(D) if queries is not None else 1.0
+        if isinstance(scale, bool) or not isinstance(scale, (int, float, np.floating, np.integer)) or not math.isfinite(scale):
+            raise ValueError(f"scale must be a finite number or None, not {scale!r}")
+        if self._lib.legion_attention_rows(None, FEATURE_DTYPES[self.feature_dtype], 0, 4096, None, None, D, 1, 4096, 0, 4096, 0, 4096, H, 1.0,
+                                           None, 4096, None, None, 4096, 2 ** 40) != 0:      # (n = 0: the rule's answer for this width;
+                                                                                             # nothing is enqueued, no pointer followed)
+            raise ValueError(f"{H} heads of {D} {self.feature_dtype} columns are wider than the kernel's register plan "
+                             "(legion_attention_rows in legion_hip.h)")
+        return queries, bias, H, flat, float(scale), self._local_cache_tables(cache, dev_id, "attention reads")
+
+    def _attention(self, dev, offsets, ids, queries, bias, H, scale, tables, out_dtype, return_scores, return_lse, stream):
+        """offsets, ids, queries, bias: on dev, contiguous, checked.  Returns (out [n, H, D], scores [M, H] or None, lse [n, H] or
+        None)."""
+        n, M, D = int(offsets.numel()) - 1, int(ids.numel()), self.float_feature_len
+        torch_dtype = torch.float32 if out_dtype == "float32" else torch.bfloat16
+        scores = torch.zeros((M, H), dtype=torch.float32, device=dev) if return_scores else None
+        lse = torch.full((n, H), -math.inf, dtype=torch.float32, device=dev) if return_lse else None
+        if n == 0 or M == 0:                         # (an empty tensor has no address to hand over)
+            return torch.zeros((n, H, D), dtype=torch_dtype, device=dev), scores, lse
+        out = torch.empty((n, H, D), dtype=torch_dtype, device=dev)
+        nbytes = int(self._lib.legion_attention_scratch_bytes(n, M, D, H))
+        scratch = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+        _enqueue(self._lib, "legion_attention_rows", "attention", dev, stream,
+                 (FEATURE_DTYPES[self.feature_dtype], FEATURE_DTYPES[out_dtype], self._lib.legion_feature_table(self.handle),
+                  tables[0], tables[1], D, self.total_num_nodes, _ptr(offsets), n, _ptr(ids), M, _ptr(queries), H, scale, _ptr(bias),
+                  _ptr(out), _ptr(scores), _ptr(lse), _ptr(scratch), nbytes), (offsets, ids, queries, bias, out, scores, lse, scratch))
+        return out, scores, lse
+
+    def attention(self, offsets, ids, *, queries=None, bias=None, scale=None, cache=None, dev_id=0, out_dtype="float32",
+                  return_scores=False, return_lse=False, stream=None):
+        """Softmax attention of every segment over the stored feature rows of its ids, in one pass (DGL's u_dot_v + edge_softmax +
+        u_mul_e_sum; the rule: legion_attention_rows in legion_hip.h): for segment d and head h the logits s[e, h] = scale *
+        queries[d, h] . X[ids[e]] + bias[e, h], and out[d, h] = sum_e softmax_e(s)[e] * X[ids[e]].  offsets, ids and cache as in
+        aggregate; a negative id or one past the table takes no part (the mask: there is no -inf bias).  queries: None, float32
+        [n, H, D], or [n, D] for one head; bias: None or float32 [M, H] ([M] for one head), logits must be finite; at least one of the
+        two.  scale: None for 1 / sqrt(D) with queries and 1 without.  A layer's key and value projections commute with the sum:
+        pass W_k^T q as the query and apply W_v to the result.  Returns out [n, H, D] ([n, D] for [n, D] queries) of out_dtype, a
+        segment without a live entry as zeros; then, as asked, scores float32 [M, H] (the logits, 0 for a dead entry) and lse
+        float32 [n, H] (log sum exp of a segment's logits, -inf for none).  Bit-identical from run to run.  No sync; enqueued on
+        `stream` (default: the current one)."""
+        offsets = _as_1d(offsets, torch.int64, "offsets")
+        ids = _as_1d(ids, torch.int32, "ids")
+        if offsets.numel() < 1 or offsets.numel() - 1 > self.AGGREGATE_MAX_SEGMENTS:
+            raise ValueError(f"offsets must hold n + 1 entries for 0 <= n <= {self.AGGREGATE_MAX_SEGMENTS}, not {offsets.numel()}")
+        queries, bias, H, flat, scale, tables = self._check_attention(int(offsets.numel()) - 1, int(ids.numel()), queries, bias, scale, cache,
+                                                                      dev_id, out_dtype, return_scores, return_lse)
+        dev = _torch_device(dev_id)
+        on = lambda t: None if t is None else t.to(dev).contiguous()
+        out, scores, lse = self._attention(dev, on(offsets), on(ids), on(queries), on(bias), H, scale, tables, out_dtype, return_scores,
+                                           return_lse, stream)
+        out = out[:, 0] if flat else out
+        extras = tuple(t for t in (scores, lse) if t is not None)
+        return (out,) + extras if extras else out
 
     OPTIMIZERS = {"sgd": 0, "adagrad": 1, "adam": 2}  # LEGION_UPDATE_*
     ROW_UPDATE_MAX_IDS = 2 ** 22                      # LEGION_ROW_UPDATE_MAX_IDS

@@ -163,6 +163,9 @@ SIGNATURES = {
     "legion_in_edges": (c_i32, [c_p, c_p, c_p, c_i32, c_p, c_i64, c_p, c_p, c_p]),
     "legion_aggregate_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32]),
     "legion_aggregate_rows": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_p, c_p, c_i64]),
+    "legion_attention_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
+    "legion_attention_rows": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_f32, c_p, c_p, c_p,
+                                      c_p, c_p, c_i64]),
     "legion_row_update_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "legion_row_update": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_p, c_p, c_p,
                                   c_p, c_i64]),
