@@ -802,8 +802,8 @@ int32_t legion_aggregate_rows(legion_stream_t stream, int32_t dtype, int32_t out
  * offsets, ids, out or scratch; scratch_bytes below legion_attention_scratch_bytes(n, M, D, heads).  n == 0 returns 0 and enqueues
  * nothing.
  * Not offered: heads as column slices of one row (every head reads the whole row: slice the queries with zeros instead); -inf masks;
- * the backward pass; striped cliques, peer stripes, the replica and the hybrid tier (one local cache table only); the pool, the server
- * and the wire. */
+ * striped cliques, peer stripes, the replica and the hybrid tier (one local cache table only); the pool, the server and the wire.  The
+ * backward pass is legion_attention_rows_backward. */
 #define LEGION_ATTENTION_MAX_HEADS 8
 int64_t legion_attention_scratch_bytes(int32_t n, int64_t M, int32_t D, int32_t heads);
 int32_t legion_attention_rows(legion_stream_t stream, int32_t dtype, int32_t out_dtype, const void* full_table,
@@ -813,6 +813,54 @@ int32_t legion_attention_rows(legion_stream_t stream, int32_t dtype, int32_t out
                               const float* bias /* float32[M, heads], or NULL */, void* out /* [n, heads, D] of out_dtype */,
                               float* scores_out /* float32[M, heads], or NULL */, float* lse_out /* float32[n, heads], or NULL */,
                               void* scratch, int64_t scratch_bytes);
+/* The backward pass of legion_attention_rows, new in this build; no reference counterpart: the gradients of a loss with respect to
+ * the queries, the bias and the source rows, from the gradient of out, in one pass -- each source row read once for all heads, the
+ * logits recomputed, no M x D gathered copy and no stored probabilities.  grad_rows is one float32 row per ENTRY, the form
+ * legion_row_update takes with ids: an id that several entries name is combined there.  All buffers are device memory.  The call is
+ * enqueued on `stream`, on the device current at the call; nothing is read back and it may be captured into a graph.
+ *
+ * offsets, ids, the tables, queries, heads, scale and bias are the forward call's; grad_out (dO) and out are float32[n, heads, D], lse
+ * float32[n, heads]: out and lse are the forward's float32 out and lse_out.  For segment d, head h and a live entry e with the stored
+ * row x = X[ids[e]] as rule 6 of legion_attention_rows resolves it, all in float32:
+ *   1. s[e, h] as rule 1 of legion_attention_rows, in its order (a lane's columns in column order, the pairwise tree over the C lanes,
+ *      one fmaf with scale and bias); p[e, h] = expf(s[e, h] - lse[d, h]), HIP's device expf;
+ *   2. delta[d, h] = sum_c dO[d, h, c] * out[d, h, c] and t[e, h] = sum_c dO[d, h, c] * x[c], summed as the logit's dot is;
+ *      dS[e, h] = p[e, h] * (t[e, h] - delta[d, h]);
+ *   3. grad_bias[e, h] = dS[e, h];
+ *   4. grad_rows[e, c] = g_{heads-1} with g_h = fmaf(scale * dS[e, h], queries[d, h, c], fmaf(p[e, h], dO[d, h, c], g_{h-1})), g_{-1} = 0:
+ *      the heads summed in order 0 .. heads - 1; without queries the outer fmaf falls away;
+ *   5. grad_queries[d, h, c] = scale * sum_e dS[e, h] * x[c]: fmafs in the order in which rule 7 of legion_attention_rows adds a
+ *      chunk's entries (group g takes entries g, g + G, ... in order), the groups' sums added by the pairwise tree over lane distances
+ *      C, 2C, ... 32, the chunks' sums of a segment longer than 256 entries in chunk order from 0, then one product with scale;
+ *   6. a dead entry (ids[e] < 0 or >= N) gets grad_bias 0 and a grad_rows row of zeros, and no memory is read for it; a segment
+ *      without a live entry gets a grad_queries row of zeros.  Entries of ids that lie in no segment are not written.  Without queries
+ *      (bias alone) the q terms vanish and grad_queries must be NULL;
+ *   7. each of grad_queries (float32[n, heads, D]), grad_bias (float32[M, heads]) and grad_rows (float32[M, D]) may be NULL and is then
+ *      not formed, but not all three; offsets are clamped and memory safety is as rule 6 of legion_attention_rows: no address depends
+ *      on a value of queries, bias, grad_out, out or lse;
+ *   8. the result is a pure function of the arguments, bit-identical from run to run: no floating-point atomic, every sum has one
+ *      order.
+ * scratch: device memory, 16-byte aligned, of at least legion_attention_backward_scratch_bytes(n, M, D, heads) bytes (host-only: the
+ * aggregation's first words and a partial record of heads x D float32 for every chunk of a segment longer than 256 entries; -1 for n,
+ * M, D or heads the call refuses).  Without grad_queries no record is written and no finishing launch is made.
+ * Returns 0, or -1 -- nothing enqueued, no buffer touched -- for: what legion_attention_rows refuses of the arguments they share; a
+ * null grad_out, out or lse; grad_queries, grad_bias and grad_rows all NULL; grad_queries without queries; a width the backward's
+ * register plan cannot hold: a lane keeps its columns of q, dO and the grad_queries sums of every head for a whole chunk, three row
+ * sets where the forward keeps two, so heads' x U x W <= 32 (float32, D % 4 == 0: 8 heads up to D 256, heads' x D <= 2048 up to D
+ * 1024; other float32: D <= 256; bf16: at most 4 heads, heads' x round_up(D, 8) <= 2048) -- a caller splits the heads over calls: the
+ * per-head outputs are independent and the calls' grad_rows add; scratch_bytes below
+ * legion_attention_backward_scratch_bytes(n, M, D, heads).  n == 0 returns 0 and enqueues nothing.
+ * Not offered: -inf masks (mask by a dead id); striped cliques, peer stripes, the replica and the hybrid tier (one local cache table
+ * only); bf16 gradients; an autograd wrapper (the caller chains attention, this call and legion_row_update). */
+int64_t legion_attention_backward_scratch_bytes(int32_t n, int64_t M, int32_t D, int32_t heads);
+int32_t legion_attention_rows_backward(legion_stream_t stream, int32_t dtype, const void* full_table, const void* cache_table /* or NULL */,
+                                       const int32_t* node_map /* int32[N], or NULL */, int32_t D, int32_t N,
+                                       const int64_t* offsets /* int64[n + 1] */, int32_t n, const int32_t* ids /* int32[M] */, int64_t M,
+                                       const float* queries /* float32[n, heads, D], or NULL */, int32_t heads, float scale,
+                                       const float* bias /* float32[M, heads], or NULL */, const float* grad_out /* float32[n, heads, D] */,
+                                       const float* out /* float32[n, heads, D] */, const float* lse /* float32[n, heads] */,
+                                       float* grad_queries /* float32[n, heads, D], or NULL */, float* grad_bias /* float32[M, heads], or NULL */,
+                                       float* grad_rows /* float32[M, D], or NULL */, void* scratch, int64_t scratch_bytes);
 /* Sparse row updates of the float32 feature table (DGL's dgl.nn.NodeEmbedding with dgl.optim.SparseAdagrad / SparseAdam, and plain
  * SGD), new in this build; no reference counterpart.  The half of "gradients" the library owns: a batch of per-row gradients with
  * duplicate ids -- what a walk or a link-prediction batch hands back for rows that are learnable embeddings -- is combined per id and

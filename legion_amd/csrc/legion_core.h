@@ -1026,6 +1026,23 @@ struct AttentionParams {
 };
 void launch_attention_rows(hipStream_t s, const AttentionParams& t, void* scratch);
 
+// its backward pass (kernels_attention_backward.hip; the rule: legion_attention_rows_backward in legion_hip.h, its refusals, register
+// plan and scratch layout attention_backward_rule.h).  The arguments are the caller's to check
+struct AttentionBackwardParams {
+    AggregateParams rows;           // the tables, offsets, ids, M, n, N, D and the stored format; weights and out null, the rest unused
+    const float* queries;           // null, or float[n x heads x D]
+    const float* bias;              // null, or float[M x heads]
+    const float* grad_out;          // float[n x heads x D]
+    const float* out;               // float[n x heads x D], the forward's
+    const float* lse;               // float[n x heads], the forward's
+    float* grad_queries;            // null, or float[n x heads x D]; only with queries
+    float* grad_bias;               // null, or float[M x heads]
+    float* grad_rows;               // null, or float[M x D]
+    int32_t heads;
+    float scale;
+};
+void launch_attention_rows_backward(hipStream_t s, const AttentionBackwardParams& t, void* scratch);
+
 // the sparse row update (kernels_update.hip; the rule: legion_row_update in legion_hip.h, its refusals, sort passes and scratch layout
 // update_rule.h).  The arguments are the caller's to check
 struct UpdateParams {

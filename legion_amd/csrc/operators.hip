@@ -22,6 +22,7 @@
 #include "in_edges_rule.h"
 #include "aggregate_rule.h"
 #include "attention_rule.h"
+#include "attention_backward_rule.h"
 #include "update_rule.h"
 #include "labor_rule.h"
 #include "topk_rule.h"
@@ -651,6 +652,38 @@ extern "C" int32_t legion_attention_rows(legion_stream_t stream, int32_t dtype, 
                                          .out_dtype = out_dtype, .reduce = LEGION_REDUCE_SUM},
                                 .queries = queries, .bias = bias, .scores_out = scores_out, .lse_out = lse_out, .heads = heads, .scale = scale};
     lg::launch_attention_rows(static_cast<hipStream_t>(stream), t, scratch);
+    return 0;
+}
+
+// Its backward pass (the rule: legion_hip.h; the refusals, the register plan and the scratch size: attention_backward_rule.h).  As
+// above: every check comes before the launch.
+extern "C" int64_t legion_attention_backward_scratch_bytes(int32_t n, int64_t M, int32_t D, int32_t heads)
+{
+    return attention_backward_scratch_bytes(n, M, D, heads);
+}
+
+extern "C" int32_t legion_attention_rows_backward(legion_stream_t stream, int32_t dtype, const void* full_table, const void* cache_table,
+                                                  const int32_t* node_map, int32_t D, int32_t N, const int64_t* offsets, int32_t n,
+                                                  const int32_t* ids, int64_t M, const float* queries, int32_t heads, float scale,
+                                                  const float* bias, const float* grad_out, const float* out, const float* lse,
+                                                  float* grad_queries, float* grad_bias, float* grad_rows, void* scratch,
+                                                  int64_t scratch_bytes)
+{
+    const AttentionBackwardArgs args{.dtype = dtype, .n = n, .D = D, .heads = heads, .M = M, .scratch_bytes = scratch_bytes,
+                                     .full_table = full_table != nullptr, .cache_table = cache_table != nullptr,
+                                     .node_map = node_map != nullptr, .offsets = offsets != nullptr, .ids = ids != nullptr,
+                                     .queries = queries != nullptr, .bias = bias != nullptr, .grad_out = grad_out != nullptr,
+                                     .out = out != nullptr, .lse = lse != nullptr, .grad_queries = grad_queries != nullptr,
+                                     .grad_bias = grad_bias != nullptr, .grad_rows = grad_rows != nullptr, .scratch = scratch != nullptr};
+    if (attention_backward_refusal(args) != AttentionBackwardRefusal::Ok) return -1;
+    if (n == 0) return 0;
+    const lg::AttentionBackwardParams t{.rows = {.full_table = full_table, .cache_table = cache_table, .node_map = node_map, .offsets = offsets,
+                                                 .ids = ids, .weights = nullptr, .out = nullptr, .M = M, .n = n, .N = N, .D = D, .dtype = dtype,
+                                                 .out_dtype = LEGION_FEATURE_F32, .reduce = LEGION_REDUCE_SUM},
+                                        .queries = queries, .bias = bias, .grad_out = grad_out, .out = out, .lse = lse,
+                                        .grad_queries = grad_queries, .grad_bias = grad_bias, .grad_rows = grad_rows, .heads = heads,
+                                        .scale = scale};
+    lg::launch_attention_rows_backward(static_cast<hipStream_t>(stream), t, scratch);
     return 0;
 }
 

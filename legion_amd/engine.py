@@ -1869,6 +1869,62 @@ class FeatureStorage:
         extras = tuple(t for t in (scores, lse) if t is not None)
         return (out,) + extras if extras else out
 
+    ATTENTION_GRADS = ("queries", "bias", "rows")
+
+    def attention_backward(self, offsets, ids, grad_out, out, lse, *, queries=None, bias=None, scale=None, grads=ATTENTION_GRADS,
+                           cache=None, dev_id=0, stream=None):
+        """The gradients of attention(offsets, ids, queries=, bias=, scale=, cache=) from the gradient of its result, in one pass
+        over the stored rows (the rule: legion_attention_rows_backward in legion_hip.h).  offsets, ids, queries, bias, scale and cache
+        are the forward call's; out and lse are its float32 results (return_lse=True), grad_out the gradient of out: float32
+        [n, H, D], or [n, D] for one head; lse float32 [n, H].  grads: which gradients to form, a non-empty subset of ("queries",
+        "bias", "rows"); "queries" needs queries.  Returns a tuple of those asked for, in that order:
+        grad_queries in the shape of queries, grad_bias float32 [M, H], grad_rows float32 [M, D] -- one row per entry of ids, what
+        update_rows(ids, grad_rows, combine="sum") takes; a dead entry's are zeros.  H heads of D columns must fit the backward's
+        register plan, narrower than the forward's: split the heads over calls and add the grad_rows.  Bit-identical from run to run.
+        No sync; enqueued on `stream` (default: the current one)."""
+        offsets = _as_1d(offsets, torch.int64, "offsets")
+        ids = _as_1d(ids, torch.int32, "ids")
+        if offsets.numel() < 1 or offsets.numel() - 1 > self.AGGREGATE_MAX_SEGMENTS:
+            raise ValueError(f"offsets must hold n + 1 entries for 0 <= n <= {self.AGGREGATE_MAX_SEGMENTS}, not {offsets.numel()}")
+        n, M, D = int(offsets.numel()) - 1, int(ids.numel()), self.float_feature_len
+        queries, bias, H, flat, scale, tables = self._check_attention(n, M, queries, bias, scale, cache, dev_id, "float32", False, False)
+        if isinstance(grads, str) or not grads or len(set(grads)) != len(grads) or not set(grads) <= set(self.ATTENTION_GRADS):
+            raise ValueError(f"grads must be a non-empty subset of {self.ATTENTION_GRADS}, not {grads!r}")
+        if "queries" in grads and queries is None:
+            raise ValueError("grads asks for 'queries' and the call has no queries")
+        rows = {}
+        for name, x in (("grad_out", grad_out), ("out", out)):
+            x = x if isinstance(x, torch.Tensor) else torch.as_tensor(x)
+            x = x.unsqueeze(1) if x.dim() == 2 and H == 1 else x
+            if x.dtype != torch.float32 or tuple(x.shape) != (n, H, D):
+                raise ValueError(f"{name} must be float32 [{n}, {H}, {D}]{f' or [{n}, {D}]' if H == 1 else ''}, not {x.dtype} {tuple(x.shape)}")
+            rows[name] = x
+        lse = lse if isinstance(lse, torch.Tensor) else torch.as_tensor(lse)
+        if lse.dtype != torch.float32 or tuple(lse.shape) != (n, H):
+            raise ValueError(f"lse must be float32 [{n}, {H}], not {lse.dtype} {tuple(lse.shape)}")
+        if self._lib.legion_attention_rows_backward(None, FEATURE_DTYPES[self.feature_dtype], 4096, None, None, D, 1, 4096, 0, 4096, 0, 4096, H,
+                                                    1.0, None, 4096, 4096, 4096, None, 4096, None, 4096, 2 ** 40) != 0:      # (n = 0, as in
+                                                                                                                             # _check_attention)
+            raise ValueError(f"{H} heads of {D} {self.feature_dtype} columns are wider than the backward's register plan "
+                             "(legion_attention_rows_backward in legion_hip.h): split the heads over calls")
+        dev = _torch_device(dev_id)
+        zeros = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=dev)      # (grad_rows: entries in no segment stay zeros)
+        got = {"queries": zeros(n, H, D) if "queries" in grads else None, "bias": zeros(M, H) if "bias" in grads else None,
+               "rows": zeros(M, D) if "rows" in grads else None}
+        if n > 0 and M > 0:                          # (an empty tensor has no address to hand over)
+            on = lambda t: None if t is None else t.to(dev).contiguous()
+            offsets, ids, queries, bias, grad_out, out, lse = (on(t) for t in (offsets, ids, queries, bias, rows["grad_out"], rows["out"], lse))
+            nbytes = int(self._lib.legion_attention_backward_scratch_bytes(n, M, D, H))
+            scratch = torch.empty(((nbytes + 15) // 16 * 2,), dtype=torch.int64, device=dev)
+            _enqueue(self._lib, "legion_attention_rows_backward", "attention_backward", dev, stream,
+                     (FEATURE_DTYPES[self.feature_dtype], self._lib.legion_feature_table(self.handle), tables[0], tables[1], D,
+                      self.total_num_nodes, _ptr(offsets), n, _ptr(ids), M, _ptr(queries), H, scale, _ptr(bias), _ptr(grad_out), _ptr(out),
+                      _ptr(lse), _ptr(got["queries"]), _ptr(got["bias"]), _ptr(got["rows"]), _ptr(scratch), nbytes),
+                     (offsets, ids, queries, bias, grad_out, out, lse, scratch) + tuple(got.values()))
+        if flat and got["queries"] is not None:
+            got["queries"] = got["queries"][:, 0]
+        return tuple(got[name] for name in self.ATTENTION_GRADS if name in grads)
+
     OPTIMIZERS = {"sgd": 0, "adagrad": 1, "adam": 2}  # LEGION_UPDATE_*
     ROW_UPDATE_MAX_IDS = 2 ** 22                      # LEGION_ROW_UPDATE_MAX_IDS
     STATE_ROWS = {"sgd": (), "adagrad": ("state1",), "adam": ("state1", "state2", "state_pow")}

@@ -166,6 +166,9 @@ SIGNATURES = {
     "legion_attention_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
     "legion_attention_rows": (c_i32, [c_p, c_i32, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_f32, c_p, c_p, c_p,
                                       c_p, c_p, c_i64]),
+    "legion_attention_backward_scratch_bytes": (c_i64, [c_i32, c_i64, c_i32, c_i32]),
+    "legion_attention_rows_backward": (c_i32, [c_p, c_i32, c_p, c_p, c_p, c_i32, c_i32, c_p, c_i32, c_p, c_i64, c_p, c_i32, c_f32, c_p, c_p, c_p,
+                                               c_p, c_p, c_p, c_p, c_p, c_i64]),
     "legion_row_update_scratch_bytes": (c_i64, [c_i32, c_i32, c_i32]),
     "legion_row_update": (c_i32, [c_p, c_p, c_p, c_p, c_i32, c_i32, c_p, c_p, c_i32, c_i32, c_i32, c_f32, c_f32, c_f32, c_f32, c_p, c_p, c_p,
                                   c_p, c_i64]),
